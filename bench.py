@@ -13,12 +13,23 @@ N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ..
 WORLD_SIZE in the environment) or plainly as above, in which case this process starts N fresh children -- one per GPU,
 before it has touched a GPU itself -- and waits for them.  One rank per GPU over RCCL (torch.distributed "nccl").
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel of the step (largest total time among the
-MFMA GEMM kernels): algorithmic FLOPs of its launches divided by their durations inside the timed region, measured with
-HIP events that carry the dispatch's own begin / end timestamps (w2v2_gemm_timed -> hipExtLaunchKernelGGL: the duration
-rocprofv3 reports for the kernel); `traffic` / `mfma_busy` come from the committed rocprofv3 PMC passes of the same command under profiles/.
-`cpu_baseline` times the CPU oracle (oracle/w2v2_oracle.py, kind "port") on the host cores with the protocol of
-BASELINE.md section 3 (config 1: bs 8, CE head).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps (wall clock: `value`, `ms_per_step`),
+writes the outputs of the last timed step if `--dump-outputs DIR` is given, and prints the line.  Everything else is
+measured only with `--full`:
+  * per-step HIP-event times (median / p10 / p90) and, for N > 1, the RCCL self-check and the solo pass (`ddp`);
+  * `roofline` for the dominant kernel of the step (largest total time among the MFMA GEMM kernels): algorithmic FLOPs of
+    its launches divided by their durations inside the timed region, measured with HIP events that carry the dispatch's
+    own begin / end timestamps (w2v2_gemm_timed -> hipExtLaunchKernelGGL: the duration rocprofv3 reports for the
+    kernel); `traffic` / `mfma_busy` come from the committed rocprofv3 PMC passes of the same command under profiles/;
+  * `roofline_families` (tail_families), `eer` (eer_leg) and the short legs under `also`, all behind the timed region;
+  * `cpu_baseline`: the CPU oracle (oracle/w2v2_oracle.py, kind "port") on the host cores with the protocol of
+    BASELINE.md section 3 (config 1: bs 8, CE head).
+`--no-cpu-baseline` / `--no-families` / `--no-eer` / `--no-also` drop single legs of a `--full` run.
+
+`--dump-outputs DIR`: DIR/<name>.npy (float32) of what the last timed step handed back (dump_outputs).  Every input is
+seeded, so two builds run with the same arguments can be compared output for output.  The default workload (w2v2-base,
+f16) has no order-dependent reduction on its path and dumps the same bits in every run; --dtype f32, --unfreeze-cnn and
+--model ecapa still reach f32 atomics (split-K products, the layer-0 conv backward, ECAPA) and agree only to rounding.
 """
 import argparse
 import json
@@ -57,6 +68,33 @@ def synth_batch(batch, n_samples, num_speakers, seed, device):
     wav = (wav - mean) / (std + 1e-5)
     label = torch.randint(0, num_speakers, (batch,), generator=g)
     return wav.to(device), label.to(device)
+
+
+DUMP_MAX_ELEMENTS = 1 << 22      # per array (16 MB of float32): the four arrays of a dump stay under 64 MB
+DUMP_WEIGHT_SAMPLE = 1 << 20     # master-weight elements kept by a dump
+
+
+def _seeded_sample(t, n, seed):
+    """n elements of t (flattened) at fixed, seeded, sorted positions: the same positions for the same numel.  Positions
+    are drawn with replacement (cheap for the 10^8-element weight arena), so a sample may hold an element twice."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    idx = torch.randint(0, t.numel(), (n,), generator=g).sort().values
+    return t.reshape(-1)[idx.to(t.device)]
+
+
+def dump_outputs(path, loss, softmax, emb, flat):
+    """--dump-outputs: what the last timed training step handed back -- the loss and the softmax that train_step returns,
+    the pooled embeddings it computed, and the f32 master weights after its optimiser update (a fixed, seeded sample of
+    DUMP_WEIGHT_SAMPLE elements) -- as DIR/<name>.npy in float32.  An array above DUMP_MAX_ELEMENTS is replaced by a fixed,
+    seeded sample of that many elements (flattened)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.reshape(1), "softmax": softmax, "embedding": emb,
+              "weights_sample": _seeded_sample(flat, min(DUMP_WEIGHT_SAMPLE, flat.numel()), 20211)}
+    for i, (name, t) in enumerate(arrays.items()):
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            t = _seeded_sample(t, DUMP_MAX_ELEMENTS, 1000 + i)
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_baseline(batch=8, n_samples=48000, num_speakers=1211):
@@ -275,6 +313,12 @@ def parse_args():
                     help="base = BASELINE configs[1] (the metric's workload); large = configs[3] geometry "
                          "(24 layers, H=1024; use --seconds 5 --batch 32); ecapa = configs[4] (ECAPA-TDNN on 300 x 40 "
                          "filterbank frames, HBM-roofline entry)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-step HIP-event times, the GEMM roofline of the timed region, the "
+                         "tail-family pass, the eval-EER leg, the legs under `also`, the CPU baseline, and for N > 1 the "
+                         "RCCL self-check and the solo pass (--model ecapa: its family / GEMM pass)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, < 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-families", action="store_true", help="skip the tail-family pass (4 extra steps with HIP events, after the timed region)")
     ap.add_argument("--no-eer", action="store_true", help="skip the eval-EER leg (32 synthetic utterances, after the timed region)")
@@ -284,6 +328,8 @@ def parse_args():
     ap.add_argument("--unfreeze-cnn", action="store_true",
                     help="completely_freeze_feature_extractor=False ablation (127.2 GFLOP/utt)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.dtype is None:
         a.dtype = "f32" if a.model == "ecapa" else "f16"
     return a
@@ -362,18 +408,20 @@ def run(args):
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
-        # per-rank confirmation that the collective runs on the GPUs over RCCL: every rank contributes rank + 1
-        chk = torch.full((1024,), float(rank + 1), device=dev)
-        dist.all_reduce(chk)
-        torch.cuda.synchronize()
-        ok = bool((chk == world * (world + 1) / 2).all())
-        flags = [None] * world
-        dist.all_gather_object(flags, {"rank": rank, "device": torch.cuda.get_device_name(local_rank), "allreduce_ok": ok})
-        rccl = {"backend": dist.get_backend(), "ranks": flags}
+        if args.full:
+            # per-rank confirmation that the collective runs on the GPUs over RCCL: every rank contributes rank + 1
+            chk = torch.full((1024,), float(rank + 1), device=dev)
+            dist.all_reduce(chk)
+            torch.cuda.synchronize()
+            ok = bool((chk == world * (world + 1) / 2).all())
+            flags = [None] * world
+            dist.all_gather_object(flags, {"rank": rank, "device": torch.cuda.get_device_name(local_rank), "allreduce_ok": ok})
+            rccl = {"backend": dist.get_backend(), "ranks": flags}
+    dump = (lambda *t: dump_outputs(args.dump_outputs, *t)) if args.dump_outputs and rank == 0 else None
 
     if args.model == "ecapa":
         from tools.ecapa_bench import bench_ecapa
-        bench_ecapa(args, world, rank, dev, dist)
+        bench_ecapa(args, world, rank, dev, dist, dump=dump)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -418,7 +466,7 @@ def run(args):
         trainer.train_step(wav, label)
     sync()
     solo_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         # A 1-GPU figure from the SAME invocation (same box, same thermal state): every rank steps alone -- no
         # collective, same kernels -- for K steps; the data-parallel pass below is then read against it
         # (`ddp.step_time_ratio_vs_solo` = solo / ddp step time = what the overlapped all-reduce costs; the driver
@@ -441,25 +489,36 @@ def run(args):
         sync()
     skipped0 = int(store.scaler[3]) if store.scaler is not None else 0
     ring = ("gemm16_ring_256x128_kernel", "gemm16_phased_256x256_kernel")
-    ops.Gemm.profile_begin(lambda g: g.kernel_name in ring)
+    prof, marks = None, None
+    if args.full:
+        ops.Gemm.profile_begin(lambda g: g.kernel_name in ring)
+        # SURVEY 8(d) timing protocol: besides the wall clock over the K steps (the figure `value` is computed from), one
+        # HIP event per step boundary on the compute stream -> per-step device times, reported as median / p10 / p90
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     n_skip_layers = 0
-    # SURVEY 8(d) timing protocol: besides the wall clock over the K steps (the figure `value` is computed from), one HIP
-    # event per step boundary on the compute stream -> per-step device times, reported as median / p10 / p90
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     step_skips = []
     t0 = time.perf_counter()
-    marks[0].record()
+    if marks:
+        marks[0].record()
     for i in range(args.steps):
-        loss, _ = trainer.train_step(wav, label)
-        marks[i + 1].record()
+        loss, softmax = trainer.train_step(wav, label)
+        if marks:
+            marks[i + 1].record()
         n_skip_layers += len(plan._skip)
         step_skips.append(len(plan._skip))
     sync()
     elapsed = time.perf_counter() - t0
-    step_ms = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)])
-    prof = ops.Gemm.profile_end()
+    if args.full:
+        step_ms = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)])
+        prof = ops.Gemm.profile_end()
+    if dump is not None:
+        dump(loss, softmax, plan.emb, store.flat)
     ddp = None
-    if world > 1:
+    if world > 1 and not args.full:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)                 # the contract: MAX over ranks
+        elapsed = float(t.item())
+    elif world > 1:
         mine = torch.tensor([elapsed, float(np.median(step_ms)), solo_ms, float(n_skip_layers)], dtype=torch.float64,
                             device=dev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -481,17 +540,18 @@ def run(args):
         # LayerDrop: a skipped layer does no forward and no backward work (3 x its forward FLOPs); the expectation is
         # p = 0.05 of the encoder, the figure below uses the layers this rank actually skipped in the timed steps
         done = raw - 3.0 * fl["layer"] * n_skip_layers / args.steps
-        out = {
-            "metric": (f"utterances/sec (w2v2-{args.model} + {args.pooling} + AAM-softmax training step, "
-                       f"{args.seconds:g} s clips)"),
-            "value": round(utt / elapsed, 2), "unit": "utterances/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        per_step = {} if not args.full else {
             "ms_per_step_median": round(float(np.median(step_ms)), 3),
             "ms_per_step_p10": round(float(np.percentile(step_ms, 10)), 3),
             "ms_per_step_p90": round(float(np.percentile(step_ms, 90)), 3),
             "ms_per_step_no_layerdrop_median": (round(float(np.median(step_ms[np.array(step_skips) == 0])), 3)
                                                 if any(k == 0 for k in step_skips) else None),
-            "step_timing": "HIP events on the compute stream at every step boundary (rank 0); ms_per_step = wall clock / K",
+            "step_timing": "HIP events on the compute stream at every step boundary (rank 0); ms_per_step = wall clock / K"}
+        out = {
+            "metric": (f"utterances/sec (w2v2-{args.model} + {args.pooling} + AAM-softmax training step, "
+                       f"{args.seconds:g} s clips)"),
+            "value": round(utt / elapsed, 2), "unit": "utterances/sec", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3), **per_step,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": args.dtype, "data": "synthetic",
             "config": {"workload": f"wav2vec2-{args.model} + AAM-softmax({args.speakers}), {args.pooling} pooling, "
@@ -518,7 +578,7 @@ def run(args):
             out["rccl"] = rccl
         if ddp is not None:
             out["ddp"] = ddp
-        if prof["launches"]:
+        if prof is not None and prof["launches"]:
             desc = {"gemm16_ring_256x128_kernel": "256x128x64 3-stage LDS-DMA ring MFMA GEMM: conv4-6, projection, QKV, "
                                               "out-proj, FFN2 forward + the N<=2304 data-gradient products",
                     "gemm16_phased_256x256_kernel": "256x256x64 phased LDS-DMA MFMA GEMM (two wave groups in anti-phase): conv1-3, "
@@ -573,14 +633,14 @@ def run(args):
             out["roofline"] = entry(*ranked[0])
             if len(ranked) > 1:
                 out["roofline_second_kernel"] = entry(*ranked[1])
-        if world == 1 and not args.no_families and not os.environ.get("W2V2_BENCH_NO_FAMILY_PASS"):
+        if args.full and world == 1 and not args.no_families and not os.environ.get("W2V2_BENCH_NO_FAMILY_PASS"):
             try:
                 out["roofline_families"] = tail_families(trainer, plan, store, wav, label)
             except Exception as ex:          # a side leg must never cost the headline line
                 out["roofline_families"] = {"error": repr(ex)}
-        if world == 1 and args.model == "base" and args.pooling == "mean+std" and not args.no_eer:
+        if args.full and world == 1 and args.model == "base" and args.pooling == "mean+std" and not args.no_eer:
             out["eer"] = eer_leg(store, dev, args.dtype)
-        if world == 1 and args.dtype == "f16" and args.model == "base" and not args.no_also:
+        if args.full and world == 1 and args.dtype == "f16" and args.model == "base" and not args.no_also:
             # Short legs of the same engine on the other BASELINE configurations, so that the driver's line carries them
             # (the headline's step and warm-up counts each; `value` above is untouched by them):
             #   bf16          configs[1] says "bf16"; the headline is fp16 because only fp16 operands keep the embedding
@@ -636,7 +696,7 @@ def run(args):
             try:
                 from types import SimpleNamespace
                 from tools.ecapa_bench import bench_ecapa
-                e = bench_ecapa(SimpleNamespace(batch=66, frames=300, steps=5, warmup=2, dtype="f32"), 1, 0, dev, None,
+                e = bench_ecapa(SimpleNamespace(batch=66, frames=300, steps=5, warmup=2, dtype="f32", full=True), 1, 0, dev, None,
                                 emit=False)
                 also["ecapa_f32_b66"] = {k: e[k] for k in ("ms_per_step", "value", "unit", "steps", "warmup", "dtype", "mfma",
                                                           "model_tflops_per_gpu", "roofline", "roofline_families",
@@ -645,7 +705,7 @@ def run(args):
             except Exception as ex:                    # a side leg must never cost the headline line
                 also["ecapa_f32_b66"] = {"error": repr(ex)}
             out["also"] = also
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

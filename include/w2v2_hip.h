@@ -237,9 +237,15 @@ int w2v2_layernorm_bwd_fold(const w2v2_ln_fold* entries, int n, int M, int H, vo
 int w2v2_dropout(const void* x, void* y, int64_t n, float p, uint64_t seed, int dtype, void* stream);
 /* dx = dy * gelu'(pre)  (exact erf GELU, ACT2FN["gelu"]). */
 int w2v2_gelu_bwd(const void* dy, const void* pre, void* dx, int64_t n, int dtype, void* stream);
-/* dx[m][n] = dy * gelu'(pre) over a dense [M][N] matrix and colsum[n] += sum_m dx[m][n] (f32 atomics, caller zeroes):
- * GELU backward of the positional convolution fused with its bias gradient (HF:360-368).  N % 8 == 0, 16-byte aligned. */
-int w2v2_gelu_bwd_colsum(const void* dy, const void* pre, void* dx, float* colsum, int M, int N, int dtype, void* stream);
+/* Workspace rows of the fixed-order column reductions below: `partial` holds W2V2_PARTIAL_ROWS x (columns) f32; each
+ * row block of the first pass WRITES one row, one w2v2_colsum row block then adds the rows to the target in a fixed
+ * order (no atomics across blocks: the result is bitwise the same in every run). */
+#define W2V2_PARTIAL_ROWS 256
+/* dx[m][n] = dy * gelu'(pre) over a dense [M][N] matrix and colsum[n] += sum_m dx[m][n] (fixed order through `partial`,
+ * caller zeroes): GELU backward of the positional convolution fused with its bias gradient (HF:360-368).  N % 8 == 0,
+ * 16-byte aligned. */
+int w2v2_gelu_bwd_colsum(const void* dy, const void* pre, void* dx, float* colsum, float* partial, int M, int N, int dtype,
+                         void* stream);
 /* y = x + a (gradient joins). */
 int w2v2_add(const void* x, const void* a, void* y, int64_t n, int dtype, void* stream);
 /* out[n] += sum_m x[m][n]   (bias gradients; f32 atomics, caller zeroes). */
@@ -259,14 +265,14 @@ int w2v2_cast(const float* x, void* y, int64_t n, int dtype, void* stream);
 int w2v2_transpose_many(const void* src, void* dst, const int64_t* table, int n, int blocks_per_matrix,
                         int dtype, void* stream);
 /* SpecAugment time mask HF:1290-1292: h[m][:] = embed where mask[m].  Backward: d_embed += sum of
- * masked rows of dh (atomics), masked rows of dh zeroed in place. */
+ * masked rows of dh (fixed order through `partial`, W2V2_PARTIAL_ROWS x H f32), masked rows of dh zeroed in place. */
 int w2v2_mask_fill(void* h, const uint8_t* mask, const float* embed, int M, int H, int dtype,
                    void* stream);
 /* SpecAugment feature mask HF:1294-1304 (`mask_feature_prob`, ref: config/network/wav2vec2_fc.yaml:56): h[b][t][c] = 0
  * where mask[b][c] (mask [B][H] bytes, 8-byte aligned, drawn on the host by the HF sampler AFTER the time mask).  The
  * backward is the same call on the gradient. */
 int w2v2_mask_feature(void* h, const uint8_t* mask, int B, int T, int H, int dtype, void* stream);
-int w2v2_mask_fill_bwd(void* dh, const uint8_t* mask, float* d_embed, int M, int H, int dtype,
+int w2v2_mask_fill_bwd(void* dh, const uint8_t* mask, float* d_embed, float* partial, int M, int H, int dtype,
                        void* stream);
 /* CLS token (ref: src/models/wav2vec2.py:128-140): y[b][0][:] = c, y[b][1+t][:] = x[b][t][:]. */
 int w2v2_prepend_token(const void* x, void* y, float c, int B, int T, int H, int dtype, void* stream);

@@ -1614,6 +1614,42 @@ def test_fused_aam_class_weight_gradient_vs_torch(B, C, E, dtype):
         assert rel_l2(dW2.cpu(), Wr.grad) < 1e-5
 
 
+@pytest.mark.parametrize("M", [9834, 40000])
+def test_pos_conv_bias_and_mask_embed_gradients_are_bitwise_reproducible(M):
+    """The column sums of gelu_bwd_colsum (pos-conv bias gradient) and mask_fill_bwd (masked_spec_embed gradient) go
+    through a fixed-order fold of per-block partial rows: repeated calls on the same inputs give the same bits (the former
+    cross-block atomics did not), and the sums stay within rounding of an f64 reference.  M = 40000 exceeds the 256
+    partial rows mask_fill_bwd can use at 64 rows per block."""
+    o = ops()
+    H = 768
+    dy, pre = rnd(M, H, seed=1).half().to(DEV), rnd(M, H, seed=2, scale=1.5).half().to(DEV)
+    h = rnd(M, H, seed=3).half()
+    mask = (torch.arange(M) % 3 == 0).to(torch.uint8).to(DEV)
+    cs, de = [], []
+    for _ in range(4):
+        dx, c = torch.empty_like(dy), torch.full((H,), 0.25, device=DEV)
+        o.gelu_bwd_colsum(dy, pre, dx, c, M, H)
+        dh, d = h.to(DEV), torch.zeros(H, device=DEV)
+        o.mask_fill_bwd(dh, mask, d)
+        torch.cuda.synchronize()
+        cs.append(c.cpu())
+        de.append(d.cpu())
+    assert all(torch.equal(cs[0], c) for c in cs[1:]) and all(torch.equal(de[0], d) for d in de[1:])
+    # a call on a side stream gets a workspace of its own (no race with the compute stream) and the same bits
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        dx2, c2 = torch.empty_like(dy), torch.full((H,), 0.25, device=DEV)
+        o.gelu_bwd_colsum(dy, pre, dx2, c2, M, H)
+        ws_side = o._partial_workspace(H, dy.device, o.stream())
+    torch.cuda.synchronize()
+    assert ws_side.data_ptr() != o._partial_workspace(H, dy.device, o.stream()).data_ptr()
+    assert torch.equal(c2.cpu(), cs[0])
+    ref = 0.25 + dx.double().sum(0).cpu()
+    assert float((cs[0].double() - ref).abs().max()) < 1e-4 * float(dx.double().abs().sum(0).max()) + 1e-6
+    assert rel_l2(de[0], h.double()[mask.cpu().bool()].sum(0)) < 1e-5
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("M,N", [(9834, 768), (301, 64), (17, 1024)])
 def test_gelu_backward_with_column_sums_in_one_pass(M, N, dtype):

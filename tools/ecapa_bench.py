@@ -77,8 +77,10 @@ class _FamilyTimer:
         return out
 
 
-def bench_ecapa(args, world, rank, dev, dist, emit=True):
-    """emit=False: return the line's dict instead of printing it (bench.py `also.ecapa_f32_b66`)."""
+def bench_ecapa(args, world, rank, dev, dist, emit=True, dump=None):
+    """emit=False: return the line's dict instead of printing it (bench.py `also.ecapa_f32_b66`).  args.full (default
+    True) = run pass 2 (families + GEMM roofline); dump(loss, softmax, embedding, master weights) is called on rank 0 with
+    the last timed step's outputs (bench.py --dump-outputs)."""
     from w2v2_speaker_amd import ops
     from w2v2_speaker_amd.ecapa import EcapaConfig, EcapaPlan, EcapaStore, EcapaTrainer
     from w2v2_speaker_amd.optim.schedule import OneCycle
@@ -132,21 +134,26 @@ def bench_ecapa(args, world, rank, dev, dist, emit=True):
     # pass 1: the timed region of the metric, no per-launch events (they serialise the host against the stream)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = tr.train_step(*next_batch())
+        loss, softmax = tr.train_step(*next_batch())
     sync()
     elapsed = time.perf_counter() - t0
+    if dump is not None and rank == 0:
+        dump(loss, softmax, plan.emb, st.flat)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     # pass 2 (not part of `value`): the same steps with HIP events around the HBM-bound families and the GEMMs
-    psteps = 0 if os.environ.get("W2V2_BENCH_NO_FAMILY_PASS") else min(args.steps, 5)
-    ft.on = True
-    ops.Gemm.profile_begin(lambda gm: True)
-    for _ in range(psteps):
-        tr.train_step(*next_batch())
-    gp = ops.Gemm.profile_end()
-    fam = ft.summary()
+    full = getattr(args, "full", True)
+    psteps = 0 if os.environ.get("W2V2_BENCH_NO_FAMILY_PASS") or not full else min(args.steps, 5)
+    gp, fam = {"launches": 0}, {}
+    if psteps:
+        ft.on = True
+        ops.Gemm.profile_begin(lambda gm: True)
+        for _ in range(psteps):
+            tr.train_step(*next_batch())
+        gp = ops.Gemm.profile_end()
+        fam = ft.summary()
     ft.restore()
     if rank != 0:
         return

@@ -4,11 +4,13 @@
 # every LDS-DMA piece in flight.   bash tools/loop_waits.sh gemm_ring.hip "IDF16_DF16_Lb0E"
 f=$1; pat=${2:-.}
 root=$(dirname "$(dirname "$(realpath "$0")")")
-cd /tmp && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I$root/include -I$root/w2v2_speaker_amd/csrc --cuda-device-only -S $root/w2v2_speaker_amd/csrc/$f -o /tmp/lw.s 2>/dev/null
-python3 - "$pat" <<'P'
+# a private scratch folder: a fixed file name in the shared temp folder collides with another user's (or run's) file
+tmp=$(mktemp -d); trap 'rm -rf "$tmp"' EXIT
+cd "$tmp" && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I$root/include -I$root/w2v2_speaker_amd/csrc --cuda-device-only -S $root/w2v2_speaker_amd/csrc/$f -o "$tmp/lw.s" 2>/dev/null
+python3 - "$pat" "$tmp/lw.s" <<'P'
 import re,sys
 pat=sys.argv[1]
-lines=open('/tmp/lw.s').read().split('\n')
+lines=open(sys.argv[2]).read().split('\n')
 cur=None; inasm=False; out={}
 for i,l in enumerate(lines):
     m=re.match(r'^(_Z\w+):',l)

@@ -38,6 +38,6 @@ if [ -z "$MODEL" ]; then
   cd $OLDPWD
 fi
 unset W2V2_BENCH_NO_FAMILY_PASS
-python3 bench.py $MODEL > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_err.log
+python3 bench.py --full $MODEL > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_err.log
 tail -c 600 $OUT/${TAG}_bench_line.json
 head -30 $OUT/${TAG}_kernel_stats.txt

@@ -26,7 +26,7 @@ for R in 0 8 16; do
     for N in 1 2 4 8; do
       [ "$N" -gt "$MAXG" ] && continue
       [ "$N" = 1 ] && [ "$CH" != 8 ] && continue          # the channel cap is irrelevant without a collective
-      LINE=$(W2V2_RESERVE_CUS=$R NCCL_MAX_NCHANNELS=$CH python3 bench.py --gpus $N --steps $STEPS --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1)
+      LINE=$(W2V2_RESERVE_CUS=$R NCCL_MAX_NCHANNELS=$CH python3 bench.py --gpus $N --steps $STEPS --warmup 5 --full --no-cpu-baseline 2>/dev/null | tail -1)
       # a line whose rccl.ranks does not list N answering ranks (or a failed all-reduce check) stops the sweep
       V=$(echo "$LINE" | python3 -c "
 import sys, json

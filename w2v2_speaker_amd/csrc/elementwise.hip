@@ -81,7 +81,7 @@ extern "C" int w2v2_gelu_bwd(const void* dy, const void* pre, void* dx, int64_t 
 // 32 column lanes x 8 columns and 8 row lanes per workgroup, rows strided over grid.y, two rows in flight per thread.
 template <typename T>
 __global__ __launch_bounds__(256) void gelu_bwd_colsum_kernel(const T* __restrict__ dy, const T* __restrict__ pre,
-                                                              T* __restrict__ dx, float* __restrict__ out, int M, int N) {
+                                                              T* __restrict__ dx, float* __restrict__ partial, int M, int N) {
   __shared__ float red[8][32 * 8];
   const int tx = threadIdx.x, ty = threadIdx.y;
   const int col = (blockIdx.x * 32 + tx) * 8;
@@ -119,24 +119,25 @@ __global__ __launch_bounds__(256) void gelu_bwd_colsum_kernel(const T* __restric
     float s = 0.f;
 #pragma unroll
     for (int r = 0; r < 8; ++r) s += red[r][t];
-    unsafeAtomicAdd(out + c, s);
+    partial[(int64_t)blockIdx.y * N + c] = s;       // row blockIdx.y of the partials: folded in a fixed order by colsum
   }
 }
 
-extern "C" int w2v2_gelu_bwd_colsum(const void* dy, const void* pre, void* dx, float* colsum, int M, int N, int dtype,
-                                    void* stream) {
-  W2V2_REQUIRE(dy && pre && dx && colsum && M >= 0 && N > 0, "gelu_bwd_colsum: bad arguments");
+extern "C" int w2v2_gelu_bwd_colsum(const void* dy, const void* pre, void* dx, float* colsum, float* partial, int M, int N,
+                                    int dtype, void* stream) {
+  W2V2_REQUIRE(dy && pre && dx && colsum && partial && M >= 0 && N > 0, "gelu_bwd_colsum: bad arguments");
   W2V2_REQUIRE(N % 8 == 0 && (((uintptr_t)dy | (uintptr_t)pre | (uintptr_t)dx) & 15) == 0,
                "gelu_bwd_colsum: N must be a multiple of 8 and the matrices 16-byte aligned");
   if (M == 0) return 0;
   int gy = (int)cdiv(M, 8 * 8);
-  if (gy > 160) gy = 160;
+  if (gy > 160) gy = 160;            // <= W2V2_PARTIAL_ROWS rows of partials
   dim3 grid((unsigned)cdiv(N, 32 * 8), gy), block(32, 8);
   W2V2_DISPATCH_ACT(dtype, "gelu_bwd_colsum",
     hipLaunchKernelGGL(gelu_bwd_colsum_kernel<AT>, grid, block, 0, as_stream(stream), (const AT*)dy, (const AT*)pre, (AT*)dx,
-                       colsum, M, N););
+                       partial, M, N););
   W2V2_CHECK_LAUNCH("gelu_bwd_colsum");
-  return 0;
+  // gy <= 256 partial rows: colsum runs ONE row block, one add per column in a fixed order (bitwise reproducible)
+  return w2v2_colsum(partial, N, colsum, gy, N, W2V2_F32, stream);
 }
 extern "C" int w2v2_add(const void* x, const void* a, void* y, int64_t n, int dtype, void* stream) {
   return launch_binary<1>(x, a, y, n, dtype, stream, "add");
@@ -319,11 +320,11 @@ __global__ void mask_fill_kernel(T* __restrict__ h, const uint8_t* __restrict__ 
 }
 
 // d_embed[c] += sum over masked rows of dh[m][c]; masked rows zeroed.  32 row lanes x 8 column lanes
-// (64 columns) per block; per-block LDS reduction, then ONE atomic per column per block (a naive
-// per-element atomicAdd serialises ~1300 rows on the same 768 addresses: 0.25 ms).
+// (64 columns) per block; per-block LDS reduction into row blockIdx.y of `partial`, which w2v2_colsum then folds in a
+// fixed order (atomics across blocks made the gradient differ from run to run in its last bits).
 template <typename T>
 __global__ __launch_bounds__(256) void mask_fill_bwd_kernel(T* __restrict__ dh, const uint8_t* __restrict__ mask,
-                                                            float* __restrict__ d_embed, int M, int H) {
+                                                            float* __restrict__ partial, int M, int H) {
   __shared__ float red[32][64];
   const int cl = threadIdx.x & 7, rl = threadIdx.x >> 3;
   const int col = blockIdx.x * 64 + cl * 8;
@@ -345,7 +346,7 @@ __global__ __launch_bounds__(256) void mask_fill_bwd_kernel(T* __restrict__ dh, 
     float s = 0.f;
     for (int r = 0; r < 32; ++r) s += red[r][threadIdx.x];
     const int c = blockIdx.x * 64 + threadIdx.x;
-    if (c < H && s != 0.f) unsafeAtomicAdd(d_embed + c, s);
+    if (c < H) partial[(int64_t)blockIdx.y * H + c] = s;
   }
 }
 
@@ -389,16 +390,18 @@ extern "C" int w2v2_mask_fill(void* h, const uint8_t* mask, const float* embed, 
   return 0;
 }
 
-extern "C" int w2v2_mask_fill_bwd(void* dh, const uint8_t* mask, float* d_embed, int M, int H, int dtype, void* stream) {
-  W2V2_REQUIRE(dh && mask && d_embed && H % 8 == 0, "mask_fill_bwd: bad arguments");
+extern "C" int w2v2_mask_fill_bwd(void* dh, const uint8_t* mask, float* d_embed, float* partial, int M, int H, int dtype,
+                                  void* stream) {
+  W2V2_REQUIRE(dh && mask && d_embed && partial && H % 8 == 0, "mask_fill_bwd: bad arguments");
   if (M <= 0) return 0;
   int gy = (int)cdiv(M, 32 * 2);          // two rows per thread: the mask test + load of a row is a dependent chain
   if (gy < 1) gy = 1;
+  if (gy > W2V2_PARTIAL_ROWS) gy = W2V2_PARTIAL_ROWS;     // rows are strided over grid.y: fewer blocks walk more rows
   dim3 grid((unsigned)cdiv(H, 64), gy);
   W2V2_DISPATCH_ACT(dtype, "mask_fill_bwd",
-    hipLaunchKernelGGL(mask_fill_bwd_kernel<AT>, grid, dim3(256), 0, as_stream(stream), (AT*)dh, mask, d_embed, M, H););
+    hipLaunchKernelGGL(mask_fill_bwd_kernel<AT>, grid, dim3(256), 0, as_stream(stream), (AT*)dh, mask, partial, M, H););
   W2V2_CHECK_LAUNCH("mask_fill_bwd");
-  return 0;
+  return w2v2_colsum(partial, H, d_embed, gy, H, W2V2_F32, stream);      // one row block: fixed order, one add per column
 }
 
 // ------------------------------------------------------------------------------------- CLS token

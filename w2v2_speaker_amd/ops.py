@@ -379,11 +379,27 @@ def gelu_bwd(dy, pre, dx) -> None:
                "gelu_bwd")
 
 
+PARTIAL_ROWS = 256              # W2V2_PARTIAL_ROWS (include/w2v2_hip.h): rows of a fixed-order column-sum workspace
+_PARTIAL_WS = {}
+
+
+def _partial_workspace(N: int, device, st: int) -> torch.Tensor:
+    """[PARTIAL_ROWS, N] f32 partial column sums of gelu_bwd_colsum / mask_fill_bwd: one per (N, device, stream st).  Calls
+    on one stream share it safely (the fold that reads it is enqueued before the next call can write it); a call on
+    another stream gets a workspace of its own, so two streams never race on one."""
+    key = (N, str(device), st)
+    if key not in _PARTIAL_WS:
+        _PARTIAL_WS[key] = torch.empty(PARTIAL_ROWS * N, dtype=torch.float32, device=device)
+    return _PARTIAL_WS[key]
+
+
 def gelu_bwd_colsum(dy, pre, dx, colsum_out, M: int, N: int) -> None:
-    """dx = dy * gelu'(pre) over [M, N] and colsum_out[n] += sum_m dx[m, n] in one pass."""
+    """dx = dy * gelu'(pre) over [M, N] and colsum_out[n] += sum_m dx[m, n] (fixed order: bitwise reproducible)."""
     _dev(dy, pre, dx, colsum_out)
-    _lib.check(lib().w2v2_gelu_bwd_colsum(dy.data_ptr(), pre.data_ptr(), dx.data_ptr(), colsum_out.data_ptr(), M, N,
-                                          dt(dy), stream()), "gelu_bwd_colsum")
+    st = stream()
+    ws = _partial_workspace(N, dy.device, st)
+    _lib.check(lib().w2v2_gelu_bwd_colsum(dy.data_ptr(), pre.data_ptr(), dx.data_ptr(), colsum_out.data_ptr(),
+                                          ws.data_ptr(), M, N, dt(dy), st), "gelu_bwd_colsum")
 
 
 def add(x, a, y) -> None:
@@ -441,8 +457,10 @@ def mask_feature(h, mask_u8, B: int, T: int) -> None:
 def mask_fill_bwd(dh, mask_u8, d_embed) -> None:
     _dev(dh, mask_u8, d_embed)
     H = dh.shape[-1]
-    _lib.check(lib().w2v2_mask_fill_bwd(dh.data_ptr(), mask_u8.data_ptr(), d_embed.data_ptr(), dh.numel() // H, H,
-                                        dt(dh), stream()), "mask_fill_bwd")
+    st = stream()
+    ws = _partial_workspace(H, dh.device, st)
+    _lib.check(lib().w2v2_mask_fill_bwd(dh.data_ptr(), mask_u8.data_ptr(), d_embed.data_ptr(), ws.data_ptr(),
+                                        dh.numel() // H, H, dt(dh), st), "mask_fill_bwd")
 
 
 def prepend_token(x, y, c: float) -> None:
