@@ -177,6 +177,15 @@ int w2v2_conv0_stats(const float* wav, const float* w /*[C][k]*/, float* partial
  * W2V2_CONV0_NO_GRAM=1 keeps the convolution-based statistics (A/B). */
 int w2v2_conv0_stats_mfma(const float* wav, const float* w, float* partial, float* mean_rstd,
                           int B, int N, int C, int k, int stride, float eps, void* stream);
+/* Variable-length batch (evaluation): frames = device int32[B], 1 <= frames[b] <= L, the valid conv-0 frames of each
+ * utterance.  Statistics of utterance b over its first frames[b] frames only (chunks past the end skipped, the
+ * straddling chunk counts its valid frames, the fold divides by frames[b]): bit-identical to the plain entry on the
+ * utterance alone (B = 1, its own length), same workspace.  The _mfma form covers the window-moment path (k == 10);
+ * its convolution-statistics branch (k != 10 or W2V2_CONV0_NO_GRAM) returns an error. */
+int w2v2_conv0_stats_len(const float* wav, const float* w, float* partial, float* mean_rstd, const int* frames,
+                         int B, int N, int C, int k, int stride, float eps, void* stream);
+int w2v2_conv0_stats_mfma_len(const float* wav, const float* w, float* partial, float* mean_rstd, const int* frames,
+                              int B, int N, int C, int k, int stride, float eps, void* stream);
 int w2v2_conv0_apply(const float* wav, const float* w, const float* mean_rstd, const float* gamma,
                      const float* beta, void* y, int dtype, int B, int N, int C, int k, int stride,
                      void* stream);
@@ -290,6 +299,10 @@ int w2v2_prepend_token(const void* x, void* y, float c, int B, int T, int H, int
  * reproducible packed weights). */
 int w2v2_posconv_regroup(const void* x, void* xg, int B, int T, int H, int G, int K, int pad_left,
                          int dtype, void* stream);
+/* Variable-length batch: as w2v2_posconv_regroup, with frames t >= lens[b] (device int32[B], 1 <= lens[b] <= T)
+ * written as zeros -- the zero padding Conv1d(padding = K/2) gives the utterance alone. */
+int w2v2_posconv_regroup_len(const void* x, void* xg, const int* lens, int B, int T, int H, int G, int K, int pad_left,
+                             int dtype, void* stream);
 /* Weight gradient of the grouped positional conv as a correlation on the matrix cores (replaces the implicit-GEMM
  * call for 16-bit activations): dY [B*T, H] = gradient at the conv output (before the weight-norm), xg [B, G, T+K-1, H/G]
  * = posconv_regroup(x, pad_left = K/2); dwf [G][K*Cg][Cg] f32 is OVERWRITTEN (row (tap, ci), column co).
@@ -322,6 +335,11 @@ int w2v2_softmax_fwd(const float* s, void* p, void* p_drop, int64_t rows, int T,
                      float drop_p, uint64_t seed, int dtype, void* stream);
 int w2v2_softmax_bwd(const float* dp_drop, const void* p, void* ds, int64_t rows, int T, int64_t ld,
                      float drop_p, uint64_t seed, int dtype, void* stream);
+/* Variable-length batch, eval (no dropout): rows = B * heads * T; row r is query r % T of utterance r / (heads * T),
+ * normalised over its keys < lens[b] (device int32[B], 1 <= lens[b] <= T), p = 0 for the other keys, all-zero rows
+ * for queries >= lens[b].  Valid rows bit-identical to w2v2_softmax_fwd at T = lens[b]. */
+int w2v2_softmax_fwd_len(const float* s, void* p, const int* lens, int B, int heads, int T, int64_t ld, int dtype,
+                         void* stream);
 /* Fused multi-head self-attention over QKV [B,T,3,heads,d] (HF:438-548 minus the projections),
  * one workgroup per (batch, head, query tile); saves row log-sum-exp for the backward.
  * ctx [B,T,heads*d].  bwd writes dqkv [B,T,3,heads,d]. */
@@ -330,6 +348,12 @@ int w2v2_attention_fwd(const void* qkv, void* ctx, float* lse, int B, int T, int
 int w2v2_attention_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse,
                        void* dqkv, float* delta /*[B,heads,T] scratch*/, int B, int T, int heads,
                        int d, float scale, float drop_p, uint64_t seed, int dtype, void* stream);
+/* Variable-length batch, eval (no dropout): the fused forward with the per-utterance bound lens[b] (device int32[B],
+ * 1 <= lens[b] <= T) in place of T; buffers keep the row stride of T.  Key / value rows >= lens[b] never enter the
+ * arithmetic, ctx rows >= lens[b] are written as zeros, lse is written for rows < lens[b].  With the geometry forced
+ * (W2V2_ATTN_GEOM), valid rows are bit-identical to w2v2_attention_fwd on the utterance alone at T = lens[b]. */
+int w2v2_attention_fwd_len(const void* qkv, void* ctx, float* lse, const int* lens, int B, int T, int heads, int d,
+                           float scale, int dtype, void* stream);
 
 /* -------------------------------------------------------------------------------------- pooling
  * ref: src/layers/pooling.py:24-44,74-80,118-136.  x [B,T,H] act dtype -> out f32.
@@ -341,6 +365,10 @@ int w2v2_attention_bwd(const void* qkv, const void* ctx, const void* dctx, const
  * mode 16 + t: frame t -> [B,H]  (IndexPool1D "random", ref: src/layers/pooling.py:125-126,150-154: the HOST draws t
  *         with random.randint like the reference; NoPooling, :160-166, is the same call on the [B*T, 1, H] view) */
 int w2v2_pool_fwd(const void* x, float* out, int B, int T, int H, int mode, int dtype, void* stream);
+/* Variable-length batch: modes 0-5 over the first lens[b] frames (device int32[B], 1 <= lens[b] <= T) of each
+ * utterance, rows strided by T; bit-identical to w2v2_pool_fwd on the [1, lens[b], H] slice. */
+int w2v2_pool_fwd_len(const void* x, float* out, const int* lens, int B, int T, int H, int mode, int dtype,
+                      void* stream);
 /* dx [B,T,H] act dtype from dout f32 and the forward output (std/mean reused; max needs x). */
 int w2v2_pool_bwd(const void* x, const float* out, const float* dout, void* dx, int B, int T, int H,
                   int mode, int dtype, void* stream);

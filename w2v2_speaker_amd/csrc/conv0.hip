@@ -86,6 +86,60 @@ __global__ void conv0_finalize_kernel(const float* __restrict__ partial, float* 
   mr[(int64_t)i * 2 + 1] = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps));
 }
 
+// Variable-length batch: utterance b has frames[b] valid frames.  Chunks past its end are skipped, the chunk that
+// straddles it counts its valid frames only, and the finalize folds the first cdiv(frames[b], C0_FRAMES) partials in
+// chunk order and divides by frames[b]: the same sums in the same order as conv0_kernel<float, false> + finalize on the
+// utterance alone, because the chunking starts at frame 0 in both.
+__global__ __launch_bounds__(256) void conv0_stats_len_kernel(const float* __restrict__ wav, const float* __restrict__ w,
+                                                              float* __restrict__ partial, const int* __restrict__ frames,
+                                                              int N, int C, int k, int stride) {
+  extern __shared__ float xs[];
+  const int b = blockIdx.y;
+  const int l0 = blockIdx.x * C0_FRAMES;
+  const int nf = min(C0_FRAMES, frames[b] - l0);
+  if (nf <= 0) return;                               // uniform: the whole chunk lies past the end of the utterance
+  const int nsamp = (nf - 1) * stride + k;
+  const float* src = wav + (int64_t)b * N + (int64_t)l0 * stride;
+  for (int i = threadIdx.x; i < nsamp; i += 256) xs[i] = src[i];
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float wr[C0_MAXK];
+#pragma unroll
+    for (int j = 0; j < C0_MAXK; ++j) wr[j] = j < k ? w[c * k + j] : 0.f;
+    float s1 = 0.f, s2 = 0.f;
+    for (int f = 0; f < nf; ++f) {
+      const float* xp = xs + f * stride;
+      float acc = 0.f;
+#pragma unroll
+      for (int j = 0; j < C0_MAXK; ++j)
+        if (j < k) acc = fmaf(wr[j], xp[j], acc);
+      s1 += acc;
+      s2 = fmaf(acc, acc, s2);
+    }
+    float* pt = partial + (((int64_t)b * gridDim.x + blockIdx.x) * C + c) * 2;
+    pt[0] = s1;
+    pt[1] = s2;
+  }
+}
+
+__global__ void conv0_finalize_len_kernel(const float* __restrict__ partial, float* __restrict__ mr,
+                                          const int* __restrict__ frames, int B, int C, int nchunk, float eps) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * C) return;
+  const int b = i / C, c = i - b * C;
+  const int L = frames[b], nc = (L + C0_FRAMES - 1) / C0_FRAMES;
+  double s1 = 0.0, s2 = 0.0;
+  for (int j = 0; j < nc; ++j) {
+    const float* pt = partial + (((int64_t)b * nchunk + j) * C + c) * 2;
+    s1 += (double)pt[0];
+    s2 += (double)pt[1];
+  }
+  const double mu = s1 / (double)L;
+  const double var = s2 / (double)L - mu * mu;
+  mr[(int64_t)i * 2] = (float)mu;
+  mr[(int64_t)i * 2 + 1] = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps));
+}
+
 // ------------------------------------------------------------------------------ matrix-core variant (bf16 activations)
 // The VALU kernel above spends 10 FMA + 10 LDS broadcasts per output on the convolution and stores 2 bytes per
 // lane.  Here the convolution of 16 frames x 16 channels is ONE v_mfma_f32_16x16x32_bf16 with f32-class accuracy:
@@ -339,6 +393,84 @@ __global__ __launch_bounds__(256) void conv0_gram_finalize_kernel(const double* 
     mr[((int64_t)b * C + c) * 2 + 1] = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps));
   }
 }
+// Variable-length forms of the two window-moment kernels: blocks past the end of utterance b are skipped, the block that
+// straddles it counts its valid frames, the finalize folds the first cdiv(frames[b], fpb) partials and divides by
+// frames[b] -- the same sums in the same order as the two kernels above on the utterance alone.
+template <int K>
+__global__ __launch_bounds__(64) void conv0_gram_len_kernel(const float* __restrict__ wav, double* __restrict__ partial,
+                                                            const int* __restrict__ frames, int N, int stride,
+                                                            int fpb) {
+  constexpr int NR = K * (K + 1) / 2, NV = K + NR;
+  extern __shared__ float xs[];                      // the block's samples: (fpb - 1) * stride + K floats
+  __shared__ double red[NV][65];                     // (pitch 65: the fold below reads a row per lane)
+  const int b = blockIdx.y;
+  const int f0 = blockIdx.x * fpb;                   // frames [f0, f0 + nf) of utterance b; one wave per block
+  const int nf = min(fpb, frames[b] - f0);
+  if (nf <= 0) return;                               // uniform: a block past the end writes nothing (never read)
+  const float* src = wav + (int64_t)b * N + (int64_t)f0 * stride;
+  const int nsamp = (nf - 1) * stride + K;
+  for (int i = threadIdx.x; i < nsamp; i += 64) xs[i] = src[i];
+  __syncthreads();
+  double acc[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) acc[i] = 0.0;
+  for (int f = threadIdx.x; f < nf; f += 64) {       // lanes `stride` floats apart: conflict-free LDS reads for odd strides
+    float x[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) x[j] = xs[f * stride + j];
+    int idx = K;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      acc[j] += (double)x[j];
+#pragma unroll
+      for (int j2 = j; j2 < K; ++j2) acc[idx++] += (double)x[j] * (double)x[j2];
+    }
+  }
+  // fold over the 64 lanes in lane order through LDS (a shuffle tree costs 2 x 6 ds_bpermute per value: 780 per wave)
+#pragma unroll
+  for (int i = 0; i < NV; ++i) red[i][threadIdx.x] = acc[i];
+  __syncthreads();
+  for (int i = threadIdx.x; i < NV; i += 64) {
+    double v = 0.0;
+    for (int j = 0; j < 64; ++j) v += red[i][j];
+    partial[((int64_t)b * gridDim.x + blockIdx.x) * NV + i] = v;
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void conv0_gram_finalize_len_kernel(const double* __restrict__ partial,
+                                                                      const float* __restrict__ w,
+                                                                      float* __restrict__ mr,
+                                                                      const int* __restrict__ frames, int C, int nblk,
+                                                                      int fpb, float eps) {
+  constexpr int NR = K * (K + 1) / 2, NV = K + NR;
+  __shared__ double G[NV];
+  const int b = blockIdx.x;
+  const int L = frames[b], nb = (L + fpb - 1) / fpb;  // the first nb partials of the utterance, in block order
+  if (threadIdx.x < NV) {
+    double v = 0.0;
+    for (int j = 0; j < nb; ++j) v += partial[((int64_t)b * nblk + j) * NV + threadIdx.x];
+    G[threadIdx.x] = v;
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    double wr[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) wr[j] = (double)w[c * K + j];
+    double s1 = 0.0, s2 = 0.0;
+    int idx = K;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      s1 += wr[j] * G[j];
+#pragma unroll
+      for (int j2 = j; j2 < K; ++j2) s2 += (j2 == j ? 1.0 : 2.0) * wr[j] * wr[j2] * G[idx++];
+    }
+    const double mu = s1 / (double)L;
+    const double var = s2 / (double)L - mu * mu;
+    mr[((int64_t)b * C + c) * 2] = (float)mu;
+    mr[((int64_t)b * C + c) * 2 + 1] = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps));
+  }
+}
 constexpr int C0_GRAM_FRAMES = 640;     // frames per workgroup of the window-moment kernel
 
 extern "C" int w2v2_conv0_workspace_floats(int N, int C, int k, int stride);
@@ -399,6 +531,49 @@ extern "C" int w2v2_conv0_stats_mfma(const float* wav, const float* w, float* pa
   hipLaunchKernelGGL(conv0_finalize_kernel, dim3((unsigned)cdiv((int64_t)B * C, 256)), dim3(256), 0,
                      as_stream(stream), partial, mean_rstd, B, C, nchunk, L, eps);
   W2V2_CHECK_LAUNCH("conv0_stats_mfma");
+  return 0;
+}
+
+// Variable-length forms of the two statistics entries (frames = device int32[B], 1 <= frames[b] <= L): the statistics of
+// utterance b over its first frames[b] frames, bit-identical to the plain entry on the utterance alone.  The 16-bit path
+// covers the window-moment kernel (k = 10); the split-bf16 convolution statistics branch has no length-aware form.
+extern "C" int w2v2_conv0_stats_len(const float* wav, const float* w, float* partial, float* mean_rstd,
+                                    const int* frames, int B, int N, int C, int k, int stride, float eps, void* stream) {
+  if (conv0_check("conv0_stats_len", B, N, C, k, stride)) return -1;
+  W2V2_REQUIRE(wav && w && partial && mean_rstd && frames, "conv0_stats_len: null pointer");
+  const int L = (N - k) / stride + 1;
+  const int nchunk = (int)cdiv(L, C0_FRAMES);
+  const size_t lds = ((size_t)(C0_FRAMES - 1) * stride + k) * sizeof(float);
+  hipLaunchKernelGGL(conv0_stats_len_kernel, dim3((unsigned)nchunk, B), dim3(256), lds, as_stream(stream), wav, w,
+                     partial, frames, N, C, k, stride);
+  hipLaunchKernelGGL(conv0_finalize_len_kernel, dim3((unsigned)cdiv((int64_t)B * C, 256)), dim3(256), 0,
+                     as_stream(stream), partial, mean_rstd, frames, B, C, nchunk, eps);
+  W2V2_CHECK_LAUNCH("conv0_stats_len");
+  return 0;
+}
+
+extern "C" int w2v2_conv0_stats_mfma_len(const float* wav, const float* w, float* partial, float* mean_rstd,
+                                         const int* frames, int B, int N, int C, int k, int stride, float eps,
+                                         void* stream) {
+  if (!conv0_mfma_ok(C, k))
+    return w2v2_conv0_stats_len(wav, w, partial, mean_rstd, frames, B, N, C, k, stride, eps, stream);
+  if (conv0_check("conv0_stats_mfma_len", B, N, C, k, stride)) return -1;
+  W2V2_REQUIRE(wav && w && partial && mean_rstd && frames, "conv0_stats_mfma_len: null pointer");
+  static const bool no_gram = getenv("W2V2_CONV0_NO_GRAM") != nullptr;
+  W2V2_REQUIRE(k == 10 && !no_gram,
+               "conv0_stats_mfma_len: variable lengths need the window-moment statistics (k = 10, W2V2_CONV0_NO_GRAM unset)");
+  const int L = (N - k) / stride + 1;
+  const int nblk = (int)cdiv(L, C0_GRAM_FRAMES);
+  double* gp = reinterpret_cast<double*>(partial);
+  const size_t lds = ((size_t)(C0_GRAM_FRAMES - 1) * stride + 10) * sizeof(float);
+  W2V2_REQUIRE(lds <= 64 * 1024, "conv0_stats_mfma_len: stride %d too large for the window-moment kernel", stride);
+  W2V2_REQUIRE((int64_t)nblk * 130 <= (int64_t)w2v2_conv0_workspace_floats(N, C, k, stride),
+               "conv0_stats_mfma_len: workspace too small for %d window-moment blocks", nblk);
+  hipLaunchKernelGGL((conv0_gram_len_kernel<10>), dim3((unsigned)nblk, B), dim3(64), lds, as_stream(stream), wav, gp,
+                     frames, N, stride, C0_GRAM_FRAMES);
+  hipLaunchKernelGGL((conv0_gram_finalize_len_kernel<10>), dim3(B), dim3(256), 0, as_stream(stream), (const double*)gp,
+                     w, mean_rstd, frames, C, nblk, C0_GRAM_FRAMES, eps);
+  W2V2_CHECK_LAUNCH("conv0_stats_mfma_len");
   return 0;
 }
 

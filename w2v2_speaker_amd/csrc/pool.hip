@@ -75,6 +75,80 @@ __global__ __launch_bounds__(256) void pool_meanstd_kernel(const T* __restrict__
   }
 }
 
+// Variable-length batch: pool_meanstd_kernel over the first lens[b] frames of utterance b
+template <typename T>
+__global__ __launch_bounds__(256) void pool_meanstd_len_kernel(const T* __restrict__ x, float* __restrict__ out,
+                                                               const int* __restrict__ lens, int Tn, int H,
+                                                               int with_std) {
+  __shared__ float red[4][16][8];
+  __shared__ float meanv[16][8];
+  const int b = blockIdx.y;
+  const T* xb = x + (int64_t)b * Tn * H;
+  Tn = lens[b];                                           // frames pooled; rows keep the padded stride
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int cl = lane & 15, tl = (lane >> 4) + 4 * wave;  // column lane, time lane (0..15)
+  const int col = (blockIdx.x * 16 + cl) * 8;
+  const bool active = col < H;
+  xb += col;
+  float acc[8] = {};
+  if (active)
+    for (int t = tl; t < Tn; t += 16) {
+      Vec8<T> v;
+      v.load(xb + (int64_t)t * H);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += v.v[e];
+    }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    acc[e] += __shfl_xor(acc[e], 16, 64);
+    acc[e] += __shfl_xor(acc[e], 32, 64);
+  }
+  if (lane < 16)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[wave][cl][e] = acc[e];
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    const int c = threadIdx.x >> 3, e = threadIdx.x & 7;
+    meanv[c][e] = (red[0][c][e] + red[1][c][e] + red[2][c][e] + red[3][c][e]) / (float)Tn;
+  }
+  __syncthreads();
+  float mu[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) mu[e] = meanv[cl][e];
+  const int mean_off = with_std ? H : 0;
+  const int ostride = with_std ? 2 * H : H;
+  if (active && wave == 0 && lane < 16)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) out[(int64_t)b * ostride + mean_off + col + e] = mu[e];
+  if (!with_std) return;
+  float sq[8] = {};
+  if (active)
+    for (int t = tl; t < Tn; t += 16) {
+      Vec8<T> v;
+      v.load(xb + (int64_t)t * H);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { const float d = v.v[e] - mu[e]; sq[e] = fmaf(d, d, sq[e]); }
+    }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    sq[e] += __shfl_xor(sq[e], 16, 64);
+    sq[e] += __shfl_xor(sq[e], 32, 64);
+  }
+  __syncthreads();
+  if (lane < 16)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[wave][cl][e] = sq[e];
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    const int c = threadIdx.x >> 3, e = threadIdx.x & 7;
+    const int cc = (blockIdx.x * 16 + c) * 8 + e;
+    if (cc < H) {
+      const float m2 = red[0][c][e] + red[1][c][e] + red[2][c][e] + red[3][c][e];
+      out[(int64_t)b * ostride + cc] = sqrtf(m2 / (float)(Tn - 1));  // unbiased; T == 1 -> NaN like torch
+    }
+  }
+}
+
 // dx = dmean/T + dstd * (x - mean) / ((T-1) * std)
 template <typename T>
 __global__ void pool_meanstd_bwd_kernel(const T* __restrict__ x, const float* __restrict__ out,
@@ -125,6 +199,21 @@ __global__ void pool_select_kernel(const T* __restrict__ x, float* __restrict__ 
   } else {
     r = to_f32<T>(xb[(int64_t)(Tn - 1) * H]);
   }
+  out[i] = r;
+}
+
+// max / first / last over the first lens[b] frames (middle = last, ref: pooling.py), same order as pool_select_kernel
+template <typename T>
+__global__ void pool_select_len_kernel(const T* __restrict__ x, float* __restrict__ out, const int* __restrict__ lens,
+                                       int B, int Tn, int H, int mode) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * H) return;
+  const int b = (int)(i / H), c = (int)(i - (int64_t)b * H);
+  const int Lb = lens[b];
+  const T* xb = x + (int64_t)b * Tn * H + c;
+  float r = to_f32<T>(xb[mode == 4 ? (int64_t)(Lb - 1) * H : 0]);
+  if (mode == 2)
+    for (int t = 1; t < Lb; ++t) r = fmaxf(r, to_f32<T>(xb[(int64_t)t * H]));
   out[i] = r;
 }
 
@@ -236,6 +325,25 @@ __global__ void pool_quantile_kernel(const T* __restrict__ x, float* __restrict_
 }
 
 template <typename T>
+__global__ void pool_quantile_len_kernel(const T* __restrict__ x, float* __restrict__ out, const int* __restrict__ lens,
+                                         int B, int Tn, int H) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * H) return;
+  const int b = (int)(i / H), c = (int)(i - (int64_t)b * H);
+  const int Lb = lens[b];
+  const T* xb = x + (int64_t)b * Tn * H + c;
+  const QRanks r = quantile_ranks(Lb);
+  uint32_t key[QN];
+  select_keys<T>(xb, Lb, H, r.k, key);
+  float* ob = out + (int64_t)b * 5 * H + c;
+  ob[0] = key_value(key[0]);
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+    ob[(int64_t)(q + 1) * H] = lerp_torch(key_value(key[1 + 2 * q]), key_value(key[2 + 2 * q]), r.w[q]);
+  ob[(int64_t)4 * H] = key_value(key[7]);
+}
+
+template <typename T>
 __global__ void pool_quantile_bwd_kernel(const T* __restrict__ x, const float* __restrict__ dout, T* __restrict__ dx,
                                          int B, int Tn, int H) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -331,5 +439,29 @@ extern "C" int w2v2_pool_bwd(const void* x, const float* out, const float* dout,
                          B, T, H, mode););
   }
   W2V2_CHECK_LAUNCH("pool_bwd");
+  return 0;
+}
+
+extern "C" int w2v2_pool_fwd_len(const void* x, float* out, const int* lens, int B, int T, int H, int mode, int dtype,
+                                 void* stream) {
+  W2V2_REQUIRE(x && out && lens && B > 0 && T > 0 && H > 0 && mode >= 0 && mode <= 5,
+               "pool_fwd_len: bad arguments (mode %d, T %d; the frame-index mode has no length-aware form)", mode, T);
+  hipStream_t st = as_stream(stream);
+  if (mode == 5) {
+    dim3 grid((unsigned)cdiv((int64_t)B * H, 64));
+    W2V2_DISPATCH_ACT(dtype, "pool_fwd_len",
+      hipLaunchKernelGGL(pool_quantile_len_kernel<AT>, grid, dim3(64), 0, st, (const AT*)x, out, lens, B, T, H););
+  } else if (mode <= 1) {
+    W2V2_REQUIRE(H % 8 == 0, "pool_fwd_len: H must be a multiple of 8");
+    dim3 grid((unsigned)cdiv(H, 128), B);
+    W2V2_DISPATCH_ACT(dtype, "pool_fwd_len",
+      hipLaunchKernelGGL(pool_meanstd_len_kernel<AT>, grid, dim3(256), 0, st, (const AT*)x, out, lens, T, H,
+                         mode == 0););
+  } else {
+    dim3 grid((unsigned)cdiv((int64_t)B * H, 256));
+    W2V2_DISPATCH_ACT(dtype, "pool_fwd_len",
+      hipLaunchKernelGGL(pool_select_len_kernel<AT>, grid, dim3(256), 0, st, (const AT*)x, out, lens, B, T, H, mode););
+  }
+  W2V2_CHECK_LAUNCH("pool_fwd_len");
   return 0;
 }

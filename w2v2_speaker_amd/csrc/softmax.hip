@@ -25,6 +25,30 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* __restric
   }
 }
 
+// Variable-length batch (eval only, no dropout): row r is query r % Tn of utterance r / (heads * Tn), which has
+// lens[b] valid keys.  Keys >= lens[b] get p = 0, rows of padded queries are all zeros; a valid row runs the same
+// per-lane loops and wave reductions as softmax_fwd_kernel with Tn = lens[b], so it is bit-identical to it.
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_fwd_len_kernel(const float* __restrict__ s, T* __restrict__ p,
+                                                              const int* __restrict__ lens, int64_t rows, int Tn,
+                                                              int64_t ld, int heads) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int Lb = lens[row / ((int64_t)heads * Tn)];
+  const int q = (int)(row % Tn);
+  const int nv = q < Lb ? Lb : 0;                   // valid keys of this row
+  const float* sr = s + row * ld;
+  float mx = -INFINITY;
+  for (int c = lane; c < nv; c += 64) mx = fmaxf(mx, sr[c]);
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int c = lane; c < nv; c += 64) sum += __expf(sr[c] - mx);
+  sum = wave_sum(sum);
+  const float inv = 1.0f / sum;
+  for (int c = lane; c < Tn; c += 64) p[row * ld + c] = from_f32<T>(c < nv ? __expf(sr[c] - mx) * inv : 0.f);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restrict__ dpd, const T* __restrict__ p,
                                                           T* __restrict__ ds, int64_t rows, int Tn, int64_t ld,
@@ -74,5 +98,17 @@ extern "C" int w2v2_softmax_bwd(const float* dp_drop, const void* p, void* ds, i
     hipLaunchKernelGGL(softmax_bwd_kernel<AT>, grid, dim3(256), 0, as_stream(stream), dp_drop, (const AT*)p,
                        (AT*)ds, rows, T, ld, drop_p, ik, seed););
   W2V2_CHECK_LAUNCH("softmax_bwd");
+  return 0;
+}
+
+extern "C" int w2v2_softmax_fwd_len(const float* s, void* p, const int* lens, int B, int heads, int T, int64_t ld,
+                                    int dtype, void* stream) {
+  W2V2_REQUIRE(s && p && lens && B > 0 && heads > 0 && T > 0 && ld >= T, "softmax_fwd_len: bad arguments");
+  const int64_t rows = (int64_t)B * heads * T;
+  dim3 grid((unsigned)cdiv(rows, 4));
+  W2V2_DISPATCH_ACT(dtype, "softmax_fwd_len",
+    hipLaunchKernelGGL(softmax_fwd_len_kernel<AT>, grid, dim3(256), 0, as_stream(stream), s, (AT*)p, lens, rows, T,
+                       ld, heads););
+  W2V2_CHECK_LAUNCH("softmax_fwd_len");
   return 0;
 }

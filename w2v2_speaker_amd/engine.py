@@ -109,6 +109,24 @@ def encoder_backward_schedule(num_layers: int, skip: Sequence[int], pair_uppers:
     return ev
 
 
+def valid_lengths(cfg: W2V2Config, lengths, batch: int, n_samples: int) -> List[int]:
+    """Per-utterance valid sample counts of a variable-length forward as Python ints, checked against the plan: one per
+    row, at most the plan's N, and long enough for one encoder frame (400 samples for the standard conv stack)."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_cuda or lengths.is_floating_point() or lengths.is_complex():
+            raise ValueError("lengths must be Python ints or a CPU integer tensor")
+        lengths = lengths.reshape(-1).tolist()
+    lens = [int(n) for n in lengths]
+    if len(lens) != batch:
+        raise ValueError(f"lengths: {len(lens)} values for a batch of {batch}")
+    for n in lens:
+        if n > n_samples:
+            raise ValueError(f"lengths: {n} samples is longer than the plan's {n_samples}")
+        if min(cfg.conv_lengths(n)) < 1:
+            raise ValueError(f"lengths: {n} samples is too short for one encoder frame")
+    return lens
+
+
 @dataclass
 class LayerBufs:
     qkv: torch.Tensor
@@ -183,6 +201,10 @@ class Plan:
         self._cnn_version = -1
         self._asp = {}
         self.grouped = False
+        # variable-length evaluation (forward(..., lengths=)): device int32 table [conv-0 frames | encoder frames] of the
+        # current forward, or None on the fixed-length path
+        self._len_dev, self._len = None, None
+        self.frame_lengths: Optional[List[int]] = None
         self._alloc()
         self._build_gemms()
 
@@ -532,18 +554,44 @@ class Plan:
         return (self.seed * 1000003 + step) * 4096 + layer * 8 + _SITE[site]
 
     # ------------------------------------------------------------------------------------------ forward
+    def _set_lengths(self, lengths) -> None:
+        """Validate per-utterance sample counts and upload the frame counts of every length-aware stage (conv-0 frames,
+        encoder frames incl. the CLS token) in one host-to-device copy."""
+        if self.train:
+            raise NotImplementedError("lengths: evaluation plans only (there is no backward for variable lengths)")
+        if self.paired:
+            raise NotImplementedError("lengths: the paired-input model has no variable-length path")
+        if self.pooling in ("attentive", "random", "none"):
+            raise NotImplementedError(f"lengths: pooling {self.pooling!r} has no variable-length form "
+                                      "(supported: mean+std, mean, max, first, first+cls, last, middle, quantile)")
+        lens = valid_lengths(self.cfg, lengths, self.B, self.N)
+        f0 = [self.cfg.conv_lengths(n)[0] for n in lens]
+        te = [self.cfg.num_frames(n) + (1 if self.cls else 0) for n in lens]
+        if self._len_dev is None:
+            self._len_dev = torch.empty(2, self.B, dtype=torch.int32, device=self.dev)
+        self._len_dev.copy_(torch.tensor([f0, te], dtype=torch.int32))
+        self._len = self._len_dev
+        self.frame_lengths = te
+
     def forward(self, wav: torch.Tensor, mask: Optional[torch.Tensor] = None, skip_layers: Sequence[int] = (),
-                step: int = 0, feature_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                step: int = 0, feature_mask: Optional[torch.Tensor] = None, lengths=None) -> torch.Tensor:
         """wav [B,N] (or [B,1,N]) f32 on the GPU -> last_hidden_state [B,T,H] (act dtype).
         mask: [B,T0] uint8/bool SpecAugment time mask, feature_mask: [B,H] uint8/bool SpecAugment feature mask
         (HF:1294-1304; training only).  Dropout is active iff the plan was built with train=True and the
-        regularisation probabilities are > 0."""
+        regularisation probabilities are > 0.
+        lengths: valid samples per utterance (ints or a CPU integer tensor; evaluation plans).  Every cross-frame
+        reduction (conv-0 GroupNorm statistics, positional-conv padding, attention, pooling) then sees each utterance's own
+        frames only, so row b equals the utterance alone at its own length; padded samples may hold any finite values.
+        ``frame_lengths`` gives the encoder frames of each row; rows of the output past them are unspecified."""
         cfg, st, reg = self.cfg, self.store, self.reg
         B, T, M, H = self.B, self.T, self.M, cfg.hidden_size
         if wav.dim() == 3:
             wav = wav[:, 0, :]
         wav = wav.contiguous()
         assert wav.shape == (self.Bc, self.N) and wav.dtype == torch.float32 and wav.is_cuda
+        self._len, self.frame_lengths = None, None
+        if lengths is not None:
+            self._set_lengths(lengths)
         self._refresh_packs()
         self._wav = wav
         tr = self.train
@@ -575,7 +623,10 @@ class Plan:
             self._fmask = feature_mask.to(torch.uint8).contiguous().view(-1)
             ops.mask_feature(self.h0, self._fmask, B, self.T0)
         G, K = cfg.num_conv_pos_embedding_groups, cfg.num_conv_pos_embeddings
-        ops.posconv_regroup(self.hx, self.xg, B, T, H, G, K, K // 2)
+        if self._len is not None:
+            ops.posconv_regroup_len(self.hx, self.xg, self._len[1], B, T, H, G, K, K // 2)
+        else:
+            ops.posconv_regroup(self.hx, self.xg, B, T, H, G, K, K // 2)
         if self.pos_direct:      # image-resident direct convolution (csrc/posconv_direct.hip), bit-equal to the GEMM
             ops.posconv_direct(self.xg, self.posw_f, self.pos, self.pos_pre, mp("encoder.pos_conv_embed.conv.bias"), B, T, G,
                                self.Cg, K, H, 0)
@@ -600,13 +651,7 @@ class Plan:
             lb, gl = self.lb[l if tr else 0], self.g_layer[l]
             pre = f"encoder.layers.{l}."
             gl["qkv"]()
-            if self.fused:
-                ops.attention_fwd(lb.qkv, lb.ctx, lb.lse, B, T, heads, d, d ** -0.5, pa, self._sd("attn", l, step))
-            else:
-                gl["scores"]()
-                ops.softmax_fwd(self.S, lb.p, lb.pd if pa > 0 else None, B * heads * T, T, self.Tl, pa,
-                                self._sd("attn", l, step))
-                gl["ctx"]()
+            self._attention(l, lb, gl, pa, step)
             gl["out"]()
             ops.layernorm_fwd(xin, lb.a, mp(pre + "layer_norm.weight"), mp(pre + "layer_norm.bias"), lb.x1, lb.mean1,
                               lb.rstd1, cfg.layer_norm_eps, ph, self._sd("post_attn", l, step))
@@ -622,6 +667,25 @@ class Plan:
                               xout, lb.mean2, lb.rstd2, cfg.layer_norm_eps, ph, self._sd("ffn", l, step))
         self.out = (self.X[cfg.num_hidden_layers] if self.all_x else self.X[cfg.num_hidden_layers % 2]).view(B, T, H)
         return self.out
+
+    def _attention(self, l: int, lb: LayerBufs, gl, pa: float, step: int) -> None:
+        """Self-attention of block l from lb.qkv into lb.ctx: fused (16-bit, head dim 64) or scores GEMM + softmax +
+        context GEMM; the length-aware kernels when the forward has lengths."""
+        B, T, heads, d = self.B, self.T, self.cfg.num_attention_heads, self.cfg.head_dim
+        lens = None if self._len is None else self._len[1]
+        if self.fused:
+            if lens is not None:
+                ops.attention_fwd_len(lb.qkv, lb.ctx, lb.lse, lens, B, T, heads, d, d ** -0.5)
+            else:
+                ops.attention_fwd(lb.qkv, lb.ctx, lb.lse, B, T, heads, d, d ** -0.5, pa, self._sd("attn", l, step))
+            return
+        gl["scores"]()
+        if lens is not None:
+            ops.softmax_fwd_len(self.S, lb.p, lens, B, heads, T, self.Tl)
+        else:
+            ops.softmax_fwd(self.S, lb.p, lb.pd if pa > 0 else None, B * heads * T, T, self.Tl, pa,
+                            self._sd("attn", l, step))
+        gl["ctx"]()
 
     def _ln_params_for_input_of(self, l: int):
         """Pre-LN encoder: the LayerNorm that produces X[l], the normalised input of block l (its ``layer_norm``), or -- for
@@ -663,13 +727,7 @@ class Plan:
                 self._res_src[l] = res
                 continue
             gl["qkv"]()
-            if self.fused:
-                ops.attention_fwd(lb.qkv, lb.ctx, lb.lse, B, T, heads, d, d ** -0.5, pa, self._sd("attn", l, step))
-            else:
-                gl["scores"]()
-                ops.softmax_fwd(self.S, lb.p, lb.pd if pa > 0 else None, B * heads * T, T, self.Tl, pa,
-                                self._sd("attn", l, step))
-                gl["ctx"]()
+            self._attention(l, lb, gl, pa, step)
             gl["out"]()
             ops.layernorm_fwd(res, lb.a, mp(pre + "final_layer_norm.weight"), mp(pre + "final_layer_norm.bias"), lb.x1,
                               lb.mean1, lb.rstd1, eps, ph, self._sd("post_attn", l, step))          # lb.a <- s1
@@ -695,6 +753,7 @@ class Plan:
         assert wav.shape == (self.Bc, self.N) and wav.dtype == torch.float32 and wav.is_cuda
         self._refresh_packs()
         self._wav = wav
+        self._len = None
         self._cnn_forward(wav)
         return self.conv[-1]
 
@@ -706,6 +765,13 @@ class Plan:
         the channels -> GELU; layer 0 in one kernel, layers 1-6 as GEMM (bias epilogue) + an in-place LayerNorm-GELU pass."""
         cfg, mp = self.cfg, self.store.mp
         fe = "feature_extractor.conv_layers."
+        if not self.ln_conv and self._len is not None:     # GroupNorm statistics over each utterance's own frames
+            ops.conv0_groupnorm_gelu_len(wav, mp(fe + "0.conv.weight"), mp(fe + "0.layer_norm.weight"),
+                                         mp(fe + "0.layer_norm.bias"), self.conv[0], self.stats0, self._len[0],
+                                         cfg.conv_kernel[0], cfg.conv_stride[0])
+            for g in self.g_conv:
+                g()
+            return
         if not self.ln_conv:
             ops.conv0_groupnorm_gelu(wav, mp(fe + "0.conv.weight"), mp(fe + "0.layer_norm.weight"), mp(fe + "0.layer_norm.bias"),
                                      self.conv[0], self.stats0, cfg.conv_kernel[0], cfg.conv_stride[0])
@@ -729,9 +795,10 @@ class Plan:
         self.dn.view(-1).copy_(dfeat.to(self.adt).contiguous().view(-1))
         self._backward_cnn()
 
-    def embed(self, wav, mask=None, skip_layers=(), step: int = 0, feature_mask=None) -> torch.Tensor:
-        """ref: src/lightning_modules/speaker/wav2vec2_fc.py:414-431 -> pooled embedding [B,E] f32."""
-        out = self.forward(wav, mask, skip_layers, step, feature_mask)
+    def embed(self, wav, mask=None, skip_layers=(), step: int = 0, feature_mask=None, lengths=None) -> torch.Tensor:
+        """ref: src/lightning_modules/speaker/wav2vec2_fc.py:414-431 -> pooled embedding [B,E] f32.  lengths: see
+        forward(); each row is then pooled over its own frames."""
+        out = self.forward(wav, mask, skip_layers, step, feature_mask, lengths=lengths)
         if self.pooling == "attentive":
             return self._asp_for(out).forward()
         self._pool_fwd(out)
@@ -739,7 +806,9 @@ class Plan:
 
     def _pool_fwd(self, out: torch.Tensor) -> None:
         B, T, H = out.shape
-        if self.no_pool:
+        if self._len is not None:
+            ops.pool_fwd_len(out, self.emb, self._len[1], self.pool_mode)
+        elif self.no_pool:
             ops.pool_fwd(out.view(B * T, 1, H), self.emb, POOL_MODES["first"])      # f32 copy of every frame
         elif self.pooling == "random":
             import random
@@ -757,7 +826,7 @@ class Plan:
         """ref: src/lightning_modules/speaker/wav2vec2_fc.py:440-463 (compute_ensemble_embedding): the pooled
         embedding of each of the last ``num_ensembles`` hidden states (hidden_states[L+1-n : L+1])."""
         assert self.pooling != "attentive", "ensemble pooling shares one stat-pooling layer: use a stateless pool"
-        self.forward(wav, None, (), 0)
+        self.forward(wav, None, (), 0)          # (fixed length: the hidden-state ensemble has no variable-length form)
         hs = self.hidden_states()
         out = []
         for h in hs[len(hs) - num_ensembles:]:

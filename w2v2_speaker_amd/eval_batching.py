@@ -1,0 +1,49 @@
+"""Length bucketing for batched variable-length evaluation (host only: no device work, testable on the CPU).
+
+Utterances are sorted by length, each is given a padded length (its length rounded up to ``quantum`` samples; all
+utterances with the same padded length form a bucket) and every bucket is cut into batches of at most
+``min(max_batch, max_batch_samples // padded_n)`` rows -- at least one, so an utterance longer than the sample budget runs
+alone.  Every batch of a bucket has the same shape (the last, partial one included: the caller fills its unused rows
+with dummy audio and drops their outputs), so one static plan serves the whole bucket, and buckets come in length order.
+"""
+from __future__ import annotations
+
+from typing import List, Sequence, Tuple
+
+DEFAULT_QUANTUM = 32000                      # 2 s at 16 kHz
+DEFAULT_MAX_BATCH_SAMPLES = 66 * 48000       # the benchmark's training batch: an eval plan never holds more audio
+DEFAULT_MAX_BATCH = 64
+
+
+def plan_batches(lengths: Sequence[int], quantum: int = DEFAULT_QUANTUM,
+                 max_batch_samples: int = DEFAULT_MAX_BATCH_SAMPLES,
+                 max_batch: int = DEFAULT_MAX_BATCH) -> List[Tuple[Tuple[int, ...], int, int]]:
+    """-> [(indices, padded_n, batch)] in ascending padded length: `indices` (positions in `lengths`, at most `batch` of
+    them, ascending length, ties in input order) run in one forward of a plan of shape (batch, padded_n).
+    Deterministic; every index appears exactly once."""
+    if quantum < 1 or max_batch_samples < 1 or max_batch < 1:
+        raise ValueError("plan_batches: quantum, max_batch_samples and max_batch must be positive")
+    lens = [int(n) for n in lengths]
+    if any(n < 1 for n in lens):
+        raise ValueError("plan_batches: every length must be positive")
+    order = sorted(range(len(lens)), key=lambda i: (lens[i], i))
+    out: List[Tuple[Tuple[int, ...], int, int]] = []
+    i = 0
+    while i < len(order):
+        padded = -(-lens[order[i]] // quantum) * quantum
+        j = i
+        while j < len(order) and lens[order[j]] <= padded:
+            j += 1
+        batch = max(1, min(max_batch, max_batch_samples // padded))
+        for k in range(i, j, batch):
+            out.append((tuple(order[k:min(k + batch, j)]), padded, batch))
+        i = j
+    return out
+
+
+def min_samples(conv_kernel: Sequence[int], conv_stride: Sequence[int]) -> int:
+    """Fewest samples that give one frame out of the conv stack (400 for wav2vec2's): the length of dummy rows."""
+    n = 1
+    for k, s in reversed(list(zip(conv_kernel, conv_stride))):
+        n = (n - 1) * s + k
+    return n

@@ -25,6 +25,8 @@ import torch
 from ... import ops
 from ...config import W2V2Config, Wav2Vec2RegularisationConfig
 from ...engine import Plan
+from ...eval_batching import (DEFAULT_MAX_BATCH, DEFAULT_MAX_BATCH_SAMPLES, DEFAULT_QUANTUM, min_samples,
+                              plan_batches)
 from ...evaluation.speaker.cosine_distance import CosineDistanceEvaluator, EmbeddingSample, EvaluationPair
 from ...models.handles import ModelHandle
 from ...optim.loss import AngularAdditiveMarginSoftMaxLoss, CrossEntropyLoss
@@ -48,6 +50,7 @@ def _load_checkpoint_file(path: str, trust_pickle: bool):
 
 
 MAX_PLANS = 8      # static plans kept per module (LRU): evaluation over variable-length utterances builds one per length
+MAX_BUCKET_PLANS = 12     # plans of compute_speaker_embeddings' length buckets (their own LRU, one per bucket shape)
 
 
 @dataclass
@@ -212,6 +215,8 @@ class Wav2vec2FCModule(torch.nn.Module):
         self.schedule = OneCycle(max_lr=max_lr, total_steps=max_steps)
         self.process_group = process_group
         self._plans: "OrderedDict[Tuple, Plan]" = OrderedDict()
+        self._bucket_plans: "OrderedDict[Tuple, Plan]" = OrderedDict()
+        self.bucket_plans_built = 0
         self._trainers: Dict[Tuple, SpeakerTrainer] = {}
         self.steps = 0              # ref: counts backward calls since on_train_start (the freeze schedule)
         self.schedule_step = 0      # position in the learning-rate schedule (restored from a checkpoint)
@@ -316,6 +321,56 @@ class Wav2vec2FCModule(torch.nn.Module):
         if plan.no_pool:               # NoPooling: [B, T, features], like the reference (its fc layers act on the last dim)
             emb = emb.view(plan.B, plan.T, -1)
         return emb
+
+    def _bucket_plan(self, batch: int, n: int) -> Plan:
+        pooling = self.cfg.test_stat_pooling_type
+        key = (batch, n, pooling)
+        if key in self._bucket_plans:
+            self._bucket_plans.move_to_end(key)
+            return self._bucket_plans[key]
+        plan = Plan(self.store, batch, n, train=False, reg=self.reg, pooling=pooling,
+                    insert_cls_token=(pooling == "first+cls"), aam_margin=self.margin, aam_scale=self.scale)
+        self.bucket_plans_built += 1
+        self._bucket_plans[key] = plan
+        while len(self._bucket_plans) > MAX_BUCKET_PLANS:
+            self._bucket_plans.popitem(last=False)
+        return plan
+
+    def compute_speaker_embeddings(self, waveforms, *, quantum: int = DEFAULT_QUANTUM,
+                                   max_batch_samples: int = DEFAULT_MAX_BATCH_SAMPLES,
+                                   max_batch: int = DEFAULT_MAX_BATCH) -> List[torch.Tensor]:
+        """Embeddings of many utterances of different lengths, batched: one per waveform ([N] or [1, N]), in input order,
+        each equal to ``compute_speaker_embedding(w)`` for that waveform alone (hidden FC layers included).  The utterances
+        are bucketed by length (eval_batching.plan_batches) and each batch runs one variable-length forward, in which every
+        cross-frame reduction sees each utterance's own frames only."""
+        xs = []
+        for w in waveforms:
+            x = self._prep_input(w)
+            if x.dim() != 2 or x.shape[0] != 1:
+                raise ValueError(f"compute_speaker_embeddings: expected one utterance per waveform, got {tuple(w.shape)}")
+            xs.append(x[0])
+        out: List[Optional[torch.Tensor]] = [None] * len(xs)
+        fill = min_samples(self.store.cfg.conv_kernel, self.store.cfg.conv_stride)
+        for idx, n, batch in plan_batches([x.shape[0] for x in xs], quantum, max_batch_samples, max_batch):
+            plan = self._bucket_plan(batch, n)
+            wav = torch.zeros(batch, n, dtype=torch.float32, device=self.device)
+            lens = [fill] * batch           # unused rows of a bucket's last batch: silence of the minimum length
+            for j, i in enumerate(idx):
+                wav[j, :xs[i].shape[0]].copy_(xs[i])
+                lens[j] = xs[i].shape[0]
+            plan.embed(wav, lengths=lens)
+            emb = plan.speaker_embedding(self.cfg.embedding_layer_idx)
+            for j, i in enumerate(idx):
+                out[i] = emb[j:j + 1].clone()
+        return out
+
+    def evaluate_trials(self, pairs: List[EvaluationPair], audio_by_key, **batching) -> dict:
+        """Score a trial list: every utterance the pairs name (key -> waveform in ``audio_by_key``) is embedded once with
+        compute_speaker_embeddings (``batching``: its keyword arguments) and the module's evaluator scores the pairs --
+        the same dict as test_epoch_end over the batch-size-1 test loop."""
+        keys = sorted({k for p in pairs for k in (p.sample1_id, p.sample2_id)})
+        embs = self.compute_speaker_embeddings([audio_by_key[k] for k in keys], **batching)
+        return self._evaluate_embeddings([{"embedding": torch.cat(embs).detach().to("cpu"), "sample_id": keys}], pairs)
 
     def _linear(self, x: torch.Tensor, i: int, relu: bool) -> torch.Tensor:
         W, b = self.store.p(f"fc_list.{i}.0.weight"), self.store.p(f"fc_list.{i}.0.bias")

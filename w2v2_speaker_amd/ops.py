@@ -254,6 +254,31 @@ def conv0_groupnorm_gelu(wav: torch.Tensor, w: torch.Tensor, gamma: torch.Tensor
                                   out.data_ptr(), dt(out), B, N, Cc, k, stride, stream()), "conv0_apply")
 
 
+def conv0_stats_len(wav, w, work, frames, k: int, stride: int, mfma: bool, eps: float = 1e-5) -> torch.Tensor:
+    """Variable-length conv-0 GroupNorm statistics: frames = device int32 [B] valid frames per utterance.  Returns the
+    {mean, rstd} view [B, C, 2] of `work` (conv0_workspace())."""
+    _dev(wav, w, work, frames)
+    assert frames.dtype == torch.int32
+    B, N = wav.shape
+    Cc = w.shape[0]
+    mr = work[work.numel() - B * Cc * 2:]
+    fn = lib().w2v2_conv0_stats_mfma_len if mfma else lib().w2v2_conv0_stats_len
+    _lib.check(fn(wav.data_ptr(), w.data_ptr(), work.data_ptr(), mr.data_ptr(), frames.data_ptr(), B, N, Cc, k, stride,
+                  eps, stream()), "conv0_stats_len")
+    return mr.view(B, Cc, 2)
+
+
+def conv0_groupnorm_gelu_len(wav, w, gamma, beta, out, work, frames, k: int, stride: int, eps: float = 1e-5) -> None:
+    """conv0_groupnorm_gelu with the GroupNorm statistics of each utterance over its first frames[b] frames (the apply
+    pass is per frame and needs no lengths; frames past the end are computed and left unspecified)."""
+    _dev(wav, w, gamma, beta, out, work, frames)
+    B, N = wav.shape
+    Cc = w.shape[0]
+    mr = conv0_stats_len(wav, w, work, frames, k, stride, is16(out.dtype), eps)
+    _lib.check(lib().w2v2_conv0_apply(wav.data_ptr(), w.data_ptr(), mr.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                      out.data_ptr(), dt(out), B, N, Cc, k, stride, stream()), "conv0_apply")
+
+
 def conv0_layernorm_gelu(wav, w, bias, gamma, beta, out, k: int, stride: int, eps: float = 1e-5) -> None:
     """Layer 0 of the feat_extract_norm="layer" family: out [B, L, C] = GELU(LN_C(conv0(wav) + bias)) (HF:275-299)."""
     _dev(wav, w, bias, gamma, beta, out)
@@ -496,6 +521,13 @@ def posconv_regroup(x, xg, B: int, T: int, H: int, G: int, K: int, pad_left: int
                "posconv_regroup")
 
 
+def posconv_regroup_len(x, xg, lens, B: int, T: int, H: int, G: int, K: int, pad_left: int) -> None:
+    """posconv_regroup with frames t >= lens[b] (device int32 [B]) written as zeros."""
+    _dev(x, xg, lens)
+    _lib.check(lib().w2v2_posconv_regroup_len(x.data_ptr(), xg.data_ptr(), lens.data_ptr(), B, T, H, G, K, pad_left,
+                                              dt(x), stream()), "posconv_regroup_len")
+
+
 def weightnorm_scratch(H: int, G: int, K: int, device) -> torch.Tensor:
     """f32 scratch of weightnorm_pack (``sumsq``) / weightnorm_bwd (``dot``): per-tap result + per-block partials."""
     return torch.empty(int(lib().w2v2_weightnorm_scratch_floats(H, G, K)), dtype=torch.float32, device=device)
@@ -521,6 +553,13 @@ def softmax_fwd(s, p, p_drop, rows: int, T: int, ld: int, drop_p: float, seed: i
                                       stream()), "softmax_fwd")
 
 
+def softmax_fwd_len(s, p, lens, B: int, heads: int, T: int, ld: int) -> None:
+    """Eval softmax of a variable-length batch: rows B * heads * T, keys < lens[b] (device int32 [B]), padded rows zero."""
+    _dev(s, p, lens)
+    _lib.check(lib().w2v2_softmax_fwd_len(s.data_ptr(), p.data_ptr(), lens.data_ptr(), B, heads, T, ld, dt(p),
+                                          stream()), "softmax_fwd_len")
+
+
 def softmax_bwd(dp_drop, p, ds, rows: int, T: int, ld: int, drop_p: float, seed: int) -> None:
     _dev(dp_drop, p, ds)
     _lib.check(lib().w2v2_softmax_bwd(dp_drop.data_ptr(), p.data_ptr(), ds.data_ptr(), rows, T, ld, drop_p, seed,
@@ -531,6 +570,14 @@ def attention_fwd(qkv, ctx, lse, B: int, T: int, heads: int, d: int, scale: floa
     _dev(qkv, ctx, lse)
     _lib.check(lib().w2v2_attention_fwd(qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), B, T, heads, d, scale,
                                         drop_p, seed, dt(qkv), stream()), "attention_fwd")
+
+
+def attention_fwd_len(qkv, ctx, lse, lens, B: int, T: int, heads: int, d: int, scale: float) -> None:
+    """Eval fused attention of a variable-length batch: utterance b attends over its first lens[b] (device int32 [B])
+    frames; ctx rows past them are zeros."""
+    _dev(qkv, ctx, lse, lens)
+    _lib.check(lib().w2v2_attention_fwd_len(qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), lens.data_ptr(), B, T, heads,
+                                            d, scale, dt(qkv), stream()), "attention_fwd_len")
 
 
 def attention_bwd(qkv, ctx, dctx, lse, dqkv, delta, B: int, T: int, heads: int, d: int, scale: float,
@@ -546,6 +593,14 @@ def pool_fwd(x, out, mode: int) -> None:
     _dev(x, out)
     B, T, H = x.shape
     _lib.check(lib().w2v2_pool_fwd(x.data_ptr(), out.data_ptr(), B, T, H, mode, dt(x), stream()), "pool_fwd")
+
+
+def pool_fwd_len(x, out, lens, mode: int) -> None:
+    """pool_fwd over the first lens[b] (device int32 [B]) frames of each utterance of x [B, T, H]."""
+    _dev(x, out, lens)
+    B, T, H = x.shape
+    _lib.check(lib().w2v2_pool_fwd_len(x.data_ptr(), out.data_ptr(), lens.data_ptr(), B, T, H, mode, dt(x), stream()),
+               "pool_fwd_len")
 
 
 def pool_bwd(x, out, dout, dx, mode: int) -> None:
