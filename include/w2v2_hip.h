@@ -134,7 +134,8 @@ int w2v2_tune_gemm_f32_tile(int tile);
  * kernel. */
 int w2v2_tune_gemm_ring_debug(int bits);
 /* Tools / tests: which kernel the LAST exact-f32 product ran on -- 0 = register-staged, else 10 fi + stages of the
- * LDS-DMA kernel (e.g. 52 = 160 x 128 tiles, two-stage ring). */
+ * LDS-DMA kernel (e.g. 52 = 160 x 128 tiles, two-stage ring); + 1000 = its time-attribution instantiation (tile codes
+ * >= 200 of w2v2_tune_gemm_f32_tile, tools only: garbage results). */
 int w2v2_gemm_f32_last_kernel(void);
 
 /* Grouped weight-gradient GEMM (the backward of HF:520-526,544,565-572 nn.Linear weights/biases):

@@ -741,3 +741,69 @@ def test_no_compiler_vmcnt_inside_the_k_loops_of_the_lds_dma_gemms():
         assert "_Z" in out, (src, out[-400:])                   # the kernel was found and compiled
         inner = [l for l in out.splitlines() if "Depth=2" in l or "Depth=3" in l]
         assert not inner, (src, inner[:4])
+
+
+# What the PARENT of the routing refactor answered for tests/gemm_route_cases.py::CASES (its library, built from the commit
+# before gemm_route existed, run over the same table; no GPU: 256 CUs) -- per configuration, one family per case, in order.
+GEMM_ROUTE_EXPECTED = {
+    "default":
+        "2 2 4 2 4 1 2 2 2 4 2 4 1 2 2 2 4 2 4 1 2 2 2 4 2 4 1 2 10 10 10 10 10 10 10 2 2 2 2 2 2 2 3 3 3 3 3 "
+        "1 1 1 10 10 -1 3 3 2 9 3 2 2 2 -1 -1 -1 -1 -1 9 10 9 10 9 9 9 10 10 9 1 1 2 3 3 1 2 2 2 2 2 4 4 4 4 -1 -1 -1",
+    "no_gemm_ph":
+        "2 2 2 2 2 1 2 2 2 2 2 2 1 2 2 2 2 2 2 1 2 2 2 2 2 2 1 2 10 10 10 10 10 10 10 2 2 2 2 2 2 2 3 3 3 3 3 "
+        "1 1 1 10 10 -1 3 3 2 9 3 2 2 2 -1 -1 -1 -1 -1 9 10 9 10 9 9 9 10 10 9 1 1 2 3 3 1 2 2 2 2 2 2 2 2 2 -1 -1 -1",
+    "no_glds3":
+        "1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 10 10 10 10 10 10 10 2 2 2 2 2 2 2 3 3 3 3 3 "
+        "1 1 1 10 10 -1 3 3 1 9 3 2 2 2 -1 -1 -1 -1 -1 9 10 9 10 9 9 9 10 10 9 1 1 1 3 3 1 1 1 1 1 1 1 1 1 1 -1 -1 -1",
+    "no_glds":
+        "3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 10 10 10 10 10 10 10 -1 -1 -1 -1 -1 -1 -1 3 3 3 3 3 "
+        "3 3 3 10 10 -1 3 3 3 9 3 -1 -1 -1 -1 -1 -1 -1 -1 9 10 9 10 9 9 9 10 10 9 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 -1 -1 -1",
+    "g3n_1024":
+        "1 2 4 1 1 1 2 1 2 4 1 1 1 2 1 2 4 1 1 1 2 1 2 4 1 1 1 2 10 10 10 10 10 10 10 2 2 2 2 2 2 2 3 3 3 3 3 "
+        "1 1 1 10 10 -1 3 3 2 9 3 2 2 2 -1 -1 -1 -1 -1 9 10 9 10 9 9 9 10 10 9 1 1 1 3 3 1 2 2 2 2 1 1 1 4 1 -1 -1 -1",
+    "f32_no_dma":
+        "2 2 4 2 4 1 2 2 2 4 2 4 1 2 2 2 4 2 4 1 2 2 2 4 2 4 1 2 9 9 9 9 9 9 9 2 2 2 2 2 2 2 3 3 3 3 3 "
+        "1 1 1 9 9 -1 3 3 2 9 3 2 2 2 -1 -1 -1 -1 -1 9 9 9 9 9 9 9 9 9 9 1 1 2 3 3 1 2 2 2 2 2 4 4 4 4 -1 -1 -1",
+    "reserve_32":
+        "4 4 4 4 4 1 2 4 4 4 4 4 1 2 4 4 4 4 4 1 2 4 4 4 4 4 1 2 10 10 10 10 10 10 10 2 2 2 2 2 2 2 3 3 3 3 3 "
+        "1 1 1 10 10 -1 3 3 2 9 3 2 2 2 -1 -1 -1 -1 -1 9 10 9 10 9 9 9 10 10 9 1 1 2 3 3 1 2 2 2 2 2 4 4 4 2 -1 -1 -1",
+    "kernel_1":
+        "1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 10 10 10 10 10 10 10 2 2 2 2 2 2 2 3 3 3 3 3 "
+        "1 1 1 10 10 -1 3 3 1 9 3 2 2 2 -1 -1 -1 -1 -1 9 10 9 10 9 9 9 10 10 9 1 1 1 3 3 1 2 1 1 1 1 1 1 1 1 -1 -1 -1",
+    "kernel_2":
+        "2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 10 10 10 10 10 10 10 2 2 2 2 2 2 2 3 3 3 3 3 "
+        "1 1 1 10 10 -1 3 3 2 9 3 2 2 2 -1 -1 -1 -1 -1 9 10 9 10 9 9 9 10 10 9 2 2 2 3 3 1 2 2 2 2 2 2 2 2 2 -1 -1 -1",
+    "kernel_4":
+        "4 4 4 4 4 2 4 4 4 4 4 4 2 4 4 4 4 4 4 4 4 4 4 4 4 4 4 4 10 10 10 10 10 10 10 2 2 2 2 2 2 2 3 3 3 3 3 "
+        "1 1 1 10 10 -1 3 3 2 9 3 2 2 2 -1 -1 -1 -1 -1 9 10 9 10 9 9 9 10 10 9 4 4 4 3 3 1 2 2 2 2 2 4 4 4 4 -1 -1 -1",
+    "f32_tile_1":
+        "2 2 4 2 4 1 2 2 2 4 2 4 1 2 2 2 4 2 4 1 2 2 2 4 2 4 1 2 9 9 9 9 9 9 9 2 2 2 2 2 2 2 3 3 3 3 3 "
+        "1 1 1 9 9 -1 3 3 2 9 3 2 2 2 -1 -1 -1 -1 -1 9 9 9 9 9 9 9 9 9 9 1 1 2 3 3 1 2 2 2 2 2 4 4 4 4 -1 -1 -1",
+    "f32_tile_13":
+        "2 2 4 2 4 1 2 2 2 4 2 4 1 2 2 2 4 2 4 1 2 2 2 4 2 4 1 2 10 10 10 10 10 10 10 2 2 2 2 2 2 2 3 3 3 3 3 "
+        "1 1 1 10 10 -1 3 3 2 9 3 2 2 2 -1 -1 -1 -1 -1 9 10 9 10 9 9 9 10 10 9 1 1 2 3 3 1 2 2 2 2 2 4 4 4 4 -1 -1 -1",
+}
+
+
+def test_gemm_routing_table():
+    """w2v2_gemm_kernel_of = the route w2v2_gemm launches by (csrc/gemm.hip gemm_route): family per descriptor over the step's
+    shapes (fp16 / bf16 with 16-bit and f32 C, exact f32, two-term weights), transposed operands, split-K, misaligned
+    pointers, accepted and rejected k_ext, f32 products the LDS-DMA kernel can and cannot take -- under no switch, under each
+    A/B switch of the dispatch and under the forced families / f32 tiles, each in a fresh process (the switches are read
+    once).  The expectation is the parent commit's answer, not this code's."""
+    import json
+    import subprocess
+    import gemm_route_cases as g
+    assert len(g.CASES) >= 60 and [c[0] for c in g.CONFIGS] == list(GEMM_ROUTE_EXPECTED)
+    switches = {k for _, env, _ in g.CONFIGS for k in env}
+    for name, env, tune in g.CONFIGS:
+        e = {k: v for k, v in os.environ.items() if k not in switches and k != "W2V2_LIB_AB"}
+        e.update(env, ROUTE_TUNE=tune)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gemm_route_cases.py")], env=e, capture_output=True,
+                             text=True, timeout=600)
+        line = [l for l in out.stdout.splitlines() if l.startswith("ROUTE ")]
+        assert line, (name, out.stderr[-2000:])
+        got, want = json.loads(line[0][6:]), [int(x) for x in GEMM_ROUTE_EXPECTED[name].split()]
+        assert len(got) == len(want) == len(g.CASES)
+        wrong = [(i, g.CASES[i], got[i], want[i]) for i in range(len(want)) if got[i] != want[i]]
+        assert not wrong, (name, wrong[:5])

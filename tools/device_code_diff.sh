@@ -1,0 +1,70 @@
+#!/bin/bash
+# Device code of one .hip file in two source trees, kernel by kernel: compiles both to gfx950 assembly with the flags of
+# _build.FLAGS, drops comments / directives / metadata, renumbers the local labels and says per kernel whether the
+# instruction streams are identical.  What a host-side refactor has to show (the kernels did not move) --
+#     bash tools/device_code_diff.sh gemm_ring.hip /path/to/parent/tree [/path/to/this/tree] [-v]
+# -v prints a unified diff of every differing kernel.  Kernels present in one tree only are listed as such; the
+# instantiations of a template that gained ONE parameter are compared with the old kernel of the remaining parameters.
+f=$1; old=$2; new=${3:-$(dirname "$(dirname "$(realpath "$0")")")}; verbose=0
+for a in "$@"; do [ "$a" = "-v" ] && verbose=1; done
+[ "$new" = "-v" ] && new=$(dirname "$(dirname "$(realpath "$0")")")
+tmp=$(mktemp -d); trap 'rm -rf "$tmp"' EXIT
+for side in old new; do
+  root=${!side}
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result --cuda-device-only -S \
+    "$root/w2v2_speaker_amd/csrc/$f" -o "$tmp/$side.s" 2>"$tmp/$side.err" || { cat "$tmp/$side.err"; exit 1; }
+done
+python3 - "$tmp/old.s" "$tmp/new.s" "$verbose" "$f" <<'P'
+import difflib, re, sys
+
+def kernels(path):
+    out, cur, body = {}, None, []
+    for l in open(path):
+        l = l.rstrip()
+        m = re.match(r'^(_Z\w+):', l)
+        if m and cur is None:
+            cur, body = m.group(1), []
+            continue
+        if cur is None:
+            continue
+        s = l.split(';')[0].strip()               # comments carry line numbers and register statistics
+        if not s or s.startswith('.') and not s.startswith(('.LBB', '.Lpost_getpc')):
+            continue
+        body.append(s)
+        if s == 's_endpgm':
+            # local labels are numbered per translation unit: renumber in order of appearance
+            names = {}
+            def ren(m):
+                return names.setdefault(m.group(0), 'L%d' % len(names))
+            out[cur] = [re.sub(r'\.LBB\d+_\d+|\.Lpost_getpc\d+', ren, x) for x in body]
+            cur = None
+    return out
+
+old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+verbose = sys.argv[3] == '1'
+# a kernel template that GAINED one parameter: its instantiations are compared with the old kernel of the remaining ones
+# (listed under the new name)
+for n in [k for k in new if k not in old]:
+    for m in re.finditer(r'L[bi]\d+E', n):
+        o = n[:m.start()] + n[m.end():]
+        if o in old and o not in new:
+            old[n] = old[o]
+            break
+for o in [k for k in old if k not in new and any(old[k] is old.get(n) for n in new)]:
+    del old[o]
+same = [k for k in old if k in new and old[k] == new[k]]
+diff = [k for k in old if k in new and old[k] != new[k]]
+print(f"{sys.argv[4]}: {len(old)} kernels before, {len(new)} after; {len(same)} identical, {len(diff)} differing, "
+      f"{len([k for k in old if k not in new])} only before, {len([k for k in new if k not in old])} only after")
+for k in diff:
+    d = list(difflib.unified_diff(old[k], new[k], lineterm='', n=2))
+    plus = sum(1 for x in d if x.startswith('+') and not x.startswith('+++'))
+    minus = sum(1 for x in d if x.startswith('-') and not x.startswith('---'))
+    print(f"  DIFFERS {k}: {len(old[k])} -> {len(new[k])} instructions (-{minus} +{plus})")
+    if verbose:
+        print('\n'.join('      ' + x for x in d))
+for k in old:
+    if k not in new: print(f"  ONLY BEFORE {k}: {len(old[k])} instructions")
+for k in new:
+    if k not in old: print(f"  ONLY AFTER  {k}: {len(new[k])} instructions")
+P

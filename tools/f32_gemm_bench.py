@@ -3,7 +3,8 @@
 timed: ROUNDS interleaved rounds of 5 launches per code, the median per code is printed.
     CODES="0 14 15 215 415" python3 tools/f32_gemm_bench.py
 codes: 1..4 register-staged tiles; 11..15 LDS-DMA fi = 1..5; +100 XCD-contiguous tiles;
-+200 no DMA in the loop, +400 no barrier, +800 no vmcnt wait (debug variants: garbage results, timing only).
++200 no DMA in the loop, +400 no barrier, +800 no vmcnt wait (debug variants: garbage results, timing only; a separate
+DBG instantiation of the kernel that exists for K-contiguous operands on x14 / x15 -- elsewhere the three bits are ignored).
 """
 import os
 import statistics

@@ -193,18 +193,13 @@ extern "C" int w2v2_traffic_probe(float* buf, int64_t n, int channels, int lds_b
                "traffic_probe: bad arguments");
   if (n == 0) return 0;
   W2V2_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 15) == 0, "traffic_probe: 16-byte aligned buffer");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&traffic_probe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr_set = true;
-  }
   const int64_t chunk = 16384;                                  // floats per pacing step (64 KiB)
   // s_memrealtime counts at a fixed 100 MHz; one pacing step of every channel = channels * 64 KiB of the bucket
   int64_t cycles = 0;
   if (gbps > 0.f) cycles = (int64_t)(1e8 * (double)channels * (double)chunk * 4.0 / ((double)gbps * 1e9));    // gbps = bucket bytes per second
-  hipLaunchKernelGGL(traffic_probe_kernel, dim3((unsigned)channels), dim3(256), (size_t)(lds_bytes > 16 ? lds_bytes : 16),
-                     as_stream(stream), buf, n, chunk, cycles);
+  if (w2v2_launch_lds<&traffic_probe_kernel>("traffic_probe_kernel", dim3((unsigned)channels), dim3(256),
+                                             (size_t)(lds_bytes > 16 ? lds_bytes : 16), as_stream(stream), buf, n, chunk, cycles) != 0)
+    return -1;
   W2V2_CHECK_LAUNCH("traffic_probe");
   return 0;
 }

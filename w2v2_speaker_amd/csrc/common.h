@@ -1,6 +1,7 @@
 // Shared device/host helpers for the gfx950 kernels of libw2v2hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <math.h>
@@ -27,6 +28,67 @@ extern thread_local char g_w2v2_err[512];
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---------------------------------------------------------------- launching a kernel with dynamic LDS
+// Kernel-timestamp timing of single launches (w2v2_gemm_timed, gemm.hip): when a slot's events are armed, a launcher
+// with the hook (TIMED = true: the 256x128 ring and the phased 256x256 GEMM) hands them to hipExtLaunchKernelGGL, which
+// stamps the dispatch's own begin / end (what rocprofv3 reports) instead of bracketing the launch with two stream events
+// (+3 us of dispatch time per launch).  The hook disarms the timer; w2v2_gemm_timed reads `armed` back to tell whether the
+// product went to a kernel that has it.
+struct W2v2PendingTimer { hipEvent_t start, stop; bool armed; };
+W2v2PendingTimer& w2v2_pending_timer();
+
+// THE way to launch a kernel that asks for dynamic LDS.  More than 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize
+// raised first, and that attribute belongs to (kernel, DEVICE): raised once per kernel instantiation and device (a later
+// launch that asks for more raises it again), never on every launch -- the step makes ~240 GEMM launches -- and a failure
+// is reported with the kernel's name and the byte count.  Launch errors: the caller's W2V2_CHECK_LAUNCH, as everywhere.
+constexpr int W2V2_MAX_DEVICES = 64;
+template <auto KERNEL, bool TIMED = false, typename... Args>
+static int w2v2_launch_lds(const char* name, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+  static size_t raised[W2V2_MAX_DEVICES] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) W2V2_FAIL("%s: no current device", name);
+  size_t beyond = 0;                              // (a device index past the table: raised on every launch)
+  size_t& have = (dev >= 0 && dev < W2V2_MAX_DEVICES) ? raised[dev] : beyond;
+  if (lds > have) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess)
+      W2V2_FAIL("%s: cannot raise the dynamic LDS limit to %zu bytes on device %d: %s", name, lds, dev, hipGetErrorString(e));
+    have = lds;
+  }
+  if constexpr (TIMED) {
+    W2v2PendingTimer& pt = w2v2_pending_timer();
+    if (pt.armed) {
+      pt.armed = false;
+      hipExtLaunchKernelGGL(KERNEL, grid, block, lds, st, pt.start, pt.stop, 0, args...);
+      return 0;
+    }
+  }
+  hipLaunchKernelGGL(KERNEL, grid, block, lds, st, args...);
+  return 0;
+}
+
+// ---------------------------------------------------------------- dispatch switches, CU count (defined in gemm.hip)
+// The environment switches of the GEMM and weight-gradient dispatch (w2v2_gemm, w2v2_wgrad_grouped), read ONCE per
+// process by w2v2_switches(); the comments at the routing code say what each default was measured against.
+struct W2v2Switches {
+  bool no_glds;       // W2V2_NO_GLDS set: no LDS-DMA GEMM kernel at all (everything register-staged)
+  bool glds3;         // W2V2_NO_GLDS3 unset: the 256x128 ring kernel
+  bool tile256;       // W2V2_NO_GEMM_PH unset: 256x256 tiles (phased kernel) at all
+  bool persistent;    // W2V2_G3_NONPERSISTENT unset: the ring kernel's persistent tile loop
+  int g3n;            // W2V2_G3N (512): smallest N of the 256x128 kernel
+  bool defer;         // W2V2_NO_DEFER unset: deferred stores of the ring kernel
+  bool wt_stores;     // W2V2_EPI_WT (1; "0..." = off): write-through stores of the full-line epilogues
+  bool late_dma;      // W2V2_PH_LATE (0; set and not "0..." = on): phased kernel, DMA pieces between the MFMAs (tools only)
+  int reserve_cus;    // W2V2_RESERVE_CUS (0): CUs kept out of the persistent GEMM grids
+  bool f32_no_dma;    // W2V2_F32_NO_DMA (set and not "0..."): exact-f32 products on the register-staged kernel only
+  bool wgrad_ring;    // W2V2_WGRAD_V1 unset: 256-row weight-gradient kernels
+  bool wgrad_ring4;   // W2V2_NO_WGRAD4 unset: 256x256 weight-gradient tiles
+  bool wgrad_phased;  // W2V2_NO_WGRAD_PH unset: ... on the phased kernel
+};
+const W2v2Switches& w2v2_switches();
+int w2v2_device_cus();   // CUs of the device (queried once per process; 256 when there is none to ask)
+
 // ---------------------------------------------------------------- LDS-DMA piece (global_load_lds_dwordx4)
 // 16 bytes per lane from `src` (per lane) to LDS at lds + 16 * lane (`lds`: wave-uniform pointer into __shared__ memory).
 // Inline assembly instead of __builtin_amdgcn_global_load_lds ON PURPOSE: the compiler's waitcnt pass treats an LDS read
@@ -35,10 +97,14 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // of the phased and ring GEMMs, behind their own counted `vmcnt(8)` / `vmcnt(6)`): every K tile then waits for ALL
 // pieces in flight, which is exactly what the counted waits of a multi-stage ring are there to avoid.  A kernel that uses
 // this helper must order every piece against its readers itself (s_waitcnt vmcnt(n) + barrier) -- __syncthreads() does
-// NOT wait for these pieces -- and must not use the builtin as well (the compiler does not know M0 changed here).
+// NOT wait for these pieces.  The statement overwrites M0 and says so in its clobber list, so the compiler re-loads M0
+// in front of anything of its own that reads it (LDS-DMA builtins, ds_*_gws, s_sendmsg, v_interp / movrel forms).
+// `lds_addr`: the wave-uniform LDS BYTE address of the piece, in a scalar register.
+__device__ __forceinline__ void w2v2_dma16(const void* src, uint32_t lds_addr) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(src) : "memory", "m0");
+}
 __device__ __forceinline__ void w2v2_dma16(const void* src, void* lds) {
-  const uint32_t l = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(l), "v"(src) : "memory");
+  w2v2_dma16(src, __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds));
 }
 
 // `s_waitcnt vmcnt(0)` as an instruction the COMPILER sees (the builtin, not inline assembly).  Its waitcnt pass does not

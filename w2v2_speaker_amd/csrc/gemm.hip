@@ -315,68 +315,47 @@ __global__ __launch_bounds__(256) void gemm16_dma_128_kernel(const GemmArgs g) {
     }
   }
 
-  TC* Cz = reinterpret_cast<TC*>(g.C) + z0 * g.c_s0 + z1 * g.c_s1;
-  const TC* auxz = g.aux ? reinterpret_cast<const TC*>(g.aux) + z0 * g.aux_s0 + z1 * g.aux_s1 : nullptr;
-  TC* auxo = g.aux ? reinterpret_cast<TC*>(g.aux) + z0 * g.aux_s0 + z1 * g.aux_s1 : nullptr;
-  const float* bias = g.bias ? g.bias + z1 * g.bias_s1 : nullptr;
   tile_epilogue<TC, FM, FN>(g, acc, reinterpret_cast<float*>(smem_raw), m0, n0, wm, wn, z0, z1, split);
 }
 
-static const bool g_w2v2_no_glds = getenv("W2V2_NO_GLDS") != nullptr;   // A/B switches for benchmarking
-static const bool g_w2v2_glds3 = getenv("W2V2_NO_GLDS3") == nullptr;
-static const bool g_w2v2_tile256 = getenv("W2V2_NO_GEMM_PH") == nullptr;        // 256x256 tiles at all
-static const bool g_w2v2_persistent = getenv("W2V2_G3_NONPERSISTENT") == nullptr;
-static const int g_w2v2_g3n = getenv("W2V2_G3N") ? atoi(getenv("W2V2_G3N")) : 512;  // smallest N of the 256x128 kernel
+// ------------------------------------------------------------------------------ switches, CU count
+// Every environment switch of the GEMM and weight-gradient dispatch, read once per process.  A/B switches for
+// benchmarking unless noted; the measurement behind a default stands at its field.
+const W2v2Switches& w2v2_switches() {
+  static const W2v2Switches sw = [] {
+    W2v2Switches s;
+    auto env_int = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    auto env_on = [](const char* name, bool dflt) { const char* e = getenv(name); return e ? e[0] != '0' : dflt; };
+    s.no_glds = getenv("W2V2_NO_GLDS") != nullptr;
+    s.glds3 = getenv("W2V2_NO_GLDS3") == nullptr;
+    s.tile256 = getenv("W2V2_NO_GEMM_PH") == nullptr;
+    s.persistent = getenv("W2V2_G3_NONPERSISTENT") == nullptr;
+    s.g3n = env_int("W2V2_G3N", 512);
+    s.defer = getenv("W2V2_NO_DEFER") == nullptr;
+    s.wt_stores = env_on("W2V2_EPI_WT", true);
+    s.late_dma = env_on("W2V2_PH_LATE", false);
+    s.reserve_cus = env_int("W2V2_RESERVE_CUS", 0);
+    s.f32_no_dma = env_on("W2V2_F32_NO_DMA", false);
+    s.wgrad_ring = getenv("W2V2_WGRAD_V1") == nullptr;
+    s.wgrad_ring4 = getenv("W2V2_NO_WGRAD4") == nullptr;
+    s.wgrad_phased = getenv("W2V2_NO_WGRAD_PH") == nullptr;
+    return s;
+  }();
+  return sw;
+}
 
-static int g_w2v2_ncu = 0;
-int w2v2_gemm_device_cus() {
-  if (g_w2v2_ncu == 0) {
-    int dev = 0;
+// (one device per process: queried once, not on every launch; 256 without a device -- w2v2_gemm_kernel_of runs without one)
+int w2v2_device_cus() {
+  static const int ncu = [] {
+    int dev = 0, v = 0;
     (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&g_w2v2_ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || g_w2v2_ncu <= 0)
-      g_w2v2_ncu = 256;
-    // data-parallel runs: the persistent ring kernels fill every CU's registers, so RCCL's all-reduce workgroups
-    // (side stream) only run between them; W2V2_RESERVE_CUS=n keeps n CUs out of the persistent grids
-    const char* r = getenv("W2V2_RESERVE_CUS");
-    if (r && atoi(r) > 0 && atoi(r) < g_w2v2_ncu) g_w2v2_ncu -= atoi(r);
-  }
-  return g_w2v2_ncu;
+    return (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+  }();
+  return ncu;
 }
-
-template <typename TE, int FM, int FN, typename TC>
-static void launch_glds(const GemmArgs& a, dim3 grid, hipStream_t st) {
-  constexpr size_t lds = (size_t)2 * (32 * FM + 32 * FN) * 64 * sizeof(bf16_t);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm16_dma_128_kernel<TE, FM, FN, TC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm16_dma_128_kernel<TE, FM, FN, TC>), grid, dim3(256), lds, st, a);
-}
-
-// ------------------------------------------------------------------------------ host dispatch
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-template <typename TE, int FM, int FN, typename TC>
-static void launch_bf16(const GemmArgs& a, dim3 grid, hipStream_t st) {
-  constexpr size_t lds = (size_t)2 * (32 * FM + 32 * FN) * 64 * sizeof(bf16_t);
-  const bool ta = a.A.trans, tb = a.B.trans;
-#define W2V2_LAUNCH(TA_, TB_)                                                                   \
-  do {                                                                                          \
-    static bool attr_set = false;                                                               \
-    if (!attr_set) {                                                                            \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm16_regstage_kernel<TE, FM, FN, TA_, TB_, TC>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
-      attr_set = true;                                                                          \
-    }                                                                                           \
-    hipLaunchKernelGGL((gemm16_regstage_kernel<TE, FM, FN, TA_, TB_, TC>), grid, dim3(256), lds, st, a);  \
-  } while (0)
-  if (!ta && !tb) W2V2_LAUNCH(false, false);
-  else if (!ta && tb) W2V2_LAUNCH(false, true);
-  else if (ta && !tb) W2V2_LAUNCH(true, false);
-  else W2V2_LAUNCH(true, true);
-#undef W2V2_LAUNCH
+int w2v2_gemm_device_cus() {
+  const int ncu = w2v2_device_cus(), r = w2v2_switches().reserve_cus;
+  return (r > 0 && r < ncu) ? ncu - r : ncu;
 }
 
 // tuning hook (tools/gemm_shapes.py): force the kernel family of the K-contiguous 16-bit products.
@@ -390,6 +369,208 @@ extern "C" int w2v2_tune_gemm_kernel(int family) {
   return old;
 }
 
+// ------------------------------------------------------------------------------ routing (decides, launches nothing)
+// What w2v2_gemm launches for a descriptor.  family: 4 = phased 256x256, 2 = 256x128 ring, 1 = 128-row LDS-DMA kernel,
+// 3 = register-staged, 9 = exact f32 (register-staged), 10 = exact f32 with LDS-DMA staging; the per-launch choices that
+// travel to the kernel (defer_ok, wt_stores, late_dma, k_per_split, tiles) are in the GemmArgs the route fills.
+struct GemmRoute {
+  int family;
+  bool narrow;       // families 1 and 3: 128 x 64 tiles instead of 128 x 128
+  dim3 grid;         // families 1 and 3 (the persistent kernels and the f32 kernels size their own grids)
+  int f32_rows;      // family 10: tile height fi (rows = 32 fi) of the LDS-DMA kernel
+};
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Validates `d`, fills `a` and decides the route, as a function of the descriptor, the switches, the CU count and the
+// forced family alone: w2v2_gemm = gemm_route + launch, w2v2_gemm_kernel_of = gemm_route.  Writes no global.
+static int gemm_route(const w2v2_gemm_desc* d, int force, GemmArgs& a, GemmRoute& r) {
+  W2V2_REQUIRE(d != nullptr, "w2v2_gemm: null descriptor");
+  W2V2_REQUIRE(d->M > 0 && d->N > 0 && d->K >= 0 && d->batch > 0, "w2v2_gemm: bad shape M=%d N=%d K=%d batch=%d",
+               d->M, d->N, d->K, d->batch);
+  W2V2_REQUIRE(d->A.ptr && d->B.ptr && d->C, "w2v2_gemm: null operand");
+  W2V2_REQUIRE(d->dtype_ab == W2V2_F32 || d->dtype_ab == W2V2_BF16 || d->dtype_ab == W2V2_F16,
+               "w2v2_gemm: bad dtype_ab %d", d->dtype_ab);
+  W2V2_REQUIRE(d->dtype_c == W2V2_F32 || d->dtype_c == d->dtype_ab, "w2v2_gemm: dtype_c %d must be f32 or dtype_ab (%d)",
+               d->dtype_c, d->dtype_ab);
+  W2V2_REQUIRE(d->epilogue >= 0 && d->epilogue <= W2V2_EPI_MUL, "w2v2_gemm: bad epilogue %d", d->epilogue);
+  const int split = d->split_k > 1 ? d->split_k : 1;
+  const int atomic = (split > 1 || d->accumulate) ? 1 : 0;
+  if (atomic) {
+    W2V2_REQUIRE(d->dtype_c == W2V2_F32, "w2v2_gemm: split_k/accumulate need an f32 C");
+    W2V2_REQUIRE(d->epilogue == W2V2_EPI_NONE || (split == 1) || d->epilogue == W2V2_EPI_BIAS,
+                 "w2v2_gemm: split_k supports EPI_NONE/EPI_BIAS only");
+  }
+  if (d->epilogue == W2V2_EPI_BIAS || d->epilogue == W2V2_EPI_BIAS_GELU || d->epilogue == W2V2_EPI_BIAS_GELU_GRAD)
+    W2V2_REQUIRE(d->bias != nullptr, "w2v2_gemm: bias epilogue without bias");
+  if (d->epilogue == W2V2_EPI_GELU_BWD || d->epilogue == W2V2_EPI_ADD || d->epilogue == W2V2_EPI_MUL ||
+      d->epilogue == W2V2_EPI_BIAS_GELU_GRAD)
+    W2V2_REQUIRE(d->aux != nullptr, "w2v2_gemm: epilogue %d needs aux", d->epilogue);
+  if (d->epilogue == W2V2_EPI_SCALE_RC)
+    W2V2_REQUIRE(d->row_scale && d->col_scale, "w2v2_gemm: EPI_SCALE_RC needs row/col scales");
+
+  const bool f32 = d->dtype_ab == W2V2_F32;
+  const int oal = f32 ? 4 : 8;                          // operand elements per 16 bytes
+  a.M = d->M; a.N = d->N; a.K = d->K;
+  a.epilogue = d->epilogue; a.split_k = split; a.atomic = atomic;
+  a.tiles_m = a.tiles_n = 0;
+  a.batch_inner = d->batch_inner > 0 ? d->batch_inner : 1;
+  auto cvt = [&](const w2v2_operand& o) {
+    OpDev v;
+    v.ptr = o.ptr; v.ld = o.ld; v.seg_len = o.seg_len; v.seg_stride = o.seg_stride; v.trans = o.trans ? 1 : 0;
+    v.vec_ok = aligned16(o.ptr) && (o.ld % oal == 0) && (o.seg_stride % oal == 0) && (o.stride0 % oal == 0) &&
+               (o.stride1 % oal == 0);
+    return v;
+  };
+  a.A = cvt(d->A);
+  a.B = cvt(d->B);
+  a.a_s0 = d->A.stride0; a.a_s1 = d->A.stride1; a.b_s0 = d->B.stride0; a.b_s1 = d->B.stride1;
+  a.C = d->C; a.ldc = d->ldc; a.c_s0 = d->c_stride0; a.c_s1 = d->c_stride1;
+  a.aux = d->aux; a.ldaux = d->ldaux; a.aux_s0 = d->aux_stride0; a.aux_s1 = d->aux_stride1;
+  a.bias = d->bias; a.bias_s1 = d->bias_stride1;
+  a.row_scale = d->row_scale; a.col_scale = d->col_scale;
+  a.alpha = d->alpha;
+  a.k_ext = d->k_ext; a.n_ext_from = d->n_ext_from; a.b_lo_off = d->b_lo_offset;
+  a.defer_ok = 0;
+  a.wt_stores = 1;
+  a.late_dma = 0;
+  a.xcd_tiles = 0;
+  a.dbg_bits = 0;
+  const int cal = d->dtype_c == W2V2_F32 ? 4 : 8;     // elements per 16 bytes
+  a.c_vec_ok = aligned16(d->C) && (d->ldc % cal == 0) && (d->c_stride0 % cal == 0) && (d->c_stride1 % cal == 0);
+  a.aux_vec_ok = d->aux && aligned16(d->aux) && (d->ldaux % cal == 0) && (d->aux_stride0 % cal == 0) &&
+                 (d->aux_stride1 % cal == 0);
+  r.family = 0; r.narrow = false; r.grid = dim3(1); r.f32_rows = 0;
+
+  const int bk = f32 ? 32 : 64;                          // K tile of the kernels
+  a.k_per_split = (int)(cdiv(cdiv(d->K, split), bk) * bk);
+  if (a.k_per_split == 0) a.k_per_split = bk;
+  if (f32) {
+    r.f32_rows = w2v2_gemm_f32_dma_rows(a, d->M, d->N, d->K, split, d->batch);
+    r.family = r.f32_rows > 0 ? 10 : 9;               // 10: gemm_f32_dma.hip
+    return 0;
+  }
+
+  const W2v2Switches& sw = w2v2_switches();
+  const int64_t ncu = w2v2_gemm_device_cus();
+  const bool glds = !a.A.trans && !a.B.trans && a.A.vec_ok && a.B.vec_ok && (d->K % 64 == 0) && d->K >= 64 && !sw.no_glds;
+  // 64-column tiles for N <= 64 -- and, on the LDS-DMA kernel, wherever 128-column tiles would leave more than half of
+  // the CUs without a workgroup (the AAM logits: 66 x 5994 x 1536 is 47 tiles of 128 x 128 on 256 CUs streaming 18 MB
+  // of class weights: 33.6 -> 29.3 us; the register-staged kernel measured 2 us slower with the narrower tile)
+  r.narrow = d->N <= 64 || (glds && cdiv(d->M, 128) * cdiv(d->N, 128) * split * d->batch * 2 <= ncu);
+  a.tiles_m = (int)cdiv(d->M, 128); a.tiles_n = (int)cdiv(d->N, r.narrow ? 64 : 128);
+  r.grid = dim3(a.tiles_m * a.tiles_n, split, d->batch);
+
+  // What the two persistent 256-row kernels can take at all.  The phased kernel on top: plain single products, 16-bit
+  // outputs through the full-line register epilogue only (lines_ok, gemm_common.h), and its DMA sources are 32-bit
+  // element offsets from the operand base.
+  const bool ring_ok = glds && split == 1 && !atomic;
+  auto extent = [](const w2v2_operand& o, int64_t rows, int64_t K) -> int64_t {
+    return (o.seg_len > 0 ? (rows / o.seg_len + 1) * o.seg_stride + o.seg_len * o.ld : rows * o.ld) + K;
+  };
+  const bool fits32 = extent(d->A, d->M, d->K) < (int64_t(1) << 31) && extent(d->B, d->N, d->K) < (int64_t(1) << 31);
+  const bool phased_ok = ring_ok && d->k_ext == 0 && d->batch == 1 && fits32 && (d->dtype_c == W2V2_F32 || lines_ok(a));
+  bool ring, phased;
+  if (force != 0 && ring_ok && d->k_ext == 0 && d->batch == 1) {     // tools: w2v2_tune_gemm_kernel
+    ring = force >= 2;
+    phased = force == 4 && phased_ok;
+  } else {
+    // 256x128 3-stage kernel for the encoder shapes; the conv stack (N = 512, M ~ 3e5) measures
+    // slightly faster on the 128x128 kernel at 2 workgroups per CU
+    // (two-term weights exist on this kernel only: such a request takes it whatever the shape)
+    ring = ring_ok && (d->k_ext != 0 || (d->N >= sw.g3n && d->M >= 1024 && sw.glds3));
+    // 256x256 tiles when they fill the chip: >= 85 % of the CU slots of the last round busy (FFN1, dH, conv stack)
+    phased = false;
+    if (ring && phased_ok && d->N >= 512 && sw.tile256) {
+      // measured per shape with tools/gemm_shapes.py (FAMILIES=0,1,2,3,4): a 256x256 tile step runs ~1.2x the flops
+      // per second of a 256x128 one (1.25 below), so the larger tile wins whenever its last-round fill is not worse by more than
+      // that (conv3: 620 tiles = 0.81 vs 0.97 -> 174 vs 183 us; conv5: 156 tiles = 0.61 vs 0.61 -> 41 vs 47 us;
+      // FFN2-shaped N = 768 products: 117 tiles = 0.46 vs 0.91 -> 73 vs 52 us stay on the 256x128 ring)
+      const int64_t t4 = cdiv(d->M, 256) * cdiv(d->N, 256), t3 = cdiv(d->M, 256) * cdiv(d->N, 128);
+      const double fill4 = (double)t4 / (double)(cdiv(t4, ncu) * ncu), fill3 = (double)t3 / (double)(cdiv(t3, ncu) * ncu);
+      phased = fill4 * 1.25 >= fill3 && t4 * 2 >= ncu && (double)d->N / (double)(cdiv(d->N, 256) * 256) >= 0.9;
+    }
+  }
+  if (d->k_ext != 0)
+    W2V2_REQUIRE(ring && d->k_ext == d->K && d->n_ext_from >= 0 && d->n_ext_from % 128 == 0 && d->b_lo_offset % 8 == 0,
+                 "w2v2_gemm: two-term weights (k_ext) need k_ext == K, n_ext_from %% 128 == 0 and K-contiguous 16-byte "
+                 "aligned operands with K %% 64 == 0 (M=%d N=%d K=%d)", d->M, d->N, d->K);
+  r.family = phased ? 4 : ring ? 2 : glds ? 1 : 3;
+  // Store flavour of the full-line register epilogues: write-through (sc1) stores leave nothing dirty in L2 at the
+  // kernel's end (round 3: -0.4 % step time over all writers).  Re-measured per product in round 4
+  // (tools/gemm_attrib.py variants 32 / 64, profiles/r04_gemm_attrib.txt): with the ten-instruction IEEE division gone
+  // from the GELU epilogue, write-through wins or ties on every product of the step (FFN1 68.8 vs 76.3 us plain, dH 60.0
+  // vs 64.2, conv1 568 vs 562), and in-step 12.29 vs 12.48 ms with plain stores everywhere.  W2V2_EPI_WT=0 forces plain
+  // write-back stores (A/B).
+  a.wt_stores = sw.wt_stores;
+  // Phased kernel, placement of the DMA pieces: in a phase's read segment (the product) or between its MFMAs
+  // (W2V2_PH_LATE=1, tools only).  Stand-alone, back to back, the heavy-epilogue products look faster with the pieces
+  // between the MFMAs (FFN1 80.3 -> 69.3 us, dH 67.4 -> 63.8; the main loop itself is unchanged, "-epi" columns of
+  // profiles/r04_gemm_attrib.txt) -- IN THE STEP the same choice measured +0.6 % (11.50 -> 11.57 ms, three ABAB rounds
+  // in one call): an artefact of timing one kernel against itself, not a property of the kernel.  Off.
+  a.late_dma = sw.late_dma;
+  // 256x128 ring: the stores of a tile may be issued under the next tile's main loop (single 16-bit full-line output)
+  if (r.family == 2)
+    a.defer_ok = sw.defer && d->dtype_c != W2V2_F32 && lines_ok(a) && (d->N % 128 == 0) &&
+                 d->epilogue != W2V2_EPI_BIAS_GELU && d->epilogue != W2V2_EPI_BIAS_GELU_GRAD;
+  return 0;
+}
+
+// Which kernel family w2v2_gemm sends a descriptor to, decided by the dispatch code ITSELF (the route, nothing launched);
+// < 0 = the descriptor is rejected.  Profilers label launches with it instead of mirroring the heuristics.
+extern "C" int w2v2_gemm_kernel_of(const w2v2_gemm_desc* d) {
+  GemmArgs a;
+  GemmRoute r;
+  return gemm_route(d, g_w2v2_force, a, r) != 0 ? -1 : r.family;
+}
+
+// ------------------------------------------------------------------------------ launch
+template <typename TE, int FM, int FN, typename TC>
+static int launch_glds(const GemmArgs& a, dim3 grid, hipStream_t st) {
+  constexpr size_t lds = (size_t)2 * (32 * FM + 32 * FN) * 64 * sizeof(bf16_t);
+  return w2v2_launch_lds<&gemm16_dma_128_kernel<TE, FM, FN, TC>>("gemm16_dma_128_kernel", grid, dim3(256), lds, st, a);
+}
+
+template <typename TE, int FM, int FN, typename TC>
+static int launch_regstage(const GemmArgs& a, dim3 grid, hipStream_t st) {
+  constexpr size_t lds = (size_t)2 * (32 * FM + 32 * FN) * 64 * sizeof(bf16_t);
+#define W2V2_LAUNCH(TA_, TB_) \
+  return w2v2_launch_lds<&gemm16_regstage_kernel<TE, FM, FN, TA_, TB_, TC>>("gemm16_regstage_kernel", grid, dim3(256), lds, st, a)
+  if (!a.A.trans && !a.B.trans) W2V2_LAUNCH(false, false);
+  else if (!a.A.trans && a.B.trans) W2V2_LAUNCH(false, true);
+  else if (a.A.trans && !a.B.trans) W2V2_LAUNCH(true, false);
+  else W2V2_LAUNCH(true, true);
+#undef W2V2_LAUNCH
+}
+
+// TE = operand element type (selects the MFMA instruction), TC = float or TE
+template <typename TE, typename TC>
+static int launch_128(const GemmArgs& a, const GemmRoute& r, hipStream_t st) {
+  if (r.family == 1) return r.narrow ? launch_glds<TE, 4, 2, TC>(a, r.grid, st) : launch_glds<TE, 4, 4, TC>(a, r.grid, st);
+  return r.narrow ? launch_regstage<TE, 4, 2, TC>(a, r.grid, st) : launch_regstage<TE, 4, 4, TC>(a, r.grid, st);
+}
+
+extern "C" int w2v2_gemm(const w2v2_gemm_desc* d, void* stream) {
+  GemmArgs a;
+  GemmRoute r;
+  if (gemm_route(d, g_w2v2_force, a, r) != 0) return -1;
+  hipStream_t st = as_stream(stream);
+  const bool c32 = d->dtype_c == W2V2_F32;
+  int rc;
+  switch (r.family) {
+    case 4: rc = w2v2_launch_phased_256x256(a, d->dtype_ab, d->dtype_c, d->M, d->N, d->batch, st); break;
+    case 2: rc = w2v2_launch_ring_256x128(a, d->dtype_ab, d->dtype_c, d->M, d->N, d->batch, w2v2_switches().persistent, st); break;
+    case 9: case 10: rc = w2v2_launch_gemm_f32(a, d->M, d->N, d->K, a.split_k, d->batch, r.f32_rows, st); break;   // gemm_f32.hip
+    default:
+      if (d->dtype_ab == W2V2_BF16) rc = c32 ? launch_128<bf16_t, float>(a, r, st) : launch_128<bf16_t, bf16_t>(a, r, st);
+      else rc = c32 ? launch_128<f16_t, float>(a, r, st) : launch_128<f16_t, f16_t>(a, r, st);
+      break;
+  }
+  if (rc != 0) return rc;
+  W2V2_CHECK_LAUNCH("w2v2_gemm");
+  return 0;
+}
+
 // ------------------------------------------------------------------------------ timed launches (bench.py roofline)
 #include <vector>
 W2v2PendingTimer& w2v2_pending_timer() {
@@ -397,18 +578,6 @@ W2v2PendingTimer& w2v2_pending_timer() {
   return t;
 }
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_timer_slots;
-extern "C" int w2v2_gemm(const w2v2_gemm_desc* d, void* stream);
-// Which kernel family w2v2_gemm sends a descriptor to, decided by the dispatch code ITSELF (a dry run: validation +
-// decision, no launch): 4 = phased 256x256, 2 = 256x128 ring, 1 = 128-row LDS-DMA kernel, 3 = register-staged, 9 = exact
-// f32; < 0 = the descriptor is rejected.  Profilers label launches with it instead of mirroring the heuristics.
-static thread_local int g_gemm_dry = 0, g_gemm_family = 0;
-extern "C" int w2v2_gemm_kernel_of(const w2v2_gemm_desc* d) {
-  g_gemm_dry = 1;
-  g_gemm_family = 0;
-  const int rc = w2v2_gemm(d, nullptr);
-  g_gemm_dry = 0;
-  return rc != 0 ? -1 : g_gemm_family;
-}
 extern "C" int w2v2_gemm_timed(const w2v2_gemm_desc* d, void* stream, int slot) {
   W2V2_REQUIRE(slot >= 0 && slot < (1 << 16), "w2v2_gemm_timed: slot %d out of range", slot);
   while ((int)g_timer_slots.size() <= slot) {
@@ -435,167 +604,5 @@ extern "C" int w2v2_timer_read(int first_slot, int n, float* ms_out) {
     if (hipEventSynchronize(e.second) != hipSuccess || hipEventElapsedTime(ms_out + i, e.first, e.second) != hipSuccess)
       W2V2_FAIL("w2v2_timer_read: slot %d was never launched", first_slot + i);
   }
-  return 0;
-}
-
-extern "C" int w2v2_gemm(const w2v2_gemm_desc* d, void* stream) {
-  W2V2_REQUIRE(d != nullptr, "w2v2_gemm: null descriptor");
-  W2V2_REQUIRE(d->M > 0 && d->N > 0 && d->K >= 0 && d->batch > 0, "w2v2_gemm: bad shape M=%d N=%d K=%d batch=%d",
-               d->M, d->N, d->K, d->batch);
-  W2V2_REQUIRE(d->A.ptr && d->B.ptr && d->C, "w2v2_gemm: null operand");
-  W2V2_REQUIRE(d->dtype_ab == W2V2_F32 || d->dtype_ab == W2V2_BF16 || d->dtype_ab == W2V2_F16,
-               "w2v2_gemm: bad dtype_ab %d", d->dtype_ab);
-  W2V2_REQUIRE(d->dtype_c == W2V2_F32 || d->dtype_c == d->dtype_ab, "w2v2_gemm: dtype_c %d must be f32 or dtype_ab (%d)",
-               d->dtype_c, d->dtype_ab);
-  W2V2_REQUIRE(d->epilogue >= 0 && d->epilogue <= W2V2_EPI_MUL, "w2v2_gemm: bad epilogue %d", d->epilogue);
-  const int split = d->split_k > 1 ? d->split_k : 1;
-  const int atomic = (split > 1 || d->accumulate) ? 1 : 0;
-  if (atomic) {
-    W2V2_REQUIRE(d->dtype_c == W2V2_F32, "w2v2_gemm: split_k/accumulate need an f32 C");
-    W2V2_REQUIRE(d->epilogue == W2V2_EPI_NONE || (split == 1) || d->epilogue == W2V2_EPI_BIAS,
-                 "w2v2_gemm: split_k supports EPI_NONE/EPI_BIAS only");
-  }
-  if (d->epilogue == W2V2_EPI_BIAS || d->epilogue == W2V2_EPI_BIAS_GELU || d->epilogue == W2V2_EPI_BIAS_GELU_GRAD)
-    W2V2_REQUIRE(d->bias != nullptr, "w2v2_gemm: bias epilogue without bias");
-  if (d->epilogue == W2V2_EPI_GELU_BWD || d->epilogue == W2V2_EPI_ADD || d->epilogue == W2V2_EPI_MUL ||
-      d->epilogue == W2V2_EPI_BIAS_GELU_GRAD)
-    W2V2_REQUIRE(d->aux != nullptr, "w2v2_gemm: epilogue %d needs aux", d->epilogue);
-  if (d->epilogue == W2V2_EPI_SCALE_RC)
-    W2V2_REQUIRE(d->row_scale && d->col_scale, "w2v2_gemm: EPI_SCALE_RC needs row/col scales");
-
-  GemmArgs a;
-  a.M = d->M; a.N = d->N; a.K = d->K;
-  a.epilogue = d->epilogue; a.split_k = split; a.atomic = atomic;
-  a.batch_inner = d->batch_inner > 0 ? d->batch_inner : 1;
-  auto cvt = [&](const w2v2_operand& o, int64_t s0, int64_t s1) {
-    OpDev r;
-    r.ptr = o.ptr; r.ld = o.ld; r.seg_len = o.seg_len; r.seg_stride = o.seg_stride; r.trans = o.trans ? 1 : 0;
-    r.vec_ok = aligned16(o.ptr) && (o.ld % 8 == 0) && (o.seg_stride % 8 == 0) && (s0 % 8 == 0) && (s1 % 8 == 0);
-    return r;
-  };
-  a.A = cvt(d->A, d->A.stride0, d->A.stride1);
-  a.B = cvt(d->B, d->B.stride0, d->B.stride1);
-  a.a_s0 = d->A.stride0; a.a_s1 = d->A.stride1; a.b_s0 = d->B.stride0; a.b_s1 = d->B.stride1;
-  a.C = d->C; a.ldc = d->ldc; a.c_s0 = d->c_stride0; a.c_s1 = d->c_stride1;
-  a.aux = d->aux; a.ldaux = d->ldaux; a.aux_s0 = d->aux_stride0; a.aux_s1 = d->aux_stride1;
-  a.bias = d->bias; a.bias_s1 = d->bias_stride1;
-  a.row_scale = d->row_scale; a.col_scale = d->col_scale;
-  a.alpha = d->alpha;
-  a.k_ext = d->k_ext; a.n_ext_from = d->n_ext_from; a.b_lo_off = d->b_lo_offset;
-  static const bool defer_env = getenv("W2V2_NO_DEFER") == nullptr;   // A/B switch
-  a.defer_ok = 0;
-  a.wt_stores = 1;
-  a.late_dma = 0;
-  a.xcd_tiles = 0;
-  const int cal = d->dtype_c == W2V2_F32 ? 4 : 8;     // elements per 16 bytes
-  a.c_vec_ok = aligned16(d->C) && (d->ldc % cal == 0) && (d->c_stride0 % cal == 0) && (d->c_stride1 % cal == 0);
-  a.aux_vec_ok = d->aux && aligned16(d->aux) && (d->ldaux % cal == 0) && (d->aux_stride0 % cal == 0) &&
-                 (d->aux_stride1 % cal == 0);
-  hipStream_t st = as_stream(stream);
-
-  if (d->dtype_ab != W2V2_F32) {
-    const bool glds = !a.A.trans && !a.B.trans && a.A.vec_ok && a.B.vec_ok && (d->K % 64 == 0) && d->K >= 64 &&
-                      !g_w2v2_no_glds;
-    // 64-column tiles for N <= 64 -- and, on the LDS-DMA kernel, wherever 128-column tiles would leave more than half of
-    // the CUs without a workgroup (the AAM logits: 66 x 5994 x 1536 is 47 tiles of 128 x 128 on 256 CUs streaming 18 MB
-    // of class weights: 33.6 -> 29.3 us; the register-staged kernel measured 2 us slower with the narrower tile)
-    const bool narrow = d->N <= 64 || (glds && cdiv(d->M, 128) * cdiv(d->N, 128) * split * d->batch * 2 <=
-                                                   (int64_t)w2v2_gemm_device_cus());
-    const int BM = 128, BN = narrow ? 64 : 128;
-    a.tiles_m = (int)cdiv(d->M, BM); a.tiles_n = (int)cdiv(d->N, BN);
-    a.k_per_split = (int)(cdiv(cdiv(d->K, split), 64) * 64);
-    if (a.k_per_split == 0) a.k_per_split = 64;
-    dim3 grid(a.tiles_m * a.tiles_n, split, d->batch);
-    // 256x128 3-stage kernel for the encoder shapes; the conv stack (N = 512, M ~ 3e5) measures
-    // slightly faster on the 128x128 kernel at 2 workgroups per CU
-    // (two-term weights exist on this kernel only: such a request takes it whatever the shape)
-    const bool big = glds && split == 1 && !atomic &&
-                     (d->k_ext != 0 || (d->N >= g_w2v2_g3n && d->M >= 1024 && g_w2v2_glds3));
-    // 256x256 tiles when they fill the chip: >= 85 % of the CU slots of the last round busy (FFN1, dH, conv stack)
-    bool huge = false;
-    if (big && d->k_ext == 0 && d->N >= 512 && d->batch == 1 && g_w2v2_tile256) {
-      const int64_t t4 = cdiv(d->M, 256) * cdiv(d->N, 256), ncu = w2v2_gemm_device_cus();
-      // the phased kernel keeps its DMA sources as 32-bit element offsets from the operand base
-      auto extent = [](const w2v2_operand& o, int64_t rows, int64_t K) -> int64_t {
-        return (o.seg_len > 0 ? (rows / o.seg_len + 1) * o.seg_stride + o.seg_len * o.ld : rows * o.ld) + K;
-      };
-      const bool fits32 = extent(d->A, d->M, d->K) < (int64_t(1) << 31) && extent(d->B, d->N, d->K) < (int64_t(1) << 31);
-      // measured per shape with tools/gemm_shapes.py (FAMILIES=0,1,2,3,4): a 256x256 tile step runs ~1.2x the flops
-      // per second of a 256x128 one (1.25 below), so the larger tile wins whenever its last-round fill is not worse by more than
-      // that (conv3: 620 tiles = 0.81 vs 0.97 -> 174 vs 183 us; conv5: 156 tiles = 0.61 vs 0.61 -> 41 vs 47 us;
-      // FFN2-shaped N = 768 products: 117 tiles = 0.46 vs 0.91 -> 73 vs 52 us stay on the 256x128 ring)
-      const int64_t t3 = cdiv(d->M, 256) * cdiv(d->N, 128);
-      const double fill4 = (double)t4 / (double)(cdiv(t4, ncu) * ncu), fill3 = (double)t3 / (double)(cdiv(t3, ncu) * ncu);
-      // 16-bit outputs of the 256x256 kernels go through the full-line register epilogue only
-      const bool lines = d->dtype_c == W2V2_F32 ||
-                         (a.c_vec_ok && (d->N % 64 == 0) && (d->aux == nullptr || a.aux_vec_ok));
-      huge = lines && fill4 * 1.25 >= fill3 && t4 * 2 >= ncu &&
-             (double)d->N / (double)(cdiv(d->N, 256) * 256) >= 0.9 && fits32;
-    }
-    bool big_ = big;
-    if (g_w2v2_force != 0 && glds && split == 1 && !atomic && d->k_ext == 0 && d->batch == 1) {
-      auto extent = [](const w2v2_operand& o, int64_t rows, int64_t K) -> int64_t {
-        return (o.seg_len > 0 ? (rows / o.seg_len + 1) * o.seg_stride + o.seg_len * o.ld : rows * o.ld) + K;
-      };
-      big_ = g_w2v2_force >= 2;
-      huge = g_w2v2_force == 4 && extent(d->A, d->M, d->K) < (int64_t(1) << 31) && extent(d->B, d->N, d->K) < (int64_t(1) << 31) &&
-             (d->dtype_c == W2V2_F32 || (a.c_vec_ok && (d->N % 64 == 0) && (d->aux == nullptr || a.aux_vec_ok)));
-    }
-    if (d->k_ext != 0)
-      W2V2_REQUIRE(big && !huge && d->k_ext == d->K && d->n_ext_from >= 0 && d->n_ext_from % 128 == 0 &&
-                       d->b_lo_offset % 8 == 0,
-                   "w2v2_gemm: two-term weights (k_ext) need k_ext == K, n_ext_from %% 128 == 0 and K-contiguous 16-byte "
-                   "aligned operands with K %% 64 == 0 (M=%d N=%d K=%d)", d->M, d->N, d->K);
-    // TE = operand element type (selects the MFMA instruction), TC = float or TE
-    // Store flavour of the full-line register epilogues: write-through (sc1) stores leave nothing dirty in L2 at the
-    // kernel's end (round 3: -0.4 % step time over all writers).  Re-measured per product in round 4
-    // (tools/gemm_attrib.py variants 32 / 64, profiles/r04_gemm_attrib.txt): with the ten-instruction IEEE division gone
-    // from the GELU epilogue, write-through wins or ties on every product of the step (FFN1 68.8 vs 76.3 us plain, dH 60.0
-    // vs 64.2, conv1 568 vs 562), and in-step 12.29 vs 12.48 ms with plain stores everywhere.  W2V2_EPI_WT=0 forces plain
-    // write-back stores (A/B).
-    {
-      static const char* wt_env = getenv("W2V2_EPI_WT");
-      a.wt_stores = wt_env ? (wt_env[0] != '0') : 1;
-    }
-    // Phased kernel, placement of the DMA pieces: in a phase's read segment (the product) or between its MFMAs
-    // (W2V2_PH_LATE=1, tools only).  Stand-alone, back to back, the heavy-epilogue products look faster with the pieces
-    // between the MFMAs (FFN1 80.3 -> 69.3 us, dH 67.4 -> 63.8; the main loop itself is unchanged, "-epi" columns of
-    // profiles/r04_gemm_attrib.txt) -- IN THE STEP the same choice measured +0.6 % (11.50 -> 11.57 ms, three ABAB rounds
-    // in one call): an artefact of timing one kernel against itself, not a property of the kernel.  Off.
-    {
-      static const char* late_env = getenv("W2V2_PH_LATE");
-      a.late_dma = late_env ? (late_env[0] != '0') : 0;
-    }
-    g_gemm_family = huge ? 4 : big_ ? 2 : glds ? 1 : 3;
-    if (g_gemm_dry) return 0;                     // w2v2_gemm_kernel_of: the dispatch decision only, nothing launched
-#define W2V2_GEMM_LAUNCH(TE, TC)                                                                         \
-    do {                                                                                                 \
-      if (huge) w2v2_launch_phased_256x256(a, d->dtype_ab, d->dtype_c, d->M, d->N, d->batch, st);        \
-      else if (big_) w2v2_launch_ring_256x128(a, d->dtype_ab, d->dtype_c, d->M, d->N, d->batch, g_w2v2_persistent, st); \
-      else if (glds) { if (narrow) launch_glds<TE, 4, 2, TC>(a, grid, st); else launch_glds<TE, 4, 4, TC>(a, grid, st); } \
-      else { if (narrow) launch_bf16<TE, 4, 2, TC>(a, grid, st); else launch_bf16<TE, 4, 4, TC>(a, grid, st); }         \
-    } while (0)
-    if (big_ && !huge)
-      a.defer_ok = defer_env && d->dtype_c != W2V2_F32 && a.c_vec_ok && (d->N % 128 == 0) && !atomic &&
-                   (d->aux == nullptr || a.aux_vec_ok) &&
-                   d->epilogue != W2V2_EPI_BIAS_GELU && d->epilogue != W2V2_EPI_BIAS_GELU_GRAD;
-    if (d->dtype_ab == W2V2_BF16) {
-      if (d->dtype_c == W2V2_F32) W2V2_GEMM_LAUNCH(bf16_t, float); else W2V2_GEMM_LAUNCH(bf16_t, bf16_t);
-    } else {
-      if (d->dtype_c == W2V2_F32) W2V2_GEMM_LAUNCH(f16_t, float); else W2V2_GEMM_LAUNCH(f16_t, f16_t);
-    }
-#undef W2V2_GEMM_LAUNCH
-  } else {
-    W2V2_REQUIRE(d->dtype_c == W2V2_F32, "w2v2_gemm: f32 operands need an f32 C");
-    // f32 rows are 16-byte vectors of FOUR elements
-    auto vec4 = [&](const w2v2_operand& o) {
-      return aligned16(o.ptr) && (o.ld % 4 == 0) && (o.seg_stride % 4 == 0) && (o.stride0 % 4 == 0) && (o.stride1 % 4 == 0);
-    };
-    a.A.vec_ok = vec4(d->A); a.B.vec_ok = vec4(d->B);
-    g_gemm_family = w2v2_gemm_f32_dma_rows(a, d->M, d->N, d->K, split, d->batch) > 0 ? 10 : 9;   // 10: gemm_f32_dma.hip
-    if (g_gemm_dry) return 0;
-    w2v2_launch_gemm_f32(a, d->M, d->N, d->K, split, d->batch, st);       // gemm_f32.hip
-  }
-  W2V2_CHECK_LAUNCH("w2v2_gemm");
   return 0;
 }

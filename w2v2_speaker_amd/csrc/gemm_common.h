@@ -40,12 +40,15 @@ struct GemmArgs {
   int c_vec_ok;    // 8-element vector stores to C legal
   int aux_vec_ok;  // 8-element vector access to aux legal
   int defer_ok;    // 256x128 ring kernel: stores of a tile may be issued under the next tile's main loop
-  int wt_stores;   // full-line epilogue: 1 = write-through (sc1) stores, 0 = plain write-back stores (see w2v2_gemm)
-  int late_dma;    // phased kernel: DMA pieces of a phase issued between its MFMAs (host-side choice, see w2v2_gemm)
+  int wt_stores;   // full-line epilogue: 1 = write-through (sc1) stores, 0 = plain write-back stores (see gemm_route)
+  int late_dma;    // phased kernel: DMA pieces of a phase issued between its MFMAs (host-side choice, see gemm_route)
   // two-term weights (w2v2_hip.h): tiles with n0 >= n_ext_from run k_ext more K steps against B + b_lo_off
   int k_ext, n_ext_from;
   int64_t b_lo_off;
-  int xcd_tiles;   // gemm_f32_dma: 1 = every XCD takes a contiguous run of tiles (set by w2v2_launch_gemm_f32)
+  int xcd_tiles;   // gemm_f32_dma: 1 = every XCD takes a contiguous run of tiles (set by w2v2_launch_gemm_f32), else 0
+  // tools only: time-attribution bits of the w2v2_tune_* hooks.  Read by the DBG instantiations of the kernels alone (the
+  // product kernels never look at it); last, so that every other field keeps its kernel-argument offset
+  int dbg_bits;
 };
 
 __device__ __forceinline__ int64_t outer_off(const OpDev& o, int64_t idx) {
@@ -358,7 +361,7 @@ __device__ __forceinline__ void epilogue_direct(const GemmArgs& g, TC* __restric
 // and one instruction writes 8 rows x 128 contiguous bytes.  aux rows are FETCHED in the same pattern (packed, four
 // fragments = 32 registers at a time, all loads of a batch in flight before the first use) and swapped back.
 // host-side eligibility (wave-uniform): 16-bit C (and aux), 16-byte aligned rows, every 64-column wave tile inside N
-__device__ __forceinline__ bool lines_ok(const GemmArgs& g) {
+__host__ __device__ __forceinline__ bool lines_ok(const GemmArgs& g) {
   return g.c_vec_ok && !g.atomic && (g.N & 63) == 0 && (g.aux == nullptr || g.aux_vec_ok);
 }
 
@@ -523,29 +526,27 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 typedef __attribute__((address_space(1))) const void gvoid_t;
 typedef __attribute__((address_space(3))) void lvoid_t;
 
-// CUs the persistent grids may fill (W2V2_RESERVE_CUS keeps some out for RCCL's channels); gemm.hip
-// Kernel-timestamp timing of single launches (w2v2_gemm_timed): when a slot's events are pending, the launch helpers of
-// the two dominant kernels hand them to hipExtLaunchKernelGGL, which stamps the dispatch's own begin / end (what
-// rocprofv3 reports) instead of bracketing the launch with two stream events (+3 us of dispatch time per launch).
-struct W2v2PendingTimer { hipEvent_t start, stop; bool armed; };
-W2v2PendingTimer& w2v2_pending_timer();
-#define W2V2_LAUNCH_MAYBE_TIMED(KERNEL, GRID, BLOCK, LDS, STREAM, ARGS)                                         \
-  do {                                                                                                          \
-    W2v2PendingTimer& pt_ = w2v2_pending_timer();                                                               \
-    if (pt_.armed) {                                                                                            \
-      pt_.armed = false;                                                                                        \
-      hipExtLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, pt_.start, pt_.stop, 0, ARGS);                    \
-    } else {                                                                                                    \
-      hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, ARGS);                                               \
-    }                                                                                                           \
-  } while (0)
+// `s_waitcnt vmcnt(N)` in front of a barrier: all but the N most recent vector-memory operations of this wave (its
+// LDS-DMA pieces) have landed
+template <int N> __device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// CUs the persistent grids may fill: w2v2_device_cus() (common.h) minus W2V2_RESERVE_CUS, which keeps some out for RCCL's
+// channels -- data-parallel runs: the persistent ring kernels fill every CU's registers, so RCCL's all-reduce workgroups
+// (side stream) only run between them
 int w2v2_gemm_device_cus();
-// cross-file launchers: dtype_ab / dtype_c are the W2V2_* codes (16-bit operands; C 16-bit of the same type or f32)
-void w2v2_launch_ring_256x128(const GemmArgs& a, int dtype_ab, int dtype_c, int M, int N, int batch, bool persistent,
-                              hipStream_t st);
-void w2v2_launch_phased_256x256(const GemmArgs& a, int dtype_ab, int dtype_c, int M, int N, int batch, hipStream_t st);
-// gemm_f32.hip: exact-f32 products (f32 operands, f32 C); split = split-K factor (atomics), chooses its own tile
-void w2v2_launch_gemm_f32(GemmArgs a, int M, int N, int K, int split, int batch, hipStream_t st);
+// cross-file launchers: dtype_ab / dtype_c are the W2V2_* codes (16-bit operands; C 16-bit of the same type or f32);
+// != 0: the launch could not be prepared (message in w2v2_last_error)
+int w2v2_launch_ring_256x128(const GemmArgs& a, int dtype_ab, int dtype_c, int M, int N, int batch, bool persistent,
+                             hipStream_t st);
+int w2v2_launch_phased_256x256(const GemmArgs& a, int dtype_ab, int dtype_c, int M, int N, int batch, hipStream_t st);
+// gemm_f32.hip: exact-f32 products (f32 operands, f32 C); split = split-K factor (atomics); dma_rows = what
+// w2v2_gemm_f32_dma_rows answered for this product (0: register-staged kernel, which chooses its own tile)
+int w2v2_launch_gemm_f32(GemmArgs a, int M, int N, int K, int split, int batch, int dma_rows, hipStream_t st);
 int w2v2_gemm_f32_dma_rows(const GemmArgs& a, int M, int N, int K, int split, int batch);   // gemm_f32.hip: 0 = register-staged
-// gemm_f32_dma.hip: the LDS-DMA variant, (32 fi) x 128 tiles, nst-stage ring; the caller has checked eligibility
-void w2v2_launch_gemm_f32_dma(const GemmArgs& a, int M, int N, int split, int batch, int fi, int nst, hipStream_t st);
+// gemm_f32_dma.hip: the LDS-DMA variant, (32 fi) x 128 tiles, nst-stage ring; the caller has checked eligibility.
+// a.dbg_bits != 0 selects the DBG instantiation (tools; w2v2_gemm_f32_dma_has_dbg says where one exists)
+int w2v2_launch_gemm_f32_dma(const GemmArgs& a, int M, int N, int split, int batch, int fi, int nst, hipStream_t st);
+bool w2v2_gemm_f32_dma_has_dbg(const GemmArgs& a, int fi);

@@ -250,33 +250,29 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_mfma_kernel(const GemmArgs g)
 }
 
 template <bool TA, bool TB, int BM, int BN>
-static void launch_f32(GemmArgs a, int M, int N, int split, int batch, hipStream_t st) {
+static int launch_f32(GemmArgs a, int M, int N, int split, int batch, hipStream_t st) {
   constexpr size_t lds = sizeof(float) * 2 * 32 * ((BM + (TA ? 4 : 1)) + (BN + (TB ? 4 : 1)));
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_mfma_kernel<TA, TB, BM, BN>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
   a.tiles_m = (int)cdiv(M, BM);
   a.tiles_n = (int)cdiv(N, BN);
   dim3 grid(a.tiles_m * a.tiles_n, split, batch);
-  hipLaunchKernelGGL((gemm_f32_mfma_kernel<TA, TB, BM, BN>), grid, dim3(256), lds, st, a);
+  return w2v2_launch_lds<&gemm_f32_mfma_kernel<TA, TB, BM, BN>>("gemm_f32_mfma_kernel", grid, dim3(256), lds, st, a);
 }
 
 template <int BM, int BN>
-static void launch_f32_layout(const GemmArgs& a, int M, int N, int split, int batch, hipStream_t st) {
-  if (!a.A.trans && !a.B.trans) launch_f32<false, false, BM, BN>(a, M, N, split, batch, st);
-  else if (!a.A.trans && a.B.trans) launch_f32<false, true, BM, BN>(a, M, N, split, batch, st);
-  else if (a.A.trans && !a.B.trans) launch_f32<true, false, BM, BN>(a, M, N, split, batch, st);
-  else launch_f32<true, true, BM, BN>(a, M, N, split, batch, st);
+static int launch_f32_layout(const GemmArgs& a, int M, int N, int split, int batch, hipStream_t st) {
+  if (!a.A.trans && !a.B.trans) return launch_f32<false, false, BM, BN>(a, M, N, split, batch, st);
+  if (!a.A.trans && a.B.trans) return launch_f32<false, true, BM, BN>(a, M, N, split, batch, st);
+  if (a.A.trans && !a.B.trans) return launch_f32<true, false, BM, BN>(a, M, N, split, batch, st);
+  return launch_f32<true, true, BM, BN>(a, M, N, split, batch, st);
 }
 
 // tools: 0 = the choice below; 1..4 = the register-staged kernel on 128x128 / 64x128 / 128x64 / 64x64; 11..15 = the LDS-DMA
 // kernel (gemm_f32_dma.hip) on (32 fi) x 128 tiles, fi = t - 10; + 100: the same with XCD-contiguous tiles (+ 200, 400, 800:
-// timing-only variants without the loop's DMA / barrier / vmcnt wait).  An ineligible product ignores a DMA code.
+// timing-only variants without the loop's DMA / barrier / vmcnt wait -- the DBG instantiation of the kernel, which exists
+// where tools/f32_gemm_bench.py times it, w2v2_gemm_f32_dma_has_dbg; elsewhere these three bits are ignored).  An
+// ineligible product ignores a DMA code.
 static int g_f32_tile_force = 0;
-static int g_f32_last_kernel = 0;
+static int g_f32_last_kernel = 0;     // 0 = register-staged, else 10 fi + stages (+ 1000: the DBG instantiation)
 extern "C" int w2v2_gemm_f32_last_kernel(void) { return g_f32_last_kernel; }
 extern "C" int w2v2_tune_gemm_f32_tile(int t) {
   const int old = g_f32_tile_force;
@@ -286,11 +282,10 @@ extern "C" int w2v2_tune_gemm_f32_tile(int t) {
 }
 
 // Which kernel an exact-f32 product runs on: 0 = the register-staged kernel below, else the tile height fi (rows = 32 fi)
-// of the LDS-DMA kernel (gemm_f32_dma.hip).  Also asked by w2v2_gemm's dry run (w2v2_gemm_kernel_of: family 10 instead of 9).
+// of the LDS-DMA kernel (gemm_f32_dma.hip).  Part of w2v2_gemm's routing (family 10 instead of 9): decides only.
 int w2v2_gemm_f32_dma_rows(const GemmArgs& a, int M, int N, int K, int split, int batch) {
   // plain 16-byte aligned operands whose every 16-byte piece is whole
-  static const bool no_dma = [] { const char* e = getenv("W2V2_F32_NO_DMA"); return e && e[0] != '0'; }();
-  const bool dma_ok = !no_dma && a.A.vec_ok && a.B.vec_ok && a.A.seg_len <= 0 && a.B.seg_len <= 0 && K % 4 == 0 &&
+  const bool dma_ok = !w2v2_switches().f32_no_dma && a.A.vec_ok && a.B.vec_ok && a.A.seg_len <= 0 && a.B.seg_len <= 0 && K % 4 == 0 &&
                       (!a.A.trans || M % 4 == 0) && (!a.B.trans || N % 4 == 0) && M > 64 && N > 64;
   if (!dma_ok) return 0;
   const int force = g_f32_tile_force % 100;
@@ -316,9 +311,7 @@ int w2v2_gemm_f32_dma_rows(const GemmArgs& a, int M, int N, int K, int split, in
   return fi;
 }
 
-void w2v2_launch_gemm_f32(GemmArgs a, int M, int N, int K, int split, int batch, hipStream_t st) {
-  a.k_per_split = (int)(cdiv(cdiv(K, split), 32) * 32);
-  if (a.k_per_split == 0) a.k_per_split = 32;
+int w2v2_launch_gemm_f32(GemmArgs a, int M, int N, int K, int split, int batch, int dma_rows, hipStream_t st) {
   // Tile choice, from every product of the ECAPA step timed on each tile (tools/ecapa_gemm_shapes.py F32_TILE=1..4,
   // round 5: best-per-shape 19.3 ms against 20.2 for the round-4 rule "largest tile that fills 60 % of the slots"):
   //   * 128 x 128 (2 workgroups per CU = 512 slots, the fastest main loop) when the grid is at least ~0.9 of a round AND
@@ -329,12 +322,12 @@ void w2v2_launch_gemm_f32(GemmArgs a, int M, int N, int K, int split, int batch,
   //   * else 64 x 64: skinny and short-K products (N = 128 Res2Net convolutions, K = 128 .. 200) are bound by the
   //     global-load latency of a 12-trip K loop, which only more resident workgroups hide (41.7 -> 30.6 us).
   const int64_t cus = w2v2_gemm_device_cus();
-  const int fi = w2v2_gemm_f32_dma_rows(a, M, N, K, split, batch);
-  if (fi > 0) {
-    a.xcd_tiles = g_f32_tile_force / 100;         // bit 0: XCD-contiguous tiles; bits 1-3: timing-only variants (tools)
-    g_f32_last_kernel = 10 * fi + 2;
-    w2v2_launch_gemm_f32_dma(a, M, N, split, batch, fi, 2, st);
-    return;
+  if (const int fi = dma_rows) {
+    const int code = g_f32_tile_force / 100;      // bit 0: XCD-contiguous tiles; bits 1-3: timing-only variants (tools)
+    a.xcd_tiles = code & 1;
+    a.dbg_bits = w2v2_gemm_f32_dma_has_dbg(a, fi) ? code >> 1 : 0;
+    g_f32_last_kernel = 10 * fi + 2 + (a.dbg_bits ? 1000 : 0);
+    return w2v2_launch_gemm_f32_dma(a, M, N, split, batch, fi, 2, st);
   }
   g_f32_last_kernel = 0;
   auto wgs = [&](int bm, int bn) { return cdiv(M, bm) * cdiv(N, bn) * (int64_t)split * batch; };
@@ -356,8 +349,8 @@ void w2v2_launch_gemm_f32(GemmArgs a, int M, int N, int K, int split, int batch,
     case 4: bm = 64; bn = 64; break;
     default: break;
   }
-  if (bm == 128 && bn == 128) launch_f32_layout<128, 128>(a, M, N, split, batch, st);
-  else if (bm == 64 && bn == 128) launch_f32_layout<64, 128>(a, M, N, split, batch, st);
-  else if (bm == 128 && bn == 64) launch_f32_layout<128, 64>(a, M, N, split, batch, st);
-  else launch_f32_layout<64, 64>(a, M, N, split, batch, st);
+  if (bm == 128 && bn == 128) return launch_f32_layout<128, 128>(a, M, N, split, batch, st);
+  if (bm == 64 && bn == 128) return launch_f32_layout<64, 128>(a, M, N, split, batch, st);
+  if (bm == 128 && bn == 64) return launch_f32_layout<128, 64>(a, M, N, split, batch, st);
+  return launch_f32_layout<64, 64>(a, M, N, split, batch, st);
 }

@@ -38,22 +38,15 @@ template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
 
 __device__ __attribute__((aligned(16))) float g_f32_zero16[4] = {0.f, 0.f, 0.f, 0.f};
 
-// One 1 KiB LDS-DMA piece: 16 bytes per lane from `src` to LDS byte address lds + 16 lane.  Written as inline assembly on
-// purpose: for the builtin (__builtin_amdgcn_global_load_lds) the compiler's waitcnt pass treats every later LDS read as
-// possibly aliasing the piece and puts `s_waitcnt vmcnt(0)` in front of the first ds_read behind it -- in this loop that
-// is the fragment read of the NEXT k-group, so every K tile waited out the full latency of the pieces it had just
-// issued (tile kt + 1's, which nothing reads before the next barrier).  The ring's own counted waits below order the
-// pieces against their readers.  Nothing else in this kernel uses M0.
-__device__ __forceinline__ void f32_dma16(const float* src, uint32_t lds) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(src) : "memory");
-}
-
-template <int N> __device__ __forceinline__ void f32_wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <bool TA, bool TB, int FI, int NST>
+// The 1 KiB LDS-DMA pieces are w2v2_dma16 (common.h: inline assembly, so that the compiler's waitcnt pass does not put
+// `s_waitcnt vmcnt(0)` in front of the first ds_read behind a piece -- in this loop that is the fragment read of the NEXT
+// k-group, so every K tile waited out the full latency of the pieces it had just issued, tile kt + 1's, which nothing
+// reads before the next barrier).  The ring's own counted waits below order the pieces against their readers.
+//
+// DBG (tools only, w2v2_tune_gemm_f32_tile + 200 / 400 / 800 -> g.dbg_bits 1 / 2 / 4): the same kernel without the loop's
+// DMA pieces / barrier / vmcnt wait, for time attribution (garbage results).  The product kernel (DBG = false) has none of
+// these tests and never reads g.dbg_bits.
+template <bool TA, bool TB, int FI, int NST, bool DBG = false>
 __global__ __launch_bounds__(256, 2) void gemm_f32_dma_kernel(const GemmArgs g) {
   constexpr int BM = 32 * FI, BN = 128, BK = 32;
   constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;
@@ -66,7 +59,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_dma_kernel(const GemmArgs g) 
   const int kl = lane >> 5, rl = lane & 31;
   const int ntile = g.tiles_m * g.tiles_n;
   const int tile = (g.xcd_tiles & 1) ? xcd_remap(blockIdx.x, ntile) : (int)blockIdx.x;
-  const bool dbg_nodma = g.xcd_tiles & 2, dbg_nobar = g.xcd_tiles & 4, dbg_nowait = g.xcd_tiles & 8;      // tools only (garbage results)
+  const int dbg = DBG ? g.dbg_bits : 0;
+  const bool dbg_nodma = dbg & 1, dbg_nobar = dbg & 2, dbg_nowait = dbg & 4;
   const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
   const int z = blockIdx.z;
@@ -125,7 +119,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_dma_kernel(const GemmArgs g) 
     constexpr int p = decltype(pc)::value;
     constexpr int off = p < FI ? p * 1024 : A_BYTES + (p - FI) * 1024;      // + the wave's part, in stage_lds
     const char* s = kof[p] < krem ? pp[p] : reinterpret_cast<const char*>(zero);
-    f32_dma16(reinterpret_cast<const float*>(s), stage_lds + off);
+    w2v2_dma16(s, stage_lds + off);
     pp[p] += inc[p];
   };
   // LDS byte address of this wave's first A piece of stage st (its B pieces: + A_BYTES - the A part + the B part)
@@ -203,8 +197,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_dma_kernel(const GemmArgs g) 
   int st = 0;                                        // stage of tile kt
   for (int kt = 0; kt < nk; ++kt) {
     if (dbg_nowait) {
-    } else if (NST > 2 && kt + NST - 1 <= nk) f32_wait_vmcnt<(NST - 2) * PW>();   // NST - 1 tiles issued, the oldest must be in
-    else f32_wait_vmcnt<0>();
+    } else if (NST > 2 && kt + NST - 1 <= nk) wait_vmcnt<(NST - 2) * PW>();   // NST - 1 tiles issued, the oldest must be in
+    else wait_vmcnt<0>();
     if (!dbg_nobar) __builtin_amdgcn_s_barrier();    // tile kt visible to all; stage (kt - 1) % NST free again
     const int nt = kt + NST - 1;                     // the tile whose pieces go out under this one, into the stage just freed
     const bool more = nt < nk && !dbg_nodma;
@@ -284,44 +278,45 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_dma_kernel(const GemmArgs g) 
     }
 }
 
-template <bool TA, bool TB, int FI, int NST>
-static void launch_dma(GemmArgs a, int M, int N, int split, int batch, hipStream_t st) {
+template <bool TA, bool TB, int FI, int NST, bool DBG = false>
+static int launch_dma(GemmArgs a, int M, int N, int split, int batch, hipStream_t st) {
   constexpr size_t lds = (size_t)NST * (32 * FI + 128) * 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_dma_kernel<TA, TB, FI, NST>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-    if (getenv("W2V2_F32_OCC")) {                     // tools: resident workgroups per CU of this instantiation
-      int nb = -1;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gemm_f32_dma_kernel<TA, TB, FI, NST>, 256, lds);
-      fprintf(stderr, "gemm_f32_dma<%d,%d,FI=%d,NST=%d>: %zu B LDS, %d workgroups per CU\n", (int)TA, (int)TB, FI, NST, lds, nb);
-    }
+  static bool first = true;
+  if (first && getenv("W2V2_F32_OCC")) {              // tools: resident workgroups per CU of this instantiation
+    int nb = -1;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gemm_f32_dma_kernel<TA, TB, FI, NST, DBG>, 256, lds);
+    fprintf(stderr, "gemm_f32_dma<%d,%d,FI=%d,NST=%d>: %zu B LDS, %d workgroups per CU\n", (int)TA, (int)TB, FI, NST, lds, nb);
   }
+  first = false;
   a.tiles_m = (int)cdiv(M, 32 * FI);
   a.tiles_n = (int)cdiv(N, 128);
   dim3 grid(a.tiles_m * a.tiles_n, split, batch);
-  hipLaunchKernelGGL((gemm_f32_dma_kernel<TA, TB, FI, NST>), grid, dim3(256), lds, st, a);
+  return w2v2_launch_lds<&gemm_f32_dma_kernel<TA, TB, FI, NST, DBG>>("gemm_f32_dma_kernel", grid, dim3(256), lds, st, a);
 }
 
+// The DBG instantiations: what tools/f32_gemm_bench.py times with the + 200 / 400 / 800 codes -- both operands
+// K-contiguous, the two tall tiles (codes x14 / x15)
+bool w2v2_gemm_f32_dma_has_dbg(const GemmArgs& a, int fi) { return !a.A.trans && !a.B.trans && (fi == 4 || fi == 5); }
+
 template <int FI, int NST>
-static void launch_dma_layout(const GemmArgs& a, int M, int N, int split, int batch, hipStream_t st) {
-  if (!a.A.trans && !a.B.trans) launch_dma<false, false, FI, NST>(a, M, N, split, batch, st);
-  else if (!a.A.trans && a.B.trans) launch_dma<false, true, FI, NST>(a, M, N, split, batch, st);
-  else if (a.A.trans && !a.B.trans) launch_dma<true, false, FI, NST>(a, M, N, split, batch, st);
-  else launch_dma<true, true, FI, NST>(a, M, N, split, batch, st);
+static int launch_dma_layout(const GemmArgs& a, int M, int N, int split, int batch, hipStream_t st) {
+  if constexpr (FI >= 4) {
+    if (a.dbg_bits != 0) return launch_dma<false, false, FI, NST, true>(a, M, N, split, batch, st);   // (has_dbg: the caller's test)
+  }
+  if (!a.A.trans && !a.B.trans) return launch_dma<false, false, FI, NST>(a, M, N, split, batch, st);
+  if (!a.A.trans && a.B.trans) return launch_dma<false, true, FI, NST>(a, M, N, split, batch, st);
+  if (a.A.trans && !a.B.trans) return launch_dma<true, false, FI, NST>(a, M, N, split, batch, st);
+  return launch_dma<true, true, FI, NST>(a, M, N, split, batch, st);
 }
 
 // fi = 1..5 (rows = 32 fi).  nst: the kernel is written for any ring depth; only the two-stage ring is instantiated -- a
 // third stage (fi <= 2: 60 / 72 KiB) halves the resident workgroups and measured 5-20 % slower on every product.
-void w2v2_launch_gemm_f32_dma(const GemmArgs& a, int M, int N, int split, int batch, int fi, int nst, hipStream_t st) {
-#define F32_DMA_CASE(FI_, NST_) launch_dma_layout<FI_, NST_>(a, M, N, split, batch, st)
+int w2v2_launch_gemm_f32_dma(const GemmArgs& a, int M, int N, int split, int batch, int fi, int nst, hipStream_t st) {
   switch (fi * 10 + nst) {
-    case 12: F32_DMA_CASE(1, 2); break;
-    case 22: F32_DMA_CASE(2, 2); break;
-    case 32: F32_DMA_CASE(3, 2); break;
-    case 42: F32_DMA_CASE(4, 2); break;
-    default: F32_DMA_CASE(5, 2); break;
+    case 12: return launch_dma_layout<1, 2>(a, M, N, split, batch, st);
+    case 22: return launch_dma_layout<2, 2>(a, M, N, split, batch, st);
+    case 32: return launch_dma_layout<3, 2>(a, M, N, split, batch, st);
+    case 42: return launch_dma_layout<4, 2>(a, M, N, split, batch, st);
+    default: return launch_dma_layout<5, 2>(a, M, N, split, batch, st);
   }
-#undef F32_DMA_CASE
 }

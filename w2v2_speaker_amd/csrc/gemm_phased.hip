@@ -275,30 +275,30 @@ __global__ __launch_bounds__(512) void gemm16_phased_256x256_kernel(const GemmAr
   }   // tile loop
 }
 
-static int g_w2v2_dbg = 0;            // tools only (w2v2_tune_gemm_debug): DBG variant of the phased kernel, fp16 in / fp16 out
+static int g_ph_dbg = 0;              // tools only (w2v2_tune_gemm_debug): DBG variant of the phased kernel, fp16 in / fp16 out
+extern "C" int w2v2_tune_gemm_debug(int bits) {
+  const int old = g_ph_dbg;
+  g_ph_dbg = bits;
+  return old;
+}
+
 template <typename TE, typename TC, int DBG = 0>
-static void launch_ph(GemmArgs a, int M, int N, int batch, hipStream_t st) {
+static int launch_ph(GemmArgs a, int M, int N, int batch, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * (256 + 256) * 64 * sizeof(bf16_t);   // 128 KiB
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm16_phased_256x256_kernel<TE, TC, DBG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
   a.tiles_m = (int)cdiv(M, 256);
   a.tiles_n = (int)cdiv(N, 256);
   const int tiles = a.tiles_m * a.tiles_n;
   const int ncu = w2v2_gemm_device_cus();
   dim3 grid(tiles < ncu ? tiles : ncu, 1, batch);
-  W2V2_LAUNCH_MAYBE_TIMED((gemm16_phased_256x256_kernel<TE, TC, DBG>), grid, dim3(512), lds, st, a);
+  return w2v2_launch_lds<&gemm16_phased_256x256_kernel<TE, TC, DBG>, true>("gemm16_phased_256x256_kernel", grid, dim3(512), lds, st, a);
 }
 template <typename TE, typename TC>
-static void launch_ph_dbg(GemmArgs a, int M, int N, int batch, hipStream_t st) {
-  if (g_w2v2_dbg & 192) a.wt_stores = (g_w2v2_dbg & 128) ? 1 : 0;    // tools: bit 6 forces plain, bit 7 write-through stores
-  const int g_w2v2_dbg = ::g_w2v2_dbg & 63;
-  if (g_w2v2_dbg == 0 && a.late_dma) return launch_ph<TE, TC, 32>(a, M, N, batch, st);   // the product's second variant
+static int launch_ph_dbg(GemmArgs a, int M, int N, int batch, hipStream_t st) {
+  if (g_ph_dbg & 192) a.wt_stores = (g_ph_dbg & 128) ? 1 : 0;    // tools: bit 6 forces plain, bit 7 write-through stores
+  const int variant = g_ph_dbg & 63;
+  if (variant == 0 && a.late_dma) return launch_ph<TE, TC, 32>(a, M, N, batch, st);   // the product's second variant
   if constexpr (std::is_same<TE, f16_t>::value && std::is_same<TC, f16_t>::value) {
-    switch (g_w2v2_dbg) {
+    switch (variant) {
       case 1: return launch_ph<TE, TC, 1>(a, M, N, batch, st);
       case 2: return launch_ph<TE, TC, 2>(a, M, N, batch, st);
       case 4: return launch_ph<TE, TC, 4>(a, M, N, batch, st);
@@ -310,24 +310,13 @@ static void launch_ph_dbg(GemmArgs a, int M, int N, int batch, hipStream_t st) {
       case 24: return launch_ph<TE, TC, 24>(a, M, N, batch, st);
       case 48: return launch_ph<TE, TC, 0>(a, M, N, batch, st);    // tools: the read-segment placement whatever the host chose
       case 40: return launch_ph<TE, TC, 40>(a, M, N, batch, st);
-
       default: break;
     }
   }
-  launch_ph<TE, TC>(a, M, N, batch, st);
+  return launch_ph<TE, TC>(a, M, N, batch, st);
 }
-void w2v2_launch_phased_256x256(const GemmArgs& a, int dtype_ab, int dtype_c, int M, int N, int batch, hipStream_t st) {
-  if (dtype_ab == W2V2_BF16) {
-    if (dtype_c == W2V2_F32) launch_ph_dbg<bf16_t, float>(a, M, N, batch, st);
-    else launch_ph_dbg<bf16_t, bf16_t>(a, M, N, batch, st);
-  } else {
-    if (dtype_c == W2V2_F32) launch_ph_dbg<f16_t, float>(a, M, N, batch, st);
-    else launch_ph_dbg<f16_t, f16_t>(a, M, N, batch, st);
-  }
-}
-
-extern "C" int w2v2_tune_gemm_debug(int bits) {
-  const int old = g_w2v2_dbg;
-  g_w2v2_dbg = bits;
-  return old;
+int w2v2_launch_phased_256x256(const GemmArgs& a, int dtype_ab, int dtype_c, int M, int N, int batch, hipStream_t st) {
+  if (dtype_ab == W2V2_BF16)
+    return dtype_c == W2V2_F32 ? launch_ph_dbg<bf16_t, float>(a, M, N, batch, st) : launch_ph_dbg<bf16_t, bf16_t>(a, M, N, batch, st);
+  return dtype_c == W2V2_F32 ? launch_ph_dbg<f16_t, float>(a, M, N, batch, st) : launch_ph_dbg<f16_t, f16_t>(a, M, N, batch, st);
 }

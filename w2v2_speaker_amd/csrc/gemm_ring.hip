@@ -8,14 +8,6 @@
 // as 4x2, 64x64 per wave, 87 FLOP/B) and a 3-stage LDS ring (144 KiB) with a COUNTED wait: while tile t
 // is multiplied, tiles t+1 and t+2 are in flight; per K tile one raw s_barrier and `s_waitcnt vmcnt(G)`
 // (G = this wave's DMA pieces per stage), never vmcnt(0) in the loop.
-template <int S> __device__ __forceinline__ void wait_vmcnt() {
-  if constexpr (S == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (S == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (S == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (S == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else static_assert(S == 0 || S == 4 || S == 6 || S == 8, "unsupported count");
-}
-
 template <typename TE, typename TC, bool DBG = false>
 __global__ __launch_bounds__(512) void gemm16_ring_256x128_kernel(const GemmArgs g) {
   constexpr int BM = 256, BN = 128, FM = 4, FN = 4;
@@ -141,9 +133,9 @@ __global__ __launch_bounds__(512) void gemm16_ring_256x128_kernel(const GemmArgs
   };
   // multiply stage `base`; when kload >= 0 the DMA pieces of K tile kload go to `nxt`, spread over the MFMA groups
   // (issued back to back behind the barrier they keep both waves of a SIMD in the queue-limited DMA issue)
-  // tools only (w2v2_tune_gemm_ring_debug, carried in g.late_dma for ring launches; results are garbage):
+  // tools only (w2v2_tune_gemm_ring_debug -> g.dbg_bits, read by the DBG instantiation alone; results are garbage):
   //   1 = no DMA pieces in the steady-state loop, 2 = no barrier in the loop, 4 = no vmcnt wait in the loop, 8 = no fragment reads
-  const int dbg = DBG ? g.late_dma : 0;
+  const int dbg = DBG ? g.dbg_bits : 0;
   auto compute = [&](const bf16_t* base, bf16_t* nxt, int kload) {
     if (dbg & 1) kload = -1;
     const bf16_t* a0 = base + aoff + lo0;
@@ -259,26 +251,14 @@ __global__ __launch_bounds__(512) void gemm16_ring_256x128_kernel(const GemmArgs
 }
 
 template <typename TE, typename TC, bool DBG>
-static void launch_ring_v(GemmArgs a, int M, int N, int batch, bool persistent, hipStream_t st) {
+static int launch_ring_v(GemmArgs a, int M, int N, int batch, bool persistent, hipStream_t st) {
   constexpr size_t lds = (size_t)3 * (256 + 128) * 64 * sizeof(bf16_t);   // 144 KiB
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm16_ring_256x128_kernel<TE, TC, DBG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
   a.tiles_m = (int)cdiv(M, 256);
   a.tiles_n = (int)cdiv(N, 128);
   const int ncu = persistent ? w2v2_gemm_device_cus() : (1 << 30);
   const int tiles = a.tiles_m * a.tiles_n;
   dim3 grid(tiles < ncu ? tiles : ncu, 1, batch);
-  W2V2_LAUNCH_MAYBE_TIMED((gemm16_ring_256x128_kernel<TE, TC, DBG>), grid, dim3(512), lds, st, a);
-}
-template <typename TE, typename TC>
-static void launch_ring(GemmArgs a, int M, int N, int batch, bool persistent, hipStream_t st) {
-  if (a.late_dma != 0 && sizeof(TC) == 2 && sizeof(TE) == 2 && std::is_same<TE, f16_t>::value)
-    launch_ring_v<f16_t, f16_t, true>(a, M, N, batch, persistent, st);      // tools: attribution variants, fp16 in / fp16 out only
-  else launch_ring_v<TE, TC, false>(a, M, N, batch, persistent, st);
+  return w2v2_launch_lds<&gemm16_ring_256x128_kernel<TE, TC, DBG>, true>("gemm16_ring_256x128_kernel", grid, dim3(512), lds, st, a);
 }
 
 static int g_ring_dbg = 0;            // tools only: time-attribution variants of the ring kernel's K loop (garbage results)
@@ -287,15 +267,21 @@ extern "C" int w2v2_tune_gemm_ring_debug(int bits) {
   g_ring_dbg = bits & 63;          // bit 4: the attribution kernel with nothing removed (its own baseline); bit 5: no epilogue
   return old;
 }
-void w2v2_launch_ring_256x128(const GemmArgs& a_in, int dtype_ab, int dtype_c, int M, int N, int batch, bool persistent,
-                              hipStream_t st) {
-  GemmArgs a = a_in;
-  a.late_dma = g_ring_dbg;
-  if (dtype_ab == W2V2_BF16) {
-    if (dtype_c == W2V2_F32) launch_ring<bf16_t, float>(a, M, N, batch, persistent, st);
-    else launch_ring<bf16_t, bf16_t>(a, M, N, batch, persistent, st);
-  } else {
-    if (dtype_c == W2V2_F32) launch_ring<f16_t, float>(a, M, N, batch, persistent, st);
-    else launch_ring<f16_t, f16_t>(a, M, N, batch, persistent, st);
+template <typename TE, typename TC>
+static int launch_ring(GemmArgs a, int M, int N, int batch, bool persistent, hipStream_t st) {
+  if constexpr (std::is_same<TE, f16_t>::value && std::is_same<TC, f16_t>::value) {
+    if (g_ring_dbg != 0) {                                  // tools: attribution variants, fp16 in / fp16 out only
+      a.dbg_bits = g_ring_dbg;
+      return launch_ring_v<f16_t, f16_t, true>(a, M, N, batch, persistent, st);
+    }
   }
+  return launch_ring_v<TE, TC, false>(a, M, N, batch, persistent, st);
+}
+int w2v2_launch_ring_256x128(const GemmArgs& a, int dtype_ab, int dtype_c, int M, int N, int batch, bool persistent,
+                             hipStream_t st) {
+  if (dtype_ab == W2V2_BF16)
+    return dtype_c == W2V2_F32 ? launch_ring<bf16_t, float>(a, M, N, batch, persistent, st)
+                               : launch_ring<bf16_t, bf16_t>(a, M, N, batch, persistent, st);
+  return dtype_c == W2V2_F32 ? launch_ring<f16_t, float>(a, M, N, batch, persistent, st)
+                             : launch_ring<f16_t, f16_t>(a, M, N, batch, persistent, st);
 }

@@ -190,9 +190,9 @@ extern "C" int w2v2_weightnorm_pack(const float* g, const float* v, float* sumsq
   hipLaunchKernelGGL(tap_finalize_kernel, dim3(K), dim3(256), 0, st, sumsq + K, sumsq, K, nb);
   const size_t lds = ((size_t)Cg * (K + 1) + K) * sizeof(float);
   W2V2_DISPATCH_ACT(dtype, "weightnorm_pack", {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wn_pack_kernel<AT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(wn_pack_kernel<AT>, dim3(H, 2), dim3(256), lds, st, g, v, sumsq, (AT*)wf, (AT*)wb, Cg, K);
+    if (w2v2_launch_lds<&wn_pack_kernel<AT>>("wn_pack_kernel", dim3(H, 2), dim3(256), lds, st, g, v, (const float*)sumsq,
+                                             (AT*)wf, (AT*)wb, Cg, K) != 0)
+      return -1;
   });
   W2V2_CHECK_LAUNCH("weightnorm_pack");
   return 0;
@@ -266,9 +266,8 @@ extern "C" int w2v2_weightnorm_bwd(const float* g, const float* v, const float* 
   W2V2_REQUIRE(lds <= 160 * 1024, "weightnorm_bwd: group tile does not fit LDS (Cg=%d K=%d)", Cg, K);
   hipStream_t st = as_stream(stream);
   const int nb = wn_blocks(H);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wn_bwd_gather_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(wn_bwd_gather_kernel, dim3(H), dim3(256), lds, st, v, dwf, dv, dot + K, Cg, K);
+  if (w2v2_launch_lds<&wn_bwd_gather_kernel>("wn_bwd_gather_kernel", dim3(H), dim3(256), lds, st, v, dwf, dv, dot + K, Cg, K) != 0)
+    return -1;
   hipLaunchKernelGGL(tap_finalize_kernel, dim3(K), dim3(256), 0, st, dot + K, dot, K, nb);
   const int64_t total = (int64_t)H * Cg * K;
   int nbk = (int)(cdiv(total, 256) > 4096 ? 4096 : cdiv(total, 256));

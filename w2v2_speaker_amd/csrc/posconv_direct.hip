@@ -217,11 +217,11 @@ extern "C" int w2v2_posconv_direct(const void* xg, const void* w, void* out, voi
   hipStream_t st = as_stream(stream);
 #define PD_LAUNCH(TE_, MODE_, CG_)                                                                                  \
   do {                                                                                                               \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&posconv_direct_kernel<TE_, MODE_, CG_>),                 \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, PdGeom<CG_>::LDS);                          \
-    hipLaunchKernelGGL((posconv_direct_kernel<TE_, MODE_, CG_>), grid, dim3(256), PdGeom<CG_>::LDS, st,               \
-                       (const bf16_t*)xg, (const bf16_t*)w, (bf16_t*)out, (bf16_t*)aux, bias, B, T, G, K, ldc, mblocks, \
-                       xg_elems);                                                                                    \
+    if (w2v2_launch_lds<&posconv_direct_kernel<TE_, MODE_, CG_>>("posconv_direct_kernel", grid, dim3(256),            \
+                                                                 (size_t)PdGeom<CG_>::LDS, st, (const bf16_t*)xg,      \
+                                                                 (const bf16_t*)w, (bf16_t*)out, (bf16_t*)aux, bias, B, \
+                                                                 T, G, K, ldc, mblocks, xg_elems) != 0)               \
+      return -1;                                                                                                     \
   } while (0)
 #define PD_LAUNCH_T(TE_)                                                                                             \
   do {                                                                                                               \

@@ -179,15 +179,8 @@ int launch_posconv_wgrad(const bf16_t* dY, const bf16_t* xg, float* dwf, int B, 
   const int CG = 16 * NF;
   const size_t lds = (size_t)2 * (PW_TC + PW_TC + 4 * TW) * CG * 2;
   W2V2_REQUIRE(lds <= 160 * 1024, "posconv_wgrad: K=%d Cg=%d needs %zu bytes of LDS", K, CG, lds);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&posconv_wgrad_kernel<TE, NF, TW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((posconv_wgrad_kernel<TE, NF, TW>), dim3(G * (K / (4 * TW))), dim3(256), lds, st, dY, xg, dwf, B, T,
-                     H, G, K);
-  return 0;
+  return w2v2_launch_lds<&posconv_wgrad_kernel<TE, NF, TW>>("posconv_wgrad_kernel", dim3(G * (K / (4 * TW))), dim3(256), lds,
+                                                            st, dY, xg, dwf, B, T, H, G, K);
 }
 
 }  // namespace

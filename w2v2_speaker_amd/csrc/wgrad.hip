@@ -556,36 +556,26 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring4_kernel(const WgArgs a
   }
 }
 
+// which of the grouped weight-gradient kernels a launch takes
+struct WgradRoute {
+  bool ring;      // 256-row tiles (else the 128x128 two-stage kernel)
+  bool ring4;     // ... 256x256 tiles on the four-stage ring
+  bool phased;    // ... on the phased kernel (wgrad_phased.hip)
+  int late;       // phased kernel: DMA pieces of a phase (0..2) issued between its MFMAs (tools)
+};
+
 template <typename TE>
-static void wgrad_launch(const WgArgs& a, int tiles, bool ring, bool ring4, hipStream_t st) {
-  if (ring4) {
+static int wgrad_launch(const WgArgs& a, int tiles, const WgradRoute& r, hipStream_t st) {
+  if (r.ring4) {
     constexpr size_t lds = (size_t)4 * 32 * (256 + 256) * sizeof(bf16_t);   // 128 KiB
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_grouped_ring4_kernel<TE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((wgrad_grouped_ring4_kernel<TE>), dim3(tiles), dim3(512), lds, st, a);
-  } else if (ring) {
-    constexpr size_t lds = (size_t)3 * 64 * (256 + 128) * sizeof(bf16_t);   // 144 KiB
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_grouped_ring_kernel<TE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(wgrad_grouped_ring_kernel<TE>, dim3(tiles), dim3(512), lds, st, a);
-  } else {
-    constexpr size_t lds = (size_t)2 * 2 * 64 * 128 * sizeof(bf16_t);   // 64 KiB
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_grouped_kernel<TE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(wgrad_grouped_kernel<TE>, dim3(tiles), dim3(256), lds, st, a);
+    return w2v2_launch_lds<&wgrad_grouped_ring4_kernel<TE>>("wgrad_grouped_ring4_kernel", dim3(tiles), dim3(512), lds, st, a);
   }
+  if (r.ring) {
+    constexpr size_t lds = (size_t)3 * 64 * (256 + 128) * sizeof(bf16_t);   // 144 KiB
+    return w2v2_launch_lds<&wgrad_grouped_ring_kernel<TE>>("wgrad_grouped_ring_kernel", dim3(tiles), dim3(512), lds, st, a);
+  }
+  constexpr size_t lds = (size_t)2 * 2 * 64 * 128 * sizeof(bf16_t);   // 64 KiB
+  return w2v2_launch_lds<&wgrad_grouped_kernel<TE>>("wgrad_grouped_kernel", dim3(tiles), dim3(256), lds, st, a);
 }
 
 static int g_wgrad_force = 0;
@@ -595,6 +585,32 @@ extern "C" int w2v2_tune_wgrad_kernel(int family) {
   return old;
 }
 
+// The choice, as a function of the problem sizes, the CU count (the RAW count: these grids are not persistent, nothing is
+// reserved), the switches and the forced family (tools / tests: 1 = 128x128, 2 = 256x128 ring, 3 = 256x256x32 ring,
+// 4 = phased, 5 / 6 = phased with one / both DMA pieces of a phase between its MFMAs)
+static WgradRoute wgrad_route(const w2v2_wgrad_problem* probs, int n, int ncu, const W2v2Switches& sw, int force) {
+  int max_out = 0;
+  int64_t t4 = 0, t3 = 0;                             // tiles of 256x256 / 256x128 over all problems
+  for (int i = 0; i < n; ++i) {
+    max_out = probs[i].n_out > max_out ? probs[i].n_out : max_out;
+    t4 += cdiv(probs[i].n_out, 256) * cdiv(probs[i].n_in, 256);
+    t3 += cdiv(probs[i].n_out, 256) * cdiv(probs[i].n_in, 128);
+  }
+  WgradRoute r;
+  // 256-row ring kernel unless every problem is narrower than one 256-row tile (or W2V2_WGRAD_V1 is set)
+  r.ring = force ? force >= 2 : (max_out > 128 && sw.wgrad_ring);
+  // 256x256 tiles when they alone fill >= 80 % of the CUs (e.g. the 8 problems of two w2v2-base blocks: 216 tiles)
+  // ... and when their rounds over the chip cost less than the rounds of 256x128 tiles (a 256x256 tile takes ~1.7x
+  // the time of a 256x128 one; problems narrower than 256 rows -- the 128-channel Res2Net TDNNs of ECAPA -- leave
+  // half of a 256x256 tile empty, so a mixed group can need MORE time on the large tiles)
+  r.ring4 = force ? force >= 3
+                  : (r.ring && t4 * 10 >= (int64_t)ncu * 8 && cdiv(t4, ncu) * 17 <= cdiv(t3, ncu) * 10 && sw.wgrad_ring4);
+  // the same 256x256 tiles on the phased kernel (wgrad_phased.hip): bit-equal results, anti-phase wave groups
+  r.phased = force ? force >= 4 : (r.ring4 && sw.wgrad_phased);
+  r.late = force >= 4 ? force - 4 : 0;
+  return r;
+}
+
 extern "C" int w2v2_wgrad_grouped(const w2v2_wgrad_problem* probs, int n, int tokens, int tokens_padded, int dtype,
                                   void* stream) {
   W2V2_REQUIRE(probs && n > 0 && n <= WG_MAXP, "wgrad_grouped: need 1..%d problems", WG_MAXP);
@@ -602,35 +618,9 @@ extern "C" int w2v2_wgrad_grouped(const w2v2_wgrad_problem* probs, int n, int to
                "wgrad_grouped: tokens_padded must be tokens rounded up to a multiple of 64");
   WgArgs a;
   int tiles = 0;
-  // 256-row ring kernel unless every problem is narrower than one 256-row tile (or W2V2_WGRAD_V1 is set)
-  int max_out = 0;
-  for (int i = 0; i < n; ++i) max_out = probs[i].n_out > max_out ? probs[i].n_out : max_out;
-  static const bool env_ring = getenv("W2V2_WGRAD_V1") == nullptr, env_ring4 = getenv("W2V2_NO_WGRAD4") == nullptr;   // A/B switches
-  static const bool env_phased = getenv("W2V2_NO_WGRAD_PH") == nullptr;
-  const int force = g_wgrad_force;                   // tools / tests: 1 = 128x128, 2 = 256x128 ring, 3 = 256x256x32 ring, 4 = phased
-  const bool ring = force ? force >= 2 : (max_out > 128 && env_ring);
-  // 256x256 tiles when they alone fill >= 80 % of the CUs (e.g. the 8 problems of two w2v2-base blocks: 216 tiles)
-  int64_t t4 = 0;
-  for (int i = 0; i < n; ++i) t4 += cdiv(probs[i].n_out, 256) * cdiv(probs[i].n_in, 256);
-  static int ncu_cached = 0;                         // (one device per process: queried once, not on every launch)
-  if (ncu_cached == 0) {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    ncu_cached = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  const int ncu = ncu_cached;
-  // ... and when their rounds over the chip cost less than the rounds of 256x128 tiles (a 256x256 tile takes ~1.7x
-  // the time of a 256x128 one; problems narrower than 256 rows -- the 128-channel Res2Net TDNNs of ECAPA -- leave
-  // half of a 256x256 tile empty, so a mixed group can need MORE time on the large tiles)
-  int64_t t3 = 0;
-  for (int i = 0; i < n; ++i) t3 += cdiv(probs[i].n_out, 256) * cdiv(probs[i].n_in, 128);
-  const bool ring4 = force ? force >= 3
-                           : (ring && t4 * 10 >= (int64_t)ncu * 8 && cdiv(t4, ncu) * 17 <= cdiv(t3, ncu) * 10 && env_ring4);
-  // the same 256x256 tiles on the phased kernel (wgrad_phased.hip): bit-equal results, anti-phase wave groups
-  const bool phased = force ? force >= 4 : (ring4 && env_phased);
-  const int late = force >= 4 ? force - 4 : 0;
-  const int bm = ring ? 256 : 128;
-  const int bn = ring4 ? 256 : 128;
+  const WgradRoute r = wgrad_route(probs, n, w2v2_device_cus(), w2v2_switches(), g_wgrad_force);
+  const int bm = r.ring ? 256 : 128;
+  const int bn = r.ring4 ? 256 : 128;
   for (int i = 0; i < n; ++i) {
     const w2v2_wgrad_problem& q = probs[i];
     W2V2_REQUIRE(q.dY && q.X && q.dW, "wgrad_grouped: null operand in problem %d", i);
@@ -653,8 +643,10 @@ extern "C" int w2v2_wgrad_grouped(const w2v2_wgrad_problem* probs, int n, int to
   a.total_tiles = tiles;
   a.ktiles = tokens_padded / 64;
   W2V2_REQUIRE(dtype == W2V2_BF16 || dtype == W2V2_F16, "wgrad_grouped: needs a 16-bit activation dtype (got %d)", dtype);
-  if (phased) w2v2_launch_wgrad_phased(a, dtype, tiles, late, as_stream(stream));
-  else W2V2_DISPATCH_16(dtype, "wgrad_grouped", wgrad_launch<AT>(a, tiles, ring, ring4, as_stream(stream)););
+  int rc = -1;
+  if (r.phased) rc = w2v2_launch_wgrad_phased(a, dtype, tiles, r.late, as_stream(stream));
+  else W2V2_DISPATCH_16(dtype, "wgrad_grouped", rc = wgrad_launch<AT>(a, tiles, r, as_stream(stream)););
+  if (rc != 0) return rc;
   W2V2_CHECK_LAUNCH("wgrad_grouped");
   return 0;
 }

@@ -29,5 +29,5 @@ struct WgArgs {
 
 
 // wgrad_phased.hip: the 256x256x64 phased kernel; `dtype` = W2V2_BF16 / W2V2_F16, one workgroup per tile
-// late = DMA pieces of a phase (0..2) issued between its MFMAs
-void w2v2_launch_wgrad_phased(const WgArgs& a, int dtype, int tiles, int late, hipStream_t st);
+// late = DMA pieces of a phase (0..2) issued between its MFMAs; != 0: the launch could not be prepared
+int w2v2_launch_wgrad_phased(const WgArgs& a, int dtype, int tiles, int late, hipStream_t st);

@@ -331,25 +331,18 @@ __global__ __launch_bounds__(512) void wgrad_grouped_phased_kernel(const WgArgs 
 }
 
 template <typename TE, int LATE>
-static void launch_phased(const WgArgs& a, int tiles, hipStream_t st) {
+static int launch_phased(const WgArgs& a, int tiles, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * 4 * 64 * 128 * sizeof(bf16_t);   // 128 KiB
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_grouped_phased_kernel<TE, LATE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((wgrad_grouped_phased_kernel<TE, LATE>), dim3(tiles), dim3(512), lds, st, a);
+  return w2v2_launch_lds<&wgrad_grouped_phased_kernel<TE, LATE>>("wgrad_grouped_phased_kernel", dim3(tiles), dim3(512), lds, st, a);
 }
 
-void w2v2_launch_wgrad_phased(const WgArgs& a, int dtype, int tiles, int late, hipStream_t st) {
+int w2v2_launch_wgrad_phased(const WgArgs& a, int dtype, int tiles, int late, hipStream_t st) {
   if (dtype == W2V2_BF16) {
-    if (late == 1) launch_phased<bf16_t, 1>(a, tiles, st);
-    else if (late == 2) launch_phased<bf16_t, 2>(a, tiles, st);
-    else launch_phased<bf16_t, 0>(a, tiles, st);
-  } else {
-    if (late == 1) launch_phased<f16_t, 1>(a, tiles, st);
-    else if (late == 2) launch_phased<f16_t, 2>(a, tiles, st);
-    else launch_phased<f16_t, 0>(a, tiles, st);
+    if (late == 1) return launch_phased<bf16_t, 1>(a, tiles, st);
+    if (late == 2) return launch_phased<bf16_t, 2>(a, tiles, st);
+    return launch_phased<bf16_t, 0>(a, tiles, st);
   }
+  if (late == 1) return launch_phased<f16_t, 1>(a, tiles, st);
+  if (late == 2) return launch_phased<f16_t, 2>(a, tiles, st);
+  return launch_phased<f16_t, 0>(a, tiles, st);
 }
