@@ -153,6 +153,10 @@ typedef struct {
 } w2v2_wgrad_problem;
 int w2v2_wgrad_grouped(const w2v2_wgrad_problem* problems, int n, int tokens, int tokens_padded,
                        int dtype /* W2V2_BF16 or W2V2_F16: element type of dY and X */, void* stream);
+/* The kernel w2v2_wgrad_grouped sends these problems to, from a dry run of its routing itself (nothing is launched, no
+ * operand pointer is read, only n_out / n_in): 1 = 128x128 two-stage, 2 = 256x128 ring, 3 = 256x256x32 ring,
+ * 4 = 256x256x64 phased (also under the forced families 5 / 6); < 0 = n outside 1..32. */
+int w2v2_wgrad_kernel_of(const w2v2_wgrad_problem* problems, int n);
 /* Tools only (tools/gemm_shapes.py, tests): force the kernel of the grouped weight gradients -- 0 = the library's own
  * choice, 1 = 128x128 two-stage, 2 = 256x128 ring, 3 = 256x256x32 ring, 4 = 256x256x64 phased (5 / 6: with one / both DMA
  * pieces of a phase issued between its MFMAs).  Returns the previous value. */

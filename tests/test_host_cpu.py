@@ -807,3 +807,46 @@ def test_gemm_routing_table():
         assert len(got) == len(want) == len(g.CASES)
         wrong = [(i, g.CASES[i], got[i], want[i]) for i in range(len(want)) if got[i] != want[i]]
         assert not wrong, (name, wrong[:5])
+
+
+# What the PARENT of this entry point answered for tests/wgrad_route_cases.py::CASES: its tree with w2v2_wgrad_kernel_of (the
+# export alone) applied, run over the same table (no GPU: 256 CUs) -- per configuration, one family per case, in order.  The
+# "default" row also equals the parent's Python copy of the tile rule (ops.WgradGroup.__init__) evaluated on these shapes.
+WGRAD_ROUTE_EXPECTED = {
+    "default": "2 4 4 2 2 4 2 2 2 1 2 2 1 1 1 2 -1 -1",
+    "wgrad_v1": "1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 -1 -1",
+    "no_wgrad4": "2 2 2 2 2 2 2 2 2 1 2 2 1 1 1 2 -1 -1",
+    "no_wgrad_ph": "2 3 3 2 2 3 2 2 2 1 2 2 1 1 1 2 -1 -1",
+    "force_1": "1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 1 -1 -1",
+    "force_2": "2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 2 -1 -1",
+    "force_3": "3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 3 -1 -1",
+    "force_4": "4 4 4 4 4 4 4 4 4 4 4 4 4 4 4 4 -1 -1",
+    "force_5": "4 4 4 4 4 4 4 4 4 4 4 4 4 4 4 4 -1 -1",
+    "force_6": "4 4 4 4 4 4 4 4 4 4 4 4 4 4 4 4 -1 -1",
+}
+
+
+def test_wgrad_routing_table():
+    """w2v2_wgrad_kernel_of = the route w2v2_wgrad_grouped launches by (csrc/wgrad.hip wgrad_route): 1 = 128x128, 2 = 256x128
+    ring, 3 = 256x256 ring, 4 = phased, < 0 = problem count out of range -- over one / two / four blocks of w2v2-base and
+    wav2vec2-large, the eight projection slices, ECAPA-like mixes with 128-row problems and single narrow problems, under no
+    switch, under W2V2_WGRAD_V1 / W2V2_NO_WGRAD4 / W2V2_NO_WGRAD_PH and under the forced families 1-6, each in a fresh
+    process (the switches are read once).  The expectation is not this code's answer: the literals were recorded from the
+    parent commit's library with this export alone added, and the no-switch row was cross-checked against the Python copy
+    of the rule that ops.WgradGroup carried at the parent."""
+    import json
+    import subprocess
+    import wgrad_route_cases as g
+    assert len(g.CASES) >= 12 and [c[0] for c in g.CONFIGS] == list(WGRAD_ROUTE_EXPECTED)
+    switches = {k for _, env, _ in g.CONFIGS for k in env}
+    for name, env, force in g.CONFIGS:
+        e = {k: v for k, v in os.environ.items() if k not in switches and k != "W2V2_LIB_AB"}
+        e.update(env, ROUTE_FORCE=str(force))
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "wgrad_route_cases.py")], env=e, capture_output=True,
+                             text=True, timeout=600)
+        line = [l for l in out.stdout.splitlines() if l.startswith("ROUTE ")]
+        assert line, (name, out.stderr[-2000:])
+        got, want = json.loads(line[0][6:]), [int(x) for x in WGRAD_ROUTE_EXPECTED[name].split()]
+        assert len(got) == len(want) == len(g.CASES)
+        wrong = [(g.CASES[i][0], got[i], want[i]) for i in range(len(want)) if got[i] != want[i]]
+        assert not wrong, (name, wrong)

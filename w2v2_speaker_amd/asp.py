@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from .engine import _pad64
 from .ops import EPI_ADD, EPI_BIAS, Gemm, WgradGroup
 
 ASP_PREFIX = "stat_pooling.pooling_layer."
@@ -43,7 +44,7 @@ class AttentivePool:
         self.x, self.emb, self.dx = x, emb, dx
 
         def ep(rows, cols):     # zero-padded to a multiple of 64 rows: legal K-major operand of the grouped wgrad
-            full = torch.zeros((rows + 63) // 64 * 64, cols, dtype=adt, device=dev)
+            full = torch.zeros(_pad64(rows), cols, dtype=adt, device=dev)
             v = full[:rows]
             v._w2v2_padded = full
             return v

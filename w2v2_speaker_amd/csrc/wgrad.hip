@@ -650,3 +650,12 @@ extern "C" int w2v2_wgrad_grouped(const w2v2_wgrad_problem* probs, int n, int to
   W2V2_CHECK_LAUNCH("wgrad_grouped");
   return 0;
 }
+
+// Which kernel w2v2_wgrad_grouped sends these problems to, decided by wgrad_route ITSELF (nothing launched, only n_out / n_in
+// read): 1 = 128x128, 2 = 256x128 ring, 3 = 256x256 ring, 4 = phased (forced families 5 / 6 are the phased kernel too);
+// < 0 = n out of range.  Profilers label launches with it instead of mirroring the tile rule.
+extern "C" int w2v2_wgrad_kernel_of(const w2v2_wgrad_problem* probs, int n) {
+  if (!probs || n <= 0 || n > WG_MAXP) return -1;
+  const WgradRoute r = wgrad_route(probs, n, w2v2_device_cus(), w2v2_switches(), g_wgrad_force);
+  return r.phased ? 4 : r.ring4 ? 3 : r.ring ? 2 : 1;
+}

@@ -9,9 +9,8 @@ ref: src/layers/pooling.py, src/optim/loss/aam_softmax.py, src/optim/loss/cross_
 """
 from __future__ import annotations
 
-import os
-
 import math
+import os
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Sequence
 
@@ -38,6 +37,33 @@ def _splitk(m_tiles: int, n_tiles: int, k: int, batch: int = 1) -> int:
 
 def _tiles(n: int, t: int = 128) -> int:
     return (n + t - 1) // t
+
+
+def _pad64(n: int) -> int:
+    """n rounded up to a multiple of 64: the padded token rows of a K-major weight-gradient operand (csrc/wgrad.hip)."""
+    return (n + 63) // 64 * 64
+
+
+def _wb(name: str):
+    return name + ".weight", name + ".bias"
+
+
+@dataclass(frozen=True)
+class PlanSwitches:
+    """The environment switches of a plan, read ONCE when it is constructed (like W2v2Switches on the C side): descriptors,
+    buffers and the backward schedule are all built from the same record, whatever the environment does afterwards."""
+    wgrad_group: int = 0              # W2V2_WGRAD_GROUP: blocks per grouped weight-gradient launch, 1 / 2 / 4 (0: the plan decides)
+    no_wgrad_pairs: bool = False      # W2V2_NO_WGRAD_PAIRS: one weight-gradient launch per block
+    no_ln_fold: bool = False          # W2V2_NO_LN_FOLD: one gamma / beta fold launch per LayerNorm
+    no_posconv_direct: bool = False   # W2V2_NO_POSCONV_DIRECT: positional convolution through the implicit GEMM
+    pos_dw_gemm: bool = False         # W2V2_POS_DW_GEMM: its weight gradient through the transposing GEMM
+
+    @classmethod
+    def from_env(cls) -> "PlanSwitches":
+        env = os.environ.get
+        group = env("W2V2_WGRAD_GROUP")
+        return cls(max(1, min(4, int(group))) if group else 0, bool(env("W2V2_NO_WGRAD_PAIRS")),
+                   bool(env("W2V2_NO_LN_FOLD")), bool(env("W2V2_NO_POSCONV_DIRECT")), bool(env("W2V2_POS_DW_GEMM")))
 
 
 def encoder_backward_schedule(num_layers: int, skip: Sequence[int], pair_uppers: Sequence[int], grouped: bool = True,
@@ -200,7 +226,12 @@ class Plan:
         self._pack_version = -1
         self._cnn_version = -1
         self._asp = {}
-        self.grouped = False
+        self.sw = PlanSwitches.from_env()
+        # 16-bit training: the weight gradients of a block (or of several) are ONE grouped, atomic-free launch
+        self.grouped = train and store.flat_lp_t is not None
+        self.wg_group = self._wgrad_group_size() if train else 2
+        self.g_wgrad_pair, self._wgrad_cache = {}, {}
+        self.head, self.fc, self._lnfold = None, None, None
         # variable-length evaluation (forward(..., lengths=)): device int32 table [conv-0 frames | encoder frames] of the
         # current forward, or None on the fixed-length path
         self._len_dev, self._len = None, None
@@ -212,9 +243,8 @@ class Plan:
         """How many consecutive blocks share one grouped weight-gradient launch: 2 (pairs, since round 3) unless FOUR fill
         the chip's rounds of 256 x 256 tiles strictly better (wav2vec2-large: 192 tiles per block -> pairs 384 = 1.5
         rounds, fours 768 = 3.0).  W2V2_WGRAD_GROUP forces 1 / 2 / 4 (tests, A/B)."""
-        env = os.environ.get("W2V2_WGRAD_GROUP")
-        if env:
-            return max(1, min(4, int(env)))
+        if self.sw.wgrad_group:
+            return self.sw.wgrad_group
         cfg = self.cfg
         H, I = cfg.hidden_size, cfg.intermediate_size
         c = lambda n: -(-n // 256)
@@ -236,8 +266,12 @@ class Plan:
             probs = []
             for l in layers:
                 probs += self.g_layer[l]["wgrad_problems"]
-            self._wgrad_cache[layers] = WgradGroup(probs, self.M, (self.M + 63) // 64 * 64)
+            self._wgrad_cache[layers] = WgradGroup(probs, self.M, _pad64(self.M))
         return self._wgrad_cache[layers]
+
+    def _x(self, l: int) -> torch.Tensor:
+        """Activation buffer of index l: input of block l, output of block l - 1 (all kept, or two in ping-pong)."""
+        return self.X[l if self.all_x else l % 2]
 
     # ------------------------------------------------------------------------------------------ buffers
     def _e(self, *shape, dtype=None) -> torch.Tensor:
@@ -246,7 +280,7 @@ class Plan:
     def _ep(self, rows: int, cols: int, pad_rows: int = 0) -> torch.Tensor:
         """[rows, cols] activation whose storage is padded with ZERO rows up to a multiple of 64 (at least
         ``pad_rows``): it can be the K-major operand of the grouped weight-gradient GEMM (csrc/wgrad.hip contract)."""
-        rp = max((rows + 63) // 64 * 64, pad_rows)
+        rp = max(_pad64(rows), pad_rows)
         full = torch.zeros(rp, cols, dtype=self.adt, device=self.dev)
         v = full[:rows]
         v._w2v2_padded = full
@@ -285,7 +319,7 @@ class Plan:
         self.Cg, self.Tp = H // G, T + K - 1
         # the direct convolution kernel is built for 48 (w2v2-base) and 64 (wav2vec2-large, round 6) channels per group at
         # 128 taps; everything else (the tiny test geometry, the exact-f32 mode) runs the implicit GEMM
-        self.pos_direct = (ops.is16(self.adt) and self.Cg in (48, 64) and K == 128 and not os.environ.get("W2V2_NO_POSCONV_DIRECT"))
+        self.pos_direct = (ops.is16(self.adt) and self.Cg in (48, 64) and K == 128 and not self.sw.no_posconv_direct)
         self.xg = self._e(B, G, self.Tp, self.Cg)
         self.posw_f, self.posw_b = self._e(G, self.Cg, K * self.Cg), self._e(G, self.Cg, K * self.Cg)
         self.pos_sumsq = ops.weightnorm_scratch(H, G, K, self.dev)
@@ -316,7 +350,6 @@ class Plan:
         self.head_rows = B * T if self.no_pool else B          # rows the head sees
         self.emb = self._e(self.head_rows, E, dtype=f32)
         st = self.store
-        self.head, self.fc = None, None
         if st.head == "bce":
             from .heads import BceHead
             self.head = BceHead(self.head_rows, E, w=st.p("linear.weight"), b=st.p("linear.bias"),
@@ -339,7 +372,7 @@ class Plan:
                                        emb=head_in, act_dtype=self.adt, train=self.train, margin=self.margin,
                                        scale=self.scale, loss_scale=st.scaler)
         if self.train:
-            self.demb = (self.head.demb if (self.head is not None and getattr(self, "fc", None) is None)
+            self.demb = (self.head.demb if (self.head is not None and self.fc is None)
                          else self._e(self.head_rows, E, dtype=f32))
             self.G = self._ep(M, H, 0 if (self.cls or self.paired) else proj_pad)           # running activation gradient
             # Gradient scratch of one layer's backward: Gd = df (after the dropout mask of the FFN residual branch),
@@ -348,7 +381,6 @@ class Plan:
             # of the chip instead of two 216-tile rounds of 256x128), see _build_gemms / backward.
             # two alternating sets for single / paired launches; groups of four get one set PER LAYER (they may span
             # LayerDrop-skipped layers: encoder_backward_schedule)
-            self.wg_group = self._wgrad_group_size()
             self._gsets = [dict(Gd=self._ep(M, H), Gd1=self._ep(M, H), DH=self._ep(M, I), DQKV=self._ep(M, 3 * H))
                            for _ in range(cfg.num_hidden_layers if self.wg_group > 2 else 2)]
             self.DC = self._e(M, H)
@@ -363,6 +395,7 @@ class Plan:
                 self.delta = self._e(B * heads * T, dtype=f32)
             else:
                 self.dS = torch.zeros(B * heads * T, self.Tl, dtype=self.adt, device=self.dev)
+            self._lnfold = ops.LnFoldGroup(H, self.dev)
 
     # ------------------------------------------------------------------------------------------ descriptors
     def _build_gemms(self) -> None:
@@ -406,7 +439,7 @@ class Plan:
         self.g_layer: List[Dict[str, Gemm]] = []
         for l in range(L):
             lb = self.lb[l if self.train else 0]
-            xin = self.X[l] if self.all_x else self.X[l % 2]
+            xin = self._x(l)
             pre = f"encoder.layers.{l}."
             gl: Dict[str, Gemm] = {}
             # fp16: the value and output projections run with two-term weights (W = hi + lo planes, 2 x K steps on
@@ -448,10 +481,8 @@ class Plan:
                                   st.wt("wav2vec.model." + pre + "feed_forward.intermediate_dense.weight"),
                                   st.wt("wav2vec.model." + pre + "attention.out_proj.weight"))
                     Wqkv = st.qkv_t(l)
-                self.grouped = st.flat_lp_t is not None      # bf16 mode: one grouped, atomic-free wgrad launch
                 if self.grouped:
                     pad = lambda t: t._w2v2_padded
-                    Mp = (M + 63) // 64 * 64
                     gl["wgrad_problems"] = [
                         (pad(gs["Gd"]), pad(lb.h), mg(pre + "feed_forward.output_dense.weight"),
                          mg(pre + "feed_forward.output_dense.bias")),
@@ -460,7 +491,7 @@ class Plan:
                         (pad(gs["Gd1"]), pad(lb.ctx), mg(pre + "attention.out_proj.weight"),
                          mg(pre + "attention.out_proj.bias")),
                         (pad(gs["DQKV"]), pad(xin), st.qkv(l, "g"), st.qkv(l, "g", "bias"))]
-                    gl["wgrad"] = WgradGroup(gl["wgrad_problems"], M, Mp)
+                    gl["wgrad"] = WgradGroup(gl["wgrad_problems"], M, _pad64(M))
                 gl["dW2"] = Gemm(H, I, M, gs["Gd"], lb.h, mg(pre + "feed_forward.output_dense.weight"), lda=H, ldb=I,
                                  ldc=I, transA=True, transB=True, split_k=sk(H, I), accumulate=True)
                 gl["dh"] = Gemm(M, I, H, gs["Gd"], W2, gs["DH"], lda=H, ldb=I if tb else H, ldc=I, transB=tb,
@@ -468,10 +499,9 @@ class Plan:
                 gl["dW1"] = Gemm(I, H, M, gs["DH"], lb.x1, mg(pre + "feed_forward.intermediate_dense.weight"), lda=I,
                                  ldb=H, ldc=H, transA=True, transB=True, split_k=sk(I, H), accumulate=True)
                 # post-LN: G = DH @ W1 + G (the residual path rides in G); pre-LN: G = DH @ W1 alone (the residual
-                # gradient lives in self.GR, _backward_encoder_stable)
-                gl["dx1"] = Gemm(M, H, I, gs["DH"], W1, self.G, lda=I, ldb=H if tb else I, ldc=H, transB=tb,
-                                 epilogue=EPI_NONE if self.stable else EPI_ADD, aux=None if self.stable else self.G,
-                                 ldaux=0 if self.stable else H)
+                # gradient lives in self.GR, _backward_encoder_stable); likewise "dx" below
+                into_g = {} if self.stable else dict(epilogue=EPI_ADD, aux=self.G, ldaux=H)
+                gl["dx1"] = Gemm(M, H, I, gs["DH"], W1, self.G, lda=I, ldb=H if tb else I, ldc=H, transB=tb, **into_g)
                 gl["dWo"] = Gemm(H, H, M, gs["Gd1"], lb.ctx, mg(pre + "attention.out_proj.weight"), lda=H, ldb=H, ldc=H,
                                  transA=True, transB=True, split_k=sk(H, H), accumulate=True)
                 gl["dctx"] = Gemm(M, H, H, gs["Gd1"], Wo, self.DC, lda=H, ldb=H, ldc=H, transB=tb)
@@ -494,17 +524,13 @@ class Plan:
                 gl["dWqkv"] = Gemm(3 * H, H, M, gs["DQKV"], xin, st.qkv(l, "g"), lda=3 * H, ldb=H, ldc=H, transA=True,
                                    transB=True, split_k=sk(3 * H, H), accumulate=True)
                 gl["dx"] = Gemm(M, H, 3 * H, gs["DQKV"], Wqkv, self.G, lda=3 * H, ldb=H if tb else 3 * H, ldc=H,
-                                transB=tb, epilogue=EPI_NONE if self.stable else EPI_ADD,
-                                aux=None if self.stable else self.G, ldaux=0 if self.stable else H)
+                                transB=tb, **into_g)
             self.g_layer.append(gl)
         # weight gradients of two consecutive layers (l, l-1; l counted down from the top) in one launch
-        self.g_wgrad_pair = {}
-        self._wgrad_cache = {}
-        if self.train and getattr(self, "grouped", False) and not os.environ.get("W2V2_NO_WGRAD_PAIRS"):
-            Mp = (M + 63) // 64 * 64
+        if self.grouped and not self.sw.no_wgrad_pairs:
             for l in range(L - 1, 0, -2):
                 self.g_wgrad_pair[l] = WgradGroup(self.g_layer[l]["wgrad_problems"] +
-                                                  self.g_layer[l - 1]["wgrad_problems"], M, Mp)
+                                                  self.g_layer[l - 1]["wgrad_problems"], M, _pad64(M))
         if self.train:
             mg = st.mg
             # pos-conv backward: weight gradient (packed layout) and data gradient (flipped weights)
@@ -632,41 +658,7 @@ class Plan:
                                self.Cg, K, H, 0)
         else:
             self.g_pos()
-        if self.stable:
-            return self._forward_encoder_stable(step)
-        x = self.X[0]
-        ops.layernorm_fwd(self.hx, self.pos, mp("encoder.layer_norm.weight"), mp("encoder.layer_norm.bias"), x,
-                          self.mean0, self.rstd0, cfg.layer_norm_eps)
-        if tr and reg.hidden_dropout > 0:
-            ops.dropout_(x, reg.hidden_dropout, self._sd("prologue", 0, step))
-        heads, d = cfg.num_attention_heads, cfg.head_dim
-        pa = reg.attention_dropout if tr else 0.0
-        ph = reg.hidden_dropout if tr else 0.0
-        for l in range(cfg.num_hidden_layers):
-            xin = self.X[l] if self.all_x else self.X[l % 2]
-            xout = self.X[l + 1] if self.all_x else self.X[(l + 1) % 2]
-            if l in self._skip:                 # LayerDrop (HF:698-709): the layer is the identity
-                ops.copy_strided(xin, H, xout, H, xin.shape[0], H)
-                continue
-            lb, gl = self.lb[l if tr else 0], self.g_layer[l]
-            pre = f"encoder.layers.{l}."
-            gl["qkv"]()
-            self._attention(l, lb, gl, pa, step)
-            gl["out"]()
-            ops.layernorm_fwd(xin, lb.a, mp(pre + "layer_norm.weight"), mp(pre + "layer_norm.bias"), lb.x1, lb.mean1,
-                              lb.rstd1, cfg.layer_norm_eps, ph, self._sd("post_attn", l, step))
-            gl["ffn1"]()
-            if tr and reg.activation_dropout > 0:
-                # HF:566-569 intermediate_dropout.  The SAME keep decisions (same stream key, same element index) are
-                # applied to the saved gelu'(pre): the backward product "dh" multiplies by it, which is then exactly
-                # d(dropout(gelu(pre))) / d(pre) -- no separate dropout backward, no mask tensor
-                ops.dropout_(lb.h, reg.activation_dropout, self._sd("act", l, step))
-                ops.dropout_(lb.hpre, reg.activation_dropout, self._sd("act", l, step))
-            gl["ffn2"]()
-            ops.layernorm_fwd(lb.x1, lb.f, mp(pre + "final_layer_norm.weight"), mp(pre + "final_layer_norm.bias"),
-                              xout, lb.mean2, lb.rstd2, cfg.layer_norm_eps, ph, self._sd("ffn", l, step))
-        self.out = (self.X[cfg.num_hidden_layers] if self.all_x else self.X[cfg.num_hidden_layers % 2]).view(B, T, H)
-        return self.out
+        return self._encoder_forward(step)
 
     def _attention(self, l: int, lb: LayerBufs, gl, pa: float, step: int) -> None:
         """Self-attention of block l from lb.qkv into lb.ctx: fused (16-bit, head dim 64) or scores GEMM + softmax +
@@ -691,56 +683,78 @@ class Plan:
         """Pre-LN encoder: the LayerNorm that produces X[l], the normalised input of block l (its ``layer_norm``), or -- for
         l = number of blocks -- the encoder's final ``layer_norm`` (HF:791)."""
         n = f"encoder.layers.{l}.layer_norm" if l < self.cfg.num_hidden_layers else "encoder.layer_norm"
-        return n + ".weight", n + ".bias"
+        return _wb(n)
 
-    def _forward_encoder_stable(self, step: int) -> torch.Tensor:
-        """Pre-LN encoder (do_stable_layer_norm, HF:611-654,729-802) on the SAME buffers, GEMM descriptors and fused
-        residual + dropout + LayerNorm kernel as the post-LN one, re-wired:
+    def _encoder_forward(self, step: int) -> torch.Tensor:
+        """The transformer encoder, hx (projection output) and pos (positional embedding) -> self.out.  Both checkpoint families
+        run ONE block (_block_forward: same buffers, GEMM descriptors and fused residual + dropout + LayerNorm kernel), re-wired:
+        Post-LN (HF:382-726):
+            X[0] = drop(LN(hx + pos))
+            block l:  a = out_proj(attn(qkv(X[l])))                lb.x1 = LN1_l(X[l] + drop(a))        [s1 -> lb.a]
+                      f = ffn2(gelu(ffn1(lb.x1)))                  X[l+1] = LN2_l(lb.x1 + drop(f))      [s2 -> lb.f]
+            a LayerDrop-skipped block is the identity: X[l+1] = X[l].
+        Pre-LN (do_stable_layer_norm, HF:611-654,729-802):
             x_0 = drop(hx + pos)                                   X[0] = LN1_0(x_0)
             block l:  a = out_proj(attn(qkv(X[l])))                s1 = x_l + drop(a)     -> lb.a,   lb.x1 = LN2_l(s1)
                       f = ffn2(gelu(ffn1(lb.x1)))                  x_{l+1} = s1 + drop(f) -> lb.f,   X[l+1] = LN1_{l+1}(x_{l+1})
             (the last X is the encoder's final LayerNorm).  The un-normalised residual stream x_l lives in the tensor the
-            fused kernel writes its pre-norm sum into; a LayerDrop-skipped block passes it on and only re-normalises it for
-            the next block (self._res_src[l] remembers which tensor that was, for the backward)."""
-        cfg, st, reg, tr = self.cfg, self.store, self.reg, self.train
-        B, T, H = self.B, self.T, cfg.hidden_size
-        mp, eps = st.mp, cfg.layer_norm_eps
-        heads, d = cfg.num_attention_heads, cfg.head_dim
-        pa = reg.attention_dropout if tr else 0.0
-        ph = reg.hidden_dropout if tr else 0.0
-        ops.add(self.hx, self.pos, self.pos)                      # x_0 (before dropout) replaces the positional embedding
-        if ph > 0:
-            ops.dropout_(self.pos, ph, self._sd("prologue", 0, step))
-        res = self.pos
-        w0, b0 = self._ln_params_for_input_of(0)
-        ops.layernorm_fwd(res, None, mp(w0), mp(b0), self.X[0], self.mean0, self.rstd0, eps)
-        self._res_src = {}
-        L = cfg.num_hidden_layers
+            fused kernel writes its pre-norm sum into (`res` below); a LayerDrop-skipped block passes it on and only
+            re-normalises it for the next block (self._res_src[l] remembers which tensor that was, for the backward)."""
+        cfg, mp, eps = self.cfg, self.store.mp, self.cfg.layer_norm_eps
+        H, L = cfg.hidden_size, cfg.num_hidden_layers
+        ph = self.reg.hidden_dropout if self.train else 0.0
+        if self.stable:
+            ops.add(self.hx, self.pos, self.pos)                  # x_0 (before dropout) replaces the positional embedding
+            if ph > 0:
+                ops.dropout_(self.pos, ph, self._sd("prologue", 0, step))
+            res = self.pos
+            w0, b0 = self._ln_params_for_input_of(0)
+            ops.layernorm_fwd(res, None, mp(w0), mp(b0), self._x(0), self.mean0, self.rstd0, eps)
+            self._res_src = {}
+        else:
+            ops.layernorm_fwd(self.hx, self.pos, mp("encoder.layer_norm.weight"), mp("encoder.layer_norm.bias"), self._x(0),
+                              self.mean0, self.rstd0, eps)
+            if ph > 0:
+                ops.dropout_(self._x(0), ph, self._sd("prologue", 0, step))
         for l in range(L):
-            xin = self.X[l] if self.all_x else self.X[l % 2]
-            xout = self.X[l + 1] if self.all_x else self.X[(l + 1) % 2]
-            lb, gl = self.lb[l if tr else 0], self.g_layer[l]
-            wn, bn = self._ln_params_for_input_of(l + 1)
+            xin, xout, lb = self._x(l), self._x(l + 1), self.lb[l if self.train else 0]
             pre = f"encoder.layers.{l}."
-            if l in self._skip:                 # LayerDrop: x_{l+1} = x_l, re-normalised for the next block
-                ops.layernorm_fwd(res, None, mp(wn), mp(bn), xout, lb.mean2, lb.rstd2, eps)
-                self._res_src[l] = res
-                continue
-            gl["qkv"]()
-            self._attention(l, lb, gl, pa, step)
-            gl["out"]()
-            ops.layernorm_fwd(res, lb.a, mp(pre + "final_layer_norm.weight"), mp(pre + "final_layer_norm.bias"), lb.x1,
-                              lb.mean1, lb.rstd1, eps, ph, self._sd("post_attn", l, step))          # lb.a <- s1
-            gl["ffn1"]()
-            if tr and reg.activation_dropout > 0:
-                ops.dropout_(lb.h, reg.activation_dropout, self._sd("act", l, step))
-                ops.dropout_(lb.hpre, reg.activation_dropout, self._sd("act", l, step))
-            gl["ffn2"]()
-            ops.layernorm_fwd(lb.a, lb.f, mp(wn), mp(bn), xout, lb.mean2, lb.rstd2, eps, ph,
-                              self._sd("ffn", l, step))                                              # lb.f <- x_{l+1}
-            res = lb.f
-        self.out = (self.X[L] if self.all_x else self.X[L % 2]).view(B, T, H)
+            if self.stable:
+                ln_next = self._ln_params_for_input_of(l + 1)
+                if l in self._skip:                 # LayerDrop: x_{l+1} = x_l, re-normalised for the next block
+                    ops.layernorm_fwd(res, None, mp(ln_next[0]), mp(ln_next[1]), xout, lb.mean2, lb.rstd2, eps)
+                    self._res_src[l] = res
+                    continue
+                self._block_forward(l, step, res, _wb(pre + "final_layer_norm"), lb.a, ln_next, xout)
+                res = lb.f                          # lb.a <- s1, lb.f <- x_{l+1}
+            elif l in self._skip:                   # LayerDrop (HF:698-709): the layer is the identity
+                ops.copy_strided(xin, H, xout, H, xin.shape[0], H)
+            else:
+                self._block_forward(l, step, xin, _wb(pre + "layer_norm"), lb.x1, _wb(pre + "final_layer_norm"), xout)
+        self.out = self._x(L).view(self.B, self.T, H)
         return self.out
+
+    def _block_forward(self, l: int, step: int, res1: torch.Tensor, ln1, res2: torch.Tensor, ln2, xout: torch.Tensor) -> None:
+        """Transformer block l of either family (wiring: _encoder_forward): attention of X[l], lb.x1 = LN(res1 + drop(a))
+        with the parameters named ln1, FFN of lb.x1, xout = LN(res2 + drop(f)) with the parameters named ln2.  The fused
+        kernel leaves the two pre-norm sums in lb.a and lb.f."""
+        reg, tr, mp, eps = self.reg, self.train, self.store.mp, self.cfg.layer_norm_eps
+        lb, gl = self.lb[l if tr else 0], self.g_layer[l]
+        ph = reg.hidden_dropout if tr else 0.0
+        gl["qkv"]()
+        self._attention(l, lb, gl, reg.attention_dropout if tr else 0.0, step)
+        gl["out"]()
+        ops.layernorm_fwd(res1, lb.a, mp(ln1[0]), mp(ln1[1]), lb.x1, lb.mean1, lb.rstd1, eps, ph,
+                          self._sd("post_attn", l, step))
+        gl["ffn1"]()
+        if tr and reg.activation_dropout > 0:
+            # HF:566-569 intermediate_dropout.  The SAME keep decisions (same stream key, same element index) are
+            # applied to the saved gelu'(pre): the backward product "dh" multiplies by it, which is then exactly
+            # d(dropout(gelu(pre))) / d(pre) -- no separate dropout backward, no mask tensor
+            ops.dropout_(lb.h, reg.activation_dropout, self._sd("act", l, step))
+            ops.dropout_(lb.hpre, reg.activation_dropout, self._sd("act", l, step))
+        gl["ffn2"]()
+        ops.layernorm_fwd(res2, lb.f, mp(ln2[0]), mp(ln2[1]), xout, lb.mean2, lb.rstd2, eps, ph, self._sd("ffn", l, step))
 
     def conv_features(self, wav: torch.Tensor) -> torch.Tensor:
         """The conv feature extractor alone (HF:382-419; ref: src/models/wav2vec2.py:163-169,
@@ -908,14 +922,12 @@ class Plan:
             else:
                 ops.pool_bwd(self.out, self.emb, demb, self.G.view(B, T, H), self.pool_mode)
         notify("head")
-        if getattr(self, "_lnfold", None) is None:
-            self._lnfold = ops.LnFoldGroup(H, self.dev)
-        lnfold = self._lnfold if not os.environ.get("W2V2_NO_LN_FOLD") else None
+        lnfold = None if self.sw.no_ln_fold else self._lnfold
         if self.stable:
             self._backward_encoder_stable(notify)               # leaves d(loss)/d(hx + pos) in self.G
         for ev in (() if self.stable else
                    encoder_backward_schedule(cfg.num_hidden_layers, self._skip, self.g_wgrad_pair, self.grouped,
-                                             1 if os.environ.get("W2V2_NO_WGRAD_PAIRS") else getattr(self, "wg_group", 2))):
+                                             1 if self.sw.no_wgrad_pairs else self.wg_group)):
             kind = ev[0]
             if kind == "body":
                 self._layer_backward_body(ev[1], lnfold)
@@ -942,7 +954,7 @@ class Plan:
             ops.gelu_bwd(self.G, self.pos_pre, self.P1)
             ops.colsum(self.P1, mg("encoder.pos_conv_embed.conv.bias"), M, H)
         G_, K = cfg.num_conv_pos_embedding_groups, cfg.num_conv_pos_embeddings
-        if ops.is16(self.P1.dtype) and not os.environ.get("W2V2_POS_DW_GEMM"):
+        if ops.is16(self.P1.dtype) and not self.sw.pos_dw_gemm:
             ops.posconv_wgrad(self.P1, self.xg, self.dwf, B, T, H, G_, K)      # correlation kernel (posconv_wgrad.hip)
         else:
             self.g_pos_dw()                                                    # exact-f32 mode: implicit GEMM
@@ -991,72 +1003,45 @@ class Plan:
             notify("cnn")
 
     def _backward_encoder_stable(self, notify) -> None:
-        """Backward of _forward_encoder_stable.  Two running gradients: self.G = d(loss)/dX[l+1] (the NORMALISED input of
-        the block above: what its QKV data-gradient product wrote) and self.GR = d(loss)/dx_{l+1} (the un-normalised
+        """Backward of the pre-LN wiring of _encoder_forward.  Two running gradients: self.G = d(loss)/dX[l+1] (the NORMALISED
+        input of the block above: what its QKV data-gradient product wrote) and self.GR = d(loss)/dx_{l+1} (the un-normalised
         residual stream, accumulated over every block above).  Per block, top down:
             GR += LN_bwd(G)  [the LayerNorm that fed X[l+1]]      df = drop(GR)  -> FFN backward -> G = d(LN2_l output)
             GR += LN_bwd(G)  [final_layer_norm of block l]         da = drop(GR)  -> attention backward -> G = dX[l]
         A LayerDrop-skipped block only passes its re-normalisation back.  One weight-gradient launch per block (the
         grouped kernel in the 16-bit modes), LayerNorm gamma / beta folded at once; the gradient of a block's FIRST
         LayerNorm is produced by the block BELOW it (or the prologue), so the layer buckets are notified at the end."""
-        cfg, st, reg = self.cfg, self.store, self.reg
-        B, T, M, H = self.B, self.T, self.M, cfg.hidden_size
-        mp, mg = st.mp, st.mg
-        step = self._step
-        heads, d = cfg.num_attention_heads, cfg.head_dim
-        pa, ph = reg.attention_dropout, reg.hidden_dropout
-        L = cfg.num_hidden_layers
+        # (follow-up, not done here: reuse encoder_backward_schedule and the LayerNorm fold group -- the open finding on this function in ADVICE.md)
+        mp, mg = self.store.mp, self.store.mg
+        step, ph, L = self._step, self.reg.hidden_dropout, self.cfg.num_hidden_layers
         G, GR = self.G, self.GR
         GR.zero_()
         for l in reversed(range(L)):
-            lb, gl = self.lb[l], self.g_layer[l]
+            lb, gs = self.lb[l], self._gsets[l % len(self._gsets)]
             wn, bn = self._ln_params_for_input_of(l + 1)
             if l in self._skip:
                 ops.layernorm_bwd(G, self._res_src[l], lb.mean2, lb.rstd2, mp(wn), G, None, mg(wn), mg(bn))
                 ops.add(GR, G, GR)
                 G.zero_()                       # X[l] fed a skipped block: nothing flows into it
                 continue
-            gs = self._gsets[l % len(self._gsets)]
-            pre = f"encoder.layers.{l}."
-            grouped = self.grouped
+            w2, b2 = _wb(f"encoder.layers.{l}.final_layer_norm")
             ops.layernorm_bwd(G, lb.f, lb.mean2, lb.rstd2, mp(wn), G, None, mg(wn), mg(bn))
             ops.add(GR, G, GR)                                  # GR = d x_{l+1}
             gs["Gd"].copy_(GR)
             if ph > 0:
                 ops.dropout_(gs["Gd"], ph, self._sd("ffn", l, step))
-            if not grouped:
-                gl["dW2"]()
-                ops.colsum(gs["Gd"], mg(pre + "feed_forward.output_dense.bias"), M, H)
-            gl["dh"]()
-            if not grouped:
-                gl["dW1"]()
-                ops.colsum(gs["DH"], mg(pre + "feed_forward.intermediate_dense.bias"), M, cfg.intermediate_size)
-            gl["dx1"]()                                         # G = DH @ W1 = d(LN2_l output)
-            ops.layernorm_bwd(G, lb.a, lb.mean1, lb.rstd1, mp(pre + "final_layer_norm.weight"), G, None,
-                              mg(pre + "final_layer_norm.weight"), mg(pre + "final_layer_norm.bias"))
+            self._ffn_backward(l)                               # G = DH @ W1 = d(LN2_l output)
+            ops.layernorm_bwd(G, lb.a, lb.mean1, lb.rstd1, mp(w2), G, None, mg(w2), mg(b2))
             ops.add(GR, G, GR)                                  # GR = d s1 = d x_l (residual part)
             gs["Gd1"].copy_(GR)
             if ph > 0:
                 ops.dropout_(gs["Gd1"], ph, self._sd("post_attn", l, step))
-            if not grouped:
-                gl["dWo"]()
-                ops.colsum(gs["Gd1"], mg(pre + "attention.out_proj.bias"), M, H)
-            gl["dctx"]()
-            if self.fused:
-                ops.attention_bwd(lb.qkv, lb.ctx, self.DC, lb.lse, gs["DQKV"], self.delta, B, T, heads, d, d ** -0.5,
-                                  pa, self._sd("attn", l, step))
+            self._attention_backward(l)
+            if self.grouped:
+                self.g_layer[l]["wgrad"]()
             else:
-                gl["dP"]()
-                ops.softmax_bwd(self.S, lb.p, self.dS, B * heads * T, T, self.Tl, pa, self._sd("attn", l, step))
-                gl["dq"]()
-                gl["dk"]()
-                gl["dv"]()
-            if grouped:
-                gl["wgrad"]()
-            else:
-                gl["dWqkv"]()
-                ops.colsum(gs["DQKV"], st.qkv(l, "g", "bias"), M, 3 * H)
-            gl["dx"]()                                          # G = DQKV @ Wqkv = dX[l]
+                self._qkv_wgrad_ungrouped(l)
+            self.g_layer[l]["dx"]()                             # G = DQKV @ Wqkv = dX[l]
         w0, b0 = self._ln_params_for_input_of(0)
         ops.layernorm_bwd(G, self.pos, self.mean0, self.rstd0, mp(w0), G, None, mg(w0), mg(b0))
         ops.add(GR, G, GR)                                      # d x_0
@@ -1067,49 +1052,62 @@ class Plan:
             notify(f"layer{l}")
 
     def _layer_backward_body(self, l: int, lnfold) -> None:
-        """("body", l) of encoder_backward_schedule: the data-gradient chain of one transformer block."""
-        cfg, st, reg = self.cfg, self.store, self.reg
-        B, T, M, H = self.B, self.T, self.M, cfg.hidden_size
-        mp, mg = st.mp, st.mg
-        step = self._step
-        heads, d = cfg.num_attention_heads, cfg.head_dim
-        pa, ph = reg.attention_dropout, reg.hidden_dropout
-        lb, gl = self.lb[l], self.g_layer[l]
-        gs = self._gsets[l % len(self._gsets)]
-        pre = f"encoder.layers.{l}."
-        grouped = self.grouped
+        """("body", l) of encoder_backward_schedule: the data-gradient chain of one post-LN transformer block."""
+        mp, mg = self.store.mp, self.store.mg
+        step, ph = self._step, self.reg.hidden_dropout
+        lb, gs = self.lb[l], self._gsets[l % len(self._gsets)]
+        w1, b1 = _wb(f"encoder.layers.{l}.layer_norm")
+        w2, b2 = _wb(f"encoder.layers.{l}.final_layer_norm")
         # x2 = LN2(x1 + drop(f)):  G <- ds2 (residual path), Gd <- df = ds2 * dropmask
-        ops.layernorm_bwd(self.G, lb.f, lb.mean2, lb.rstd2, mp(pre + "final_layer_norm.weight"), self.G, gs["Gd"],
-                          mg(pre + "final_layer_norm.weight"), mg(pre + "final_layer_norm.bias"), ph,
+        ops.layernorm_bwd(self.G, lb.f, lb.mean2, lb.rstd2, mp(w2), self.G, gs["Gd"], mg(w2), mg(b2), ph,
                           self._sd("ffn", l, step), defer_to=lnfold)
-        if not grouped:
-            gl["dW2"]()
-            ops.colsum(gs["Gd"], mg(pre + "feed_forward.output_dense.bias"), M, H)
-        gl["dh"]()                                          # DH = (df @ W2) * gelu'(pre)   (lb.hpre holds gelu'(pre))
-        if not grouped:
-            gl["dW1"]()
-            ops.colsum(gs["DH"], mg(pre + "feed_forward.intermediate_dense.bias"), M, cfg.intermediate_size)
-        gl["dx1"]()                                         # G = DH @ W1 + G
+        self._ffn_backward(l)                               # G = DH @ W1 + G
         # x1 = LN1(x + drop(a)):  G <- ds1, Gd1 <- da
-        ops.layernorm_bwd(self.G, lb.a, lb.mean1, lb.rstd1, mp(pre + "layer_norm.weight"), self.G, gs["Gd1"],
-                          mg(pre + "layer_norm.weight"), mg(pre + "layer_norm.bias"), ph,
+        ops.layernorm_bwd(self.G, lb.a, lb.mean1, lb.rstd1, mp(w1), self.G, gs["Gd1"], mg(w1), mg(b1), ph,
                           self._sd("post_attn", l, step), defer_to=lnfold)
-        if not grouped:
+        self._attention_backward(l)
+        if not self.grouped:
+            self._qkv_wgrad_ungrouped(l)
+
+    def _ffn_backward(self, l: int) -> None:
+        """Shared by the two bodies above.  From df in Gd: [dW2, db2], DH = (df @ W2) * gelu'(pre) (lb.hpre holds gelu'(pre)),
+        [dW1, db1], G = DH @ W1 (+ G in the post-LN wiring, where the residual path rides in G).  [...]: only without the
+        grouped weight-gradient kernel (exact-f32 mode), each right after the dY it reads is final."""
+        mg, M, H, I = self.store.mg, self.M, self.cfg.hidden_size, self.cfg.intermediate_size
+        gl, gs = self.g_layer[l], self._gsets[l % len(self._gsets)]
+        pre = f"encoder.layers.{l}.feed_forward."
+        if not self.grouped:
+            gl["dW2"]()
+            ops.colsum(gs["Gd"], mg(pre + "output_dense.bias"), M, H)
+        gl["dh"]()
+        if not self.grouped:
+            gl["dW1"]()
+            ops.colsum(gs["DH"], mg(pre + "intermediate_dense.bias"), M, I)
+        gl["dx1"]()
+
+    def _attention_backward(self, l: int) -> None:
+        """Shared likewise.  From da in Gd1: [dWo, dbo], DC = da @ Wo, attention backward into DQKV (fused, or dP, softmax, dq, dk, dv)."""
+        cfg, B, T = self.cfg, self.B, self.T
+        heads, d, pa = cfg.num_attention_heads, cfg.head_dim, self.reg.attention_dropout
+        lb, gl, gs = self.lb[l], self.g_layer[l], self._gsets[l % len(self._gsets)]
+        if not self.grouped:
             gl["dWo"]()
-            ops.colsum(gs["Gd1"], mg(pre + "attention.out_proj.bias"), M, H)
+            ops.colsum(gs["Gd1"], self.store.mg(f"encoder.layers.{l}.attention.out_proj.bias"), self.M, cfg.hidden_size)
         gl["dctx"]()
         if self.fused:
             ops.attention_bwd(lb.qkv, lb.ctx, self.DC, lb.lse, gs["DQKV"], self.delta, B, T, heads, d, d ** -0.5,
-                              pa, self._sd("attn", l, step))
+                              pa, self._sd("attn", l, self._step))
         else:
             gl["dP"]()
-            ops.softmax_bwd(self.S, lb.p, self.dS, B * heads * T, T, self.Tl, pa, self._sd("attn", l, step))
+            ops.softmax_bwd(self.S, lb.p, self.dS, B * heads * T, T, self.Tl, pa, self._sd("attn", l, self._step))
             gl["dq"]()
             gl["dk"]()
             gl["dv"]()
-        if not grouped:
-            gl["dWqkv"]()
-            ops.colsum(gs["DQKV"], st.qkv(l, "g", "bias"), M, 3 * H)
+
+    def _qkv_wgrad_ungrouped(self, l: int) -> None:
+        """dWqkv, dbqkv of block l from DQKV (exact-f32 mode: the 16-bit modes have them in the grouped launch)."""
+        self.g_layer[l]["dWqkv"]()
+        ops.colsum(self._gsets[l % len(self._gsets)]["DQKV"], self.store.qkv(l, "g", "bias"), self.M, 3 * self.cfg.hidden_size)
 
     def _backward_cnn(self) -> None:
         """Backward of the 7-layer conv feature extractor (HF:382-419) -- the reference's
