@@ -388,6 +388,11 @@ int w2v2_pool_bwd(const void* x, const float* out, const float* dout, void* dx, 
  * x, a, h, s and their gradients are [B*T][.] act dtype; parameters / statistics f32.  The Wx / W2 products and
  * their data / weight gradients are w2v2_gemm / w2v2_wgrad_grouped calls made by the host. */
 int w2v2_asp_context(const void* x, float* ctx, int B, int T, int C, int dtype, void* stream);
+/* Variable-length batch (evaluation; ref call site as above, reached once per utterance by the batch-size-1 test loop of
+ * src/lightning_modules/speaker/speaker_recognition_module.py:462-470): mean / std over the first lens[b] frames
+ * (device int32[B], 1 <= lens[b] <= T) of each utterance, rows strided by T; bit-identical to w2v2_asp_context on the
+ * [1, lens[b], C] slice. */
+int w2v2_asp_context_len(const void* x, float* ctx, const int* lens, int B, int T, int C, int dtype, void* stream);
 int w2v2_asp_context_bias(const float* ctx, const float* w1 /*[A][3C]*/, const float* b1, float* cb /*[B][A]*/,
                           int B, int A, int C, void* stream);
 int w2v2_asp_bn_workspace_floats(int M, int A);
@@ -406,6 +411,11 @@ int w2v2_asp_bn_bwd(const void* dh, const void* a_pre, const float* mean_rstd, c
 /* stats [B][C][2] = {max_t s, sum_t exp(s - max)} saved for the backward */
 int w2v2_asp_pool_fwd(const void* x, const void* s, float* out, float* stats, int B, int T, int C, int dtype,
                       void* stream);
+/* Variable-length batch (evaluation; same reference call site): softmax over the first lens[b] frames (device int32[B],
+ * 1 <= lens[b] <= T) -- the scores of later frames enter neither the maximum, the sum nor the statistics (skipped, not
+ * weighted by zero); bit-identical to w2v2_asp_pool_fwd on the [1, lens[b], C] slices of x and s. */
+int w2v2_asp_pool_fwd_len(const void* x, const void* s, float* out, float* stats, const int* lens, int B, int T, int C,
+                          int dtype, void* stream);
 /* dout [B][2C] -> ds (through the softmax) and the direct part of dx (both written) */
 int w2v2_asp_pool_bwd(const void* x, const void* s, const float* out, const float* stats, const float* dout,
                       void* ds, void* dx, int B, int T, int C, int dtype, void* stream);
@@ -455,6 +465,16 @@ int w2v2_im2col_reflect(const void* x, int64_t ldx, void* col, int B, int T, int
  * chunk (speechbrain Res2NetBlock.forward) without a pass that materialises the sum. */
 int w2v2_im2col_reflect_sum(const void* x, int64_t ldx, const void* x2, int64_t ldx2, void* col, int B, int T, int Cin,
                             int k, int dilation, int dtype, void* stream);
+/* Variable-length batch (evaluation; ref: the batch-size-1 test loop of
+ * src/lightning_modules/speaker/speaker_recognition_module.py:462-470 -> ecapa_tdnn.py:110-118 -> speechbrain
+ * Conv1d(padding="same", padding_mode="reflect") on each utterance alone): lens = device
+ * int32[B], dilation (k-1)/2 < lens[b] <= T (the caller checks on the host).  Taps reflect about the utterance's own last
+ * frame lens[b] - 1; rows t >= lens[b] of col are written as zeros.  Rows t < lens[b] are bit-identical to
+ * w2v2_im2col_reflect / _sum on the [1, lens[b], Cin] slice. */
+int w2v2_im2col_reflect_len(const void* x, int64_t ldx, void* col, const int* lens, int B, int T, int Cin, int k,
+                            int dilation, int dtype, void* stream);
+int w2v2_im2col_reflect_sum_len(const void* x, int64_t ldx, const void* x2, int64_t ldx2, void* col, const int* lens,
+                                int B, int T, int Cin, int k, int dilation, int dtype, void* stream);
 int w2v2_col2im_reflect(const void* dcol, void* dx, int64_t lddx, int B, int T, int Cin, int k, int dilation,
                         int accumulate, int dtype, void* stream);
 /* y[m][0..C) = a[m][0..C) + b[m][0..C) over row-strided views (Res2Net cumulative adds); b == NULL: y = a (a strided

@@ -10,6 +10,8 @@ speechbrain state-dict names ``stat_pooling.pooling_layer.{tdnn.conv.conv, tdnn.
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 
 from . import ops
@@ -91,10 +93,17 @@ class AttentivePool:
             self.g_w1 = Gemm(A, C, M, self.da, x, dW1, lda=A, ldb=C, ldc=3 * C, transA=True, transB=True,
                              split_k=sk(A, C), accumulate=True)
 
-    def forward(self) -> torch.Tensor:
+    def forward(self, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """lens (evaluation only): device int32 [B] frame counts -- the global context, the softmax over time and the weighted
+        statistics then run over each utterance's first lens[b] frames; the stages between them work frame by frame."""
         st, B, T, C, A = self.store, self.B, self.T, self.C, self.A
         p = st.p
-        ops.asp_context(self.x, self.ctx, B, T, C)
+        if lens is not None and self.train:
+            raise NotImplementedError("attentive pooling with lengths: evaluation only (batch statistics over ragged rows)")
+        if lens is not None:
+            ops.asp_context_len(self.x, self.ctx, lens, B, T, C)
+        else:
+            ops.asp_context(self.x, self.ctx, B, T, C)
         ops.asp_context_bias(self.ctx, p(self.prefix + "tdnn.conv.conv.weight"), p(self.prefix + "tdnn.conv.conv.bias"),
                              self.cb, B, A, C)
         self.g_a()
@@ -107,7 +116,10 @@ class AttentivePool:
         ops.asp_bn_tanh(self.a_pre, self.mean_rstd, p(self.prefix + "tdnn.norm.norm.weight"),
                         p(self.prefix + "tdnn.norm.norm.bias"), self.h, B * T, A)
         self.g_s()
-        ops.asp_pool_fwd(self.x, self.s, self.emb, self.stats, B, T, C)
+        if lens is not None:
+            ops.asp_pool_fwd_len(self.x, self.s, self.emb, self.stats, lens, B, T, C)
+        else:
+            ops.asp_pool_fwd(self.x, self.s, self.emb, self.stats, B, T, C)
         return self.emb
 
     def backward(self, demb: torch.Tensor) -> None:

@@ -69,6 +69,33 @@ __global__ void asp_context_kernel(const T* __restrict__ x, float* __restrict__ 
   }
 }
 
+// Variable-length batch: asp_context_kernel over the first lens[b] frames of utterance b (rows keep the padded stride).
+// The same time lanes and the same fold order: bit-identical to asp_context_kernel on the [1, lens[b], C] slice.
+template <typename T>
+__global__ void asp_context_len_kernel(const T* __restrict__ x, float* __restrict__ ctx, const int* __restrict__ lens,
+                                       int Tn, int C) {
+  __shared__ float red[ASP_TL][64];
+  const int b = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x;
+  const bool ok = c < C;
+  const T* xp = x + (int64_t)b * Tn * C + (ok ? c : 0);
+  Tn = min(lens[b], Tn);                                  // frames that enter the statistics
+  float s = 0.f;
+  if (ok)
+    for (int t = threadIdx.y; t < Tn; t += ASP_TL) s += to_f32<T>(xp[(int64_t)t * C]);
+  const float mu = asp_block_sum(s, red) / (float)Tn;
+  float q = 0.f;
+  if (ok)
+    for (int t = threadIdx.y; t < Tn; t += ASP_TL) {
+      const float d = to_f32<T>(xp[(int64_t)t * C]) - mu;
+      q = fmaf(d, d, q);
+    }
+  q = asp_block_sum(q, red);
+  if (ok && threadIdx.y == 0) {
+    ctx[(int64_t)b * 2 * C + c] = mu;
+    ctx[(int64_t)b * 2 * C + C + c] = sqrtf(fmaxf(q / (float)Tn, ASP_EPS));
+  }
+}
+
 // cb[b][a] = b1[a] + sum_j ctx[b][j] * W1[a][C + j]        (one wave per output)
 __global__ __launch_bounds__(64) void asp_ctx_bias_kernel(const float* __restrict__ ctx, const float* __restrict__ w1,
                                                           const float* __restrict__ b1, float* __restrict__ cb, int A,
@@ -250,6 +277,47 @@ __global__ void asp_pool_fwd_kernel(const T* __restrict__ x, const T* __restrict
   }
 }
 
+// Variable-length batch: asp_pool_fwd_kernel over the first lens[b] frames of utterance b -- the scores of the frames past
+// them enter neither the maximum, nor the sum, nor the statistics (skipped, not weighted by zero).  Bit-identical to
+// asp_pool_fwd_kernel on the [1, lens[b], C] slices of x and s.
+template <typename T>
+__global__ void asp_pool_fwd_len_kernel(const T* __restrict__ x, const T* __restrict__ s, float* __restrict__ out,
+                                        float* __restrict__ stats, const int* __restrict__ lens, int Tn, int C) {
+  __shared__ float red[ASP_TL][64];
+  const int b = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x;
+  const bool ok = c < C;
+  const int64_t base = (int64_t)b * Tn * C + (ok ? c : 0);
+  Tn = min(lens[b], Tn);
+  float mx = -INFINITY;
+  if (ok)
+    for (int t = threadIdx.y; t < Tn; t += ASP_TL) mx = fmaxf(mx, to_f32<T>(s[base + (int64_t)t * C]));
+  mx = asp_block_max(mx, red);
+  float z = 0.f, m1 = 0.f;
+  if (ok)
+    for (int t = threadIdx.y; t < Tn; t += ASP_TL) {
+      const float e = __expf(to_f32<T>(s[base + (int64_t)t * C]) - mx);
+      z += e;
+      m1 = fmaf(e, to_f32<T>(x[base + (int64_t)t * C]), m1);
+    }
+  z = asp_block_sum(z, red);
+  m1 = asp_block_sum(m1, red);
+  const float inv = 1.0f / z, mean = m1 * inv;
+  float v = 0.f;
+  if (ok)
+    for (int t = threadIdx.y; t < Tn; t += ASP_TL) {
+      const float e = __expf(to_f32<T>(s[base + (int64_t)t * C]) - mx);
+      const float d = to_f32<T>(x[base + (int64_t)t * C]) - mean;
+      v = fmaf(e * d, d, v);
+    }
+  v = asp_block_sum(v, red);
+  if (ok && threadIdx.y == 0) {
+    out[(int64_t)b * 2 * C + c] = mean;
+    out[(int64_t)b * 2 * C + C + c] = sqrtf(fmaxf(v * inv, ASP_EPS));
+    stats[((int64_t)b * C + c) * 2] = mx;
+    stats[((int64_t)b * C + c) * 2 + 1] = z;
+  }
+}
+
 // dout [B][2C] = {dmean, dstd}.  With var = sum w (x - mean)^2 (d var / d mean = 0 because sum w = 1):
 //   dvar = dstd / (2 std) if var > eps;  dx_t = w_t (dmean + 2 dvar (x_t - mean));  dw_t = x_t dmean + dvar (x_t - mean)^2
 //   ds_t = w_t (dw_t - sum_u w_u dw_u)
@@ -347,6 +415,17 @@ extern "C" int w2v2_asp_context(const void* x, float* ctx, int B, int T, int C, 
   return 0;
 }
 
+extern "C" int w2v2_asp_context_len(const void* x, float* ctx, const int* lens, int B, int T, int C, int dtype,
+                                    void* stream) {
+  W2V2_REQUIRE(x && ctx && lens && B > 0 && T > 0 && C > 0, "asp_context_len: bad arguments");
+  dim3 grid((unsigned)cdiv(C, 64), B), blk(64, ASP_TL);
+  hipStream_t st = as_stream(stream);
+  W2V2_DISPATCH_ACT(dtype, "asp_context_len",
+    hipLaunchKernelGGL(asp_context_len_kernel<AT>, grid, blk, 0, st, (const AT*)x, ctx, lens, T, C););
+  W2V2_CHECK_LAUNCH("asp_context_len");
+  return 0;
+}
+
 extern "C" int w2v2_asp_context_bias(const float* ctx, const float* w1, const float* b1, float* cb, int B, int A,
                                      int C, void* stream) {
   W2V2_REQUIRE(ctx && w1 && b1 && cb && B > 0 && A > 0 && C > 0, "asp_context_bias: bad arguments");
@@ -425,6 +504,18 @@ extern "C" int w2v2_asp_pool_fwd(const void* x, const void* s, float* out, float
     hipLaunchKernelGGL(asp_pool_fwd_kernel<AT>, grid, blk, 0, st, (const AT*)x, (const AT*)s,
                             out, stats, T, C););
   W2V2_CHECK_LAUNCH("asp_pool_fwd");
+  return 0;
+}
+
+extern "C" int w2v2_asp_pool_fwd_len(const void* x, const void* s, float* out, float* stats, const int* lens, int B,
+                                     int T, int C, int dtype, void* stream) {
+  W2V2_REQUIRE(x && s && out && stats && lens && B > 0 && T > 0 && C > 0, "asp_pool_fwd_len: bad arguments");
+  dim3 grid((unsigned)cdiv(C, 64), B), blk(64, ASP_TL);
+  hipStream_t st = as_stream(stream);
+  W2V2_DISPATCH_ACT(dtype, "asp_pool_fwd_len",
+    hipLaunchKernelGGL(asp_pool_fwd_len_kernel<AT>, grid, blk, 0, st, (const AT*)x, (const AT*)s,
+                            out, stats, lens, T, C););
+  W2V2_CHECK_LAUNCH("asp_pool_fwd_len");
   return 0;
 }
 

@@ -52,6 +52,32 @@ class EcapaConfig:
                            attention_channels=16, res2net_scale=4, se_channels=16)
 
 
+def ecapa_min_frames(cfg: EcapaConfig) -> int:
+    """Fewest frames an utterance may have: 1 + the widest one-sided padding dilation * (k - 1) / 2 over every convolution of
+    the model (block 0, the Res2Net chunk convolutions, the MFA layer) -- reflect padding needs pad < length (5 for the
+    reference configuration: k = 3, dilation 4)."""
+    return 1 + max(d * (k - 1) // 2 for k, d in zip(cfg.kernel_sizes, cfg.dilations))
+
+
+def valid_frame_lengths(cfg: EcapaConfig, lengths, batch: int, frames: int) -> List[int]:
+    """Per-utterance frame counts of a padded [batch, frames, n_mels] input as Python ints; ValueError unless there is one
+    per row, none exceeds the plan's frames and each leaves every reflect padding shorter than the utterance."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_cuda or lengths.is_floating_point() or lengths.is_complex():
+            raise ValueError("lengths must be Python ints or a CPU integer tensor")
+        lengths = lengths.reshape(-1).tolist()
+    lens = [int(n) for n in lengths]
+    if len(lens) != batch:
+        raise ValueError(f"lengths: {len(lens)} values for a batch of {batch}")
+    lo = ecapa_min_frames(cfg)
+    for n in lens:
+        if n > frames:
+            raise ValueError(f"lengths: {n} frames is longer than the plan's {frames}")
+        if n < lo:
+            raise ValueError(f"lengths: {n} frames is shorter than the model's reflect padding allows ({lo})")
+    return lens
+
+
 def ecapa_param_shapes(cfg: EcapaConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     """speechbrain state-dict names under ``feature_extractor.`` (Conv1d wrapper -> .conv, BatchNorm1d -> .norm)."""
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
@@ -300,7 +326,10 @@ class _Tdnn:
 
     def forward(self) -> None:
         st, pl = self.plan.store, self.plan
-        if self.k > 1:
+        if self.k > 1 and pl._len is not None:   # variable lengths: reflect about each utterance's own end, zero rows past it
+            ops.im2col_reflect_len(self.x, self.ldx, self.col, pl._len, pl.B, pl.T, self.cin, self.k, self.dil, self.x2,
+                                   self.ldx2)
+        elif self.k > 1:
             ops.im2col_reflect(self.x, self.ldx, self.col, pl.B, pl.T, self.cin, self.k, self.dil, self.x2, self.ldx2)
         self.g_fwd()
         ops.bn_fwd(self.a, self.cout, self.work, self.mean_rstd, self.running, st.p(self.pre + "norm.norm.weight"),
@@ -377,7 +406,10 @@ class _SEBlock:
 
     def forward(self) -> None:
         pl = self.plan
-        ops.pool_fwd(self.x.view(pl.B, pl.T, self.C), self.s, ops.POOL_MODES["mean"])
+        if pl._len is not None:                  # squeeze over each utterance's own frames
+            ops.pool_fwd_len(self.x.view(pl.B, pl.T, self.C), self.s, pl._len, ops.POOL_MODES["mean"])
+        else:
+            ops.pool_fwd(self.x.view(pl.B, pl.T, self.C), self.s, ops.POOL_MODES["mean"])
         ops.skinny_linear_fwd(self.s, self.W1, self.b1, self.z, ops.ACT_RELU)
         ops.skinny_linear_fwd(self.z, self.W2, self.b2, self.g, ops.ACT_SIGMOID)
         ops.se_scale(self.x, self.g, self.y, pl.B, pl.T, self.C)
@@ -506,6 +538,9 @@ class EcapaPlan:
         self._wp_pool = torch.empty(store.n_total, dtype=adt, device=dev)
         self._wpt_pool = torch.empty(store.n_total, dtype=adt, device=dev) if (train and ops.is16(adt)) else None
         self._wp_off, self._t_rows = 0, []
+        # variable-length evaluation (embed(..., lengths=)): device int32 [B] table of frame counts, uploaded per forward
+        self._len_dev, self._len = None, None
+        self.frame_lengths: Optional[List[int]] = None
         F_ = cfg.input_mel_coefficients
         self.feat = self.buf(M, F_)
         self.x0 = self.buf(M, C[0])
@@ -581,10 +616,28 @@ class EcapaPlan:
                 ops.transpose_many(self._wp_pool, self._wpt_pool, self._t_table, self._t_table.shape[0])
             self._version = self.store.version
 
-    def embed(self, feat: torch.Tensor) -> torch.Tensor:
-        """ref: ecapa_tdnn.py:110-118 (compute_speaker_embedding): feat [B, T, n_mels] -> [B, lin_neurons] f32."""
+    def _set_lengths(self, lengths) -> None:
+        """Validate the per-utterance frame counts and upload them in one host-to-device copy."""
+        if self.train:
+            raise NotImplementedError("lengths: evaluation plans only (BatchNorm batch statistics over a ragged batch and "
+                                      "the backward have no variable-length form)")
+        lens = valid_frame_lengths(self.cfg, lengths, self.B, self.T)
+        if self._len_dev is None:
+            self._len_dev = torch.empty(self.B, dtype=torch.int32, device=self.dev)
+        self._len_dev.copy_(torch.tensor(lens, dtype=torch.int32))
+        self._len, self.frame_lengths = self._len_dev, lens
+
+    def embed(self, feat: torch.Tensor, lengths=None) -> torch.Tensor:
+        """ref: ecapa_tdnn.py:110-118 (compute_speaker_embedding): feat [B, T, n_mels] -> [B, lin_neurons] f32.
+        lengths: valid frames per utterance (ints or a CPU integer tensor, ecapa_min_frames(cfg) <= n <= T; evaluation
+        plans).  Every stage that reaches across frames (the reflect-padded convolution gathers, the SE squeeze, the global
+        context and the softmax of the attentive pooling) then sees each utterance's own frames only, so row b equals the
+        utterance alone in a (1, n) plan; padded frames may hold any finite values."""
         st, B, T = self.store, self.B, self.T
         assert feat.shape == (B, T, self.cfg.input_mel_coefficients) and feat.is_cuda
+        self._len, self.frame_lengths = None, None
+        if lengths is not None:
+            self._set_lengths(lengths)
         self._refresh()
         f2 = feat.reshape(B * T, -1)
         if self.feat.dtype == torch.float32:        # (input plumbing: the filterbank frames into the plan's padded buffer)
@@ -595,7 +648,7 @@ class EcapaPlan:
         for b in self.blocks:
             b.forward()
         self.mfa.forward()
-        self.asp.forward()
+        self.asp.forward(self._len)
         E2 = self.pooled.shape[1]
         ops.bn_fwd(self.pooled, E2, self.bn_work, self.bn_mr, self.bn_running, st.p(FE + "asp_bn.norm.weight"),
                    st.p(FE + "asp_bn.norm.bias"), self.e2, E2, B, E2, BN_EPS, BN_MOMENTUM, False, self.train)

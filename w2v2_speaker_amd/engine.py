@@ -587,9 +587,9 @@ class Plan:
             raise NotImplementedError("lengths: evaluation plans only (there is no backward for variable lengths)")
         if self.paired:
             raise NotImplementedError("lengths: the paired-input model has no variable-length path")
-        if self.pooling in ("attentive", "random", "none"):
+        if self.pooling in ("random", "none"):
             raise NotImplementedError(f"lengths: pooling {self.pooling!r} has no variable-length form "
-                                      "(supported: mean+std, mean, max, first, first+cls, last, middle, quantile)")
+                                      "(supported: mean+std, mean, max, first, first+cls, last, middle, quantile, attentive)")
         lens = valid_lengths(self.cfg, lengths, self.B, self.N)
         f0 = [self.cfg.conv_lengths(n)[0] for n in lens]
         te = [self.cfg.num_frames(n) + (1 if self.cls else 0) for n in lens]
@@ -813,8 +813,8 @@ class Plan:
         """ref: src/lightning_modules/speaker/wav2vec2_fc.py:414-431 -> pooled embedding [B,E] f32.  lengths: see
         forward(); each row is then pooled over its own frames."""
         out = self.forward(wav, mask, skip_layers, step, feature_mask, lengths=lengths)
-        if self.pooling == "attentive":
-            return self._asp_for(out).forward()
+        if self.pooling == "attentive":       # (the encoder frame counts are the table the pooling needs)
+            return self._asp_for(out).forward(None if self._len is None else self._len[1])
         self._pool_fwd(out)
         return self.emb
 

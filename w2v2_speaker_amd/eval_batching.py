@@ -13,6 +13,9 @@ from typing import List, Sequence, Tuple
 DEFAULT_QUANTUM = 32000                      # 2 s at 16 kHz
 DEFAULT_MAX_BATCH_SAMPLES = 66 * 48000       # the benchmark's training batch: an eval plan never holds more audio
 DEFAULT_MAX_BATCH = 64
+# the same policy over filterbank frames (ECAPA-TDNN: lengths in frames of the 10 ms hop of data/fbank.py)
+DEFAULT_FRAME_QUANTUM = 200                  # 2 s
+DEFAULT_MAX_BATCH_FRAMES = 66 * 300          # the benchmark's ECAPA training batch
 
 
 def plan_batches(lengths: Sequence[int], quantum: int = DEFAULT_QUANTUM,

@@ -2,14 +2,18 @@
 on the HIP path (w2v2_speaker_amd/ecapa.py).  Same config field names, same method names and argument meaning."""
 from __future__ import annotations
 
+from collections import OrderedDict
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
-from ...ecapa import EcapaConfig, EcapaPlan, EcapaStore, EcapaTrainer
+from ...ecapa import EcapaConfig, EcapaPlan, EcapaStore, EcapaTrainer, ecapa_min_frames
+from ...eval_batching import DEFAULT_FRAME_QUANTUM, DEFAULT_MAX_BATCH, DEFAULT_MAX_BATCH_FRAMES, plan_batches
 from ...optim.schedule import OneCycle
 from .wav2vec2_fc import SpeakerClassificationDataBatch
+
+MAX_BUCKET_PLANS = 12     # plans of compute_speaker_embeddings' length buckets (LRU, one per bucket shape)
 
 
 @dataclass
@@ -69,6 +73,8 @@ class EcapaTdnnModule:
         self.device = torch.device(device)
         self._plans: Dict[Tuple, EcapaPlan] = {}
         self._trainers: Dict[Tuple, EcapaTrainer] = {}
+        self._bucket_plans: "OrderedDict[Tuple, EcapaPlan]" = OrderedDict()
+        self.bucket_plans_built = 0
         self.steps = 0
 
     @classmethod
@@ -100,6 +106,55 @@ class EcapaTdnnModule:
         x = input_tensor if input_tensor.dim() == 3 else input_tensor[None]
         x = x.to(self.device, torch.float32)
         return self._plan(x.shape[0], x.shape[1], False).embed(x).clone()
+
+    def _bucket_plan(self, batch: int, frames: int) -> EcapaPlan:
+        key = (batch, frames)
+        if key in self._bucket_plans:
+            self._bucket_plans.move_to_end(key)
+            return self._bucket_plans[key]
+        plan = EcapaPlan(self.store, batch, frames, train=False, aam_margin=self.margin, aam_scale=self.scale)
+        self.bucket_plans_built += 1
+        self._bucket_plans[key] = plan
+        while len(self._bucket_plans) > MAX_BUCKET_PLANS:
+            self._bucket_plans.popitem(last=False)
+        return plan
+
+    def compute_speaker_embeddings(self, feats, *, quantum: int = DEFAULT_FRAME_QUANTUM,
+                                   max_batch_frames: int = DEFAULT_MAX_BATCH_FRAMES,
+                                   max_batch: int = DEFAULT_MAX_BATCH) -> List[torch.Tensor]:
+        """Embeddings of many utterances of different lengths, batched: one [1, lin_neurons] tensor per filterbank tensor
+        ([T, n_mels] or [1, T, n_mels]), in input order, each equal to ``compute_speaker_embedding`` of that utterance
+        alone.  The utterances are bucketed by frame count (eval_batching.plan_batches, lengths in frames) and each batch
+        runs one variable-length forward (EcapaPlan.embed(..., lengths=))."""
+        F_ = self.cfg.input_mel_coefficients
+        xs = []
+        for f in feats:
+            x = f[0] if (f.dim() == 3 and f.shape[0] == 1) else f
+            if x.dim() != 2 or x.shape[1] != F_:
+                raise ValueError(f"compute_speaker_embeddings: expected [T, {F_}] or [1, T, {F_}] per utterance, got "
+                                 f"{tuple(f.shape)}")
+            xs.append(x)
+        out: List[Optional[torch.Tensor]] = [None] * len(xs)
+        fill = ecapa_min_frames(self.model_cfg)
+        for idx, n, batch in plan_batches([x.shape[0] for x in xs], quantum, max_batch_frames, max_batch):
+            plan = self._bucket_plan(batch, n)
+            feat = torch.zeros(batch, n, F_, dtype=torch.float32, device=self.device)
+            lens = [fill] * batch           # unused rows of a bucket's last batch: zeros of the minimum length
+            for j, i in enumerate(idx):
+                feat[j, :xs[i].shape[0]].copy_(xs[i])
+                lens[j] = xs[i].shape[0]
+            emb = plan.embed(feat, lengths=lens)
+            for j, i in enumerate(idx):
+                out[i] = emb[j:j + 1].clone()
+        return out
+
+    def evaluate_trials(self, pairs, feats_by_key, **batching) -> dict:
+        """Score a trial list: every utterance the pairs name (key -> filterbank tensor in ``feats_by_key``) is embedded once
+        with compute_speaker_embeddings (``batching``: its keyword arguments) and the module's evaluator scores the pairs --
+        the same dict as test_epoch_end over the batch-size-1 test loop."""
+        keys = sorted({k for p in pairs for k in (p.sample1_id, p.sample2_id)})
+        embs = self.compute_speaker_embeddings([feats_by_key[k] for k in keys], **batching)
+        return self._evaluate([{"embedding": torch.cat(embs).detach().to("cpu"), "sample_id": keys}], pairs)
 
     def compute_speaker_prediction(self, embedding_tensor: torch.Tensor) -> torch.Tensor:
         return embedding_tensor.squeeze()                  # ref :120-122 under AAM

@@ -685,6 +685,13 @@ def asp_context(x, ctx, B: int, T: int, C: int) -> None:
     _lib.check(lib().w2v2_asp_context(x.data_ptr(), ctx.data_ptr(), B, T, C, dt(x), stream()), "asp_context")
 
 
+def asp_context_len(x, ctx, lens, B: int, T: int, C: int) -> None:
+    """asp_context over the first lens[b] (device int32 [B]) frames of each utterance of x [B*T, C]."""
+    _dev(x, ctx, lens)
+    _lib.check(lib().w2v2_asp_context_len(x.data_ptr(), ctx.data_ptr(), lens.data_ptr(), B, T, C, dt(x), stream()),
+               "asp_context_len")
+
+
 def asp_context_bias(ctx, w1, b1, cb, B: int, A: int, C: int) -> None:
     _dev(ctx, w1, b1, cb)
     _lib.check(lib().w2v2_asp_context_bias(ctx.data_ptr(), w1.data_ptr(), b1.data_ptr(), cb.data_ptr(), B, A, C,
@@ -724,6 +731,13 @@ def asp_pool_fwd(x, s, out, stats, B: int, T: int, C: int) -> None:
     _dev(x, s, out, stats)
     _lib.check(lib().w2v2_asp_pool_fwd(x.data_ptr(), s.data_ptr(), out.data_ptr(), stats.data_ptr(), B, T, C, dt(x),
                                        stream()), "asp_pool_fwd")
+
+
+def asp_pool_fwd_len(x, s, out, stats, lens, B: int, T: int, C: int) -> None:
+    """asp_pool_fwd with the softmax and the statistics over the first lens[b] (device int32 [B]) frames only."""
+    _dev(x, s, out, stats, lens)
+    _lib.check(lib().w2v2_asp_pool_fwd_len(x.data_ptr(), s.data_ptr(), out.data_ptr(), stats.data_ptr(), lens.data_ptr(),
+                                           B, T, C, dt(x), stream()), "asp_pool_fwd_len")
 
 
 def asp_pool_bwd(x, s, out, stats, dout, ds, dx, B: int, T: int, C: int) -> None:
@@ -782,6 +796,20 @@ def im2col_reflect(x, ldx: int, col, B: int, T: int, Cin: int, k: int, dilation:
     else:
         _lib.check(lib().w2v2_im2col_reflect_sum(x.data_ptr(), ldx, x2.data_ptr(), ldx2, col.data_ptr(), B, T, Cin, k,
                                                  dilation, dt(x), stream()), "im2col_reflect_sum")
+
+
+def im2col_reflect_len(x, ldx: int, col, lens, B: int, T: int, Cin: int, k: int, dilation: int, x2=None,
+                       ldx2: int = 0) -> None:
+    """im2col_reflect of a variable-length batch: lens = device int32 [B] frame counts (padding < lens[b] <= T, checked by
+    the caller); taps reflect about each utterance's own last frame, rows past it are written as zeros."""
+    _dev(x, col, lens, x2)
+    if x2 is None:
+        _lib.check(lib().w2v2_im2col_reflect_len(x.data_ptr(), ldx, col.data_ptr(), lens.data_ptr(), B, T, Cin, k,
+                                                 dilation, dt(x), stream()), "im2col_reflect_len")
+    else:
+        _lib.check(lib().w2v2_im2col_reflect_sum_len(x.data_ptr(), ldx, x2.data_ptr(), ldx2, col.data_ptr(),
+                                                     lens.data_ptr(), B, T, Cin, k, dilation, dt(x), stream()),
+                   "im2col_reflect_sum_len")
 
 
 def col2im_reflect(dcol, dx, lddx: int, B: int, T: int, Cin: int, k: int, dilation: int, accumulate: bool) -> None:
