@@ -553,6 +553,39 @@ int w2v2_adam_step(float* p, const float* g, float* m, float* v, void* pb, int p
                    float beta1, float beta2, float eps, float bias_corr1, float bias_corr2,
                    float grad_scale, const float* scaler_state, int step, int skip_slot, void* stream);
 
+/* General optimiser step: torch.optim.Adam with L2 weight decay (grad += weight_decay * p, not AdamW) or
+ * torch.optim.SGD (ref: config/optim/algo/adam.yaml, config/optim/algo/sgd.yaml: momentum 0.9, dampening 0, Nesterov,
+ * weight decay; built at src/main.py:323-335), with the gradient-norm clipping of PL's `trainer.gradient_clip_val`
+ * (torch.nn.utils.clip_grad_norm_) folded in.  Per element: gr = g * grad_scale / scaler_state[0] * norm_state[1]
+ * + weight_decay * p, i.e. unscale, then clip, then decay.
+ *   algo = W2V2_OPTIM_ADAM: the update of w2v2_adam_step on gr.  With weight_decay == 0 and norm_state == NULL the call
+ *     IS w2v2_adam_step (forwarded: same kernel, same bits).
+ *   algo = W2V2_OPTIM_SGD: buf = gr on the first step of the range that was not skipped, else
+ *     buf = momentum * buf + (1 - dampening) * gr;  p -= lr * (nesterov ? gr + momentum * buf : buf).  The buffer lives
+ *     in `m`; `v`, beta1, beta2, eps and the bias corrections are ignored (v may be NULL; m too when momentum == 0).
+ *     "First" is t = step - scaler_state[skip_slot] <= 1 (t = step without skip_slot), the count Adam's bias correction uses.
+ * norm_state (may be NULL): the {total_norm, clip_coef} record of w2v2_grad_norm; a zero coefficient (non-finite norm)
+ * skips the whole step, like scaler_state[1] != 0.  The 16-bit copy pb is refreshed as in w2v2_adam_step. */
+#define W2V2_OPTIM_ADAM 0
+#define W2V2_OPTIM_SGD 1
+int w2v2_optim_step(int algo, float* p, const float* g, float* m, float* v, void* pb, int pb_dtype, int64_t n, float lr,
+                    float beta1, float beta2, float eps, float bias_corr1, float bias_corr2, float grad_scale,
+                    float weight_decay, float momentum, float dampening, int nesterov, const float* norm_state,
+                    const float* scaler_state, int step, int skip_slot, void* stream);
+
+/* Global L2 norm of g[0..n) and the clip coefficient (torch.nn.utils.clip_grad_norm_, which PL calls after
+ * GradScaler.unscale_ for `trainer.gradient_clip_val`; ref: config/trainer/trainer.yaml).
+ * Every element is first multiplied by grad_scale / scaler_state[0] (plain grad_scale when scaler_state is NULL), squares
+ * are summed in double.  Two launches, no atomics: one partial per workgroup, reduced in a fixed order, then one workgroup
+ * adds the partials in index order; the grid depends on n alone, so equal bytes give equal bits on every launch and rank.
+ *   norm_state[0] = total_norm,  norm_state[1] = min(1, max_norm / (total_norm + 1e-6))   (1 when max_norm <= 0).
+ * A non-finite norm gives norm_state[1] = 0 and, with a record, scaler_state[1] = 1 (found_inf): the pass has read the
+ * whole slice, so it replaces w2v2_grad_scaler_check for that step.  partials: caller-owned, n_partials doubles,
+ * at least w2v2_grad_norm_partials of n (never more than 1024). */
+int w2v2_grad_norm_partials(int64_t n);
+int w2v2_grad_norm(const float* g, int64_t n, float grad_scale, float* scaler_state, float max_norm, double* partials,
+                   int n_partials, float* norm_state, void* stream);
+
 /* Dynamic loss scaling for fp16 activations = torch.cuda.amp.GradScaler, which PL `precision: 16` of the
  * reference's runs installs (ref: config/experiment/speaker_wav2vec2_aam.yaml:17).
  * state (device, 4 floats, or 8 with per-range skip counts) = {scale, found_inf, growth_tracker, skipped_steps

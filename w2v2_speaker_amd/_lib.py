@@ -12,6 +12,7 @@ from . import _build
 
 F32, BF16, F16 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_GELU_BWD, EPI_ADD, EPI_SCALE_RC, EPI_BIAS_GELU_GRAD, EPI_MUL = range(8)
+OPTIM_ADAM, OPTIM_SGD = 0, 1
 
 c_i32, c_i64, c_u64, c_f32, c_vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
 
@@ -150,6 +151,10 @@ _SIGS = {
     "w2v2_normalize_bwd": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "w2v2_adam_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32,
                                c_f32, c_f32, c_vp, c_i32, c_i32, c_vp]),
+    "w2v2_optim_step": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32,
+                                c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    "w2v2_grad_norm_partials": (c_i32, [c_i64]),
+    "w2v2_grad_norm": (c_i32, [c_vp, c_i64, c_f32, c_vp, c_f32, c_vp, c_i32, c_vp, c_vp]),
     "w2v2_weight_residual": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "w2v2_comm_unique_id": (c_i32, [c_vp]),
     "w2v2_comm_init": (c_i32, [C.POINTER(c_vp), c_vp, c_i32, c_i32, c_i32]),

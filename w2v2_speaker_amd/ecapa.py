@@ -28,6 +28,7 @@ from . import ops
 from .asp import AttentivePool
 from .heads import ClassifierHead
 from .ops import EPI_ADD, EPI_BIAS, EPI_NONE, Gemm
+from .optim import OptimConfig, fused
 
 FE = "feature_extractor."          # reference attribute name of the ECAPA_TDNN module (ecapa_tdnn.py:75)
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
@@ -148,6 +149,9 @@ class EcapaStore:
         self.asp_running = self.bn_running[FE + "asp.tdnn.norm.norm.weight"]
         self.bn_batches_tracked = 0
         self.version, self.step_count = 0, 0
+        self.optim_algo: Optional[str] = None          # see ParamStore
+        self.grad_norm = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.track_grad_norm = False
 
     def running(self, weight_name: str) -> torch.Tensor:
         """{running_mean, running_var} record of the BatchNorm whose scale parameter is ``weight_name``."""
@@ -231,11 +235,22 @@ class EcapaStore:
 
     def adam_step(self, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
                   grad_scale: float = 1.0) -> None:
-        if self.exp_avg is None:
-            self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.grad), torch.zeros_like(self.grad)
+        """Fused Adam without weight decay or clipping: optimizer_step() with the default description."""
+        self.optimizer_step(lr, beta1, OptimConfig(beta2=beta2, eps=eps), grad_scale)
+
+    def optimizer_step(self, lr: float, momentum_or_beta1: float = 0.9, cfg: Optional[OptimConfig] = None,
+                       grad_scale: float = 1.0, gradient_clip_val: float = 0.0, head_only: bool = False) -> None:
+        """Same contract as ParamStore.optimizer_step (one range: the whole arena trains; no loss-scale record)."""
+        assert not head_only, "ECAPA has no frozen-encoder step"
+        cfg = cfg if cfg is not None else fused.DEFAULT
+        fused.ensure_state(self, cfg, momentum_or_beta1)
         self.step_count += 1
-        ops.adam_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flat_lp, self.n_total, lr, beta1, beta2,
-                      eps, self.step_count, grad_scale)
+        norm = None
+        if gradient_clip_val > 0 or self.track_grad_norm:
+            fused.norm_pass(self, self.n_total, grad_scale, None, gradient_clip_val)
+            norm = self.grad_norm if gradient_clip_val > 0 else None
+        fused.launch(cfg, self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flat_lp, self.n_total, lr,
+                     momentum_or_beta1, self.step_count, grad_scale, None, 0, norm)
         self.version += 1
 
 
@@ -699,8 +714,11 @@ class EcapaPlan:
 class EcapaTrainer:
     """One training step: forward, AAM head, backward, fused Adam (ref: speaker_recognition_module.py:207-220)."""
 
-    def __init__(self, store: EcapaStore, plan: EcapaPlan, schedule, process_group=None):
+    def __init__(self, store: EcapaStore, plan: EcapaPlan, schedule, process_group=None,
+                 optimizer: Optional[OptimConfig] = None, gradient_clip_val: float = 0.0):
+        """optimizer (None = Adam, beta2 0.999, eps 1e-8, no weight decay) / gradient_clip_val: see SpeakerTrainer."""
         self.store, self.plan, self.schedule, self.step = store, plan, schedule, 0
+        self.optimizer, self.gradient_clip_val = optimizer, float(gradient_clip_val)
         self.pg = process_group                      # data parallel: ONE all-reduce of the flat gradient arena (25 MB)
         self.world = 1
         if process_group is not None:
@@ -715,7 +733,7 @@ class EcapaTrainer:
         if self.world > 1:
             import torch.distributed as dist
             dist.all_reduce(self.store.grad, group=self.pg)
-        lr, beta1 = self.schedule.at(self.step)
-        self.store.adam_step(lr, beta1, grad_scale=1.0 / self.world)
+        lr, second = self.schedule.at(self.step)           # beta1 under Adam, the momentum under SGD
+        self.store.optimizer_step(lr, second, self.optimizer, 1.0 / self.world, self.gradient_clip_val)
         self.step += 1
         return loss, softmax

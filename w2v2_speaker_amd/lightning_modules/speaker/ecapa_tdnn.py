@@ -11,6 +11,7 @@ import torch
 from ...ecapa import EcapaConfig, EcapaPlan, EcapaStore, EcapaTrainer, ecapa_min_frames
 from ...eval_batching import DEFAULT_FRAME_QUANTUM, DEFAULT_MAX_BATCH, DEFAULT_MAX_BATCH_FRAMES, plan_batches
 from ...optim.schedule import OneCycle
+from ._optim_surface import OptimizerSurface
 from .wav2vec2_fc import SpeakerClassificationDataBatch
 
 MAX_BUCKET_PLANS = 12     # plans of compute_speaker_embeddings' length buckets (LRU, one per bucket shape)
@@ -33,11 +34,11 @@ class EcapaTDNNModuleConfig:
     explicit_num_speakers: Optional[int] = None
 
 
-class EcapaTdnnModule:
+class EcapaTdnnModule(OptimizerSurface):
     def __init__(self, hyperparameters_to_save, cfg: EcapaTDNNModuleConfig, num_speakers: int,
                  loss_fn_constructor: Callable[[], object], validation_pairs=None, test_pairs=None, evaluator=None, *,
                  device="cuda", act_dtype: torch.dtype = torch.bfloat16, max_lr: float = 1e-3,
-                 max_steps: int = 100_000, init_seed: int = 20211):
+                 max_steps: int = 100_000, init_seed: int = 20211, gradient_clip_val: float = 0.0):
         """Positional arguments = ref: ecapa_tdnn.py:51-62 (what src/main.py:256-285 passes to every network class).
         ``loss_fn_constructor`` is called once and read for its type and hyper-parameters: the engine runs the ECAPA
         model under AAM-softmax (``skip_classifier`` of ref :93-95; the paper's configuration,
@@ -69,6 +70,7 @@ class EcapaTdnnModule:
             self.store.load_state_dict(dict(sd), strict=False)    # incl. every BatchNorm running_mean / running_var
         self.margin, self.scale = aam_margin, aam_scale
         self.schedule = OneCycle(max_lr=max_lr, total_steps=max_steps)
+        self.gradient_clip_val = float(gradient_clip_val)      # PL ``trainer.gradient_clip_val`` (global norm, 0 = off)
         self.skip_classifier = True                        # AAM owns the classifier weight (ref :93-95, :129-131)
         self.device = torch.device(device)
         self._plans: Dict[Tuple, EcapaPlan] = {}
@@ -171,7 +173,8 @@ class EcapaTdnnModule:
         label = batch.ground_truth.to(self.device)
         key = (x.shape[0], x.shape[1])
         if key not in self._trainers:
-            self._trainers[key] = EcapaTrainer(self.store, self._plan(x.shape[0], x.shape[1], True), self.schedule)
+            self._trainers[key] = EcapaTrainer(self.store, self._plan(x.shape[0], x.shape[1], True), self.schedule,
+                                               **self._trainer_options())
         tr = self._trainers[key]
         tr.step = self.steps
         loss, pred = tr.train_step(x, label)

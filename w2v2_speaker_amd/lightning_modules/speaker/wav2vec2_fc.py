@@ -15,6 +15,7 @@ engine's head kernels on the arena's weight, like the reference re-creates its A
 (ref: wav2vec2_fc.py:212-224)."""
 from __future__ import annotations
 
+import types
 import warnings
 from collections import OrderedDict
 from dataclasses import dataclass, field
@@ -30,9 +31,11 @@ from ...eval_batching import (DEFAULT_MAX_BATCH, DEFAULT_MAX_BATCH_SAMPLES, DEFA
 from ...evaluation.speaker.cosine_distance import CosineDistanceEvaluator, EmbeddingSample, EvaluationPair
 from ...models.handles import ModelHandle
 from ...optim.loss import AngularAdditiveMarginSoftMaxLoss, CrossEntropyLoss
+from ...optim import OptimConfig
 from ...optim.schedule import OneCycle
 from ...params import ParamStore
 from ...trainer import SpeakerTrainer
+from ._optim_surface import OptimizerSurface
 
 from ...params import _WN_OLD as _WN_LEGACY
 
@@ -132,7 +135,7 @@ def _pool_width(pooling: str) -> int:
     raise ValueError(f"unknown value for stat_pooling_type={pooling!r}")
 
 
-class Wav2vec2FCModule(torch.nn.Module):
+class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
     """A ``torch.nn.Module`` (the reference's is a LightningModule): ``parameters()`` / ``named_parameters()`` yield one
     ``nn.Parameter`` per reference parameter, in the reference's order and under its names, each a VIEW of the flat f32
     arena (``.grad`` = the matching view of the flat gradient buffer, scaled by the loss scale in the fp16 mode);
@@ -147,12 +150,15 @@ class Wav2vec2FCModule(torch.nn.Module):
                  loss_fn_constructor: Callable[[], object], validation_pairs: Optional[List[EvaluationPair]] = None,
                  test_pairs: Optional[List[EvaluationPair]] = None, evaluator=None, *, device="cuda",
                  act_dtype: torch.dtype = torch.float16, max_lr: float = 5e-5, max_steps: int = 100_000,
-                 process_group=None, init_seed: int = 20211, pretrained_state_dict=None):
+                 process_group=None, init_seed: int = 20211, pretrained_state_dict=None,
+                 gradient_clip_val: float = 0.0):
         """Positional arguments = ref: wav2vec2_fc.py:101-111.  Keyword-only extras: the device / activation dtype of
         the engine, the one-cycle schedule the reference takes from ``cfg.optim`` (src/main.py:323-335), and
         ``pretrained_state_dict`` (a path or a dict with HF ``facebook/wav2vec2-*`` weights: there is no network
-        here for ``from_pretrained``)."""
+        here for ``from_pretrained``), and ``gradient_clip_val`` (PL ``trainer.gradient_clip_val``, global norm, 0 = off).
+        ``set_optimizer`` / ``set_lr_schedule`` replace the default fused Adam under the one-cycle schedule."""
         super().__init__()
+        self.gradient_clip_val = float(gradient_clip_val)
         self.hyperparameters_to_save = hyperparameters_to_save
         self.cfg = cfg
         if cfg.wav2vec_feature_encoder_only:
@@ -427,7 +433,8 @@ class Wav2vec2FCModule(torch.nn.Module):
         pkey = (x.shape[0], x.shape[1], True, self.cfg.stat_pooling_type)
         plan = self._plan(x.shape[0], x.shape[1], True)
         if pkey not in self._trainers:
-            self._trainers[pkey] = SpeakerTrainer(self.store, plan, self.schedule, process_group=self.process_group)
+            self._trainers[pkey] = SpeakerTrainer(self.store, plan, self.schedule, process_group=self.process_group,
+                                                  **self._trainer_options())
         tr = self._trainers[pkey]
         tr.step = self.schedule_step
         if self._is_wav2vec_frozen:
@@ -493,32 +500,46 @@ class Wav2vec2FCModule(torch.nn.Module):
         statistics).  ``legacy_weight_norm_names`` (default) writes the pos-conv weight-norm pair as
         ``...conv.weight_g`` / ``...conv.weight_v`` -- the names of the reference's own stack (torch 1.9 /
         transformers ^4.8); its ``load_from_checkpoint(strict=False)`` would silently DROP the torch >= 2.1 names
-        ``parametrizations.weight.original0/1`` (load accepts both).  ``optimizer_states[0]`` is a
-        ``torch.optim.Adam.state_dict()`` in the reference's parameter order (ParamStore.torch_adam_state) and
-        ``lr_schedulers[0]`` the ``OneCycleLR`` fields a resume needs; the engine's own extras (fp16 loss-scale
+        ``parametrizations.weight.original0/1`` (load accepts both).  ``optimizer_states[0]`` is the ``state_dict()`` of
+        the torch optimiser that was set (Adam by default, or SGD; its real ``weight_decay``) in the reference's parameter
+        order (ParamStore.torch_optimizer_state) and ``lr_schedulers[0]`` the ``OneCycleLR`` / ``LambdaLR`` fields a
+        resume needs; the engine's own extras (fp16 loss-scale
         record, freeze-schedule counters) travel under ``w2v2_amd``.  What is NOT claimed: torchmetrics / callback
         states of a PL ``Trainer`` -- a ``Trainer`` resume restores weights, optimiser moments and schedule position."""
         sd = self.state_dict()
         if legacy_weight_norm_names:
             sd = OrderedDict((ParamStore.legacy_key(k), v) for k, v in sd.items())
-        # torch's groups hold the values of the NEXT optimiser step (OneCycleLR.step() writes them right after a step)
-        sch = self.schedule
-        lr, beta1 = sch.at(min(self.schedule_step, sch.total_steps - 1))
+        # torch's groups hold the values of the NEXT optimiser step (scheduler.step() writes them right after a step)
         z = lambda t: None if t is None else t.detach().clone().cpu()
-        initial_lr = sch.max_lr / sch.div_factor
-        # torch.optim.lr_scheduler.OneCycleLR.state_dict() (every key it reads back in load_state_dict / step)
-        sched_state = {"total_steps": sch.total_steps,
-                       "_schedule_phases": [
-                           {"end_step": float(sch.pct_start * sch.total_steps) - 1, "start_lr": "initial_lr", "end_lr": "max_lr",
-                            "start_momentum": "max_momentum", "end_momentum": "base_momentum"},
-                           {"end_step": sch.total_steps - 1, "start_lr": "max_lr", "end_lr": "min_lr",
-                            "start_momentum": "base_momentum", "end_momentum": "max_momentum"}],
-                       "_anneal_func_type": "cos", "cycle_momentum": True, "use_beta1": True, "base_lrs": [initial_lr],
-                       "last_epoch": self.schedule_step, "_step_count": self.schedule_step + 1, "_is_initial": False,
-                       "_get_lr_called_within_step": False, "_last_lr": [lr]}
+        sch = self.schedule
+        cfg = self.optimizer_cfg if self.optimizer_cfg is not None else OptimConfig()
+        common = {"last_epoch": self.schedule_step, "_step_count": self.schedule_step + 1, "_is_initial": False,
+                  "_get_lr_called_within_step": False}
+        if isinstance(sch, OneCycle):
+            lr, second = sch.at(min(self.schedule_step, sch.total_steps - 1))
+            initial_lr = sch.max_lr / sch.div_factor
+            # torch.optim.lr_scheduler.OneCycleLR.state_dict() (every key it reads back in load_state_dict / step)
+            sched_state = {"total_steps": sch.total_steps,
+                           "_schedule_phases": [
+                               {"end_step": float(sch.pct_start * sch.total_steps) - 1, "start_lr": "initial_lr", "end_lr": "max_lr",
+                                "start_momentum": "max_momentum", "end_momentum": "base_momentum"},
+                               {"end_step": sch.total_steps - 1, "start_lr": "max_lr", "end_lr": "min_lr",
+                                "start_momentum": "base_momentum", "end_momentum": "max_momentum"}],
+                           "_anneal_func_type": "cos", "cycle_momentum": True, "use_beta1": cfg.algo == "adam",
+                           "base_lrs": [initial_lr], "_last_lr": [lr], **common}
+            opt_state = self.store.torch_optimizer_state(lr, second, cfg, one_cycle=sch)
+        else:
+            # torch.optim.lr_scheduler.LambdaLR.state_dict() (tri-stage): a callable OBJECT is saved as its __dict__, a
+            # plain function as None; LambdaLR keeps ``initial_lr`` in the optimiser's param group
+            lr, second = sch.at(self.schedule_step)
+            fn = sch.fn
+            sched_state = {"base_lrs": [sch.base_lr], "_last_lr": [lr],
+                           "lr_lambdas": [None if isinstance(fn, types.FunctionType) else dict(fn.__dict__)], **common}
+            opt_state = self.store.torch_optimizer_state(lr, second, cfg)
+            opt_state["param_groups"][0]["initial_lr"] = sch.base_lr
         torch.save({"state_dict": sd, "global_step": self.schedule_step, "epoch": 0,
                     "pytorch-lightning_version": "1.4.5",
-                    "optimizer_states": [self.store.torch_adam_state(lr, (beta1, 0.999), 1e-8, one_cycle=sch)],
+                    "optimizer_states": [opt_state],
                     "lr_schedulers": [sched_state],
                     "w2v2_amd": {"loss_scaler": z(self.store.scaler), "steps": self.steps,
                                  "is_wav2vec_frozen": self._is_wav2vec_frozen},
@@ -553,8 +574,8 @@ class Wav2vec2FCModule(torch.nn.Module):
                 module.store.scaler[:min(rec.numel(), module.store.scaler.numel())] = rec[:module.store.scaler.numel()]
             for ost in ckpt.get("optimizer_states") or []:
                 try:
-                    if "param_groups" in ost:             # torch.optim.Adam.state_dict() (reference parameter order)
-                        module.store.load_torch_adam_state(ost)
+                    if "param_groups" in ost:             # torch Adam / SGD state_dict() (reference parameter order)
+                        module.store.load_torch_optimizer_state(ost)
                     else:                                 # round-2 files: flat moment arenas
                         module.store.load_optimizer_state(ost)
                 except (ValueError, IndexError):

@@ -12,6 +12,7 @@ import torch
 from ...config import W2V2Config, Wav2Vec2RegularisationConfig
 from ...engine import Plan
 from ...optim.schedule import OneCycle
+from ._optim_surface import OptimizerSurface
 from ...params import ParamStore
 from ...trainer import SpeakerTrainer
 
@@ -51,11 +52,11 @@ class PairedSpeakerClassificationDataBatch:
     ground_truth: torch.Tensor
 
 
-class Wav2vec2PairedSpeakerModule:
+class Wav2vec2PairedSpeakerModule(OptimizerSurface):
     def __init__(self, hyperparameters_to_save, cfg: Wav2vec2PairedSpeakerModuleConfig,
                  loss_fn_constructor: Optional[Callable[[], object]] = None, *, device="cuda",
                  act_dtype: torch.dtype = torch.float16, max_lr: float = 5e-5, max_steps: int = 100_000,
-                 process_group=None, init_seed: int = 20211):
+                 process_group=None, init_seed: int = 20211, gradient_clip_val: float = 0.0):
         """Positional arguments = ref: wav2vec2_paired_input.py:65-71.  ``loss_fn_constructor`` must build the
         reference's ``BinaryCrossEntropyLoss`` (src/optim/loss/binary_cross_entropy.py; the only loss this module is
         configured with, config/optim/loss/binary_cross_entropy.yaml) -- it is called once and checked; the arithmetic
@@ -81,6 +82,7 @@ class Wav2vec2PairedSpeakerModule:
                                 freeze_cnn=cfg.completely_freeze_feature_extractor)
         self.store.init_weights(init_seed)
         self.schedule = OneCycle(max_lr=max_lr, total_steps=max_steps)
+        self.gradient_clip_val = float(gradient_clip_val)      # PL ``trainer.gradient_clip_val`` (global norm, 0 = off)
         self.process_group = process_group
         self.device = torch.device(device)
         self._plans: Dict[Tuple, Plan] = {}
@@ -134,7 +136,7 @@ class Wav2vec2PairedSpeakerModule:
         key = (wav.shape[0] // 2, wav.shape[1])
         if key not in self._trainers:
             self._trainers[key] = SpeakerTrainer(self.store, self._plan(key[0], key[1], True), self.schedule,
-                                                 process_group=self.process_group)
+                                                 process_group=self.process_group, **self._trainer_options())
         tr = self._trainers[key]
         tr.step = self.steps
         loss, pred = tr.train_step(wav, label)

@@ -656,6 +656,39 @@ def adam_step(p, g, m, v, pb, n: int, lr: float, beta1: float, beta2: float, eps
                                     _p(scaler), step, skip_slot, stream()), "adam_step")
 
 
+def optim_step(algo: str, p, g, m, v, pb, n: int, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+               step: int = 1, grad_scale: float = 1.0, scaler=None, skip_slot: int = 0, weight_decay: float = 0.0,
+               momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False, norm_state=None) -> None:
+    """General optimiser step (w2v2_optim_step): algo "adam" (torch.optim.Adam incl. L2 weight decay) or "sgd"
+    (torch.optim.SGD; the momentum buffer is ``m``, ``v`` may be None, ``m`` too without momentum).  norm_state: the
+    {norm, clip_coef} record of grad_norm(), or None.  Adam without weight decay and without a record is adam_step()."""
+    if algo not in ("adam", "sgd"):
+        raise ValueError(f"optim_step: algo must be 'adam' or 'sgd', got {algo!r}")
+    _dev(p, g, m, v, pb, scaler, norm_state)
+    adam = algo == "adam"
+    bc1 = 1.0 - beta1 ** step if adam else 1.0
+    bc2 = 1.0 - beta2 ** step if adam else 1.0
+    _lib.check(lib().w2v2_optim_step(_lib.OPTIM_ADAM if adam else _lib.OPTIM_SGD, p.data_ptr(), g.data_ptr(), _p(m), _p(v),
+                                     _p(pb), dt(pb) if pb is not None else BF16, n, lr, beta1, beta2, eps, bc1, bc2,
+                                     grad_scale, weight_decay, momentum, dampening, int(bool(nesterov)), _p(norm_state),
+                                     _p(scaler), step, skip_slot, stream()), "optim_step")
+
+
+def grad_norm_partials(n: int) -> int:
+    """Doubles the partial buffer of grad_norm() needs for a slice of n elements (a pure function of n)."""
+    return int(lib().w2v2_grad_norm_partials(n))
+
+
+def grad_norm(g, n: int, norm_state, partials, grad_scale: float = 1.0, scaler=None, max_norm: float = 0.0) -> None:
+    """norm_state (f32[2]) = {||g[:n] * grad_scale / scaler[0]||_2, min(1, max_norm / (norm + 1e-6))}: torch's
+    clip_grad_norm_ after unscale_; bit-reproducible (fixed-order double sums into ``partials``, a float64 buffer).
+    max_norm <= 0: norm only.  A non-finite norm sets the coefficient to 0 and scaler[1] (found_inf) to 1."""
+    _dev(g, norm_state, partials, scaler)
+    assert partials.dtype == torch.float64 and norm_state.dtype == torch.float32 and norm_state.numel() >= 2
+    _lib.check(lib().w2v2_grad_norm(g.data_ptr(), n, grad_scale, _p(scaler), max_norm, partials.data_ptr(),
+                                    partials.numel(), norm_state.data_ptr(), stream()), "grad_norm")
+
+
 def weight_residual(p, lo, table) -> None:
     """lo[off:off+n] = T(p[off:off+n] - T(p[off:off+n])) for every (off, n) row of the int64 device table."""
     _dev(p, lo, table)

@@ -1,0 +1,1 @@
+from .config import OptimConfig  # noqa: F401

@@ -1,0 +1,52 @@
+"""Host side of the fused optimiser step, shared by ParamStore and EcapaStore: state arenas, the gradient-norm
+pair and the choice of entry point.  Everything here only enqueues launches; nothing reads the device."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from .. import ops
+from .config import OptimConfig
+
+DEFAULT = OptimConfig()
+
+
+def bind_algo(store, cfg: OptimConfig) -> None:
+    """A store steps under one algorithm for its lifetime (the moment arenas mean different things under each)."""
+    have = getattr(store, "optim_algo", None)
+    if have is not None and have != cfg.algo:
+        raise RuntimeError(f"optimiser state of this store belongs to {have!r}; it cannot step (or load a state "
+                           f"written) under {cfg.algo!r}")
+    store.optim_algo = cfg.algo
+
+
+def ensure_state(store, cfg: OptimConfig, second: float) -> None:
+    """Adam: exp_avg + exp_avg_sq.  SGD: the momentum buffer lives in exp_avg (none at all without momentum);
+    exp_avg_sq is never allocated."""
+    bind_algo(store, cfg)
+    if store.exp_avg is None and (cfg.algo == "adam" or second != 0):
+        store.exp_avg = torch.zeros_like(store.grad)
+    if store.exp_avg_sq is None and cfg.algo == "adam":
+        store.exp_avg_sq = torch.zeros_like(store.grad)
+
+
+def norm_pass(store, n: int, grad_scale: float, scaler, max_norm: float) -> torch.Tensor:
+    """store.grad_norm = {norm, clip coefficient} of the first n gradient elements (two launches)."""
+    if getattr(store, "_norm_partials", None) is None:
+        store._norm_partials = torch.zeros(ops.grad_norm_partials(store.grad.numel()), dtype=torch.float64,
+                                           device=store.grad.device)
+    ops.grad_norm(store.grad, n, store.grad_norm, store._norm_partials, grad_scale, scaler, max_norm)
+    return store.grad_norm
+
+
+def launch(cfg: OptimConfig, p, g, m, v, pb, n: int, lr: float, second: float, step: int, grad_scale: float,
+           scaler=None, skip_slot: int = 0, norm_state: Optional[torch.Tensor] = None) -> None:
+    """One optimiser launch over n elements.  ``second``: Adam's beta1 / SGD's momentum of this step.  The default
+    optimiser (Adam, no weight decay, no clipping) takes the entry point it always took."""
+    if cfg.algo == "adam" and cfg.weight_decay == 0 and norm_state is None:
+        ops.adam_step(p, g, m, v, pb, n, lr, second, cfg.beta2, cfg.eps, step, grad_scale, scaler, skip_slot)
+        return
+    ops.optim_step(cfg.algo, p, g, m, v, pb, n, lr, second, cfg.beta2, cfg.eps, step, grad_scale, scaler, skip_slot,
+                   weight_decay=cfg.weight_decay, momentum=second if cfg.algo == "sgd" else 0.0,
+                   dampening=cfg.dampening, nesterov=cfg.nesterov, norm_state=norm_state)

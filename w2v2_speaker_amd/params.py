@@ -22,6 +22,7 @@ import torch
 
 from . import ops
 from .config import W2V2Config
+from .optim import OptimConfig, fused
 
 ALIGN = 64  # elements
 
@@ -190,6 +191,11 @@ class ParamStore:
         self.step_count = 0
         self.step_head = 0
         self.step_body = 0
+        # optimiser: the algorithm the moment arenas belong to (set by the first step or by a loaded state), and the
+        # {global gradient norm, clip coefficient} record of the last step that clipped or tracked the norm
+        self.optim_algo: Optional[str] = None
+        self.grad_norm = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.track_grad_norm = False
 
     # ------------------------------------------------------------------ views
     def _view(self, buf: torch.Tensor, name: str) -> torch.Tensor:
@@ -385,14 +391,21 @@ class ParamStore:
                 return name[: -len(new)] + old
         return name
 
-    def torch_adam_state(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, one_cycle=None) -> Dict[str, object]:
-        """``torch.optim.Adam.state_dict()`` of the optimiser the reference builds over ``network.parameters()``
-        (ref: src/main.py:323): per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` views cut out of the flat moment
-        arenas, indexed in reference parameter order; parameters that never had a gradient (frozen CNN) have no
-        state entry, as in torch.  ``one_cycle`` (an ``optim.schedule.OneCycle``): the reference wraps this Adam in
-        ``OneCycleLR`` (ref: src/main.py:323-335), which keeps ``initial_lr / max_lr / min_lr / base_momentum /
-        max_momentum`` IN the optimiser's param group -- ``Optimizer.load_state_dict`` replaces the groups wholesale, so
-        a file without them breaks ``OneCycleLR.step()`` after a resume (KeyError: 'initial_lr')."""
+    def torch_optimizer_state(self, lr: float, second: float = 0.9, cfg: Optional[OptimConfig] = None,
+                              one_cycle=None) -> Dict[str, object]:
+        """``state_dict()`` of the torch optimiser the reference builds over ``network.parameters()`` (ref:
+        src/main.py:323): a ``torch.optim.Adam.state_dict()`` (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``) or,
+        under SGD, a ``torch.optim.SGD.state_dict()`` (``momentum_buffer``), cut out of the flat arenas and indexed in
+        reference parameter order; parameters that never had a gradient (frozen CNN) have no state entry, as in torch.
+        ``second``: beta1 / the momentum of the next step.  The group carries the real ``weight_decay``.
+        ``one_cycle`` (an ``optim.schedule.OneCycle``): the reference wraps the optimiser in ``OneCycleLR`` (ref:
+        src/main.py:323-335), which keeps ``initial_lr / max_lr / min_lr / base_momentum / max_momentum`` IN the
+        optimiser's param group -- ``Optimizer.load_state_dict`` replaces the groups wholesale, so a file without them
+        breaks ``OneCycleLR.step()`` after a resume (KeyError: 'initial_lr')."""
+        cfg = cfg if cfg is not None else fused.DEFAULT
+        if self.optim_algo is not None and self.optim_algo != cfg.algo:
+            raise RuntimeError(f"optimiser state of this store belongs to {self.optim_algo!r}, not {cfg.algo!r}")
+        sgd = cfg.algo == "sgd"
         order = self.reference_parameter_order()
         state = {}
         h = self.head_size()
@@ -408,9 +421,16 @@ class ParamStore:
             step = step_head if off < h else step_body
             if step <= 0:
                 continue
-            state[i] = {"step": step, "exp_avg": self.exp_avg[off:off + cnt].view(self.shapes[n]).detach().clone().cpu(),
-                        "exp_avg_sq": self.exp_avg_sq[off:off + cnt].view(self.shapes[n]).detach().clone().cpu()}
-        group = {"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": 0, "amsgrad": False}
+            cut = lambda t: t[off:off + cnt].view(self.shapes[n]).detach().clone().cpu()
+            state[i] = ({"momentum_buffer": cut(self.exp_avg)} if sgd else
+                        {"step": step, "exp_avg": cut(self.exp_avg), "exp_avg_sq": cut(self.exp_avg_sq)})
+        wd = cfg.weight_decay if cfg.weight_decay != 0 else 0
+        if sgd:
+            group = {"lr": lr, "momentum": second, "dampening": cfg.dampening if cfg.dampening != 0 else 0,
+                     "weight_decay": wd, "nesterov": cfg.nesterov, "maximize": False, "foreach": None,
+                     "differentiable": False, "fused": None}
+        else:
+            group = {"lr": lr, "betas": (second, cfg.beta2), "eps": cfg.eps, "weight_decay": wd, "amsgrad": False}
         if one_cycle is not None:
             initial_lr = one_cycle.max_lr / one_cycle.div_factor
             group.update(initial_lr=initial_lr, max_lr=one_cycle.max_lr, min_lr=initial_lr / one_cycle.final_div_factor,
@@ -418,48 +438,66 @@ class ParamStore:
         group["params"] = list(range(len(order)))
         return {"state": state, "param_groups": [group]}
 
-    def load_torch_adam_state(self, osd: Dict[str, object]) -> None:
-        """Inverse of torch_adam_state(): scatter a torch Adam state dict (reference parameter order) into the flat
-        moment arenas.  Parameters without an entry keep zero moments."""
+    def torch_adam_state(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, one_cycle=None) -> Dict[str, object]:
+        """torch_optimizer_state() of Adam without weight decay (the name of earlier releases)."""
+        return self.torch_optimizer_state(lr, betas[0], OptimConfig(beta2=betas[1], eps=eps), one_cycle)
+
+    def load_torch_optimizer_state(self, osd: Dict[str, object]) -> None:
+        """Inverse of torch_optimizer_state(): scatter a torch Adam / SGD state dict (reference parameter order) into the
+        flat arenas.  Parameters without an entry keep zero state.  The algorithm is read off the param group (``betas``
+        = Adam); a state written under the other algorithm than this store steps under raises."""
+        group = osd["param_groups"][0]
+        sgd = "betas" not in group
+        fused.bind_algo(self, OptimConfig("sgd" if sgd else "adam"))
         order = self.reference_parameter_order()
-        if self.exp_avg is None:
+        if self.exp_avg is None and (not sgd or osd["state"]):
             self.exp_avg = torch.zeros_like(self.grad)
+        if self.exp_avg_sq is None and not sgd:
             self.exp_avg_sq = torch.zeros_like(self.grad)
         h = self.head_size()
         sh = sb = 0
+        key = "momentum_buffer" if sgd else "exp_avg"
         for i, st in osd["state"].items():
             n = order[int(i)]
             off = self.offsets[n]
-            if off >= self.n_train:
+            if off >= self.n_train or st.get(key) is None:
                 continue
-            ea = torch.as_tensor(st["exp_avg"]).to(self.device, torch.float32).reshape(-1)
-            if tuple(torch.as_tensor(st["exp_avg"]).shape) != tuple(self.shapes[n]):
-                raise ValueError(f"optimizer state of {n}: shape {tuple(st['exp_avg'].shape)} != {self.shapes[n]}")
+            ea = torch.as_tensor(st[key]).to(self.device, torch.float32).reshape(-1)
+            if tuple(torch.as_tensor(st[key]).shape) != tuple(self.shapes[n]):
+                raise ValueError(f"optimizer state of {n}: shape {tuple(st[key].shape)} != {self.shapes[n]}")
             self.exp_avg[off:off + ea.numel()].copy_(ea)
-            self.exp_avg_sq[off:off + ea.numel()].copy_(torch.as_tensor(st["exp_avg_sq"]).to(self.device, torch.float32).reshape(-1))
+            if not sgd:
+                self.exp_avg_sq[off:off + ea.numel()].copy_(torch.as_tensor(st["exp_avg_sq"]).to(self.device, torch.float32).reshape(-1))
+            # torch's SGD keeps no step count: all the kernel asks is whether the buffer exists yet (step >= 2 next time)
+            cnt = 1 if sgd else int(st["step"])
             if off < h:
-                sh = max(sh, int(st["step"]))
+                sh = max(sh, cnt)
             else:
-                sb = max(sb, int(st["step"]))
+                sb = max(sb, cnt)
         self.step_head, self.step_body = sh, sb
         self.step_count = max(sh, sb)
         if self.scaler is not None:
             self.scaler[4:6] = 0.0            # the loaded counts are torch's (skipped steps already excluded)
 
+    load_torch_adam_state = load_torch_optimizer_state
+
     # ------------------------------------------------------------------ optimiser / schedule state (resume)
     def optimizer_state(self) -> Dict[str, object]:
-        """What a PL checkpoint keeps under ``optimizer_states`` (torch Adam's exp_avg / exp_avg_sq / step) plus the
-        fp16 loss-scale record: a resume continues the moments, the bias correction and the scale."""
+        """What a PL checkpoint keeps under ``optimizer_states`` (torch Adam's exp_avg / exp_avg_sq / step; under SGD
+        the momentum buffer in ``exp_avg`` and no ``exp_avg_sq``) plus the fp16 loss-scale record: a resume continues the
+        moments, the bias correction and the scale."""
         z = lambda t: None if t is None else t.detach().clone().cpu()
         return {"exp_avg": z(self.exp_avg), "exp_avg_sq": z(self.exp_avg_sq), "step_head": self.step_head,
                 "step_body": self.step_body, "loss_scaler": z(self.scaler)}
 
     def load_optimizer_state(self, st: Dict[str, object]) -> None:
         if st.get("exp_avg") is not None:
-            ea, es = torch.as_tensor(st["exp_avg"]), torch.as_tensor(st["exp_avg_sq"])
+            ea, es = torch.as_tensor(st["exp_avg"]), st.get("exp_avg_sq")
             if ea.numel() != self.n_train:
                 raise ValueError(f"optimizer state of {ea.numel()} elements does not fit this arena ({self.n_train})")
-            self.exp_avg, self.exp_avg_sq = ea.to(self.device, torch.float32), es.to(self.device, torch.float32)
+            fused.bind_algo(self, OptimConfig("sgd" if es is None else "adam"))      # (SGD keeps one arena)
+            self.exp_avg = ea.to(self.device, torch.float32)
+            self.exp_avg_sq = None if es is None else torch.as_tensor(es).to(self.device, torch.float32)
         self.step_head, self.step_body = int(st.get("step_head", 0)), int(st.get("step_body", 0))
         self.step_count = max(self.step_head, self.step_body)
         if self.scaler is not None and st.get("loss_scaler") is not None:
@@ -576,15 +614,25 @@ class ParamStore:
 
     def adam_step(self, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
                   grad_scale: float = 1.0, head_only: bool = False) -> None:
-        """head_only: the wav2vec2 network is frozen (ref: wav2vec2_fc.py:339-361 ``wav2vec_initially_frozen``),
+        """Fused Adam without weight decay or clipping: optimizer_step() with the default description."""
+        self.optimizer_step(lr, beta1, OptimConfig(beta2=beta2, eps=eps), grad_scale, 0.0, head_only)
+
+    def optimizer_step(self, lr: float, momentum_or_beta1: float = 0.9, cfg: Optional[OptimConfig] = None,
+                       grad_scale: float = 1.0, gradient_clip_val: float = 0.0, head_only: bool = False) -> None:
+        """The optimiser step of every trainer.  ``momentum_or_beta1``: the schedule's second value, beta1 under Adam and
+        the momentum under SGD (what torch's OneCycleLR cycles for each).  ``cfg`` (None = Adam, beta2 0.999, eps 1e-8, no
+        weight decay).  ``gradient_clip_val`` > 0: torch's clip_grad_norm_ (PL ``trainer.gradient_clip_val``) over exactly
+        the slice that is stepped, folded into the optimiser launch; ``self.grad_norm`` = {norm, coefficient} stays on the
+        device.  ``self.track_grad_norm`` computes the norm without clipping.
+
+        head_only: the wav2vec2 network is frozen (ref: wav2vec2_fc.py:339-361 ``wav2vec_initially_frozen``),
         only the head slice of the arena is updated.
 
-        torch.optim.Adam keeps a step count PER PARAMETER that only advances when the parameter has a
-        gradient: parameters frozen for the first steps start their bias correction at 1 when they
-        unfreeze.  Two counters (head / rest of the arena) reproduce that."""
-        if self.exp_avg is None:
-            self.exp_avg = torch.zeros_like(self.grad)
-            self.exp_avg_sq = torch.zeros_like(self.grad)
+        torch's optimisers keep their state PER PARAMETER, and it only advances when the parameter has a gradient:
+        parameters frozen for the first steps start their bias correction (Adam) / initialise their momentum buffer
+        (SGD) when they unfreeze.  Two counters (head / rest of the arena) reproduce that."""
+        cfg = cfg if cfg is not None else fused.DEFAULT
+        fused.ensure_state(self, cfg, momentum_or_beta1)
         h = self.head_size()
         self.step_head += 1
         if not head_only:
@@ -593,7 +641,14 @@ class ParamStore:
         a = (self.flat, self.grad, self.exp_avg, self.exp_avg_sq)
         lp, sc = self.flat_lp, self.scaler
         n_train = min(self.n_train, self.n_body) if self.cnn_runtime_frozen else self.n_train
-        if sc is not None:
+        n_step = h if head_only else n_train
+        norm = None
+        if gradient_clip_val > 0 or self.track_grad_norm:
+            # after the all-reduce: grad_scale = 1 / world makes this the norm of the averaged, unscaled gradient.  The
+            # pass reads the whole stepped slice and sets found_inf itself, so the scan below is not needed
+            fused.norm_pass(self, n_step, grad_scale, sc, gradient_clip_val)
+            norm = self.grad_norm if gradient_clip_val > 0 else None
+        elif sc is not None:
             # found_inf (torch GradScaler.unscale_): an overflow of ANY fp16 activation gradient (the only 16-bit
             # tensors of the backward; weight gradients are f32 sums of finite products) propagates down the chain into
             # the LAST bucket backward writes, so scanning that bucket (1.4 M of 99 M elements) decides for the step.
@@ -606,14 +661,16 @@ class ParamStore:
                 lo = self.offsets[W2V_PREFIX + "encoder.layer_norm.weight"]
                 ops.grad_scaler_check(self.grad[lo:], n_train - lo, sc)
         sh, sb = (4, 5) if sc is not None else (0, 0)         # record slots of the skipped-step counts (head / body)
+        step = lambda ts, pb, n, count, slot: fused.launch(cfg, *ts, pb, n, lr, momentum_or_beta1, count, grad_scale, sc,
+                                                           slot, norm)
         if head_only:
-            ops.adam_step(*a, lp, h, lr, beta1, beta2, eps, self.step_head, grad_scale, sc, sh)
+            step(a, lp, h, self.step_head, sh)
         elif self.step_head == self.step_body or h == 0:
-            ops.adam_step(*a, lp, n_train, lr, beta1, beta2, eps, self.step_body, grad_scale, sc, sb)
-        else:
-            ops.adam_step(*a, lp, h, lr, beta1, beta2, eps, self.step_head, grad_scale, sc, sh)
-            ops.adam_step(*(t[h:] for t in a), lp[h:] if lp is not None else None, n_train - h, lr, beta1,
-                          beta2, eps, self.step_body, grad_scale, sc, sb)
+            step(a, lp, n_train, self.step_body, sb)
+        else:               # (one norm over both ranges: the coefficient is the whole step's)
+            step(a, lp, h, self.step_head, sh)
+            step(tuple(t[h:] if t is not None else None for t in a), lp[h:] if lp is not None else None, n_train - h,
+                 self.step_body, sb)
         if sc is not None:
             ops.grad_scaler_update(sc, skipped_ranges=1 if head_only else 3)
         self.sync_transposed()

@@ -2,7 +2,8 @@
 
   forward (conv stack -> projection -> SpecAugment mask -> encoder -> pooling -> AAM/CE head)
   -> hand-written backward -> [RCCL all-reduce of gradient buckets on a side HIP stream, overlapped
-  with the rest of backward] -> fused Adam with the one-cycle lr / beta1 of this step.
+  with the rest of backward] -> fused optimiser step (Adam or SGD, optional weight decay and gradient-norm clipping)
+  with the schedule's lr / beta1-or-momentum of this step.
 
 Data parallelism is one process per GPU (``torch.distributed``, backend "nccl" == RCCL over xGMI):
 every rank holds a full replica, draws its own minibatch, and the only collective is the SUM
@@ -19,6 +20,7 @@ import numpy as np
 import torch
 
 from .engine import Plan
+from .optim import OptimConfig
 from .params import ParamStore
 from .spec_augment import compute_mask_indices
 
@@ -110,12 +112,19 @@ class BucketAllReducer:
 
 class SpeakerTrainer:
     def __init__(self, store: ParamStore, plan: Plan, schedule, process_group=None, beta2: float = 0.999,
-                 eps: float = 1e-8, layerdrop_seed: int = 1234, mask_seed: int = 7, reducer=None):
+                 eps: float = 1e-8, layerdrop_seed: int = 1234, mask_seed: int = 7, reducer=None,
+                 optimizer: Optional[OptimConfig] = None, gradient_clip_val: float = 0.0):
         """reducer: an object with bucket_ready(name) / wait() / world (default: BucketAllReducer over
-        torch.distributed; comm.CAbiBucketAllReducer runs the collective through the C ABI alone)."""
+        torch.distributed; comm.CAbiBucketAllReducer runs the collective through the C ABI alone).
+        optimizer: the optimiser description (ref: config/optim/algo/*.yaml); None = Adam with this constructor's
+        ``beta2`` / ``eps`` and no weight decay.  The schedule's second value is beta1 under Adam and the momentum under
+        SGD (what torch's OneCycleLR cycles for each).  gradient_clip_val: PL's ``trainer.gradient_clip_val`` (global
+        norm; 0 = off), applied to the all-reduced, unscaled gradient inside the optimiser launch."""
         assert plan.train
         self.store, self.plan, self.schedule = store, plan, schedule
         self.beta2, self.eps = beta2, eps
+        self.optimizer = optimizer if optimizer is not None else OptimConfig(beta2=beta2, eps=eps)
+        self.gradient_clip_val = float(gradient_clip_val)
         self.step = 0
         self.reducer = reducer if reducer is not None else BucketAllReducer(store, process_group)
         self.world = self.reducer.world
@@ -164,8 +173,8 @@ class SpeakerTrainer:
         loss, softmax = frozen_plan.head_forward_backward(label)
         self.reducer.bucket_ready("head")
         self.reducer.wait()
-        lr, beta1 = self.schedule.at(self.step)
-        store.adam_step(lr, beta1, self.beta2, self.eps, grad_scale=1.0 / self.world, head_only=True)
+        lr, second = self.schedule.at(self.step)
+        store.optimizer_step(lr, second, self.optimizer, 1.0 / self.world, self.gradient_clip_val, head_only=True)
         self.step += 1
         return loss, softmax
 
@@ -185,7 +194,7 @@ class SpeakerTrainer:
         loss, softmax = plan.head_forward_backward(label)
         plan.backward(on_bucket_ready=self.reducer.bucket_ready)
         self.reducer.wait()
-        lr, beta1 = self.schedule.at(self.step)
-        store.adam_step(lr, beta1, self.beta2, self.eps, grad_scale=1.0 / self.world)
+        lr, second = self.schedule.at(self.step)
+        store.optimizer_step(lr, second, self.optimizer, 1.0 / self.world, self.gradient_clip_val)
         self.step += 1
         return loss, softmax
