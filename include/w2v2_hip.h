@@ -586,6 +586,15 @@ int w2v2_grad_norm_partials(int64_t n);
 int w2v2_grad_norm(const float* g, int64_t n, float grad_scale, float* scaler_state, float max_norm, double* partials,
                    int n_partials, float* norm_state, void* stream);
 
+/* Gradient accumulation over the micro-batches of one optimiser step: PL `trainer.accumulate_grad_batches` = N (ref:
+ * config/trainer/trainer.yaml:33) makes N backward passes of loss / N add into .grad before optimizer.step().  Every
+ * backward here WRITES its gradient arena, so the window's sum is kept in a second f32 arena of the same layout:
+ *   first != 0:  acc[i] = g[i]            (acc is never read: a new window needs no zeroing pass)
+ *   first == 0:  acc[i] = acc[i] + g[i]   (plain f32 add, the bits of torch's acc + g)
+ * The sum stays unscaled: 1 / (world * N) belongs in grad_scale of w2v2_optim_step / w2v2_adam_step / w2v2_grad_norm.
+ * acc and g 16-byte aligned (arena slices are 64-element aligned), n >= 0 (n == 0: no launch). */
+int w2v2_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream);
+
 /* Dynamic loss scaling for fp16 activations = torch.cuda.amp.GradScaler, which PL `precision: 16` of the
  * reference's runs installs (ref: config/experiment/speaker_wav2vec2_aam.yaml:17).
  * state (device, 4 floats, or 8 with per-range skip counts) = {scale, found_inf, growth_tracker, skipped_steps

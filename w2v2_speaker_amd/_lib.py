@@ -155,6 +155,7 @@ _SIGS = {
                                 c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "w2v2_grad_norm_partials": (c_i32, [c_i64]),
     "w2v2_grad_norm": (c_i32, [c_vp, c_i64, c_f32, c_vp, c_f32, c_vp, c_i32, c_vp, c_vp]),
+    "w2v2_grad_accumulate": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
     "w2v2_weight_residual": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "w2v2_comm_unique_id": (c_i32, [c_vp]),
     "w2v2_comm_init": (c_i32, [C.POINTER(c_vp), c_vp, c_i32, c_i32, c_i32]),

@@ -120,6 +120,7 @@ class CAbiBucketAllReducer:
         self.ranges, self.members = BucketAllReducer.merge_buckets(store.grad_buckets(), bucket_merge)
         self.comm_stream = torch.cuda.Stream()
         self._issued = False
+        self.buffer = None         # the arena bucket_ready() reduces; None = store.grad (see trainer.BucketAllReducer)
 
     def bucket_ready(self, name: str) -> None:
         if self.world == 1 or name not in self.ranges:
@@ -130,7 +131,7 @@ class CAbiBucketAllReducer:
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         self.comm_stream.wait_event(ev)
-        self.comm.all_reduce_(self.store.grad[s:e], self.comm_stream)
+        self.comm.all_reduce_((self.buffer if self.buffer is not None else self.store.grad)[s:e], self.comm_stream)
         self._issued = True
 
     def broadcast_parameters(self, root: int = 0, host_counters=None):

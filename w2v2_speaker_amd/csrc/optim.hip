@@ -200,6 +200,56 @@ extern "C" int w2v2_adam_step(float* p, const float* g, float* m, float* v, void
   return 0;
 }
 
+// ------------------------------------------------------------------------------ gradient accumulation
+// PL `trainer.accumulate_grad_batches` = N (ref: config/trainer/trainer.yaml:33): autograd adds the gradient of N
+// backward passes into .grad before optimizer.step().  Here every backward WRITES store.grad, so the window's sum lives in
+// a second f32 arena: acc = g on the first micro-batch of a window (acc is never read: no zeroing pass, stale NaN / inf
+// cannot leak in), acc += g afterwards.  A plain f32 add -- nothing to contract, bit-equal to torch's acc + g; the 1 / N
+// of the mean goes into the optimiser's grad_scale.  Same structure as adam_kernel: U independent 16-byte vectors per
+// thread and pass, streaming accesses (every byte is touched once per micro-batch), no grid cap, tail on block 0.
+// 12 B/parameter (8 on the first micro-batch).
+template <int U, bool FIRST>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g,
+                                                              int64_t n) {
+  const int64_t nv = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i0 < nv; i0 += stride * U) {
+    f32x4_hw aa[U], gg[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (i < nv) {
+        gg[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4_hw*>(g) + i);
+        if (!FIRST) aa[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4_hw*>(acc) + i);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * stride;
+      if (i >= nv) break;
+      __builtin_nontemporal_store(FIRST ? gg[u] : aa[u] + gg[u], reinterpret_cast<f32x4_hw*>(acc) + i);
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const int64_t i = (nv << 2) + threadIdx.x;
+    acc[i] = FIRST ? g[i] : acc[i] + g[i];
+  }
+}
+
+extern "C" int w2v2_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream) {
+  W2V2_REQUIRE(acc && g && n >= 0, "grad_accumulate: bad arguments");
+  W2V2_REQUIRE(((uintptr_t)acc & 15) == 0 && ((uintptr_t)g & 15) == 0,
+               "grad_accumulate: acc and g must be 16-byte aligned (arena slices are 64-element aligned)");
+  if (n == 0) return 0;
+  constexpr int U = 2;                 // adam_kernel's default
+  int64_t nb = cdiv(n >> 2, 256 * U);
+  if (nb < 1) nb = 1;
+  if (first) hipLaunchKernelGGL((grad_accumulate_kernel<U, true>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), acc, g, n);
+  else hipLaunchKernelGGL((grad_accumulate_kernel<U, false>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), acc, g, n);
+  W2V2_CHECK_LAUNCH("grad_accumulate");
+  return 0;
+}
+
 // ------------------------------------------------------------------------------ global gradient norm (clipping)
 // torch.nn.utils.clip_grad_norm_ (PL `trainer.gradient_clip_val`, called after GradScaler.unscale_; ref:
 // config/trainer/trainer.yaml) over a slice of the flat f32 gradient arena, in two launches and without atomics: the

@@ -152,6 +152,8 @@ class EcapaStore:
         self.optim_algo: Optional[str] = None          # see ParamStore
         self.grad_norm = torch.zeros(2, dtype=torch.float32, device=dev)
         self.track_grad_norm = False
+        self.grad_acc: Optional[torch.Tensor] = None   # see ParamStore
+        self.accum_count = 0
 
     def running(self, weight_name: str) -> torch.Tensor:
         """{running_mean, running_var} record of the BatchNorm whose scale parameter is ``weight_name``."""
@@ -239,17 +241,19 @@ class EcapaStore:
         self.optimizer_step(lr, beta1, OptimConfig(beta2=beta2, eps=eps), grad_scale)
 
     def optimizer_step(self, lr: float, momentum_or_beta1: float = 0.9, cfg: Optional[OptimConfig] = None,
-                       grad_scale: float = 1.0, gradient_clip_val: float = 0.0, head_only: bool = False) -> None:
+                       grad_scale: float = 1.0, gradient_clip_val: float = 0.0, head_only: bool = False,
+                       grad: Optional[torch.Tensor] = None) -> None:
         """Same contract as ParamStore.optimizer_step (one range: the whole arena trains; no loss-scale record)."""
+        g = self.grad if grad is None else grad
         assert not head_only, "ECAPA has no frozen-encoder step"
         cfg = cfg if cfg is not None else fused.DEFAULT
         fused.ensure_state(self, cfg, momentum_or_beta1)
         self.step_count += 1
         norm = None
         if gradient_clip_val > 0 or self.track_grad_norm:
-            fused.norm_pass(self, self.n_total, grad_scale, None, gradient_clip_val)
+            fused.norm_pass(self, self.n_total, grad_scale, None, gradient_clip_val, g)
             norm = self.grad_norm if gradient_clip_val > 0 else None
-        fused.launch(cfg, self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.flat_lp, self.n_total, lr,
+        fused.launch(cfg, self.flat, g, self.exp_avg, self.exp_avg_sq, self.flat_lp, self.n_total, lr,
                      momentum_or_beta1, self.step_count, grad_scale, None, 0, norm)
         self.version += 1
 
@@ -715,8 +719,14 @@ class EcapaTrainer:
     """One training step: forward, AAM head, backward, fused Adam (ref: speaker_recognition_module.py:207-220)."""
 
     def __init__(self, store: EcapaStore, plan: EcapaPlan, schedule, process_group=None,
-                 optimizer: Optional[OptimConfig] = None, gradient_clip_val: float = 0.0):
-        """optimizer (None = Adam, beta2 0.999, eps 1e-8, no weight decay) / gradient_clip_val: see SpeakerTrainer."""
+                 optimizer: Optional[OptimConfig] = None, gradient_clip_val: float = 0.0,
+                 accumulate_grad_batches: int = 1):
+        """optimizer (None = Adam, beta2 0.999, eps 1e-8, no weight decay) / gradient_clip_val / accumulate_grad_batches:
+        see SpeakerTrainer."""
+        if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {accumulate_grad_batches!r}")
+        self.accumulate_grad_batches = int(accumulate_grad_batches)
+        self.stepped = False               # whether the last train_step / flush call ran the optimiser
         self.store, self.plan, self.schedule, self.step = store, plan, schedule, 0
         self.optimizer, self.gradient_clip_val = optimizer, float(gradient_clip_val)
         self.pg = process_group                      # data parallel: ONE all-reduce of the flat gradient arena (25 MB)
@@ -726,6 +736,8 @@ class EcapaTrainer:
             self.world = dist.get_world_size(process_group)
 
     def train_step(self, feat: torch.Tensor, label: torch.Tensor):
+        if self.accumulate_grad_batches > 1:
+            return self._micro_batch(feat, label)
         self.store.zero_grad()
         self.plan.embed(feat)
         loss, softmax = self.plan.head_forward_backward(label)
@@ -736,4 +748,40 @@ class EcapaTrainer:
         lr, second = self.schedule.at(self.step)           # beta1 under Adam, the momentum under SGD
         self.store.optimizer_step(lr, second, self.optimizer, 1.0 / self.world, self.gradient_clip_val)
         self.step += 1
+        self.stepped = True
         return loss, softmax
+
+    def _micro_batch(self, feat: torch.Tensor, label: torch.Tensor):
+        """One micro-batch of an accumulation window (SpeakerTrainer's protocol with the single all-reduce): the gradient
+        is added into store.grad_acc, the N-th call all-reduces that arena and steps.  The BatchNorm running statistics
+        move on every micro-batch, as in torch."""
+        store = self.store
+        store.zero_grad()
+        self.plan.embed(feat)
+        loss, softmax = self.plan.head_forward_backward(label)
+        self.plan.backward()
+        fused.accumulate(store, 0, store.n_total)
+        store.accum_count += 1
+        self.stepped = store.accum_count == self.accumulate_grad_batches
+        if self.stepped:
+            self._close_window()
+        return loss, softmax
+
+    def _close_window(self) -> None:
+        store = self.store
+        if self.world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(store.grad_acc, group=self.pg)
+        lr, second = self.schedule.at(self.step)
+        store.optimizer_step(lr, second, self.optimizer, 1.0 / (self.world * self.accumulate_grad_batches),
+                             self.gradient_clip_val, grad=store.grad_acc)
+        self.step += 1
+        store.accum_count = 0
+
+    def flush(self) -> None:
+        """Close a partial window: step on what has been accumulated, still divided by world * N (see SpeakerTrainer)."""
+        self.stepped = False
+        if self.accumulate_grad_batches == 1 or self.store.accum_count == 0:
+            return
+        self._close_window()
+        self.stepped = True

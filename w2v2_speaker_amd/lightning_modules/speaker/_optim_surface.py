@@ -17,6 +17,9 @@ from ...optim.schedule import from_torch_scheduler
 class OptimizerSurface:
     optimizer_cfg: Optional[OptimConfig] = None      # None: the fused Adam the modules always ran
     gradient_clip_val: float = 0.0                   # PL ``trainer.gradient_clip_val`` (constructor keyword)
+    accumulate_grad_batches: int = 1                 # PL ``trainer.accumulate_grad_batches`` (constructor keyword)
+    schedule_step: int = 0                           # optimiser steps taken = position in the learning-rate schedule
+    _window_trainer = None                           # the trainer whose calls opened the accumulation window
     _torch_optimizer = None
     _torch_schedule = None
 
@@ -44,7 +47,32 @@ class OptimizerSurface:
         return [self._torch_optimizer], [self._torch_schedule]
 
     def _trainer_options(self) -> dict:
-        return {"optimizer": self.optimizer_cfg, "gradient_clip_val": self.gradient_clip_val}
+        return {"optimizer": self.optimizer_cfg, "gradient_clip_val": self.gradient_clip_val,
+                "accumulate_grad_batches": self.accumulate_grad_batches}
+
+    def _set_accumulate_grad_batches(self, n) -> None:
+        if int(n) != n or n < 1:
+            raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {n!r}")
+        self.accumulate_grad_batches = int(n)
+
+    def _after_micro_batch(self, trainer) -> None:
+        """``training_step`` bookkeeping: the schedule advances only when the trainer ran the optimiser (every call at
+        ``accumulate_grad_batches`` = 1)."""
+        if trainer.stepped:
+            self.schedule_step += 1
+            self._window_trainer = None
+        else:
+            self._window_trainer = trainer
+
+    def on_train_epoch_end(self) -> None:
+        """PL steps on a partial window at the end of an epoch (each micro-batch still divided by N): flush the trainer
+        that holds the open window.  Nothing happens without one."""
+        tr = self._window_trainer
+        if tr is None:
+            return
+        tr.step = self.schedule_step
+        tr.flush()
+        self._after_micro_batch(tr)
 
     def parameters(self, recurse: bool = True):
         """One ``nn.Parameter`` view of the flat arena per parameter (``.grad`` = the matching gradient view), so that

@@ -38,7 +38,8 @@ class EcapaTdnnModule(OptimizerSurface):
     def __init__(self, hyperparameters_to_save, cfg: EcapaTDNNModuleConfig, num_speakers: int,
                  loss_fn_constructor: Callable[[], object], validation_pairs=None, test_pairs=None, evaluator=None, *,
                  device="cuda", act_dtype: torch.dtype = torch.bfloat16, max_lr: float = 1e-3,
-                 max_steps: int = 100_000, init_seed: int = 20211, gradient_clip_val: float = 0.0):
+                 max_steps: int = 100_000, init_seed: int = 20211, gradient_clip_val: float = 0.0,
+                 accumulate_grad_batches: int = 1):
         """Positional arguments = ref: ecapa_tdnn.py:51-62 (what src/main.py:256-285 passes to every network class).
         ``loss_fn_constructor`` is called once and read for its type and hyper-parameters: the engine runs the ECAPA
         model under AAM-softmax (``skip_classifier`` of ref :93-95; the paper's configuration,
@@ -71,13 +72,15 @@ class EcapaTdnnModule(OptimizerSurface):
         self.margin, self.scale = aam_margin, aam_scale
         self.schedule = OneCycle(max_lr=max_lr, total_steps=max_steps)
         self.gradient_clip_val = float(gradient_clip_val)      # PL ``trainer.gradient_clip_val`` (global norm, 0 = off)
+        self._set_accumulate_grad_batches(accumulate_grad_batches)     # PL ``trainer.accumulate_grad_batches``
         self.skip_classifier = True                        # AAM owns the classifier weight (ref :93-95, :129-131)
         self.device = torch.device(device)
         self._plans: Dict[Tuple, EcapaPlan] = {}
         self._trainers: Dict[Tuple, EcapaTrainer] = {}
         self._bucket_plans: "OrderedDict[Tuple, EcapaPlan]" = OrderedDict()
         self.bucket_plans_built = 0
-        self.steps = 0
+        self.steps = 0              # backward passes (micro-batches)
+        self.schedule_step = 0      # optimiser steps = position in the learning-rate schedule
 
     @classmethod
     def from_config(cls, cfg: EcapaTDNNModuleConfig, num_speakers: int, aam_margin: float = 0.2,
@@ -176,9 +179,10 @@ class EcapaTdnnModule(OptimizerSurface):
             self._trainers[key] = EcapaTrainer(self.store, self._plan(x.shape[0], x.shape[1], True), self.schedule,
                                                **self._trainer_options())
         tr = self._trainers[key]
-        tr.step = self.steps
+        tr.step = self.schedule_step
         loss, pred = tr.train_step(x, label)
         self.steps += 1
+        self._after_micro_batch(tr)
         return {"loss": loss, "prediction": pred}
 
     def validation_step(self, batch: SpeakerClassificationDataBatch, batch_idx: int = 0):

@@ -151,16 +151,23 @@ class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
                  test_pairs: Optional[List[EvaluationPair]] = None, evaluator=None, *, device="cuda",
                  act_dtype: torch.dtype = torch.float16, max_lr: float = 5e-5, max_steps: int = 100_000,
                  process_group=None, init_seed: int = 20211, pretrained_state_dict=None,
-                 gradient_clip_val: float = 0.0):
+                 gradient_clip_val: float = 0.0, accumulate_grad_batches: int = 1):
         """Positional arguments = ref: wav2vec2_fc.py:101-111.  Keyword-only extras: the device / activation dtype of
         the engine, the one-cycle schedule the reference takes from ``cfg.optim`` (src/main.py:323-335), and
         ``pretrained_state_dict`` (a path or a dict with HF ``facebook/wav2vec2-*`` weights: there is no network
-        here for ``from_pretrained``), and ``gradient_clip_val`` (PL ``trainer.gradient_clip_val``, global norm, 0 = off).
+        here for ``from_pretrained``), ``gradient_clip_val`` (PL ``trainer.gradient_clip_val``, global norm, 0 = off) and
+        ``accumulate_grad_batches`` (PL ``trainer.accumulate_grad_batches`` = N: one optimiser step per N ``training_step``
+        calls, on the mean of their gradients; ``on_train_epoch_end`` steps on a partial window).
         ``set_optimizer`` / ``set_lr_schedule`` replace the default fused Adam under the one-cycle schedule."""
         super().__init__()
         self.gradient_clip_val = float(gradient_clip_val)
+        self._set_accumulate_grad_batches(accumulate_grad_batches)
         self.hyperparameters_to_save = hyperparameters_to_save
         self.cfg = cfg
+        if (self.accumulate_grad_batches > 1 and cfg.wav2vec_initially_frozen and cfg.num_frozen_steps is not None
+                and cfg.num_frozen_steps % self.accumulate_grad_batches != 0):
+            raise ValueError(f"num_frozen_steps = {cfg.num_frozen_steps} is no multiple of accumulate_grad_batches = "
+                             f"{self.accumulate_grad_batches}: the unfreeze would fall inside an accumulation window")
         if cfg.wav2vec_feature_encoder_only:
             # ref: :114-128 swaps in Wav2vecLiteWrapperModule (CNN only).  The wrapper itself is mirrored
             # (models.wav2vec2.Wav2vecLiteWrapperModule, forward + conv backward); the speaker module over it is not:
@@ -280,9 +287,9 @@ class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
             self.wav2vec.model.feature_extractor.requires_grad_(False)
 
     def on_after_backward(self) -> None:
-        # ref: wav2vec2_fc.py:349-361 -- num_frozen_steps counts backward calls
+        # ref: wav2vec2_fc.py:349-361 -- num_frozen_steps counts backward calls (every micro-batch; the schedule position
+        # advances with the optimiser steps, in training_step)
         self.steps += 1
-        self.schedule_step += 1
         if (self._is_wav2vec_frozen and self.cfg.num_frozen_steps is not None
                 and self.steps >= self.cfg.num_frozen_steps):
             self.wav2vec.unfreeze()
@@ -451,6 +458,7 @@ class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
             loss, pred = tr.train_step(x, label)
             head = plan.head
         self.train_acc = head.correct.mean()
+        self._after_micro_batch(tr)
         self.on_after_backward()
         return {"loss": loss, "prediction": pred, "train_acc": self.train_acc}
 
@@ -506,6 +514,10 @@ class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
         resume needs; the engine's own extras (fp16 loss-scale
         record, freeze-schedule counters) travel under ``w2v2_amd``.  What is NOT claimed: torchmetrics / callback
         states of a PL ``Trainer`` -- a ``Trainer`` resume restores weights, optimiser moments and schedule position."""
+        if self.store.accum_count > 0:
+            raise RuntimeError(f"an accumulation window is open ({self.store.accum_count} of "
+                               f"{self.accumulate_grad_batches} micro-batches): flush it first (on_train_epoch_end()); no "
+                               "partial window is written to a file")
         sd = self.state_dict()
         if legacy_weight_norm_names:
             sd = OrderedDict((ParamStore.legacy_key(k), v) for k, v in sd.items())

@@ -56,7 +56,8 @@ class Wav2vec2PairedSpeakerModule(OptimizerSurface):
     def __init__(self, hyperparameters_to_save, cfg: Wav2vec2PairedSpeakerModuleConfig,
                  loss_fn_constructor: Optional[Callable[[], object]] = None, *, device="cuda",
                  act_dtype: torch.dtype = torch.float16, max_lr: float = 5e-5, max_steps: int = 100_000,
-                 process_group=None, init_seed: int = 20211, gradient_clip_val: float = 0.0):
+                 process_group=None, init_seed: int = 20211, gradient_clip_val: float = 0.0,
+                 accumulate_grad_batches: int = 1):
         """Positional arguments = ref: wav2vec2_paired_input.py:65-71.  ``loss_fn_constructor`` must build the
         reference's ``BinaryCrossEntropyLoss`` (src/optim/loss/binary_cross_entropy.py; the only loss this module is
         configured with, config/optim/loss/binary_cross_entropy.yaml) -- it is called once and checked; the arithmetic
@@ -83,11 +84,13 @@ class Wav2vec2PairedSpeakerModule(OptimizerSurface):
         self.store.init_weights(init_seed)
         self.schedule = OneCycle(max_lr=max_lr, total_steps=max_steps)
         self.gradient_clip_val = float(gradient_clip_val)      # PL ``trainer.gradient_clip_val`` (global norm, 0 = off)
+        self._set_accumulate_grad_batches(accumulate_grad_batches)     # PL ``trainer.accumulate_grad_batches``
         self.process_group = process_group
         self.device = torch.device(device)
         self._plans: Dict[Tuple, Plan] = {}
         self._trainers: Dict[Tuple, SpeakerTrainer] = {}
-        self.steps = 0
+        self.steps = 0              # backward passes (micro-batches)
+        self.schedule_step = 0      # optimiser steps = position in the learning-rate schedule
 
     def _get_wav2vec2_embedding_size(self):
         return self.model_cfg.hidden_size                   # ref :112-118 (768 / 1024)
@@ -138,9 +141,10 @@ class Wav2vec2PairedSpeakerModule(OptimizerSurface):
             self._trainers[key] = SpeakerTrainer(self.store, self._plan(key[0], key[1], True), self.schedule,
                                                  process_group=self.process_group, **self._trainer_options())
         tr = self._trainers[key]
-        tr.step = self.steps
+        tr.step = self.schedule_step
         loss, pred = tr.train_step(wav, label)
         self.steps += 1
+        self._after_micro_batch(tr)
         return {"loss": loss, "prediction": pred}
 
     def state_dict(self):

@@ -689,6 +689,13 @@ def grad_norm(g, n: int, norm_state, partials, grad_scale: float = 1.0, scaler=N
                                     partials.numel(), norm_state.data_ptr(), stream()), "grad_norm")
 
 
+def grad_accumulate(acc, g, n: int, first: bool) -> None:
+    """acc[:n] = g[:n] (first micro-batch of a window: acc is not read) or acc[:n] += g[:n]; f32, bit-equal to torch."""
+    _dev(acc, g)
+    assert acc.dtype == torch.float32 and g.dtype == torch.float32 and acc.numel() >= n and g.numel() >= n
+    _lib.check(lib().w2v2_grad_accumulate(acc.data_ptr(), g.data_ptr(), n, int(bool(first)), stream()), "grad_accumulate")
+
+
 def weight_residual(p, lo, table) -> None:
     """lo[off:off+n] = T(p[off:off+n] - T(p[off:off+n])) for every (off, n) row of the int64 device table."""
     _dev(p, lo, table)

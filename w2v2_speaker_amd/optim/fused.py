@@ -31,12 +31,13 @@ def ensure_state(store, cfg: OptimConfig, second: float) -> None:
         store.exp_avg_sq = torch.zeros_like(store.grad)
 
 
-def norm_pass(store, n: int, grad_scale: float, scaler, max_norm: float) -> torch.Tensor:
-    """store.grad_norm = {norm, clip coefficient} of the first n gradient elements (two launches)."""
+def norm_pass(store, n: int, grad_scale: float, scaler, max_norm: float, grad=None) -> torch.Tensor:
+    """store.grad_norm = {norm, clip coefficient} of the first n gradient elements (two launches).  ``grad``: the arena
+    to read (None = store.grad)."""
     if getattr(store, "_norm_partials", None) is None:
         store._norm_partials = torch.zeros(ops.grad_norm_partials(store.grad.numel()), dtype=torch.float64,
                                            device=store.grad.device)
-    ops.grad_norm(store.grad, n, store.grad_norm, store._norm_partials, grad_scale, scaler, max_norm)
+    ops.grad_norm(store.grad if grad is None else grad, n, store.grad_norm, store._norm_partials, grad_scale, scaler, max_norm)
     return store.grad_norm
 
 
@@ -50,3 +51,14 @@ def launch(cfg: OptimConfig, p, g, m, v, pb, n: int, lr: float, second: float, s
     ops.optim_step(cfg.algo, p, g, m, v, pb, n, lr, second, cfg.beta2, cfg.eps, step, grad_scale, scaler, skip_slot,
                    weight_decay=cfg.weight_decay, momentum=second if cfg.algo == "sgd" else 0.0,
                    dampening=cfg.dampening, nesterov=cfg.nesterov, norm_state=norm_state)
+
+
+def accumulate(store, start: int, end: int) -> None:
+    """Add store.grad[start:end] into the open accumulation window (``trainer.accumulate_grad_batches`` > 1): the first
+    micro-batch of a window (store.accum_count == 0) overwrites store.grad_acc, so the arena is never zeroed.  The arena
+    -- a second gradient arena, 4 B/parameter -- is allocated here, on the first accumulating step.  The caller advances
+    store.accum_count once per micro-batch (a micro-batch may accumulate bucket by bucket)."""
+    if store.grad_acc is None:
+        store.grad_acc = torch.empty_like(store.grad)
+    if end > start:
+        ops.grad_accumulate(store.grad_acc[start:end], store.grad[start:end], end - start, store.accum_count == 0)

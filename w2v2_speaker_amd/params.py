@@ -196,6 +196,12 @@ class ParamStore:
         self.optim_algo: Optional[str] = None
         self.grad_norm = torch.zeros(2, dtype=torch.float32, device=dev)
         self.track_grad_norm = False
+        # gradient accumulation (``trainer.accumulate_grad_batches`` > 1): the f32 sum over the open window, allocated by
+        # the first accumulating step (optim.fused.accumulate) and never at N = 1, and the number of micro-batches already
+        # in it.  The window position lives here because a module keeps one trainer per plan shape over this one store.
+        self.grad_acc: Optional[torch.Tensor] = None
+        self.accum_count = 0
+        self.accum_head_only = False      # the open window's micro-batches ran with the encoder frozen
 
     # ------------------------------------------------------------------ views
     def _view(self, buf: torch.Tensor, name: str) -> torch.Tensor:
@@ -612,13 +618,18 @@ class ParamStore:
         """Number of leading arena elements that belong to the classification head."""
         return self.grad_buckets()[0][2] if (self.head is not None or self.attentive_pool) else 0
 
+    def stepped_size(self) -> int:
+        """Number of leading arena elements a full (not head-only) optimiser step updates."""
+        return min(self.n_train, self.n_body) if self.cnn_runtime_frozen else self.n_train
+
     def adam_step(self, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
                   grad_scale: float = 1.0, head_only: bool = False) -> None:
         """Fused Adam without weight decay or clipping: optimizer_step() with the default description."""
         self.optimizer_step(lr, beta1, OptimConfig(beta2=beta2, eps=eps), grad_scale, 0.0, head_only)
 
     def optimizer_step(self, lr: float, momentum_or_beta1: float = 0.9, cfg: Optional[OptimConfig] = None,
-                       grad_scale: float = 1.0, gradient_clip_val: float = 0.0, head_only: bool = False) -> None:
+                       grad_scale: float = 1.0, gradient_clip_val: float = 0.0, head_only: bool = False,
+                       grad: Optional[torch.Tensor] = None) -> None:
         """The optimiser step of every trainer.  ``momentum_or_beta1``: the schedule's second value, beta1 under Adam and
         the momentum under SGD (what torch's OneCycleLR cycles for each).  ``cfg`` (None = Adam, beta2 0.999, eps 1e-8, no
         weight decay).  ``gradient_clip_val`` > 0: torch's clip_grad_norm_ (PL ``trainer.gradient_clip_val``) over exactly
@@ -627,6 +638,9 @@ class ParamStore:
 
         head_only: the wav2vec2 network is frozen (ref: wav2vec2_fc.py:339-361 ``wav2vec_initially_frozen``),
         only the head slice of the arena is updated.
+
+        grad: the arena the step reads -- norm pass, found-inf scan and optimiser launch alike.  None = ``self.grad``;
+        a trainer under ``accumulate_grad_batches`` > 1 passes ``self.grad_acc``, the sum over the window.
 
         torch's optimisers keep their state PER PARAMETER, and it only advances when the parameter has a gradient:
         parameters frozen for the first steps start their bias correction (Adam) / initialise their momentum buffer
@@ -638,15 +652,16 @@ class ParamStore:
         if not head_only:
             self.step_body += 1
         self.step_count = max(self.step_head, self.step_body)
-        a = (self.flat, self.grad, self.exp_avg, self.exp_avg_sq)
+        g = self.grad if grad is None else grad
+        a = (self.flat, g, self.exp_avg, self.exp_avg_sq)
         lp, sc = self.flat_lp, self.scaler
-        n_train = min(self.n_train, self.n_body) if self.cnn_runtime_frozen else self.n_train
+        n_train = self.stepped_size()
         n_step = h if head_only else n_train
         norm = None
         if gradient_clip_val > 0 or self.track_grad_norm:
             # after the all-reduce: grad_scale = 1 / world makes this the norm of the averaged, unscaled gradient.  The
             # pass reads the whole stepped slice and sets found_inf itself, so the scan below is not needed
-            fused.norm_pass(self, n_step, grad_scale, sc, gradient_clip_val)
+            fused.norm_pass(self, n_step, grad_scale, sc, gradient_clip_val, g)
             norm = self.grad_norm if gradient_clip_val > 0 else None
         elif sc is not None:
             # found_inf (torch GradScaler.unscale_): an overflow of ANY fp16 activation gradient (the only 16-bit
@@ -654,12 +669,12 @@ class ParamStore:
             # the LAST bucket backward writes, so scanning that bucket (1.4 M of 99 M elements) decides for the step.
             # Head-only steps and steps with a trainable CNN scan their whole slice.
             if head_only:
-                ops.grad_scaler_check(self.grad, h, sc)
+                ops.grad_scaler_check(g, h, sc)
             elif n_train > self.n_body or os.environ.get("W2V2_SCALER_FULL_SCAN"):      # (debug: scan the whole arena)
-                ops.grad_scaler_check(self.grad, n_train, sc)
+                ops.grad_scaler_check(g, n_train, sc)
             else:
                 lo = self.offsets[W2V_PREFIX + "encoder.layer_norm.weight"]
-                ops.grad_scaler_check(self.grad[lo:], n_train - lo, sc)
+                ops.grad_scaler_check(g[lo:], n_train - lo, sc)
         sh, sb = (4, 5) if sc is not None else (0, 0)         # record slots of the skipped-step counts (head / body)
         step = lambda ts, pb, n, count, slot: fused.launch(cfg, *ts, pb, n, lr, momentum_or_beta1, count, grad_scale, sc,
                                                            slot, norm)

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from .engine import Plan
-from .optim import OptimConfig
+from .optim import OptimConfig, fused
 from .params import ParamStore
 from .spec_augment import compute_mask_indices
 
@@ -37,6 +37,8 @@ class BucketAllReducer:
         self.ranges, self.members = self.merge_buckets(store.grad_buckets(), bucket_merge)
         self.comm_stream = torch.cuda.Stream() if store.device.type == "cuda" else None
         self.works = []
+        self.buffer = None         # the arena bucket_ready() reduces; None = store.grad (a trainer that accumulates over
+                                   # several micro-batches points it at store.grad_acc)
 
     @staticmethod
     def merge_buckets(raw: List[Tuple[str, int, int]], bucket_merge: int):
@@ -63,7 +65,7 @@ class BucketAllReducer:
         s, e = self.ranges[name]
         if e <= s:
             return
-        view = self.store.grad[s:e]
+        view = (self.buffer if self.buffer is not None else self.store.grad)[s:e]
         if self.comm_stream is None:       # CPU / gloo test path
             self.works.append(self.dist.all_reduce(view, op=self.dist.ReduceOp.SUM, group=self.pg, async_op=True))
             return
@@ -113,14 +115,23 @@ class BucketAllReducer:
 class SpeakerTrainer:
     def __init__(self, store: ParamStore, plan: Plan, schedule, process_group=None, beta2: float = 0.999,
                  eps: float = 1e-8, layerdrop_seed: int = 1234, mask_seed: int = 7, reducer=None,
-                 optimizer: Optional[OptimConfig] = None, gradient_clip_val: float = 0.0):
+                 optimizer: Optional[OptimConfig] = None, gradient_clip_val: float = 0.0,
+                 accumulate_grad_batches: int = 1):
         """reducer: an object with bucket_ready(name) / wait() / world (default: BucketAllReducer over
         torch.distributed; comm.CAbiBucketAllReducer runs the collective through the C ABI alone).
         optimizer: the optimiser description (ref: config/optim/algo/*.yaml); None = Adam with this constructor's
         ``beta2`` / ``eps`` and no weight decay.  The schedule's second value is beta1 under Adam and the momentum under
         SGD (what torch's OneCycleLR cycles for each).  gradient_clip_val: PL's ``trainer.gradient_clip_val`` (global
-        norm; 0 = off), applied to the all-reduced, unscaled gradient inside the optimiser launch."""
+        norm; 0 = off), applied to the all-reduced, unscaled gradient inside the optimiser launch.
+        accumulate_grad_batches: PL's ``trainer.accumulate_grad_batches`` = N (ref: config/trainer/trainer.yaml:33).  At
+        N > 1 one ``train_step`` call is one micro-batch: its gradient is added into ``store.grad_acc``, and only the N-th
+        call of a window all-reduces (PL's ``no_sync`` on the others), steps on the mean over world * N micro-batches and
+        advances the schedule; ``stepped`` tells which kind the last call was, ``flush()`` closes a partial window."""
         assert plan.train
+        if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {accumulate_grad_batches!r}")
+        self.accumulate_grad_batches = int(accumulate_grad_batches)
+        self.stepped = False               # whether the last train_step / flush call ran the optimiser
         self.store, self.plan, self.schedule = store, plan, schedule
         self.beta2, self.eps = beta2, eps
         self.optimizer = optimizer if optimizer is not None else OptimConfig(beta2=beta2, eps=eps)
@@ -128,6 +139,16 @@ class SpeakerTrainer:
         self.step = 0
         self.reducer = reducer if reducer is not None else BucketAllReducer(store, process_group)
         self.world = self.reducer.world
+        if self.accumulate_grad_batches > 1 and self.world > 1:
+            if not hasattr(self.reducer, "buffer"):
+                raise TypeError("accumulate_grad_batches > 1 on several ranks needs a reducer with a `buffer` attribute "
+                                "(the arena bucket_ready() reduces; None = store.grad): this one would all-reduce "
+                                "store.grad instead of the accumulated store.grad_acc")
+            at = 0
+            for s, e in sorted(self.reducer.ranges.values()):
+                assert s == at and e >= s, "the reducer's ranges must cover [0, n_train) exactly once"
+                at = e
+            assert at == store.n_train, "the reducer's ranges must cover [0, n_train) exactly once"
         self._ld_rng = np.random.RandomState(layerdrop_seed)
         self._mask_rng = np.random.RandomState(mask_seed)
 
@@ -168,6 +189,8 @@ class SpeakerTrainer:
         """Step while the whole wav2vec2 network is frozen (ref: wav2vec2_fc.py:339-347 + PL ``freeze()`` =
         requires_grad False AND eval mode): eval-mode forward, head forward/backward, Adam on the head only."""
         store = self.store
+        if self.accumulate_grad_batches > 1:
+            return self._micro_batch_frozen_encoder(frozen_plan, wav, label)
         store.zero_grad()
         frozen_plan.embed(wav, None, (), self.step)
         loss, softmax = frozen_plan.head_forward_backward(label)
@@ -176,6 +199,7 @@ class SpeakerTrainer:
         lr, second = self.schedule.at(self.step)
         store.optimizer_step(lr, second, self.optimizer, 1.0 / self.world, self.gradient_clip_val, head_only=True)
         self.step += 1
+        self.stepped = True
         return loss, softmax
 
     def train_step(self, wav: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor] = None,
@@ -189,6 +213,8 @@ class SpeakerTrainer:
             mask = self.sample_time_mask()
         if feature_mask is None:
             feature_mask = self.sample_feature_mask()
+        if self.accumulate_grad_batches > 1:
+            return self._micro_batch(wav, label, mask, skip_layers, feature_mask)
         store.zero_grad(tuple(skip_layers) if plan.grouped else None)
         plan.embed(wav, mask, skip_layers, self.step, feature_mask)
         loss, softmax = plan.head_forward_backward(label)
@@ -197,4 +223,84 @@ class SpeakerTrainer:
         lr, second = self.schedule.at(self.step)
         store.optimizer_step(lr, second, self.optimizer, 1.0 / self.world, self.gradient_clip_val)
         self.step += 1
+        self.stepped = True
         return loss, softmax
+
+    # ------------------------------------------------------------------ accumulate_grad_batches > 1
+    # A window is the N consecutive micro-batches of one optimiser step.  Every backward writes store.grad as it always
+    # did; the window's sum is kept in store.grad_acc (w2v2_grad_accumulate: the first micro-batch overwrites, so nothing
+    # is zeroed), unscaled -- 1 / (world * N) rides in the optimiser's grad_scale, next to the loss scale and the clip
+    # coefficient, so the clip sees the averaged gradient as torch's clip_grad_norm_ does.  The loss-scale record is only
+    # touched by optimizer_step, i.e. constant over a window like torch's GradScaler between update() calls.
+    def _micro_batch(self, wav, label, mask, skip_layers, feature_mask):
+        plan, store, N = self.plan, self.store, self.accumulate_grad_batches
+        if store.accum_count > 0 and store.accum_head_only:
+            raise RuntimeError("this accumulation window was opened by a frozen-encoder micro-batch; a window cannot mix "
+                               "frozen and unfrozen micro-batches (flush() first)")
+        last = store.accum_count == N - 1
+        store.zero_grad(tuple(skip_layers) if plan.grouped else None)
+        plan.embed(wav, mask, skip_layers, self.step * N + store.accum_count, feature_mask)    # a dropout seed per micro-batch
+        loss, softmax = plan.head_forward_backward(label)
+        if last and self.world > 1:
+            plan.backward(on_bucket_ready=self._accumulate_and_reduce)     # the all-reduce of grad_acc overlaps backward
+        else:
+            plan.backward()                                                # no collective (PL: no_sync)
+            fused.accumulate(store, 0, store.stepped_size())
+        store.accum_count += 1
+        store.accum_head_only = False
+        self.stepped = last
+        if last:
+            self._close_window(False)
+        return loss, softmax
+
+    def _accumulate_and_reduce(self, name: str) -> None:
+        """Bucket callback of a window's last backward: the firing bucket's merged range is final in store.grad -- add it
+        into grad_acc on the compute stream, then hand that slice of grad_acc to the reducer."""
+        if name in self.reducer.ranges:
+            fused.accumulate(self.store, *self.reducer.ranges[name])
+            self.reducer.buffer = self.store.grad_acc
+        self.reducer.bucket_ready(name)
+
+    def _micro_batch_frozen_encoder(self, frozen_plan: Plan, wav, label):
+        store, N = self.store, self.accumulate_grad_batches
+        if store.accum_count > 0 and not store.accum_head_only:
+            raise RuntimeError("this accumulation window was opened by an unfrozen micro-batch; a window cannot mix frozen "
+                               "and unfrozen micro-batches (flush() first)")
+        last = store.accum_count == N - 1
+        store.zero_grad()
+        frozen_plan.embed(wav, None, (), self.step * N + store.accum_count)
+        loss, softmax = frozen_plan.head_forward_backward(label)
+        fused.accumulate(store, 0, store.head_size())
+        store.accum_count += 1
+        store.accum_head_only = True
+        self.stepped = last
+        if last:
+            if self.world > 1:
+                self.reducer.buffer = store.grad_acc
+                self.reducer.bucket_ready("head")
+            self._close_window(True)
+        return loss, softmax
+
+    def _close_window(self, head_only: bool) -> None:
+        store = self.store
+        self.reducer.wait()
+        lr, second = self.schedule.at(self.step)
+        store.optimizer_step(lr, second, self.optimizer, 1.0 / (self.world * self.accumulate_grad_batches),
+                             self.gradient_clip_val, head_only=head_only, grad=store.grad_acc)
+        self.step += 1
+        store.accum_count = 0
+
+    def flush(self) -> None:
+        """Close a partial window (the end of an epoch): all-reduce what has been accumulated and step on it, still
+        divided by world * N -- PL divides every micro-batch's loss by N, also those of a short last window.  Nothing
+        happens when no window is open."""
+        store = self.store
+        self.stepped = False
+        if self.accumulate_grad_batches == 1 or store.accum_count == 0:
+            return
+        if self.world > 1:
+            self.reducer.buffer = store.grad_acc
+            for name in (("head",) if store.accum_head_only else tuple(self.reducer.ranges)):
+                self.reducer.bucket_ready(name)
+        self._close_window(store.accum_head_only)
+        self.stepped = True
