@@ -290,6 +290,15 @@ int w2v2_mask_fill_bwd(void* dh, const uint8_t* mask, float* d_embed, float* par
                        void* stream);
 /* CLS token (ref: src/models/wav2vec2.py:128-140): y[b][0][:] = c, y[b][1+t][:] = x[b][t][:]. */
 int w2v2_prepend_token(const void* x, void* y, float c, int B, int T, int H, int dtype, void* stream);
+/* Paired-input sequence at per-pair lengths (ref: wav2vec2_paired_input.py:181-197): feat [R][H] row-major, y [B][T][H],
+ * the four tables device int32[B].  With ta = left_frames[b], tb = right_frames[b]:
+ *   y[b][0] = cls_c,  y[b][1 .. ta] = feat[left_row[b] ..],  y[b][ta+1] = sep_c,
+ *   y[b][ta+2 .. ta+tb+1] = feat[right_row[b] ..],  y[b][ta+tb+2] = sep_c,  every later frame = 0.
+ * Rows may be shared between pairs and come in any order; only named rows are read.  The caller guarantees
+ * ta, tb >= 1, ta + tb + 3 <= T and both row ranges inside [0, R) (checked on the host before the tables are uploaded);
+ * H % 8 == 0, T >= 5. */
+int w2v2_pair_assemble(const void* feat, void* y, const int* left_row, const int* left_frames, const int* right_row,
+                       const int* right_frames, float cls_c, float sep_c, int B, int T, int H, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------- pos-conv
  * HF:326-379 grouped weight-normed Conv1d(H,H,K,pad=K/2,groups=G) as an implicit GEMM per group:

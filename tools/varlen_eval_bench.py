@@ -8,7 +8,12 @@ timed region is bracketed by device synchronisation.  Prints one JSON line.
 --model ecapa runs the same comparison on the full-width ECAPA-TDNN (C = 1024) over filterbank tensors of --min-frames to
 --max-frames frames (default 400-2000, the 4-20 s of the wav2vec2 leg at the 10 ms hop); the per-utterance path is timed
 twice, building its one-plan-per-length as it goes (what a first pass over a trial list costs) and with the plans cached.
-    python tools/varlen_eval_bench.py --model ecapa [--dtype f32|bf16]"""
+    python tools/varlen_eval_bench.py --model ecapa [--dtype f32|bf16]
+--model paired scores a seeded trial list (default 2048 trials over 256 utterances, uniform 4-20 s) with the paired-input
+model three ways: (a) one trial at a time through compute_speaker_equality (batch 1; a subset), (b) score_trials (every
+utterance through the conv stack once, trials batched through encoder-only plans), (c) score_trials with the feature reuse
+switched off (each trial's two utterances through the conv stack on their own), so that batching and reuse can be told apart.
+    python tools/varlen_eval_bench.py --model paired [--trials 2048] [--utts 256] [--subset 64] [--dtype f16]"""
 import argparse
 import json
 import os
@@ -76,9 +81,89 @@ def ecapa_main(a):
     }))
 
 
+def paired_main(a):
+    from oracle import w2v2_oracle as O
+    from w2v2_speaker_amd.config import W2V2Config
+    from w2v2_speaker_amd.data.paired import EvaluationPair
+    from w2v2_speaker_amd.eval_batching import DEFAULT_PAIR_QUANTUM, plan_pair_batches
+    from w2v2_speaker_amd.lightning_modules.speaker.wav2vec2_paired_input import (Wav2vec2PairedSpeakerModule,
+                                                                                   Wav2vec2PairedSpeakerModuleConfig)
+    dtype = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}[a.dtype]
+    cfg = W2V2Config()
+    orig = W2V2Config.from_huggingface_id
+    W2V2Config.from_huggingface_id = staticmethod(lambda _id: cfg)
+    try:
+        mod = Wav2vec2PairedSpeakerModule(None, Wav2vec2PairedSpeakerModuleConfig(), device="cuda", act_dtype=dtype)
+    finally:
+        W2V2Config.from_huggingface_id = orig
+    sd = O.make_state_dict(O.OracleConfig.base(), 20211)
+    sd["linear.weight"] = O.synth_tensor("linear.weight", (1, cfg.hidden_size), 20211)
+    sd["linear.bias"] = O.synth_tensor("linear.bias", (1,), 20211)
+    mod.store.load_state_dict(sd)
+    r = np.random.default_rng(a.seed)
+    lens = [int(x) for x in r.integers(int(a.min_s * 16000), int(a.max_s * 16000) + 1, a.utts)]
+    audio = {f"u{i}": torch.from_numpy(r.standard_normal(n).astype(np.float32)) for i, n in enumerate(lens)}
+    ij = r.integers(0, a.utts, (a.trials, 2))
+    pairs = [EvaluationPair(bool(i % 2), f"u{int(x)}", f"u{int(y)}") for i, (x, y) in enumerate(ij)]
+    sub = list(range(min(a.subset, a.trials)))
+    q = a.quantum or DEFAULT_PAIR_QUANTUM
+    one = lambda i: mod.compute_speaker_equality(audio[pairs[i].sample1_id][None], audio[pairs[i].sample2_id][None])
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, time.perf_counter() - t0
+
+    # (a) per trial at batch 1: the warm-up pass builds its plans (one per 2 s of the longer side), the timed pass reuses them
+    b0 = mod.bucket_plans_built
+    for i in sub:
+        one(i)
+    plans_a = mod.bucket_plans_built - b0 + len(mod._plans)
+    b0 = mod.bucket_plans_built + len(mod._plans)
+    ref, ta = timed(lambda: [float(one(i)[0, 0]) for i in sub])
+    assert mod.bucket_plans_built + len(mod._plans) == b0, "the per-trial pass rebuilt plans inside the timed region"
+    # (b) score_trials, (c) the same without the feature reuse; warm-up passes build the bucket plans
+    b0 = mod.bucket_plans_built
+    mod.score_trials(pairs, audio, quantum=q)
+    plans_b = mod.bucket_plans_built - b0
+    got, tb = timed(lambda: mod.score_trials(pairs, audio, quantum=q))
+    assert mod.bucket_plans_built - b0 == plans_b, "score_trials rebuilt plans inside the timed region"
+    bank_b = mod.last_bank_bytes
+    mod.score_trials(pairs, audio, quantum=q, reuse_features=False)
+    b0 = mod.bucket_plans_built
+    got_c, tc = timed(lambda: mod.score_trials(pairs, audio, quantum=q, reuse_features=False))
+    assert mod.bucket_plans_built == b0, "score_trials(reuse_features=False) rebuilt plans inside the timed region"
+    bank_c = mod.last_bank_bytes
+    fr = [cfg.num_frames(n) for n in lens]
+    lf, rf = [fr[int(x)] for x, _ in ij], [fr[int(y)] for _, y in ij]
+    batches = plan_pair_batches(lf, rf, q)
+    valid = sum(x + y + 3 for x, y in zip(lf, rf))
+    per_trial_a, per_trial_b, per_trial_c = ta / len(sub), tb / a.trials, tc / a.trials
+    print(json.dumps({
+        "metric": "varlen_eval_paired", "dtype": a.dtype, "trials": a.trials, "utterances": a.utts, "subset": len(sub),
+        "quantum_frames": q,
+        "per_trial_s": round(ta, 4), "per_trial_trials_per_s": round(1 / per_trial_a, 2),
+        "score_trials_s": round(tb, 4), "score_trials_trials_per_s": round(1 / per_trial_b, 2),
+        "score_trials_no_reuse_s": round(tc, 4), "score_trials_no_reuse_trials_per_s": round(1 / per_trial_c, 2),
+        "speedup_score_trials_vs_per_trial": round(per_trial_a / per_trial_b, 2),
+        "speedup_no_reuse_vs_per_trial": round(per_trial_a / per_trial_c, 2),
+        "speedup_reuse_alone": round(tc / tb, 2),
+        "per_trial_plans_built": plans_a, "bucket_plans_built": plans_b, "pair_batches": len(batches),
+        "padded_over_valid_frames": round(sum(b * n for _, n, b in batches) / valid, 4),
+        "bank_bytes": bank_b, "bank_bytes_no_reuse": bank_c,
+        "max_abs_logit_diff_vs_per_trial": max(abs(got[i] - ref[j]) for j, i in enumerate(sub)),
+        "max_abs_logit_diff_no_reuse_vs_per_trial": max(abs(got_c[i] - ref[j]) for j, i in enumerate(sub)),
+        "max_abs_logit": max(abs(v) for v in ref),
+    }))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="w2v2", choices=["w2v2", "ecapa"])
+    ap.add_argument("--model", default="w2v2", choices=["w2v2", "ecapa", "paired"])
+    ap.add_argument("--trials", type=int, default=2048)
+    ap.add_argument("--utts", type=int, default=256)
     ap.add_argument("--min-frames", type=int, default=400)
     ap.add_argument("--max-frames", type=int, default=2000)
     ap.add_argument("--n", type=int, default=512)
@@ -93,6 +178,8 @@ def main():
         raise SystemExit("varlen_eval_bench needs the GPU")
     if a.model == "ecapa":
         return ecapa_main(a)
+    if a.model == "paired":
+        return paired_main(a)
     from oracle import w2v2_oracle as O
     from w2v2_speaker_amd.config import W2V2Config
     from w2v2_speaker_amd.eval_batching import DEFAULT_QUANTUM, plan_batches

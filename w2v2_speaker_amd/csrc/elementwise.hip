@@ -433,6 +433,48 @@ extern "C" int w2v2_prepend_token(const void* x, void* y, float c, int B, int T,
   return 0;
 }
 
+// ------------------------------------------------------------------------------------- paired-input sequence
+// y[b] = [CLS] left [SEP] right [SEP] 0 ... 0 from rows of one feature matrix (ref: wav2vec2_paired_input.py:181-197, at
+// per-pair lengths): left = feat[lrow[b] .. + lfr[b]), right = feat[rrow[b] .. + rfr[b]).  Frames past lfr + rfr + 3 are
+// written as zeros; only the rows a pair names are read, so whatever else the matrix holds never reaches y.
+template <typename T>
+__global__ void pair_assemble_kernel(const T* __restrict__ feat, T* __restrict__ y, const int* __restrict__ lrow,
+                                     const int* __restrict__ lfr, const int* __restrict__ rrow,
+                                     const int* __restrict__ rfr, float cls_c, float sep_c, int B, int Tn, int H) {
+  const int nch = H >> 3;
+  const int64_t total = (int64_t)B * Tn * nch;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int ch = (int)(i % nch);
+    const int64_t row = i / nch;
+    const int b = (int)(row / Tn), t = (int)(row - (int64_t)b * Tn);
+    const int ta = lfr[b], tb = rfr[b];
+    Vec8<T> v;
+    if (t >= 1 && t <= ta) {
+      v.load(feat + ((int64_t)lrow[b] + (t - 1)) * H + ch * 8);
+    } else if (t >= ta + 2 && t <= ta + tb + 1) {
+      v.load(feat + ((int64_t)rrow[b] + (t - ta - 2)) * H + ch * 8);
+    } else {
+      const float c = t == 0 ? cls_c : ((t == ta + 1 || t == ta + tb + 2) ? sep_c : 0.0f);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v.v[k] = c;
+    }
+    v.store(y + row * H + ch * 8);
+  }
+}
+
+extern "C" int w2v2_pair_assemble(const void* feat, void* y, const int* left_row, const int* left_frames,
+                                  const int* right_row, const int* right_frames, float cls_c, float sep_c, int B, int T,
+                                  int H, int dtype, void* stream) {
+  W2V2_REQUIRE(feat && y && left_row && left_frames && right_row && right_frames && B > 0 && T >= 5 && H > 0 && H % 8 == 0,
+               "pair_assemble: bad arguments");
+  const int nb = ew_blocks((int64_t)B * T * (H >> 3));
+  W2V2_DISPATCH_ACT(dtype, "pair_assemble",
+    hipLaunchKernelGGL(pair_assemble_kernel<AT>, dim3(nb), dim3(256), 0, as_stream(stream), (const AT*)feat, (AT*)y,
+                       left_row, left_frames, right_row, right_frames, cls_c, sep_c, B, T, H););
+  W2V2_CHECK_LAUNCH("pair_assemble");
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------- batched transpose
 // dst_i[C][R] = src_i[R][C]^T for a table of matrices inside one arena (the bf16 weight copies): one launch
 // refreshes every pre-transposed weight after the optimiser step, so that the data-gradient GEMMs

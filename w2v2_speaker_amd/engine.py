@@ -177,7 +177,7 @@ class Plan:
                  insert_cls_token: bool = False, cls_token_constant: float = 1.0,
                  aam_margin: float = 0.2, aam_scale: float = 30.0, fused_attention: Optional[bool] = None,
                  seed: int = 7, keep_hidden_states: bool = False, paired: bool = False,
-                 sep_token_constant: float = -1.0):
+                 sep_token_constant: float = -1.0, encoder_frames: Optional[int] = None):
         cfg = store.cfg
         self.store, self.cfg, self.B, self.N, self.train = store, cfg, batch, n_samples, train
         # paired input (ref: wav2vec2_paired_input.py:163-207): the conv stack and projection run on 2B waveforms (first
@@ -202,9 +202,18 @@ class Plan:
         # ``output_hidden_states`` (ref: wav2vec2_fc.py:440-463 ensemble of layers)
         self.all_x = train or keep_hidden_states
         self.dev, self.adt = store.device, store.act_dtype
-        self.lens = cfg.conv_lengths(n_samples)
+        # encoder-only paired plan (Plan.pair_encoder): sequences of exactly `encoder_frames` frames assembled from a feature
+        # matrix the caller holds (embed_pairs); no conv stack, no projection, none of their buffers
+        self.enc_only = encoder_frames is not None
+        if self.enc_only and (not paired or train or n_samples != 0 or encoder_frames < 5):
+            raise ValueError("encoder_frames: an evaluation plan with paired=True, n_samples=0 and at least 5 frames "
+                             "([CLS] l [SEP] r [SEP]); build it with Plan.pair_encoder")
+        self.lens = [0] * len(cfg.conv_dim) if self.enc_only else cfg.conv_lengths(n_samples)
         self.T0 = self.lens[-1]                       # frames out of the CNN
-        self.T = 2 * self.T0 + 3 if paired else self.T0 + (1 if insert_cls_token else 0)
+        if self.enc_only:
+            self.T = int(encoder_frames)
+        else:
+            self.T = 2 * self.T0 + 3 if paired else self.T0 + (1 if insert_cls_token else 0)
         self.M0, self.M = self.Bc * self.T0, batch * self.T
         H, d = cfg.hidden_size, cfg.head_dim
         if fused_attention is None:
@@ -236,8 +245,18 @@ class Plan:
         # current forward, or None on the fixed-length path
         self._len_dev, self._len = None, None
         self.frame_lengths: Optional[List[int]] = None
+        # paired variable-length evaluation: device int32 [4, B] = left row | left frames | right row | right frames of the
+        # feature matrix the sequences are assembled from (ops.pair_assemble)
+        self._pair_dev = None
         self._alloc()
         self._build_gemms()
+
+    @classmethod
+    def pair_encoder(cls, store: ParamStore, batch: int, frames: int, **kw) -> "Plan":
+        """Encoder-only paired evaluation plan: `batch` sequences [CLS] left [SEP] right [SEP] of at most `frames` frames
+        (T = frames exactly), assembled by embed_pairs from rows of a projected-feature matrix (Plan.features).  It holds
+        no conv-stack or projection buffer."""
+        return cls(store, batch, 0, train=False, pooling="first", paired=True, encoder_frames=frames, **kw)
 
     def _wgrad_group_size(self) -> int:
         """How many consecutive blocks share one grouped weight-gradient launch: 2 (pairs, since round 3) unless FOUR fill
@@ -291,6 +310,11 @@ class Plan:
         f32 = torch.float32
         C = cfg.conv_dim
         Bc = self.Bc
+        if self.enc_only:
+            self.cnn_train = False
+            self.hx = self._e(M, H)                                # encoder input, written by the assemble kernel
+            self._alloc_encoder()
+            return
         self.stats0 = ops.conv0_workspace(Bc, self.N, C[0], cfg.conv_kernel[0], cfg.conv_stride[0], self.dev)
         self.conv = [self._e(Bc, L, c) for L, c in zip(self.lens, C)]
         cins = (1,) + tuple(C[:-1])
@@ -315,6 +339,13 @@ class Plan:
         self.mean_f, self.rstd_f = self._e(self.M0, dtype=f32), self._e(self.M0, dtype=f32)
         self.h0 = self._e(self.M0, H)                          # projection output (pre-CLS)
         self.hx = self._e(M, H) if (self.cls or self.paired) else self.h0       # encoder input
+        self._alloc_encoder(proj_pad)
+
+    def _alloc_encoder(self, proj_pad: int = 0) -> None:
+        """Everything from the positional convolution on (the part an encoder-only plan has too)."""
+        cfg, B, T, M, H, I = self.cfg, self.B, self.T, self.M, self.cfg.hidden_size, self.cfg.intermediate_size
+        f32 = torch.float32
+        C = cfg.conv_dim
         G, K = cfg.num_conv_pos_embedding_groups, cfg.num_conv_pos_embeddings
         self.Cg, self.Tp = H // G, T + K - 1
         # the direct convolution kernel is built for 48 (w2v2-base) and 64 (wav2vec2-large, round 6) channels per group at
@@ -404,7 +435,7 @@ class Plan:
         cins = (1,) + tuple(C[:-1])
         # conv layers 1..6: implicit GEMM over the channels-last activation of the previous layer
         self.g_conv = []
-        for i in range(1, len(C)):
+        for i in range(1, len(C) if not self.enc_only else 0):
             k, s, ci, co = cfg.conv_kernel[i], cfg.conv_stride[i], cins[i], C[i]
             cbias = st.mp(f"feature_extractor.conv_layers.{i}.conv.bias") if cfg.conv_bias else self.zero_bias
             # layer-norm family: the product only adds the bias; LayerNorm + GELU follow in place (forward())
@@ -426,8 +457,9 @@ class Plan:
                 self.g_conv_dx.append(Gemm(Mi, k * ci, co, gout, self.convw[i], self.col, lda=co, ldb=k * ci,
                                            ldc=k * ci, transB=True))
         mw, mp = st.mw, st.mp
-        self.g_proj = Gemm(self.M0, H, C[-1], self.ln_feat, mw("feature_projection.projection.weight"), self.h0,
-                           lda=C[-1], ldb=C[-1], ldc=H, epilogue=EPI_BIAS, bias=mp("feature_projection.projection.bias"))
+        self.g_proj = None if self.enc_only else Gemm(
+            self.M0, H, C[-1], self.ln_feat, mw("feature_projection.projection.weight"), self.h0,
+            lda=C[-1], ldb=C[-1], ldc=H, epilogue=EPI_BIAS, bias=mp("feature_projection.projection.bias"))
         G, K, Cg, Tp = cfg.num_conv_pos_embedding_groups, cfg.num_conv_pos_embeddings, self.Cg, self.Tp
         self.g_pos = Gemm(M, Cg, K * Cg, self.xg, self.posw_f, self.pos, lda=Cg, ldb=K * Cg, ldc=H,
                           a_seg=(T, G * Tp * Cg), batch=G, batch_inner=G, a_strides=(0, Tp * Cg),
@@ -564,7 +596,7 @@ class Plan:
     # ------------------------------------------------------------------------------------------ derived weights
     def _refresh_packs(self) -> None:
         st, cfg = self.store, self.cfg
-        if self._cnn_version != st.cnn_version:
+        if self._cnn_version != st.cnn_version and not self.enc_only:
             for i in range(1, len(cfg.conv_dim)):
                 ops.pack_conv_weight(st.mp(f"feature_extractor.conv_layers.{i}.conv.weight"), self.convw[i])
             self._cnn_version = st.cnn_version
@@ -586,7 +618,7 @@ class Plan:
         if self.train:
             raise NotImplementedError("lengths: evaluation plans only (there is no backward for variable lengths)")
         if self.paired:
-            raise NotImplementedError("lengths: the paired-input model has no variable-length path")
+            raise NotImplementedError("lengths: a paired plan takes the two sides' sample counts as pair_lengths=(left, right)")
         if self.pooling in ("random", "none"):
             raise NotImplementedError(f"lengths: pooling {self.pooling!r} has no variable-length form "
                                       "(supported: mean+std, mean, max, first, first+cls, last, middle, quantile, attentive)")
@@ -599,8 +631,97 @@ class Plan:
         self._len = self._len_dev
         self.frame_lengths = te
 
+    def _set_pair_lengths(self, pair_lengths) -> None:
+        """Validate the two sides' per-pair sample counts; upload the conv-0 frame counts of the 2B conv rows (left
+        utterances, then right) and keep the rows of self.h0 each pair is assembled from (the pair's encoder frames are
+        uploaded by _assemble_pairs)."""
+        if not self.paired or self.enc_only:
+            raise ValueError("pair_lengths: a plan built with paired=True over waveforms (an encoder-only plan takes "
+                             "embed_pairs; other plans take lengths=)")
+        if self.train:
+            raise NotImplementedError("pair_lengths: evaluation plans only (there is no backward for variable lengths)")
+        if self.pooling != "first":
+            raise NotImplementedError("pair_lengths: the paired model reads token 0 (pooling='first')")
+        try:
+            left, right = pair_lengths
+        except (TypeError, ValueError):
+            raise ValueError("pair_lengths: a pair (left, right) of per-pair sample counts") from None
+        B, T0 = self.B, self.T0
+        lens = valid_lengths(self.cfg, left, B, self.N) + valid_lengths(self.cfg, right, B, self.N)
+        if self._len_dev is None:
+            self._len_dev = torch.empty(3 * B, dtype=torch.int32, device=self.dev)   # conv-0 frames [2B] | encoder frames [B]
+        self._len_dev[:2 * B].copy_(torch.tensor([self.cfg.conv_lengths(n)[0] for n in lens], dtype=torch.int32))
+        self._len = (self._len_dev[:2 * B], self._len_dev[2 * B:])
+        fr = [self.cfg.num_frames(n) for n in lens]
+        self._pair_rows = ([b * T0 for b in range(B)], fr[:B], [(B + b) * T0 for b in range(B)], fr[B:])
+
+    def _assemble_pairs(self, feat: torch.Tensor, left_row, left_frames, right_row, right_frames) -> None:
+        """self.hx = [CLS] left [SEP] right [SEP] 0... of each pair from rows of feat [R, H] (tables: host values, checked
+        in ops.pair_assemble); the encoder frames te = ta + tb + 3 become the length table of every stage after it."""
+        B, T, H = self.B, self.T, self.cfg.hidden_size
+        if self._pair_dev is None:
+            self._pair_dev = torch.empty(4, B, dtype=torch.int32, device=self.dev)
+        if self.enc_only:                              # no conv rows: the table holds the encoder frames alone
+            if self._len_dev is None:
+                self._len_dev = torch.empty(B, dtype=torch.int32, device=self.dev)
+            self._len = (None, self._len_dev)
+        host = ops.pair_assemble(feat, self.hx.view(B, T, H), left_row, left_frames, right_row, right_frames, self.cls_c,
+                                 self.sep_c, table=self._pair_dev)
+        te = host[1] + host[3] + 3
+        self._len[1].copy_(te)
+        self.frame_lengths = te.tolist()
+
+    def embed_pairs(self, feat: torch.Tensor, left_row, left_frames, right_row, right_frames) -> torch.Tensor:
+        """Encoder-only paired plan (Plan.pair_encoder): pair b = rows [left_row[b], + left_frames[b]) and [right_row[b],
+        + right_frames[b]) of feat [R, H] (projected features in the activation dtype, e.g. Plan.features of each
+        utterance; rows may be shared between pairs) -> token 0 of each pair's encoder output [B, H] f32.  The tables are
+        host values; ta + tb + 3 <= the plan's frames.  Same code as forward(pair_lengths=) from the assembly on."""
+        if not self.enc_only:
+            raise ValueError("embed_pairs: an encoder-only paired plan (Plan.pair_encoder)")
+        assert feat.is_cuda and feat.dtype == self.adt and feat.dim() == 2 and feat.is_contiguous()
+        self._refresh_packs()
+        self._step, self._skip, self._mask, self._fmask = 0, (), None, None
+        self._assemble_pairs(feat, left_row, left_frames, right_row, right_frames)
+        self._pool_fwd(self._encode(0))
+        return self.emb
+
+    def features(self, wav: torch.Tensor, lengths=None):
+        """Conv stack + LayerNorm + projection alone (evaluation, non-paired plans; HF:382-419,1287 without dropout) ->
+        (projected frames [B, T0, H] in the activation dtype -- the plan's own buffer, valid until its next call --,
+        frames per row).  With lengths, row b's first frames[b] frames equal the utterance alone at its own length."""
+        if self.train or self.paired or self.cls:
+            raise NotImplementedError("features: non-paired evaluation plans without a CLS token")
+        cfg = self.cfg
+        if wav.dim() == 3:
+            wav = wav[:, 0, :]
+        wav = wav.contiguous()
+        assert wav.shape == (self.Bc, self.N) and wav.dtype == torch.float32 and wav.is_cuda
+        self._len, self.frame_lengths = None, None
+        frames = [self.T0] * self.B
+        if lengths is not None:
+            lens = valid_lengths(cfg, lengths, self.B, self.N)
+            if self._len_dev is None:
+                self._len_dev = torch.empty(2, self.B, dtype=torch.int32, device=self.dev)
+            frames = [cfg.num_frames(n) for n in lens]
+            self._len_dev.copy_(torch.tensor([[cfg.conv_lengths(n)[0] for n in lens], frames], dtype=torch.int32))
+            self._len = self._len_dev
+        self._refresh_packs()
+        self._wav = wav
+        self._project(wav)
+        return self.h0.view(self.B, self.T0, cfg.hidden_size), frames
+
+    def _project(self, wav: torch.Tensor) -> None:
+        """wav -> self.h0: conv stack, LayerNorm, projection (before the projection's dropout)."""
+        mp = self.store.mp
+        self._cnn_forward(wav)
+        ops.layernorm_fwd(self.conv[-1].view(self.M0, -1), None, mp("feature_projection.layer_norm.weight"),
+                          mp("feature_projection.layer_norm.bias"), self.ln_feat, self.mean_f, self.rstd_f,
+                          self.cfg.layer_norm_eps)
+        self.g_proj()
+
     def forward(self, wav: torch.Tensor, mask: Optional[torch.Tensor] = None, skip_layers: Sequence[int] = (),
-                step: int = 0, feature_mask: Optional[torch.Tensor] = None, lengths=None) -> torch.Tensor:
+                step: int = 0, feature_mask: Optional[torch.Tensor] = None, lengths=None,
+                pair_lengths=None) -> torch.Tensor:
         """wav [B,N] (or [B,1,N]) f32 on the GPU -> last_hidden_state [B,T,H] (act dtype).
         mask: [B,T0] uint8/bool SpecAugment time mask, feature_mask: [B,H] uint8/bool SpecAugment feature mask
         (HF:1294-1304; training only).  Dropout is active iff the plan was built with train=True and the
@@ -608,8 +729,13 @@ class Plan:
         lengths: valid samples per utterance (ints or a CPU integer tensor; evaluation plans).  Every cross-frame
         reduction (conv-0 GroupNorm statistics, positional-conv padding, attention, pooling) then sees each utterance's own
         frames only, so row b equals the utterance alone at its own length; padded samples may hold any finite values.
-        ``frame_lengths`` gives the encoder frames of each row; rows of the output past them are unspecified."""
+        ``frame_lengths`` gives the encoder frames of each row; rows of the output past them are unspecified.
+        pair_lengths: (left, right) valid samples of each pair's two utterances (paired evaluation plans; wav [2B,N] =
+        left utterances, then right).  Pair b is then [CLS] left [SEP] right [SEP] over its own ta + tb + 3 frames
+        (``frame_lengths``), equal to the pair alone at its own lengths."""
         cfg, st, reg = self.cfg, self.store, self.reg
+        if self.enc_only:
+            raise ValueError("forward: an encoder-only plan has no conv stack (embed_pairs)")
         B, T, M, H = self.B, self.T, self.M, cfg.hidden_size
         if wav.dim() == 3:
             wav = wav[:, 0, :]
@@ -618,20 +744,21 @@ class Plan:
         self._len, self.frame_lengths = None, None
         if lengths is not None:
             self._set_lengths(lengths)
+        if pair_lengths is not None:
+            self._set_pair_lengths(pair_lengths)
         self._refresh_packs()
         self._wav = wav
         tr = self.train
         self._step, self._skip, self._mask, self._fmask = step, tuple(skip_layers), None, None
         mp = st.mp
-        self._cnn_forward(wav)
-        ops.layernorm_fwd(self.conv[-1].view(self.M0, -1), None, mp("feature_projection.layer_norm.weight"),
-                          mp("feature_projection.layer_norm.bias"), self.ln_feat, self.mean_f, self.rstd_f,
-                          cfg.layer_norm_eps)
-        self.g_proj()
+        self._project(wav)
         if tr and reg.feat_proj_dropout > 0:
             ops.dropout_(self.h0, reg.feat_proj_dropout, self._sd("featproj", 0, step))
         if self.cls:
             ops.prepend_token(self.h0.view(B, self.T0, H), self.hx.view(B, T, H), self.cls_c)
+        elif pair_lengths is not None:
+            assert mask is None and feature_mask is None
+            self._assemble_pairs(self.h0, *self._pair_rows)
         elif self.paired:
             # [CLS] left [SEP] right [SEP] (constant tokens; no SpecAugment on this path) -- buffer plumbing only
             assert mask is None
@@ -648,6 +775,12 @@ class Plan:
             assert not (self.cls or self.paired)
             self._fmask = feature_mask.to(torch.uint8).contiguous().view(-1)
             ops.mask_feature(self.h0, self._fmask, B, self.T0)
+        return self._encode(step)
+
+    def _encode(self, step: int) -> torch.Tensor:
+        """self.hx (encoder input) -> last_hidden_state: positional convolution and the transformer encoder."""
+        cfg, mp = self.cfg, self.store.mp
+        B, T, H = self.B, self.T, cfg.hidden_size
         G, K = cfg.num_conv_pos_embedding_groups, cfg.num_conv_pos_embeddings
         if self._len is not None:
             ops.posconv_regroup_len(self.hx, self.xg, self._len[1], B, T, H, G, K, K // 2)
@@ -809,10 +942,11 @@ class Plan:
         self.dn.view(-1).copy_(dfeat.to(self.adt).contiguous().view(-1))
         self._backward_cnn()
 
-    def embed(self, wav, mask=None, skip_layers=(), step: int = 0, feature_mask=None, lengths=None) -> torch.Tensor:
+    def embed(self, wav, mask=None, skip_layers=(), step: int = 0, feature_mask=None, lengths=None,
+              pair_lengths=None) -> torch.Tensor:
         """ref: src/lightning_modules/speaker/wav2vec2_fc.py:414-431 -> pooled embedding [B,E] f32.  lengths: see
         forward(); each row is then pooled over its own frames."""
-        out = self.forward(wav, mask, skip_layers, step, feature_mask, lengths=lengths)
+        out = self.forward(wav, mask, skip_layers, step, feature_mask, lengths=lengths, pair_lengths=pair_lengths)
         if self.pooling == "attentive":       # (the encoder frame counts are the table the pooling needs)
             return self._asp_for(out).forward(None if self._len is None else self._len[1])
         self._pool_fwd(out)

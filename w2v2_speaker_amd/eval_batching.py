@@ -16,6 +16,9 @@ DEFAULT_MAX_BATCH = 64
 # the same policy over filterbank frames (ECAPA-TDNN: lengths in frames of the 10 ms hop of data/fbank.py)
 DEFAULT_FRAME_QUANTUM = 200                  # 2 s
 DEFAULT_MAX_BATCH_FRAMES = 66 * 300          # the benchmark's ECAPA training batch
+# ... and over encoder frames of the paired-input model (20 ms per frame; a trial is [CLS] left [SEP] right [SEP])
+DEFAULT_PAIR_QUANTUM = 100                   # 2 s
+DEFAULT_MAX_PAIR_BATCH_FRAMES = 66 * 301     # the paired training batch at 3 s + 3 s: 2 * 149 + 3 frames per pair
 
 
 def plan_batches(lengths: Sequence[int], quantum: int = DEFAULT_QUANTUM,
@@ -42,6 +45,21 @@ def plan_batches(lengths: Sequence[int], quantum: int = DEFAULT_QUANTUM,
             out.append((tuple(order[k:min(k + batch, j)]), padded, batch))
         i = j
     return out
+
+
+def plan_pair_batches(left_frames: Sequence[int], right_frames: Sequence[int], quantum: int = DEFAULT_PAIR_QUANTUM,
+                      max_batch_frames: int = DEFAULT_MAX_PAIR_BATCH_FRAMES,
+                      max_batch: int = DEFAULT_MAX_BATCH) -> List[Tuple[Tuple[int, ...], int, int]]:
+    """plan_batches for the trials of the paired-input model, in encoder frames: trial i occupies
+    ``left_frames[i] + right_frames[i] + 3`` frames of a sequence.  -> [(indices, padded_frames, batch)]."""
+    if quantum < 1 or max_batch_frames < 1 or max_batch < 1:
+        raise ValueError("plan_pair_batches: quantum, max_batch_frames and max_batch must be positive")
+    left, right = [int(n) for n in left_frames], [int(n) for n in right_frames]
+    if len(left) != len(right):
+        raise ValueError(f"plan_pair_batches: {len(left)} left and {len(right)} right frame counts")
+    if any(n < 1 for n in left + right):
+        raise ValueError("plan_pair_batches: every side of a trial needs at least one frame")
+    return plan_batches([a + b + 3 for a, b in zip(left, right)], quantum, max_batch_frames, max_batch)
 
 
 def min_samples(conv_kernel: Sequence[int], conv_stride: Sequence[int]) -> int:

@@ -1,20 +1,37 @@
 """Mirror of ``src/lightning_modules/speaker/wav2vec2_paired_input.py`` (Wav2vec2PairedSpeakerModuleConfig :27-67,
 Wav2vec2PairedSpeakerModule :70-207) + ``paired_speaker_recognition_module.py:60-140`` on the HIP path
-(engine.Plan(paired=True), heads.BceHead)."""
+(engine.Plan(paired=True), heads.BceHead).
+
+Evaluation (ref: paired_speaker_recognition_module.py:115-248): the step hooks and ``_evaluate`` follow the reference;
+``score_trials`` / ``evaluate_trials`` score a whole trial list batched -- every utterance goes through the conv stack once
+(Plan.features) into a device feature bank, and the trials, bucketed by their total frames, run through encoder-only plans
+(Plan.pair_encoder) that assemble [CLS] left [SEP] right [SEP] from rows of the bank."""
 from __future__ import annotations
 
 import dataclasses
+from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from ...config import W2V2Config, Wav2Vec2RegularisationConfig
 from ...engine import Plan
+from ...eval_batching import (DEFAULT_MAX_BATCH, DEFAULT_MAX_PAIR_BATCH_FRAMES, DEFAULT_PAIR_QUANTUM, DEFAULT_QUANTUM,
+                              min_samples, plan_batches, plan_pair_batches)
+from ...eval_metrics import calculate_eer, calculate_mdc
 from ...optim.schedule import OneCycle
 from ._optim_surface import OptimizerSurface
 from ...params import ParamStore
 from ...trainer import SpeakerTrainer
+
+
+# plans kept per LRU.  Feature buckets and the variable-length equality plans hold a conv stack (as the bucket plans of
+# wav2vec2_fc.py); the encoder-only trial plans are much smaller and their buckets span twice the length range
+MAX_BUCKET_PLANS = {"equality": 12, "features": 12, "pairs": 32}
+EQUALITY_QUANTUM = DEFAULT_QUANTUM   # compute_speaker_equality at unequal lengths: plan length rounded up to 2 s
+DEFAULT_MAX_BANK_BYTES = 8 << 30     # score_trials' feature bank: VoxCeleb1-O in fp16 is about 3 GB of the 288 GB
 
 
 @dataclass
@@ -89,6 +106,11 @@ class Wav2vec2PairedSpeakerModule(OptimizerSurface):
         self.device = torch.device(device)
         self._plans: Dict[Tuple, Plan] = {}
         self._trainers: Dict[Tuple, SpeakerTrainer] = {}
+        # evaluation plans, one bounded LRU each: variable-length equality plans (batch, samples), feature plans of
+        # score_trials (batch, samples), encoder-only trial plans (batch, frames)
+        self._lru: Dict[str, "OrderedDict[Tuple, Plan]"] = {k: OrderedDict() for k in ("equality", "features", "pairs")}
+        self.bucket_plans_built = 0
+        self.last_bank_bytes = 0
         self.steps = 0              # backward passes (micro-batches)
         self.schedule_step = 0      # optimiser steps = position in the learning-rate schedule
 
@@ -107,24 +129,63 @@ class Wav2vec2PairedSpeakerModule(OptimizerSurface):
                                     sep_token_constant=self.cfg.sep_token_constant)
         return self._plans[key]
 
+    def _lru_plan(self, kind: str, key: Tuple, build: Callable[[], Plan]) -> Plan:
+        plans = self._lru[kind]
+        if key in plans:
+            plans.move_to_end(key)
+            return plans[key]
+        plans[key] = build()
+        self.bucket_plans_built += 1
+        while len(plans) > MAX_BUCKET_PLANS[kind]:
+            plans.popitem(last=False)
+        return plans[key]
+
     @staticmethod
-    def _stack(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-        sq = lambda x: x[:, 0, :] if x.dim() == 3 else (x[None] if x.dim() == 1 else x)
-        a, b = sq(a), sq(b)
+    def _sq(x: torch.Tensor) -> torch.Tensor:
+        return x[:, 0, :] if x.dim() == 3 else (x[None] if x.dim() == 1 else x)
+
+    @classmethod
+    def _stack(cls, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        a, b = cls._sq(a), cls._sq(b)
         assert a.shape == b.shape                          # ref :166-168
         return torch.cat([a, b], dim=0)
 
-    def compute_speaker_equality(self, wav_tensor: torch.Tensor, other_wav_tensor: torch.Tensor) -> torch.Tensor:
-        """ref :163-207 -> equality logits [B, 1] (eval-mode forward)."""
-        wav = self._stack(wav_tensor, other_wav_tensor).to(self.device, torch.float32)
-        plan = self._plan(wav.shape[0] // 2, wav.shape[1], False)
-        emb = plan.embed(wav)
+    def _logits(self, emb: torch.Tensor) -> torch.Tensor:
+        """ref :205 ``self.linear(cls_token)``: emb [B, H] f32 -> [B, 1]."""
         from ... import ops
         B, H = emb.shape
         out = torch.zeros(B, 4, dtype=torch.float32, device=self.device)          # ldc padded to 4
         ops.gemm(B, 1, H, emb, self.store.p("linear.weight"), out, lda=H, ldb=H, ldc=4, epilogue=ops.EPI_BIAS,
                  bias=self.store.p("linear.bias"))
         return out[:, :1]
+
+    def compute_speaker_equality(self, wav_tensor: torch.Tensor, other_wav_tensor: torch.Tensor,
+                                 lengths=None) -> torch.Tensor:
+        """ref :163-207 -> equality logits [B, 1] (eval-mode forward).  [B, N] and [B, M] with N != M are accepted, as the
+        reference's contract says (paired_speaker_recognition_module.py:51-60): the shorter side is padded and each side's
+        full length is its valid length.  ``lengths=(left, right)``: valid samples per pair of a padded batch.  Either way
+        each pair is scored over its own frames only (Plan.forward(pair_lengths=)); equal shapes without ``lengths`` run
+        the fixed-length forward."""
+        a, b = self._sq(wav_tensor), self._sq(other_wav_tensor)
+        if lengths is None and a.shape == b.shape:
+            wav = torch.cat([a, b], dim=0).to(self.device, torch.float32)
+            plan = self._plan(wav.shape[0] // 2, wav.shape[1], False)
+            return self._logits(plan.embed(wav))
+        if a.shape[0] != b.shape[0]:
+            raise ValueError(f"compute_speaker_equality: batches of {a.shape[0]} and {b.shape[0]}")
+        B = a.shape[0]
+        if lengths is None:
+            lengths = ([a.shape[1]] * B, [b.shape[1]] * B)
+        n = -(-max(a.shape[1], b.shape[1]) // EQUALITY_QUANTUM) * EQUALITY_QUANTUM
+        wav = torch.zeros(2 * B, n, dtype=torch.float32, device=self.device)
+        wav[:B, :a.shape[1]].copy_(a)
+        wav[B:, :b.shape[1]].copy_(b)
+        plan = self._lru_plan("equality", (B, n), lambda: self._make_plan(B, n))
+        return self._logits(plan.embed(wav, pair_lengths=lengths))
+
+    def _make_plan(self, batch: int, n: int, **kw) -> Plan:
+        return Plan(self.store, batch, n, train=False, reg=self.reg, pooling="first", paired=True,
+                    cls_token_constant=self.cfg.cls_token_constant, sep_token_constant=self.cfg.sep_token_constant, **kw)
 
     def forward(self, input_tensor: torch.Tensor, other_input_tensor: torch.Tensor):
         return self.compute_speaker_equality(input_tensor, other_input_tensor)
@@ -146,6 +207,139 @@ class Wav2vec2PairedSpeakerModule(OptimizerSurface):
         self.steps += 1
         self._after_micro_batch(tr)
         return {"loss": loss, "prediction": pred}
+
+    # ------------------------------------------------------------------ evaluation
+    @staticmethod
+    def _utterance(w: torch.Tensor) -> torch.Tensor:
+        w = w.reshape(-1) if (w.dim() <= 1 or w.numel() == w.shape[-1]) else None
+        if w is None:
+            raise ValueError("score_trials: one utterance per key ([N] or [1, N])")
+        return w.to(torch.float32)
+
+    def score_trials(self, pairs, audio_by_key, *, quantum: int = DEFAULT_PAIR_QUANTUM,
+                     max_batch_frames: int = DEFAULT_MAX_PAIR_BATCH_FRAMES, max_batch: int = DEFAULT_MAX_BATCH,
+                     max_bank_bytes: int = DEFAULT_MAX_BANK_BYTES, reuse_features: bool = True) -> List[float]:
+        """Equality logits of a trial list (``pairs``: EvaluationPair; ``audio_by_key``: key -> waveform [N] or [1, N]), in
+        the order of ``pairs``; trial i equals ``compute_speaker_equality`` of its two utterances alone.
+        1. Every utterance the pairs name runs through the conv stack + projection ONCE (Plan.features, bucketed by length
+           with plan_batches) and its valid frames are copied into one device feature bank [sum of frames, H] in the
+           activation dtype.
+        2. The trials are bucketed by ta + tb + 3 frames (plan_pair_batches) and every batch runs an encoder-only plan
+           (Plan.pair_encoder) that assembles its sequences from rows of the bank; unused rows of a bucket's last batch are
+           one-frame dummy pairs.
+        ``quantum`` / ``max_batch_frames`` are in encoder frames (20 ms); the utterance buckets of step 1 use the same
+        numbers times the conv stack's hop (320 samples).  The bank of VoxCeleb1-O is about 3 GB in fp16; a bank above
+        ``max_bank_bytes`` (default 8 GiB) raises ValueError: split the trial list.  ``reuse_features=False`` runs each
+        trial's two utterances through step 1 on their own (a measurement aid: the cost without the reuse)."""
+        cfg = self.model_cfg
+        pairs = list(pairs)
+        if not pairs:
+            return []
+        if reuse_features:
+            keys = list(dict.fromkeys(k for p in pairs for k in (p.sample1_id, p.sample2_id)))
+            pos = {k: i for i, k in enumerate(keys)}
+            sides = [(pos[p.sample1_id], pos[p.sample2_id]) for p in pairs]
+        else:
+            keys = [k for p in pairs for k in (p.sample1_id, p.sample2_id)]
+            sides = [(2 * i, 2 * i + 1) for i in range(len(pairs))]
+        wavs = [self._utterance(audio_by_key[k]) for k in keys]
+        fill = min_samples(cfg.conv_kernel, cfg.conv_stride)
+        for k, w in zip(keys, wavs):
+            if w.shape[0] < fill:
+                raise ValueError(f"score_trials: utterance {k!r} has {w.shape[0]} samples, one frame needs {fill}")
+        frames = [cfg.num_frames(w.shape[0]) for w in wavs]
+        offset = [0]
+        for f in frames:
+            offset.append(offset[-1] + f)
+        H, adt = cfg.hidden_size, self.store.act_dtype
+        nbytes = offset[-1] * H * torch.empty(0, dtype=adt).element_size()
+        if nbytes > max_bank_bytes:
+            raise ValueError(f"score_trials: the feature bank of {len(keys)} utterances needs {nbytes} bytes, more than "
+                             f"max_bank_bytes={max_bank_bytes}: split the trial list (or raise the limit)")
+        bank = torch.empty(offset[-1], H, dtype=adt, device=self.device)
+        self.last_bank_bytes = nbytes
+        hop = int(np.prod(cfg.conv_stride))
+        for idx, n, batch in plan_batches([w.shape[0] for w in wavs], quantum * hop, max_batch_frames * hop, max_batch):
+            plan = self._lru_plan("features", (batch, n),
+                                  lambda: Plan(self.store, batch, n, train=False, reg=self.reg, pooling="first"))
+            wav = torch.zeros(batch, n, dtype=torch.float32, device=self.device)
+            lens = [fill] * batch           # unused rows of a bucket's last batch: silence of the minimum length
+            for j, i in enumerate(idx):
+                wav[j, :wavs[i].shape[0]].copy_(wavs[i])
+                lens[j] = wavs[i].shape[0]
+            feat, _ = plan.features(wav, lengths=lens)
+            for j, i in enumerate(idx):
+                bank[offset[i]:offset[i + 1]].copy_(feat[j, :frames[i]])
+        lf, rf = [frames[a] for a, _ in sides], [frames[b] for _, b in sides]
+        parts = []
+        for idx, t, batch in plan_pair_batches(lf, rf, quantum, max_batch_frames, max_batch):
+            plan = self._lru_plan("pairs", (batch, t), lambda: Plan.pair_encoder(
+                self.store, batch, t, reg=self.reg, cls_token_constant=self.cfg.cls_token_constant,
+                sep_token_constant=self.cfg.sep_token_constant))
+            rows = [[0] * batch, [1] * batch, [0] * batch, [1] * batch]      # unused rows: dummy one-frame pairs
+            for j, i in enumerate(idx):
+                a, b = sides[i]
+                rows[0][j], rows[1][j], rows[2][j], rows[3][j] = offset[a], frames[a], offset[b], frames[b]
+            parts.append((idx, self._logits(plan.embed_pairs(bank, *rows))[:len(idx), 0]))
+        order = [i for idx, _ in parts for i in idx]
+        scores = torch.cat([x for _, x in parts]).cpu().tolist()
+        out = [0.0] * len(pairs)
+        for i, v in zip(order, scores):
+            out[i] = v
+        return out
+
+    def evaluate_trials(self, pairs, audio_by_key, **batching) -> dict:
+        """The ``_evaluate`` dict of a trial list scored with score_trials (``batching``: its keyword arguments) -- what
+        test_epoch_end gives over the batch-size-1 test loop."""
+        pairs = list(pairs)
+        scores = self.score_trials(pairs, audio_by_key, **batching)
+        return self._evaluate([{"prediction": scores, "label": [int(p.same_speaker) for p in pairs]}])
+
+    def _eval_step(self, batch: PairedSpeakerClassificationDataBatch) -> dict:
+        scores = self.compute_speaker_equality(batch.primary_network_input, batch.secondary_network_input)
+        return {"prediction": scores.detach().cpu().numpy().tolist(),
+                "label": batch.ground_truth.detach().cpu().numpy().tolist()}
+
+    def validation_step(self, batch: PairedSpeakerClassificationDataBatch, batch_idx: int = 0,
+                        dataloader_idx: Optional[int] = None) -> dict:
+        """ref: paired_speaker_recognition_module.py:115-137 (without the logging)."""
+        return self._eval_step(batch)
+
+    def validation_epoch_end(self, outputs: List[dict]) -> dict:
+        return self._evaluate(outputs)                       # ref :139-144 logs its "eer" as val_eer
+
+    def test_step(self, batch: PairedSpeakerClassificationDataBatch, batch_idx: int = 0,
+                  dataloader_idx: Optional[int] = None) -> dict:
+        """ref :146-166: whole trial utterances, one pair per batch."""
+        if batch.batch_size != 1:
+            raise ValueError("expecting a batch size of 1 for evaluation")
+        return self._eval_step(batch)
+
+    def test_epoch_end(self, outputs: List[dict]) -> dict:
+        return self._evaluate(outputs)                       # ref :168-169
+
+    @staticmethod
+    def _evaluate(outputs: List[dict]) -> dict:
+        """ref :171-248: ``outputs`` = dicts with ``label`` (0 / 1, an int or a list) and ``prediction`` (the raw equality
+        logits, a number or a -- possibly nested -- list).  The logits are mapped with clip((s + 1) / 2, 0, 1) like the
+        reference, then EER (1 when its threshold is NaN or the computation fails) and minDCF."""
+        truth: List[int] = []
+        scores: List[float] = []
+        for d in outputs:
+            truth.extend(int(v) for v in np.asarray(d["label"]).reshape(-1).tolist())
+            scores.extend(np.asarray(d["prediction"], dtype=np.float64).reshape(-1).tolist())
+        scores = np.clip((np.asarray(scores, dtype=np.float64) + 1) / 2, 0, 1).tolist()
+        try:
+            eer, eer_threshold = calculate_eer(truth, scores, pos_label=1)
+            if np.isnan(eer_threshold):
+                eer = 1
+        except (ValueError, ZeroDivisionError):              # NaN scores: a very bad score instead of a crash
+            eer, eer_threshold = 1, 1337
+        try:
+            mdc, mdc_threshold = calculate_mdc(truth, scores)
+        except (ValueError, ZeroDivisionError):
+            mdc, mdc_threshold = 1, 1337
+        return {"eer": eer, "eer_threshold": eer_threshold, "mdc": mdc, "mdc_threshold": mdc_threshold}
 
     def state_dict(self):
         return self.store.state_dict()

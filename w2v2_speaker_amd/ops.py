@@ -489,6 +489,46 @@ def prepend_token(x, y, c: float) -> None:
     _lib.check(lib().w2v2_prepend_token(x.data_ptr(), y.data_ptr(), c, B, T, H, dt(x), stream()), "prepend_token")
 
 
+def pair_tables(left_row, left_frames, right_row, right_frames, rows: int, T: int) -> torch.Tensor:
+    """The four tables of pair_assemble as one CPU int32 tensor [4, B], checked against a feature matrix of ``rows`` rows
+    and sequences of ``T`` frames (the kernel trusts them): both sides at least one frame, [CLS] left [SEP] right [SEP]
+    within T, both row ranges inside the matrix.  Host only."""
+    as_list = lambda x: x.reshape(-1).tolist() if isinstance(x, torch.Tensor) else list(x)
+    cols = [[int(v) for v in as_list(x)] for x in (left_row, left_frames, right_row, right_frames)]
+    if len({len(c) for c in cols}) != 1 or not cols[0]:
+        raise ValueError("pair_assemble: the four tables need one entry per pair (at least one pair)")
+    for b, (lr, ta, rr, tb) in enumerate(zip(*cols)):
+        if ta < 1 or tb < 1:
+            raise ValueError(f"pair_assemble: pair {b} has an empty side ({ta} + {tb} frames)")
+        if ta + tb + 3 > T:
+            raise ValueError(f"pair_assemble: pair {b} needs {ta + tb + 3} frames, the sequence has {T}")
+        if lr < 0 or rr < 0 or lr + ta > rows or rr + tb > rows:
+            raise ValueError(f"pair_assemble: pair {b} reads rows [{lr}, {lr + ta}) and [{rr}, {rr + tb}) of a feature "
+                             f"matrix of {rows}")
+    return torch.tensor(cols, dtype=torch.int32)
+
+
+def pair_assemble(feat, y, left_row, left_frames, right_row, right_frames, cls_c: float, sep_c: float,
+                  table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [B, T, H] = [CLS] left [SEP] right [SEP] 0... per pair from rows of feat [R, H] (w2v2_pair_assemble).  The tables
+    are host values (Python ints or CPU integer tensors): validated here (ValueError), then uploaded into ``table``
+    (device int32 [4, B]; allocated when None).  Returns the checked host tables (CPU int32 [4, B])."""
+    _dev(feat, y)
+    B, T, H = y.shape
+    assert feat.dim() == 2 and feat.shape[1] == H and feat.dtype == y.dtype and feat.is_contiguous() and y.is_contiguous()
+    host = pair_tables(left_row, left_frames, right_row, right_frames, feat.shape[0], T)
+    if host.shape[1] != B:
+        raise ValueError(f"pair_assemble: {host.shape[1]} pairs for a batch of {B}")
+    if table is None:
+        table = torch.empty(4, B, dtype=torch.int32, device=y.device)
+    assert table.shape == (4, B) and table.dtype == torch.int32 and table.is_cuda and table.is_contiguous()
+    table.copy_(host)
+    _lib.check(lib().w2v2_pair_assemble(feat.data_ptr(), y.data_ptr(), table[0].data_ptr(), table[1].data_ptr(),
+                                        table[2].data_ptr(), table[3].data_ptr(), cls_c, sep_c, B, T, H, dt(y), stream()),
+               "pair_assemble")
+    return host
+
+
 # ------------------------------------------------------------------------------------------------ pos-conv
 def posconv_wgrad(dY, xg, dwf, B: int, T: int, H: int, G: int, K: int) -> None:
     """dwf[g][(tap, ci)][co] = sum_{b,t} xg[b,g,t+tap,ci] * dY[b,t,g*Cg+co]  (bf16 operands, f32 result, overwritten)."""
