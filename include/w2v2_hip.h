@@ -197,9 +197,20 @@ int w2v2_conv0_apply(const float* wav, const float* w, const float* mean_rstd, c
 /* Layer 0 of the feat_extract_norm="layer" family (HF:275-299; "-lv60" / xlsr checkpoints):
  * out[b, l, :] = GELU(LayerNorm_C(conv1d(wav, w [C][k], stride)[b, l, :] + bias)) -- the normalisation runs over the channels
  * of one frame (eps = nn.LayerNorm's default 1e-5 at the reference).  bias may be NULL (conv_bias=False).  f32 arithmetic,
- * `dtype` output; C % 8 == 0, C <= 512, k <= 16.  Forward only. */
+ * `dtype` output; C % 8 == 0, C <= 512, k <= 16. */
 int w2v2_conv0_layernorm_gelu(const float* wav, const float* w, const float* bias, const float* gamma, const float* beta,
                               void* out, int B, int N, int C, int k, int stride, float eps, int dtype, void* stream);
+/* Backward of w2v2_conv0_layernorm_gelu (HF:275-299 layer 0, unfrozen feature extractor): from dy = dL/d(out) [B, L, C]
+ * (`dtype`) it ADDS dw [C][k], dbias [C] (NULL when bias is NULL / not wanted), dgamma [C], dbeta [C] (f32).  The
+ * convolution, bias and LayerNorm are recomputed from the waveform as the forward computes them; there is no data gradient.
+ * The column sums leave the kernel as one partial row per workgroup in `workspace`
+ * (w2v2_conv0_layernorm_gelu_bwd_workspace_floats(B, N, C, k, stride) floats) and are folded in a fixed order by a second
+ * small launch: no atomics, bitwise the same in every run.  Same domain as the forward; outside it an error is returned
+ * before any launch. */
+int w2v2_conv0_layernorm_gelu_bwd_workspace_floats(int B, int N, int C, int k, int stride);
+int w2v2_conv0_layernorm_gelu_bwd(const float* wav, const float* w, const float* bias, const float* gamma, const float* beta,
+                                  const void* dy, float* dw, float* dbias, float* dgamma, float* dbeta, float* workspace,
+                                  int B, int N, int C, int k, int stride, float eps, int dtype, void* stream);
 /* Backward of layer 0 (unfrozen feature extractor): from dz = dL/d(layer-0 output) [B,L,C] compute dw [C][k],
  * dgamma [C], dbeta [C] (f32 atomics, caller zeroes); conv / GroupNorm are recomputed from the waveform and the
  * forward's mean_rstd.  sums [B][C][2] is f32 scratch. */
@@ -223,10 +234,19 @@ int w2v2_layernorm_fwd(const void* x, void* r_inout, const float* gamma, const f
                        float* mean, float* rstd, int M, int H, float eps, float drop_p,
                        uint64_t seed, int dtype, void* stream);
 /* y = GELU(LN(x) * gamma + beta), x and y [M, H] (y may alias x): the convolution layers of the feat_extract_norm="layer"
- * checkpoints (HF:275-299 Wav2Vec2LayerNormConvLayer: conv -> LayerNorm over the channels -> GELU).  Forward only: no
- * statistics are saved (the feature extractor of this family runs frozen, the reference's default). */
+ * checkpoints (HF:275-299 Wav2Vec2LayerNormConvLayer: conv -> LayerNorm over the channels -> GELU).  No statistics are
+ * saved: the backward recomputes them from x. */
 int w2v2_layernorm_gelu_fwd(const void* x, const float* gamma, const float* beta, void* y, int M, int H, float eps,
                             int dtype, void* stream);
+/* Backward of w2v2_layernorm_gelu_fwd (HF:275-299 layers 1-6, unfrozen feature extractor): dy and the saved pre-norm
+ * z = conv + bias, both [M, H] in `dtype`; mean / rstd are recomputed from z.  Writes dz (may alias dy) and ADDS
+ * dgamma, dbeta and dbias = sum_rows dz (the convolution's bias gradient; may be NULL) [H] f32.  The column sums leave
+ * the kernel as one partial row per workgroup in `workspace` (w2v2_layernorm_gelu_bwd_workspace_floats(M, H) floats) and
+ * are folded in a fixed order by a second small launch: no atomics, bitwise the same in every run.  H % 8 == 0, H <= 1024;
+ * outside that an error is returned before any launch. */
+int w2v2_layernorm_gelu_bwd_workspace_floats(int M, int H);
+int w2v2_layernorm_gelu_bwd(const void* dy, const void* z, const float* gamma, const float* beta, void* dz, float* dgamma,
+                            float* dbeta, float* dbias, float* workspace, int M, int H, float eps, int dtype, void* stream);
 /* s = pre-norm input (x if r was NULL).  Outputs: ds (grad wrt s; may alias dy), d_r = ds*dropmask
  * (optional; a plain copy of ds when drop_p == 0), dgamma/dbeta ADDED to (f32, caller zeroes): with a
  * workspace of w2v2_layernorm_bwd_workspace_floats(H) floats the column sums are folded in a fixed

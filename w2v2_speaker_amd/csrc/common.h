@@ -379,6 +379,13 @@ __device__ __forceinline__ void gelu_both_f(float x, float& y, float& dy) {
   dy = fmaf(x * 0.39894228040143268f, ex, 0.5f * (1.0f + erfv));
 }
 
+// the derivative alone, at the cost of gelu_both_f's one exponential (gelu_grad_f takes two)
+__device__ __forceinline__ float gelu_grad_one_exp_f(float x) {
+  float y, dy;
+  gelu_both_f(x, y, dy);
+  return dy;
+}
+
 // ---------------------------------------------------------------- counter-based RNG (dropout)
 // keep(seed, i) must be recomputable in the backward, so no mask is ever stored.  It sits in the inner loops of
 // the attention kernels (T^2 decisions per head, three times per step) where it used to be the single largest
@@ -431,3 +438,9 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+
+// ---------------------------------------------------------------- fixed-order fold of per-workgroup column partials
+// (norm.hip) partial [nblk][nslot * C] f32 -> ADDED to the targets in a fixed order, no atomics: slot s < kdw is tap s of a
+// convolution weight gradient dw[c][kdw], the three slots after them go to d0 / d1 / d2 [C] (NULL: skipped).
+int colpart_fold(const float* partial, int nblk, int nslot, int C, int kdw, float* dw, float* d0, float* d1, float* d2,
+                 void* stream);

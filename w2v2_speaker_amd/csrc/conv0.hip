@@ -625,7 +625,7 @@ __global__ void pack_conv_kernel(const float* __restrict__ w, T* __restrict__ ou
 // The normalisation runs over the CHANNELS of one frame, so a wave owns whole frames: lane i holds channels 8 i .. 8 i + 7
 // (their k taps stay in registers: 8 k floats), the frame's k samples are wave-uniform loads, the two LayerNorm reductions
 // are wave reductions, the output is one 16-byte store per lane.  Exact f32 arithmetic up to the output rounding; HBM-bound
-// on the [B, L, C] write like the group-norm apply pass.  Forward only (this family's feature extractor runs frozen).
+// on the [B, L, C] write like the group-norm apply pass.  Backward: conv0_ln_gelu_bwd_kernel below.
 template <typename T, int KMAX>
 __global__ __launch_bounds__(256) void conv0_ln_gelu_kernel(const float* __restrict__ wav, const float* __restrict__ w,
                                                             const float* __restrict__ bias, const float* __restrict__ gamma,
@@ -694,6 +694,158 @@ extern "C" int w2v2_conv0_layernorm_gelu(const float* wav, const float* w, const
     hipLaunchKernelGGL((conv0_ln_gelu_kernel<AT, 16>), grid, dim3(256), 0, as_stream(stream), wav, w, bias, gamma, beta, (AT*)out,
                        B, N, L, C, k, stride, eps, fpw););
   W2V2_CHECK_LAUNCH("conv0_layernorm_gelu");
+  return 0;
+}
+
+// Backward of the kernel above (unfrozen feature extractor).  The convolution, its bias and the LayerNorm statistics are
+// recomputed from the waveform in the forward's own order of operations, so the [B, L, C] pre-norm tensor exists in HBM in
+// neither direction; there is no data gradient (the input is the waveform).  With zh = (z - mean) * rstd, u = zh * gamma +
+// beta, du = dy * gelu'(u), g = du * gamma, dz = rstd * (g - mean_c(g) - zh * mean_c(g * zh)):
+//     dw[c][j] += sum_frames dz[c] * x[l * stride + j],  dbias += sum dz,  dgamma += sum du * zh,  dbeta += sum du.
+// A lane holds 8 (KMAX + 3) accumulators; the 8 k weights the forward keeps in registers are read from LDS here ([tap][channel],
+// two 16-byte reads per tap), which keeps the kernel free of scratch at KMAX = 16.  A wave walks runs of `fpw` frames with
+// a grid stride; the accumulators are folded over the four waves through LDS, one slot at a time, and leave as ONE
+// partial row [k taps | dgamma | dbeta | dbias][C] per workgroup for colpart_fold (fixed order, no atomics).
+constexpr int C0L_BWD_BLOCKS = 768;      // three 4-wave workgroups per CU
+constexpr int C0L_BWD_FPW = 8;
+static int c0l_bwd_nblocks(int64_t frames) {
+  const int64_t nb = cdiv(frames, (int64_t)4 * C0L_BWD_FPW);
+  return (int)(nb < C0L_BWD_BLOCKS ? nb : C0L_BWD_BLOCKS);
+}
+
+template <typename T, int KMAX>
+__global__ __launch_bounds__(256) void conv0_ln_gelu_bwd_kernel(const float* __restrict__ wav, const float* __restrict__ w,
+                                                                const float* __restrict__ bias, const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, const T* __restrict__ dy,
+                                                                float* __restrict__ partial, int B, int N, int L, int C, int k,
+                                                                int stride, float eps, int fpw) {
+  __shared__ __attribute__((aligned(16))) float wl[KMAX * 512];      // [tap][channel]
+  __shared__ float red[4][512];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nch = C >> 3;
+  const bool on = lane < nch;
+  const int c0 = on ? lane * 8 : 0;                  // (idle lanes recompute channels 0..7 and add nothing: dy = gamma = 0)
+  for (int i = threadIdx.x; i < C * k; i += 256) {
+    const int c = i / k, j = i - c * k;
+    wl[j * C + c] = w[i];
+  }
+  __syncthreads();
+  float bs[8], ga[8], be[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    bs[e] = (on && bias != nullptr) ? bias[c0 + e] : 0.f;
+    ga[e] = on ? gamma[c0 + e] : 0.f;
+    be[e] = on ? beta[c0 + e] : 0.f;
+  }
+  float aw[8][KMAX], ag[8], ab[8], az[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    ag[e] = 0.f; ab[e] = 0.f; az[e] = 0.f;
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) aw[e][j] = 0.f;
+  }
+  const int64_t total = (int64_t)B * L;
+  const int64_t step = (int64_t)gridDim.x * 4 * fpw;
+  for (int64_t f0 = ((int64_t)blockIdx.x * 4 + wave) * fpw; f0 < total; f0 += step) {
+    for (int64_t f = f0; f < f0 + fpw && f < total; ++f) {
+      const int b = (int)(f / L), l = (int)(f - (int64_t)b * L);
+      const float* xp = wav + (int64_t)b * N + (int64_t)l * stride;
+      float xv[KMAX];
+#pragma unroll
+      for (int j = 0; j < KMAX; ++j) xv[j] = j < k ? xp[j] : 0.f;       // wave-uniform addresses
+      float y[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) y[e] = bs[e];
+#pragma unroll
+      for (int j = 0; j < KMAX; ++j) {
+        if (j < k) {
+          const float4 wa = *reinterpret_cast<const float4*>(wl + j * C + c0);
+          const float4 wb = *reinterpret_cast<const float4*>(wl + j * C + c0 + 4);
+          const float wr[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+#pragma unroll
+          for (int e = 0; e < 8; ++e) y[e] = fmaf(wr[e], xv[j], y[e]);
+        }
+      }
+      float sum = 0.f;
+      if (on) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sum += y[e];
+      }
+      const float mean = wave_sum(sum) / (float)C;
+      float sq = 0.f;
+      if (on) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const float d = y[e] - mean; sq += d * d; }
+      }
+      const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
+      Vec8<T> d;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) d.v[e] = 0.f;
+      if (on) d.load(dy + f * C + c0);
+      float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float zh = (y[e] - mean) * rstd;
+        const float du = d.v[e] * gelu_grad_one_exp_f(zh * ga[e] + be[e]);
+        const float g = du * ga[e];
+        y[e] = zh;
+        d.v[e] = g;
+        c1 += g;
+        c2 = fmaf(g, zh, c2);
+        ag[e] = fmaf(du, zh, ag[e]);
+        ab[e] += du;
+      }
+      c1 = wave_sum(c1) / (float)C;
+      c2 = wave_sum(c2) / (float)C;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float dzv = rstd * (d.v[e] - c1 - y[e] * c2);
+        az[e] += dzv;
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j)
+          if (j < k) aw[e][j] = fmaf(dzv, xv[j], aw[e][j]);
+      }
+    }
+  }
+  // one slot at a time through LDS: taps 0 .. k-1, then dgamma, dbeta, dbias
+  float* pt = partial + (int64_t)blockIdx.x * (k + 3) * C;
+#pragma unroll
+  for (int s = 0; s < KMAX + 3; ++s) {
+    if (s < KMAX && s >= k) continue;                // uniform
+    const int slot = s < KMAX ? s : k + (s - KMAX);
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      red[wave][lane * 8 + e] = !on ? 0.f : s < KMAX ? aw[e][s < KMAX ? s : 0] : s == KMAX ? ag[e] : s == KMAX + 1 ? ab[e] : az[e];
+    __syncthreads();
+    for (int col = threadIdx.x; col < C; col += 256)
+      pt[(int64_t)slot * C + col] = red[0][col] + red[1][col] + red[2][col] + red[3][col];
+  }
+}
+
+extern "C" int w2v2_conv0_layernorm_gelu_bwd_workspace_floats(int B, int N, int C, int k, int stride) {
+  if (B <= 0 || k <= 0 || stride <= 0 || N < k || C <= 0) return 0;
+  const int L = (N - k) / stride + 1;
+  return c0l_bwd_nblocks((int64_t)B * L) * (k + 3) * C;
+}
+
+extern "C" int w2v2_conv0_layernorm_gelu_bwd(const float* wav, const float* w, const float* bias, const float* gamma,
+                                             const float* beta, const void* dy, float* dw, float* dbias, float* dgamma,
+                                             float* dbeta, float* workspace, int B, int N, int C, int k, int stride, float eps,
+                                             int dtype, void* stream) {
+  W2V2_REQUIRE(wav && w && gamma && beta && dy && dw && dgamma && dbeta && workspace && B > 0 && k > 0 && stride > 0 && N >= k,
+               "conv0_layernorm_gelu_bwd: bad arguments");
+  W2V2_REQUIRE(C > 0 && C % 8 == 0 && C <= 512 && k <= 16, "conv0_layernorm_gelu_bwd: C=%d (multiple of 8, <= 512), k=%d (<= 16)", C, k);
+  W2V2_REQUIRE(dtype == W2V2_F32 || dtype == W2V2_BF16 || dtype == W2V2_F16, "conv0_layernorm_gelu_bwd: bad dtype %d", dtype);
+  const int L = (N - k) / stride + 1;
+  const int nb = c0l_bwd_nblocks((int64_t)B * L);
+#define W2V2_C0LB(KM_)                                                                                                \
+  hipLaunchKernelGGL((conv0_ln_gelu_bwd_kernel<AT, KM_>), dim3(nb), dim3(256), 0, as_stream(stream), wav, w, bias, gamma, beta, \
+                     (const AT*)dy, workspace, B, N, L, C, k, stride, eps, C0L_BWD_FPW)
+  W2V2_DISPATCH_ACT(dtype, "conv0_layernorm_gelu_bwd", if (k <= 10) W2V2_C0LB(10); else W2V2_C0LB(16););
+#undef W2V2_C0LB
+  colpart_fold(workspace, nb, k + 3, C, k, dw, dgamma, dbeta, dbias, stream);
+  W2V2_CHECK_LAUNCH("conv0_layernorm_gelu_bwd");
   return 0;
 }
 

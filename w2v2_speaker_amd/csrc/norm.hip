@@ -570,3 +570,162 @@ extern "C" int w2v2_layernorm_bwd(const void* dy, const void* s, const float* me
   W2V2_CHECK_LAUNCH("layernorm_bwd");
   return 0;
 }
+
+// ------------------------------------------------------------------------------ LayerNorm + GELU backward (HF:275-299)
+// y = GELU(LN_C(z) * gamma + beta), the convolution layers 1-6 of the feat_extract_norm="layer" family, unfrozen.  The
+// forward saves no statistics: mean / rstd are recomputed from the saved pre-norm z exactly as ln_fwd_kernel computes them.
+// With zh = (z - mean) * rstd, u = zh * gamma + beta, du = dy * gelu'(u), g = du * gamma:
+//     dz = rstd * (g - mean_c(g) - zh * mean_c(g * zh)),   dgamma += sum_rows du * zh,   dbeta += sum_rows du,   dbias += sum_rows dz
+// Same layout as the forward: one wave per row, 8 consecutive channels per lane and chunk, f32 arithmetic.  The three column
+// sums stay in registers over the rows a wave walks, are folded over the four waves through LDS and leave as ONE partial row
+// per workgroup; colpart_fold adds the partial rows to the targets in a fixed order (no atomics: bitwise reproducible).
+constexpr int LNG_BWD_BLOCKS = 1024;     // four 4-wave workgroups per CU
+static int lng_bwd_nblocks(int M) { return (int)(cdiv(M, 4) < LNG_BWD_BLOCKS ? cdiv(M, 4) : LNG_BWD_BLOCKS); }
+
+template <typename T, int NC>
+__global__ __launch_bounds__(256) void ln_gelu_bwd_kernel(const T* dy, const T* __restrict__ z,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          T* dz, float* __restrict__ partial, int M, int H, float eps) {
+  __shared__ float red[4][NC * 512];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nch = H >> 3;
+  float gm[NC][8], bt[NC][8], ag[NC][8] = {}, ab[NC][8] = {}, az[NC][8] = {};
+  bool have[NC];
+#pragma unroll
+  for (int ci = 0; ci < NC; ++ci) {
+    have[ci] = lane + 64 * ci < nch;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { gm[ci][e] = 0.f; bt[ci][e] = 0.f; }
+    if (have[ci]) {
+      Vec8<float> g, b;
+      g.load(gamma + (lane + 64 * ci) * 8);
+      b.load(beta + (lane + 64 * ci) * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { gm[ci][e] = g.v[e]; bt[ci][e] = b.v[e]; }
+    }
+  }
+  for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
+    float zv[NC][8], dv[NC][8];
+    float sum = 0.f;
+#pragma unroll
+    for (int ci = 0; ci < NC; ++ci) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { zv[ci][e] = 0.f; dv[ci][e] = 0.f; }
+      if (have[ci]) {
+        const int64_t off = (int64_t)row * H + (lane + 64 * ci) * 8;
+        Vec8<T> vz, vd;
+        vz.load(z + off);
+        vd.load(dy + off);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { zv[ci][e] = vz.v[e]; dv[ci][e] = vd.v[e]; sum += vz.v[e]; }
+      }
+    }
+    const float mean = wave_sum(sum) / (float)H;
+    float sq = 0.f;
+#pragma unroll
+    for (int ci = 0; ci < NC; ++ci)
+      if (have[ci])
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const float d = zv[ci][e] - mean; sq += d * d; }
+    const float rstd = rsqrtf(wave_sum(sq) / (float)H + eps);
+    // (chunks a lane does not own hold dy = gamma = 0: du = g = 0 there, their z-hat is finite)
+    float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+    for (int ci = 0; ci < NC; ++ci)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float zh = (zv[ci][e] - mean) * rstd;
+        const float du = dv[ci][e] * gelu_grad_one_exp_f(fmaf(zh, gm[ci][e], bt[ci][e]));
+        const float g = du * gm[ci][e];
+        zv[ci][e] = zh;
+        dv[ci][e] = g;
+        c1 += g;
+        c2 = fmaf(g, zh, c2);
+        ag[ci][e] = fmaf(du, zh, ag[ci][e]);
+        ab[ci][e] += du;
+      }
+    c1 = wave_sum(c1) / (float)H;
+    c2 = wave_sum(c2) / (float)H;
+#pragma unroll
+    for (int ci = 0; ci < NC; ++ci) {
+      if (have[ci]) {
+        Vec8<T> o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          o.v[e] = rstd * (dv[ci][e] - c1 - zv[ci][e] * c2);
+          az[ci][e] += o.v[e];
+        }
+        o.store(dz + (int64_t)row * H + (lane + 64 * ci) * 8);
+      }
+    }
+  }
+  // the column partials of the four waves -> one row of [dgamma | dbeta | dbias] per workgroup
+#pragma unroll
+  for (int pass = 0; pass < 3; ++pass) {
+    __syncthreads();
+#pragma unroll
+    for (int ci = 0; ci < NC; ++ci)
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        red[wave][(ci * 64 + lane) * 8 + e] = pass == 0 ? ag[ci][e] : pass == 1 ? ab[ci][e] : az[ci][e];
+    __syncthreads();
+    for (int col = threadIdx.x; col < H; col += 256)
+      partial[((int64_t)blockIdx.x * 3 + pass) * H + col] = red[0][col] + red[1][col] + red[2][col] + red[3][col];
+  }
+}
+
+// partial [nblk][nslot * C] -> targets, ADDED in a fixed order (the scheme of ln_bwd_finalize_kernel): slot s < kdw is tap s
+// of a convolution weight gradient dw[c][kdw] (w2v2_conv0_layernorm_gelu_bwd), the three slots after them go to
+// d0 / d1 / d2 [C] (NULL: skipped).
+__global__ __launch_bounds__(1024) void colpart_fold_kernel(const float* __restrict__ partial, int nblk, int nslot, int C,
+                                                            int kdw, float* __restrict__ dw, float* __restrict__ d0,
+                                                            float* __restrict__ d1, float* __restrict__ d2) {
+  __shared__ float red[LN_FOLD_LANES][32];
+  const int cl = threadIdx.x & 31, bl = threadIdx.x >> 5;
+  const int i = blockIdx.x * 32 + cl;                 // index into [nslot][C]
+  const int n = nslot * C;
+  float s = 0.f;
+  if (i < n) {
+#pragma unroll 8
+    for (int b = bl; b < nblk; b += LN_FOLD_LANES) s += partial[(int64_t)b * n + i];
+  }
+  red[bl][cl] = s;
+  __syncthreads();
+  if (bl == 0 && i < n) {
+    float t = 0.f;
+#pragma unroll
+    for (int k = 0; k < LN_FOLD_LANES; ++k) t += red[k][cl];
+    const int slot = i / C, c = i - slot * C;
+    float* dst = slot < kdw ? dw + (int64_t)c * kdw + slot
+                            : (slot == kdw ? d0 : slot == kdw + 1 ? d1 : d2);
+    if (slot >= kdw) { if (dst == nullptr) return; dst += c; }
+    *dst += t;
+  }
+}
+
+int colpart_fold(const float* partial, int nblk, int nslot, int C, int kdw, float* dw, float* d0, float* d1, float* d2,
+                 void* stream) {
+  hipLaunchKernelGGL(colpart_fold_kernel, dim3((unsigned)cdiv((int64_t)nslot * C, 32)), dim3(32 * LN_FOLD_LANES), 0,
+                     as_stream(stream), partial, nblk, nslot, C, kdw, dw, d0, d1, d2);
+  return 0;
+}
+
+extern "C" int w2v2_layernorm_gelu_bwd_workspace_floats(int M, int H) { return M > 0 ? lng_bwd_nblocks(M) * 3 * H : 0; }
+
+extern "C" int w2v2_layernorm_gelu_bwd(const void* dy, const void* z, const float* gamma, const float* beta, void* dz,
+                                       float* dgamma, float* dbeta, float* dbias, float* workspace, int M, int H, float eps,
+                                       int dtype, void* stream) {
+  W2V2_REQUIRE(dy && z && gamma && beta && dz && dgamma && dbeta && workspace, "layernorm_gelu_bwd: null pointer");
+  W2V2_REQUIRE(H % 8 == 0 && H > 0 && H <= 8 * 64 * LN_MAXC, "layernorm_gelu_bwd: H=%d unsupported (need H%%8==0, H<=1024)", H);
+  W2V2_REQUIRE(dtype == W2V2_F32 || dtype == W2V2_BF16 || dtype == W2V2_F16, "layernorm_gelu_bwd: bad dtype %d", dtype);
+  if (M <= 0) return 0;
+  const int nb = lng_bwd_nblocks(M);
+#define W2V2_LNGB(NC_)                                                                                              \
+  hipLaunchKernelGGL((ln_gelu_bwd_kernel<AT, NC_>), dim3(nb), dim3(256), 0, as_stream(stream), (const AT*)dy, (const AT*)z, \
+                     gamma, beta, (AT*)dz, workspace, M, H, eps)
+  W2V2_DISPATCH_ACT(dtype, "layernorm_gelu_bwd", if (H <= 512) W2V2_LNGB(1); else W2V2_LNGB(2););
+#undef W2V2_LNGB
+  colpart_fold(workspace, nb, 3, H, 0, nullptr, dgamma, dbeta, dbias, stream);
+  W2V2_CHECK_LAUNCH("layernorm_gelu_bwd");
+  return 0;
+}

@@ -225,9 +225,10 @@ class Plan:
         self.ln_conv = cfg.feat_extract_norm == "layer"
         if cfg.feat_extract_norm not in ("group", "layer"):
             raise ValueError(f"feat_extract_norm must be 'group' or 'layer', got {cfg.feat_extract_norm!r}")
-        if (self.ln_conv or cfg.conv_bias) and train and not store.freeze_cnn:
-            raise NotImplementedError("the layer-norm / biased convolution stack has a forward path only: train it with the "
-                                      "feature extractor frozen (completely_freeze_feature_extractor: true, the reference's default)")
+        if not self.ln_conv and cfg.conv_bias and train and not store.freeze_cnn:
+            raise NotImplementedError("feat_extract_norm='group' with conv_bias=True (no published checkpoint has it) has a "
+                                      "forward path only: train it with the feature extractor frozen "
+                                      "(completely_freeze_feature_extractor: true, the reference's default)")
         if self.stable and (insert_cls_token or paired or keep_hidden_states):
             raise NotImplementedError("do_stable_layer_norm: the CLS-token, paired-input and hidden-state-ensemble paths are "
                                       "built for the post-LN encoder only")
@@ -328,6 +329,11 @@ class Plan:
             self.dwp = torch.zeros(max(C[i] * cfg.conv_kernel[i] * cins[i] for i in range(1, len(C))), dtype=f32,
                                    device=self.dev)
             self.sums0 = self._e(Bc, C[0], 2, dtype=f32)
+            if self.ln_conv:        # per-workgroup column partials of the two LayerNorm-GELU backward kernels
+                self.lng_ws = self._e(max(ops.lib().w2v2_layernorm_gelu_bwd_workspace_floats(Bc * L, c)
+                                          for L, c in zip(self.lens[1:], C[1:])), dtype=f32)
+                self.c0l_ws = ops.conv0_layernorm_gelu_bwd_workspace(Bc, self.N, C[0], cfg.conv_kernel[0],
+                                                                     cfg.conv_stride[0], self.dev)
         # The projection's weight gradient is ONE small problem (768 x 512 outputs = 12 tiles) over all M0 tokens: alone
         # in a grouped launch it ran on 12 CUs for 144 us.  Its token dimension is cut into PROJ_SLICES slices of
         # proj_slice_len rows (a multiple of 64), each a problem of its own writing its own partial (96 workgroups),
@@ -438,11 +444,14 @@ class Plan:
         for i in range(1, len(C) if not self.enc_only else 0):
             k, s, ci, co = cfg.conv_kernel[i], cfg.conv_stride[i], cins[i], C[i]
             cbias = st.mp(f"feature_extractor.conv_layers.{i}.conv.bias") if cfg.conv_bias else self.zero_bias
-            # layer-norm family: the product only adds the bias; LayerNorm + GELU follow in place (forward())
-            self.g_conv.append(Gemm(self.Bc * self.lens[i], co, k * ci, self.conv[i - 1], self.convw[i], self.conv[i],
+            # layer-norm family: the product only adds the bias; LayerNorm + GELU follow (_cnn_forward) -- in place, or, with
+            # the feature extractor unfrozen, from the pre-norm z the product leaves in conv_pre[i] for the backward
+            ln_train = self.ln_conv and self.cnn_train
+            self.g_conv.append(Gemm(self.Bc * self.lens[i], co, k * ci, self.conv[i - 1], self.convw[i],
+                                    self.conv_pre[i] if ln_train else self.conv[i],
                                     lda=s * ci, ldb=k * ci, ldc=co, a_seg=(self.lens[i], self.lens[i - 1] * ci),
                                     epilogue=EPI_BIAS if self.ln_conv else EPI_BIAS_GELU, bias=cbias,
-                                    aux=self.conv_pre[i] if self.cnn_train else None, ldaux=co))
+                                    aux=self.conv_pre[i] if (self.cnn_train and not self.ln_conv) else None, ldaux=co))
         if self.cnn_train:
             # conv layer i backward: dW (packed layout, f32 scratch) and the im2col-space data gradient
             self.g_conv_dw, self.g_conv_dx = [None], [None]
@@ -931,11 +940,12 @@ class Plan:
         for i, g in enumerate(self.g_conv, start=1):
             g()
             y = self.conv[i].view(-1, cfg.conv_dim[i])
-            ops.layernorm_gelu_fwd(y, mp(fe + f"{i}.layer_norm.weight"), mp(fe + f"{i}.layer_norm.bias"), y, 1e-5)
+            z = self.conv_pre[i].view(-1, cfg.conv_dim[i]) if self.cnn_train else y      # (kept for _backward_cnn)
+            ops.layernorm_gelu_fwd(z, mp(fe + f"{i}.layer_norm.weight"), mp(fe + f"{i}.layer_norm.bias"), y, 1e-5)
 
     def conv_backward(self, dfeat: torch.Tensor) -> None:
         """Backward of conv_features(): dfeat [B, L, 512] = d(loss)/d(features); the gradients of the seven conv layers
-        and the layer-0 GroupNorm are ACCUMULATED in the arena.  Needs a plan built with train=True over a store with
+        and their normalisations are ACCUMULATED in the arena.  Needs a plan built with train=True over a store with
         ``freeze_cnn=False``."""
         if not self.train or self.store.freeze_cnn:
             raise RuntimeError("conv_backward needs Plan(train=True) over ParamStore(freeze_cnn=False)")
@@ -1250,6 +1260,9 @@ class Plan:
         C = cfg.conv_dim
         cins = (1,) + tuple(C[:-1])
         mg = st.mg
+        if self.ln_conv:
+            self._backward_cnn_layer_norm()
+            return
         for i in reversed(range(1, len(C))):
             k, sd, ci, co = cfg.conv_kernel[i], cfg.conv_stride[i], cins[i], C[i]
             gout = self.dn if i == len(C) - 1 else self.dconv[i]
@@ -1267,3 +1280,32 @@ class Plan:
                       mg("feature_extractor.conv_layers.0.layer_norm.weight"),
                       mg("feature_extractor.conv_layers.0.layer_norm.bias"), cfg.conv_kernel[0], cfg.conv_stride[0])
 
+
+    def _backward_cnn_layer_norm(self) -> None:
+        """_backward_cnn for the layer-norm family (HF:275-299, "-lv60" / xlsr): every layer is conv (+ bias) -> LayerNorm
+        over the channels -> GELU.  Layers 6 .. 1: LayerNorm-GELU backward from the saved pre-norm z (in place on the
+        incoming gradient; it also yields the LayerNorm's and the conv bias's gradients), then the same weight- and
+        data-gradient products as the group-norm family.  Layer 0 recomputes its convolution from the waveform."""
+        cfg, st, B = self.cfg, self.store, self.Bc
+        C = cfg.conv_dim
+        cins = (1,) + tuple(C[:-1])
+        mp, mg = st.mp, st.mg
+        fe = "feature_extractor.conv_layers."
+        for i in reversed(range(1, len(C))):
+            k, sd, ci, co = cfg.conv_kernel[i], cfg.conv_stride[i], cins[i], C[i]
+            gout = self.dn if i == len(C) - 1 else self.dconv[i]
+            gv = gout.view(-1, co)
+            ops.layernorm_gelu_bwd(gv, self.conv_pre[i].view(-1, co), mp(fe + f"{i}.layer_norm.weight"),
+                                   mp(fe + f"{i}.layer_norm.bias"), gv, mg(fe + f"{i}.layer_norm.weight"),
+                                   mg(fe + f"{i}.layer_norm.bias"), mg(fe + f"{i}.conv.bias") if cfg.conv_bias else None,
+                                   self.lng_ws)
+            self.dwp.zero_()
+            self.g_conv_dw[i]()
+            ops.unpack_conv_grad(self.dwp, mg(fe + f"{i}.conv.weight"))
+            self.g_conv_dx[i]()
+            ops.col2im(self.col, self.dconv[i - 1], B, self.lens[i - 1], self.lens[i], ci, k, sd)
+        ops.conv0_layernorm_gelu_bwd(self._wav, mp(fe + "0.conv.weight"), mp(fe + "0.conv.bias") if cfg.conv_bias else None,
+                                     mp(fe + "0.layer_norm.weight"), mp(fe + "0.layer_norm.bias"), self.dconv[0],
+                                     mg(fe + "0.conv.weight"), mg(fe + "0.conv.bias") if cfg.conv_bias else None,
+                                     mg(fe + "0.layer_norm.weight"), mg(fe + "0.layer_norm.bias"), self.c0l_ws,
+                                     cfg.conv_kernel[0], cfg.conv_stride[0])

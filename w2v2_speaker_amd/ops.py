@@ -283,6 +283,27 @@ def conv0_layernorm_gelu(wav, w, bias, gamma, beta, out, k: int, stride: int, ep
                "conv0_layernorm_gelu")
 
 
+def conv0_layernorm_gelu_bwd_workspace(B: int, N: int, C: int, k: int, stride: int, device) -> torch.Tensor:
+    """f32 scratch of conv0_layernorm_gelu_bwd: one partial row [k + 3][C] per workgroup."""
+    n = lib().w2v2_conv0_layernorm_gelu_bwd_workspace_floats(B, N, C, k, stride)
+    return torch.empty(max(n, 1), dtype=torch.float32, device=device)
+
+
+def conv0_layernorm_gelu_bwd(wav, w, bias, gamma, beta, dy, dw, dbias, dgamma, dbeta, work, k: int, stride: int,
+                             eps: float = 1e-5) -> None:
+    """Backward of conv0_layernorm_gelu: dy [B, L, C] -> dw [C, 1, k], dbias (None with bias None), dgamma, dbeta, all
+    ADDED (fixed-order sums: bitwise reproducible); `work` from conv0_layernorm_gelu_bwd_workspace()."""
+    _dev(wav, w, bias, gamma, beta, dy, dw, dbias, dgamma, dbeta, work)
+    B, N = wav.shape
+    Cc = dy.shape[-1]
+    if work.numel() < lib().w2v2_conv0_layernorm_gelu_bwd_workspace_floats(B, N, Cc, k, stride):
+        raise ValueError("conv0_layernorm_gelu_bwd: workspace too small")
+    _lib.check(lib().w2v2_conv0_layernorm_gelu_bwd(wav.data_ptr(), w.data_ptr(), _p(bias), gamma.data_ptr(), beta.data_ptr(),
+                                                   dy.data_ptr(), dw.data_ptr(), _p(dbias), dgamma.data_ptr(),
+                                                   dbeta.data_ptr(), work.data_ptr(), B, N, Cc, k, stride, eps, dt(dy),
+                                                   stream()), "conv0_layernorm_gelu_bwd")
+
+
 def conv0_bwd(wav, w, work, gamma, beta, dz, sums, dw, dgamma, dbeta, k: int, stride: int) -> None:
     """Backward of layer 0 (see w2v2_conv0_bwd); `work` is the forward's conv0 workspace (holds mean/rstd)."""
     _dev(wav, w, work, gamma, beta, dz, sums, dw, dgamma, dbeta)
@@ -328,6 +349,24 @@ def layernorm_gelu_fwd(x, gamma, beta, y, eps: float) -> None:
     H = x.shape[-1]
     _lib.check(lib().w2v2_layernorm_gelu_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), x.numel() // H, H,
                                              eps, dt(x), stream()), "layernorm_gelu_fwd")
+
+
+def layernorm_gelu_bwd_workspace(M: int, H: int, device) -> torch.Tensor:
+    """f32 scratch of layernorm_gelu_bwd: one partial row [3][H] per workgroup."""
+    return torch.empty(max(lib().w2v2_layernorm_gelu_bwd_workspace_floats(M, H), 1), dtype=torch.float32, device=device)
+
+
+def layernorm_gelu_bwd(dy, z, gamma, beta, dz, dgamma, dbeta, dbias, work, eps: float = 1e-5) -> None:
+    """Backward of layernorm_gelu_fwd from the saved pre-norm z: dz (may alias dy) written, dgamma / dbeta / dbias (the
+    column sum of dz, may be None) ADDED in a fixed order (bitwise reproducible); `work` from layernorm_gelu_bwd_workspace()."""
+    _dev(dy, z, gamma, beta, dz, dgamma, dbeta, dbias, work)
+    H = dy.shape[-1]
+    M = dy.numel() // H
+    if work.numel() < lib().w2v2_layernorm_gelu_bwd_workspace_floats(M, H):
+        raise ValueError("layernorm_gelu_bwd: workspace too small")
+    _lib.check(lib().w2v2_layernorm_gelu_bwd(dy.data_ptr(), z.data_ptr(), gamma.data_ptr(), beta.data_ptr(), dz.data_ptr(),
+                                             dgamma.data_ptr(), dbeta.data_ptr(), _p(dbias), work.data_ptr(), M, H, eps,
+                                             dt(dy), stream()), "layernorm_gelu_bwd")
 
 
 _LN_WS = {}
