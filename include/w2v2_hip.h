@@ -519,6 +519,27 @@ int w2v2_se_bwd_x(const void* dout, const float* g, const float* ds, void* dx, i
 int w2v2_act_fwd(const float* x, float* y, int64_t n, int mode, void* stream);
 int w2v2_act_bwd(const float* dy, const float* y, float* dx, int64_t n, int mode, void* stream);
 
+/* ---------------------------------------------------------------------------------------- log-mel filterbank front-end
+ * The ECAPA input features from waveforms (the device twin of data/fbank.py + InputNormalizer2D(True), data/pipeline.py;
+ * ref: src/data/preprocess/audio_features.py:62-78, input_normalisation.py:44-75).  An utterance of n samples has
+ * F = 1 + n / 160 frames; tap j in [0, 400) of frame t reads sample 160 t - 200 + j, zero outside [0, n) BY INDEX.
+ * lens: device int32[B] SAMPLE counts (NULL: every utterance has N), 0 <= lens[b] <= N (clamped to that range).
+ *
+ * w2v2_fbank_db: wav [B][N] f32, window [400] (periodic Hamming), fbank [201][n_mels] -> db_out [B][T][n_mels] =
+ * 10 log10(max(|DFT_400(window * frame)|^2 . fbank, 1e-10)) BEFORE the top-dB clamp, T = 1 + N / 160, and partial_max
+ * [B][ceil(T / W2V2_FBANK_TILE_FRAMES)]: the maximum over tile i of frames [16 i, 16 i + 16) of the utterance (its own
+ * frames only; tiles past F_b hold -inf, rows t >= F_b of db_out zeros).
+ * w2v2_fbank_normalize: db = max(db, max over the utterance's F_b x n_mels cells - 80), then per mel channel over the
+ * utterance's F_b frames (db - mean) / (std_unbiased + 1e-5) into out (row b T + t at out + (b T + t) ldo, n_mels
+ * columns written, dtype W2V2_F32 or W2V2_BF16); rows t >= F_b are written as zeros.
+ * Every cross-frame reduction runs in an order fixed by F_b alone: rows t < F_b of a padded batch are bit-identical to
+ * the same two calls on the utterance alone (B = 1, N = n_b). */
+#define W2V2_FBANK_TILE_FRAMES 16
+int w2v2_fbank_db(const float* wav, const int* lens, const float* window, const float* fbank, float* db_out,
+                  float* partial_max, int B, int N, int T, int n_mels, void* stream);
+int w2v2_fbank_normalize(const float* db, const float* partial_max, const int* lens, void* out, int64_t ldo, int dtype,
+                         int B, int T, int n_mels, void* stream);
+
 /* ---------------------------------------------------------------------------------------- skinny linear layers
  * Exact-f32 nn.Linear / Conv1d(k=1) over a handful of rows (one per utterance): the SE bottleneck and the embedding
  * layer of ECAPA (speechbrain SEBlock / ECAPA_TDNN.fc) and the hidden fc_list of the wav2vec2 head (ref:

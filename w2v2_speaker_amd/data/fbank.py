@@ -2,8 +2,11 @@
 ``FilterBank`` -> speechbrain 0.5.x ``Fbank(n_mels=40)``; config/data/pipeline/xvector_pipeline.yaml: selector ->
 filterbank -> normalizer(channel-wise)).
 
-Host-side data preprocessing, as in the reference (its DataLoader workers run it on the CPU); not part of the GPU
-path.  speechbrain is not available here: this follows the published defaults of ``speechbrain.lobes.features.Fbank``
+Host-side data preprocessing, as in the reference (its DataLoader workers run it on the CPU).  Its device twin is
+csrc/fbank.hip (``ops.fbank_db`` + ``ops.fbank_normalize``, ``EcapaPlan.embed_waveform``,
+``EcapaTdnnModule(input_features="waveform")``): the same arithmetic followed by the channel-wise
+``InputNormalizer2D``, with the window and the mel matrix uploaded from the ``Fbank`` object below -- this file stays the
+one definition of both, and the reference of the device path's parity tests (tests/test_fbank_gpu.py).  speechbrain is not available here: this follows the published defaults of ``speechbrain.lobes.features.Fbank``
 (STFT 25 ms Hamming window / 10 ms hop / n_fft 400, centred with constant padding; power spectrum; 40 triangular
 filters equally spaced on the mel scale 2595 log10(1 + f/700) between 0 and 8000 Hz; 10 log10(max(., 1e-10)) clipped
 to 80 dB below the maximum) -- PARITY UNPINNED."""

@@ -79,6 +79,32 @@ def valid_frame_lengths(cfg: EcapaConfig, lengths, batch: int, frames: int) -> L
     return lens
 
 
+def fbank_frames(n: int) -> int:
+    """Frames of the filterbank front-end (data/fbank.py: centred STFT, hop 160) over n samples."""
+    return 1 + int(n) // ops.FBANK_HOP
+
+
+def valid_sample_lengths(cfg: EcapaConfig, lengths, batch: int, samples: int) -> List[int]:
+    """valid_frame_lengths in samples: per-utterance sample counts of a padded [batch, samples] waveform input as Python
+    ints; ValueError unless there is one per row, none exceeds ``samples`` and each gives at least ecapa_min_frames(cfg)
+    filterbank frames."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_cuda or lengths.is_floating_point() or lengths.is_complex():
+            raise ValueError("lengths must be Python ints or a CPU integer tensor")
+        lengths = lengths.reshape(-1).tolist()
+    lens = [int(n) for n in lengths]
+    if len(lens) != batch:
+        raise ValueError(f"lengths: {len(lens)} values for a batch of {batch}")
+    lo = ecapa_min_frames(cfg)
+    for n in lens:
+        if n > samples:
+            raise ValueError(f"lengths: {n} samples is longer than the batch's {samples}")
+        if n < 0 or fbank_frames(n) < lo:
+            raise ValueError(f"lengths: {n} samples give fewer frames than the model's reflect padding allows ({lo} "
+                             f"frames = {(lo - 1) * ops.FBANK_HOP} samples)")
+    return lens
+
+
 def ecapa_param_shapes(cfg: EcapaConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     """speechbrain state-dict names under ``feature_extractor.`` (Conv1d wrapper -> .conv, BatchNorm1d -> .norm)."""
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
@@ -652,7 +678,7 @@ class EcapaPlan:
         plans).  Every stage that reaches across frames (the reflect-padded convolution gathers, the SE squeeze, the global
         context and the softmax of the attentive pooling) then sees each utterance's own frames only, so row b equals the
         utterance alone in a (1, n) plan; padded frames may hold any finite values."""
-        st, B, T = self.store, self.B, self.T
+        B, T = self.B, self.T
         assert feat.shape == (B, T, self.cfg.input_mel_coefficients) and feat.is_cuda
         self._len, self.frame_lengths = None, None
         if lengths is not None:
@@ -663,6 +689,53 @@ class EcapaPlan:
             ops.copy_strided(f2, f2.shape[1], self.feat, self.feat.stride(0), B * T, f2.shape[1])
         else:
             ops.cast(f2.contiguous(), self.feat)
+        return self._embed_features()
+
+    def _frontend(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(window [400], fbank [201, n_mels]) of the host front-end on the device -- uploaded once per store from
+        data/fbank.py's Fbank, the one definition of the two in the tree -- and this plan's dB and tile-maximum buffers."""
+        st = self.store
+        if getattr(st, "_fbank_dev", None) is None:
+            from .data.fbank import Fbank
+            fb = Fbank(n_mels=self.cfg.input_mel_coefficients)
+            assert fb.n_fft == fb.win == ops.FBANK_WIN and fb.hop == ops.FBANK_HOP, \
+                "the device front-end is built for n_fft = win = 400, hop = 160"
+            st._fbank_dev = (fb.window.to(self.dev, torch.float32).contiguous(),
+                             fb.fbank.to(self.dev, torch.float32).contiguous())
+        if getattr(self, "_fb_db", None) is None:
+            self._fb_db = torch.empty(self.B, self.T, self.cfg.input_mel_coefficients, dtype=torch.float32, device=self.dev)
+            self._fb_pmax = ops.fbank_partial_max(self.B, self.T, self.dev)
+        return st._fbank_dev + (self._fb_db, self._fb_pmax)
+
+    def embed_waveform(self, wav: torch.Tensor, lengths=None) -> torch.Tensor:
+        """embed() from waveforms: wav [B, N] f32 with fbank_frames(N) == the plan's frames.  The log-mel front-end
+        (csrc/fbank.hip: data/fbank.py + the channel-wise InputNormalizer2D) writes the plan's feature buffer directly, in
+        its stride and dtype.  lengths: valid SAMPLES per utterance (valid_sample_lengths; evaluation plans) -- utterance b
+        then has fbank_frames(n_b) frames, samples past n_b never enter the arithmetic and row b equals the utterance
+        alone in a (1, fbank_frames(n_b)) plan."""
+        B, T = self.B, self.T
+        if wav.dim() != 2 or wav.shape[0] != B or fbank_frames(wav.shape[1]) != T:
+            raise ValueError(f"embed_waveform: a plan of {B} x {T} frames takes [B, N] waveforms with 1 + N // 160 == {T}, got "
+                             f"{tuple(wav.shape)}")
+        assert wav.is_cuda and wav.dtype == torch.float32
+        self._len, self.frame_lengths = None, None
+        slen = None
+        if lengths is not None:
+            ns = valid_sample_lengths(self.cfg, lengths, B, wav.shape[1])
+            self._set_lengths([fbank_frames(n) for n in ns])
+            if getattr(self, "_slen_dev", None) is None:
+                self._slen_dev = torch.empty(B, dtype=torch.int32, device=self.dev)
+            self._slen_dev.copy_(torch.tensor(ns, dtype=torch.int32))
+            slen = self._slen_dev
+        self._refresh()
+        window, fbank, db, pmax = self._frontend()
+        ops.fbank_db(wav.contiguous(), slen, window, fbank, db, pmax)
+        ops.fbank_normalize(db, pmax, slen, self.feat, self.feat.stride(0))
+        return self._embed_features()
+
+    def _embed_features(self) -> torch.Tensor:
+        """The forward from the plan's feature buffer on (shared by embed and embed_waveform)."""
+        st, B = self.store, self.B
         self.block0.forward()
         for b in self.blocks:
             b.forward()
@@ -735,11 +808,18 @@ class EcapaTrainer:
             import torch.distributed as dist
             self.world = dist.get_world_size(process_group)
 
+    def _embed(self, x: torch.Tensor) -> None:
+        """[B, T, n_mels] filterbank features, or [B, N] waveforms through the device front-end."""
+        if x.dim() == 2:
+            self.plan.embed_waveform(x)
+        else:
+            self.plan.embed(x)
+
     def train_step(self, feat: torch.Tensor, label: torch.Tensor):
         if self.accumulate_grad_batches > 1:
             return self._micro_batch(feat, label)
         self.store.zero_grad()
-        self.plan.embed(feat)
+        self._embed(feat)
         loss, softmax = self.plan.head_forward_backward(label)
         self.plan.backward()
         if self.world > 1:
@@ -757,7 +837,7 @@ class EcapaTrainer:
         move on every micro-batch, as in torch."""
         store = self.store
         store.zero_grad()
-        self.plan.embed(feat)
+        self._embed(feat)
         loss, softmax = self.plan.head_forward_backward(label)
         self.plan.backward()
         fused.accumulate(store, 0, store.n_total)

@@ -8,11 +8,12 @@ from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
-from ...ecapa import EcapaConfig, EcapaPlan, EcapaStore, EcapaTrainer, ecapa_min_frames
+from ...ecapa import EcapaConfig, EcapaPlan, EcapaStore, EcapaTrainer, ecapa_min_frames, fbank_frames
 from ...eval_batching import DEFAULT_FRAME_QUANTUM, DEFAULT_MAX_BATCH, DEFAULT_MAX_BATCH_FRAMES, plan_batches
 from ...optim.schedule import OneCycle
 from ._optim_surface import OptimizerSurface
-from .wav2vec2_fc import SpeakerClassificationDataBatch
+from ...ops import FBANK_HOP
+from .wav2vec2_fc import SpeakerClassificationDataBatch, Wav2vec2FCModule
 
 MAX_BUCKET_PLANS = 12     # plans of compute_speaker_embeddings' length buckets (LRU, one per bucket shape)
 
@@ -39,12 +40,19 @@ class EcapaTdnnModule(OptimizerSurface):
                  loss_fn_constructor: Callable[[], object], validation_pairs=None, test_pairs=None, evaluator=None, *,
                  device="cuda", act_dtype: torch.dtype = torch.bfloat16, max_lr: float = 1e-3,
                  max_steps: int = 100_000, init_seed: int = 20211, gradient_clip_val: float = 0.0,
-                 accumulate_grad_batches: int = 1):
+                 accumulate_grad_batches: int = 1, input_features: str = "fbank"):
         """Positional arguments = ref: ecapa_tdnn.py:51-62 (what src/main.py:256-285 passes to every network class).
         ``loss_fn_constructor`` is called once and read for its type and hyper-parameters: the engine runs the ECAPA
         model under AAM-softmax (``skip_classifier`` of ref :93-95; the paper's configuration,
         config/experiment/speaker_ecapa_tdnn.yaml) -- the cross-entropy + cosine ``Classifier`` variant is not on the
-        path.  ``act_dtype=torch.float32`` is the reference's own precision for this model (``precision: 32``)."""
+        path.  ``act_dtype=torch.float32`` is the reference's own precision for this model (``precision: 32``).
+        ``input_features``: "fbank" -- inputs are [B, T, n_mels] filterbank tensors, the output of the reference's
+        ``filterbank`` + ``normalizer`` pipeline stages (data/fbank.py, InputNormalizer2D) -- or "waveform": inputs are
+        what the ``selector`` stage delivers ([B, 1, N], [B, N] or [N] audio) and the two stages run on the device
+        (EcapaPlan.embed_waveform)."""
+        if input_features not in ("fbank", "waveform"):
+            raise ValueError(f"input_features: 'fbank' or 'waveform', got {input_features!r}")
+        self.input_features = input_features
         from ...evaluation.speaker.cosine_distance import CosineDistanceEvaluator
         from ...optim.loss import AngularAdditiveMarginSoftMaxLoss
         loss_fn = loss_fn_constructor()
@@ -108,9 +116,19 @@ class EcapaTdnnModule(OptimizerSurface):
 
     def compute_speaker_embedding(self, input_tensor: torch.Tensor) -> torch.Tensor:
         # ref :110-118
+        if self.input_features == "waveform":
+            x = self._prep_waveform(input_tensor)
+            return self._plan(x.shape[0], fbank_frames(x.shape[1]), False).embed_waveform(x).clone()
         x = input_tensor if input_tensor.dim() == 3 else input_tensor[None]
         x = x.to(self.device, torch.float32)
         return self._plan(x.shape[0], x.shape[1], False).embed(x).clone()
+
+    def _prep_waveform(self, input_tensor: torch.Tensor) -> torch.Tensor:
+        """[B, 1, N], [B, N] or [N] audio -> [B, N] f32 on the device (Wav2vec2FCModule's input forms)."""
+        x = Wav2vec2FCModule._prep_input(input_tensor)
+        if x.dim() != 2:
+            raise ValueError(f"expected [B, 1, N], [B, N] or [N] audio, got {tuple(input_tensor.shape)}")
+        return x.to(self.device, torch.float32).contiguous()
 
     def _bucket_plan(self, batch: int, frames: int) -> EcapaPlan:
         key = (batch, frames)
@@ -130,7 +148,12 @@ class EcapaTdnnModule(OptimizerSurface):
         """Embeddings of many utterances of different lengths, batched: one [1, lin_neurons] tensor per filterbank tensor
         ([T, n_mels] or [1, T, n_mels]), in input order, each equal to ``compute_speaker_embedding`` of that utterance
         alone.  The utterances are bucketed by frame count (eval_batching.plan_batches, lengths in frames) and each batch
-        runs one variable-length forward (EcapaPlan.embed(..., lengths=))."""
+        runs one variable-length forward (EcapaPlan.embed(..., lengths=)).
+        ``input_features="waveform"``: one waveform ([N] or [1, N]) per utterance, bucketed by SAMPLE count with the same
+        policy in units of the 160-sample hop (``quantum`` and ``max_batch_frames`` are multiplied by 160), each batch one
+        EcapaPlan.embed_waveform(..., lengths=)."""
+        if self.input_features == "waveform":
+            return self._waveform_embeddings(feats, quantum, max_batch_frames, max_batch)
         F_ = self.cfg.input_mel_coefficients
         xs = []
         for f in feats:
@@ -153,9 +176,31 @@ class EcapaTdnnModule(OptimizerSurface):
                 out[i] = emb[j:j + 1].clone()
         return out
 
+    def _waveform_embeddings(self, wavs, quantum: int, max_batch_frames: int, max_batch: int) -> List[torch.Tensor]:
+        xs = []
+        for w in wavs:
+            x = w[0] if (w.dim() == 2 and w.shape[0] == 1) else w
+            if x.dim() != 1:
+                raise ValueError(f"compute_speaker_embeddings: expected [N] or [1, N] per utterance, got {tuple(w.shape)}")
+            xs.append(x)
+        out: List[Optional[torch.Tensor]] = [None] * len(xs)
+        fill = (ecapa_min_frames(self.model_cfg) - 1) * FBANK_HOP      # fewest samples with the minimum frame count
+        for idx, n, batch in plan_batches([x.shape[0] for x in xs], quantum * FBANK_HOP, max_batch_frames * FBANK_HOP,
+                                          max_batch):
+            plan = self._bucket_plan(batch, fbank_frames(n))
+            wav = torch.zeros(batch, n, dtype=torch.float32, device=self.device)
+            lens = [fill] * batch           # unused rows of a bucket's last batch: silence of the minimum length
+            for j, i in enumerate(idx):
+                wav[j, :xs[i].shape[0]].copy_(xs[i])
+                lens[j] = xs[i].shape[0]
+            emb = plan.embed_waveform(wav, lengths=lens)
+            for j, i in enumerate(idx):
+                out[i] = emb[j:j + 1].clone()
+        return out
+
     def evaluate_trials(self, pairs, feats_by_key, **batching) -> dict:
-        """Score a trial list: every utterance the pairs name (key -> filterbank tensor in ``feats_by_key``) is embedded once
-        with compute_speaker_embeddings (``batching``: its keyword arguments) and the module's evaluator scores the pairs --
+        """Score a trial list: every utterance the pairs name (key -> filterbank tensor in ``feats_by_key``, or key ->
+        waveform under ``input_features="waveform"``) is embedded once with compute_speaker_embeddings (``batching``: its keyword arguments) and the module's evaluator scores the pairs --
         the same dict as test_epoch_end over the batch-size-1 test loop."""
         keys = sorted({k for p in pairs for k in (p.sample1_id, p.sample2_id)})
         embs = self.compute_speaker_embeddings([feats_by_key[k] for k in keys], **batching)
@@ -172,11 +217,15 @@ class EcapaTdnnModule(OptimizerSurface):
 
     def training_step(self, batch: SpeakerClassificationDataBatch, batch_idx: int = 0,
                       optimizer_idx: Optional[int] = None):
-        x = batch.network_input.to(self.device, torch.float32)
+        if self.input_features == "waveform":
+            x = self._prep_waveform(batch.network_input)
+            key = (x.shape[0], fbank_frames(x.shape[1]))
+        else:
+            x = batch.network_input.to(self.device, torch.float32)
+            key = (x.shape[0], x.shape[1])
         label = batch.ground_truth.to(self.device)
-        key = (x.shape[0], x.shape[1])
         if key not in self._trainers:
-            self._trainers[key] = EcapaTrainer(self.store, self._plan(x.shape[0], x.shape[1], True), self.schedule,
+            self._trainers[key] = EcapaTrainer(self.store, self._plan(key[0], key[1], True), self.schedule,
                                                **self._trainer_options())
         tr = self._trainers[key]
         tr.step = self.schedule_step

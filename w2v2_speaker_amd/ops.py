@@ -948,6 +948,51 @@ def copy_strided(a, lda: int, y, ldy: int, M: int, C: int) -> None:
     add_strided(a, lda, None, 0, y, ldy, M, C)
 
 
+FBANK_HOP, FBANK_WIN, FBANK_TILE_FRAMES = 160, 400, 16     # (W2V2_FBANK_TILE_FRAMES of include/w2v2_hip.h)
+
+
+def fbank_partial_max(B: int, T: int, device) -> torch.Tensor:
+    """Workspace of fbank_db / fbank_normalize: one maximum per (utterance, tile of FBANK_TILE_FRAMES frames)."""
+    return torch.empty(B, -(-T // FBANK_TILE_FRAMES), dtype=torch.float32, device=device)
+
+
+def _fbank_f32(*ts) -> None:
+    for t in ts:
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("fbank: wav, window, fbank, db and partial_max are contiguous f32 tensors")
+
+
+def fbank_db(wav, lens, window, fbank, db, partial_max) -> None:
+    """wav [B, N] f32 -> db [B, 1 + N // 160, n_mels] f32 (log-mel, before the top-dB clamp) and the per-tile maxima;
+    lens: device int32 [B] sample counts or None; window [400], fbank [201, n_mels]: those of data/fbank.py."""
+    _dev(wav, lens, window, fbank, db, partial_max)
+    _fbank_f32(wav, window, fbank, db, partial_max)
+    B, N = wav.shape
+    T, n_mels = 1 + N // FBANK_HOP, fbank.shape[1]
+    if (window.numel() != FBANK_WIN or fbank.shape[0] != FBANK_WIN // 2 + 1 or tuple(db.shape) != (B, T, n_mels)
+            or partial_max.numel() < B * -(-T // FBANK_TILE_FRAMES)
+            or (lens is not None and (lens.dtype != torch.int32 or lens.numel() != B))):
+        raise ValueError(f"fbank_db: shapes wav {tuple(wav.shape)}, window {tuple(window.shape)}, fbank "
+                         f"{tuple(fbank.shape)}, db {tuple(db.shape)}, partial_max {tuple(partial_max.shape)}")
+    _lib.check(lib().w2v2_fbank_db(wav.data_ptr(), _p(lens), window.data_ptr(), fbank.data_ptr(), db.data_ptr(),
+                                   partial_max.data_ptr(), B, N, T, n_mels, stream()), "fbank_db")
+
+
+def fbank_normalize(db, partial_max, lens, out, ldo: int) -> None:
+    """Top-dB clamp + per-channel normalisation of fbank_db's output over each utterance's own frames into ``out`` (f32 or
+    bf16, [B * T] rows of stride ldo, n_mels columns written); rows past an utterance's frames are written as zeros."""
+    _dev(db, partial_max, lens, out)
+    _fbank_f32(db, partial_max)
+    B, T, n_mels = db.shape
+    if (out.dtype not in (torch.float32, torch.bfloat16) or ldo < n_mels or out.stride(-1) != 1
+            or partial_max.numel() < B * -(-T // FBANK_TILE_FRAMES)
+            or out.untyped_storage().nbytes() // out.element_size() - out.storage_offset() < (B * T - 1) * ldo + n_mels
+            or (lens is not None and (lens.dtype != torch.int32 or lens.numel() != B))):
+        raise ValueError(f"fbank_normalize: db {tuple(db.shape)}, out {tuple(out.shape)} {out.dtype} with row stride {ldo}")
+    _lib.check(lib().w2v2_fbank_normalize(db.data_ptr(), partial_max.data_ptr(), _p(lens), out.data_ptr(), ldo, dt(out),
+                                          B, T, n_mels, stream()), "fbank_normalize")
+
+
 def se_scale(x, g, y, B: int, T: int, C: int) -> None:
     _dev(x, g, y)
     _lib.check(lib().w2v2_se_scale(x.data_ptr(), g.data_ptr(), y.data_ptr(), B, T, C, dt(x), stream()), "se_scale")
