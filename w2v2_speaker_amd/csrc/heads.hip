@@ -67,6 +67,22 @@ __device__ __forceinline__ float block_reduce_n(float v, float* sh, bool is_max)
   return r;
 }
 
+// two sums at once (the same two barriers and the same wave order as block_reduce_n)
+template <int NW>
+__device__ __forceinline__ void block_reduce_sum2(float& a, float& b, float* sha, float* shb) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) { sha[wave] = a; shb[wave] = b; }
+  __syncthreads();
+  float ra = sha[0], rb = shb[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) { ra += sha[w]; rb += shb[w]; }
+  a = ra;
+  b = rb;
+}
+
 // One workgroup per utterance row.  z_c = s*cos_c (c != y), z_y = s*phi(cos_y); loss = lse(z) - z_y.
 // dLoss/dcos_c = s * (softmax_c - [c==y]) / B * (c == y ? dphi/dcos : 1).
 // (1024 threads: the three passes over a row's ~6000 logits are a handful of dependent load rounds on B = 66 workgroups;
@@ -82,7 +98,7 @@ __global__ __launch_bounds__(AAM_ROW_THREADS) void aam_row_kernel(const float* _
                                                       float margin, float scale, const float* __restrict__ loss_scale,
                                                       float* __restrict__ correct_rows, int easy_margin) {
   constexpr int NT = AAM_ROW_THREADS, NW = NT / 64;
-  __shared__ float sh[NW];
+  __shared__ float sh[NW], sh2[NW];
   __shared__ int shi[NW];
   const int b = blockIdx.x;
   const int64_t yl = label[b];
@@ -138,9 +154,16 @@ __global__ __launch_bounds__(AAM_ROW_THREADS) void aam_row_kernel(const float* _
       correct_rows[b] = (!bad_label && best == y) ? 1.0f : 0.0f;
     }
   }
-  float sum = 0.f;
-  for (int c = threadIdx.x; c < C; c += NT) sum += __expf((c == y ? zy : cr[c] * sc) - mx);
-  sum = block_reduce_n<NW>(sum, sh, false);
+  // `sum` is the whole row; `sum_off` the off-label terms alone, folded through the same two barriers: where p_y > 1/2
+  // the label gradient is taken as -(1 - p_y) = -sum_off / sum, because p_y - 1 in f32 is rounding noise once p_y -> 1
+  // (a well-classified row lost every digit of its gradient).  Below 1/2 the subtraction is exact to an ulp of p_y.
+  float sum = 0.f, sum_off = 0.f;
+  for (int c = threadIdx.x; c < C; c += NT) {
+    const float e = __expf((c == y ? zy : cr[c] * sc) - mx);
+    sum += e;
+    if (c != y) sum_off += e;
+  }
+  block_reduce_sum2<NW>(sum, sum_off, sh, sh2);
   const float inv = 1.0f / sum;
   if (threadIdx.x == 0) loss_rows[b] = bad_label ? __builtin_nanf("") : (mx + __logf(sum)) - zy;
   const float invB = bad_label ? 0.f : (loss_scale ? loss_scale[0] : 1.0f) / (float)B;
@@ -151,7 +174,10 @@ __global__ __launch_bounds__(AAM_ROW_THREADS) void aam_row_kernel(const float* _
     softmax[(int64_t)b * ldc + c] = p;
     if (dcos_w != nullptr) {
       float g = (p - (c == y ? 1.0f : 0.0f)) * invB * sc;
-      if (c == y) g *= dphi;
+      if (c == y) {
+        if (p > 0.5f) g = -(sum_off * inv) * invB * sc;
+        g *= dphi;
+      }
       // the two F.normalize scalings are folded into the operands of the two gradient GEMMs
       dcos_w[(int64_t)b * ldc + c] = from_f32<T>(inv_w ? g * inv_w[c] : g);
       if (dcos_x != nullptr) dcos_x[(int64_t)b * ldc + c] = from_f32<T>(inv_x ? g * inv_x[b] : g);
@@ -161,7 +187,7 @@ __global__ __launch_bounds__(AAM_ROW_THREADS) void aam_row_kernel(const float* _
       }
     }
   }
-  if (rowdot != nullptr) {
+  if (rowdot != nullptr && dcos_w != nullptr) {      // no gradient pointer (evaluation): no gradient output is touched
     rd = block_reduce_n<NW>(rd, sh, false);
     if (threadIdx.x == 0) rowdot[b] = rd;
   }
