@@ -95,6 +95,37 @@ def test_asp_pool_fwd_len_bit_identical(dtype):
         assert torch.equal(stats[b:b + 1], rs), L
 
 
+def test_len_entries_at_full_lengths_equal_the_fixed_length_entries():
+    """The two forms of an operation are instantiations of one kernel body: with lens = [T] * B the variable-length
+    entry must give the bits of the fixed-length entry."""
+    from w2v2_speaker_amd import ops
+    g = torch.Generator().manual_seed(7)
+    for dtype in DTYPES:
+        B, T, C = 2, 19, 72                                   # a partial 64-channel block, T no multiple of 8 time lanes
+        lens = _i32([T] * B)
+        x = torch.randn(B, T, C, generator=g).to(DEV).to(dtype)
+        s = (3 * torch.randn(B, T, C, generator=g)).to(DEV).to(dtype)
+        ctx, ref = torch.full((B, 2 * C), 7.0, device=DEV), torch.full((B, 2 * C), 5.0, device=DEV)
+        ops.asp_context_len(x.view(B * T, C), ctx, lens, B, T, C)
+        ops.asp_context(x.view(B * T, C), ref, B, T, C)
+        assert torch.equal(ctx, ref), dtype
+        out, ro = torch.full((B, 2 * C), 7.0, device=DEV), torch.full((B, 2 * C), 5.0, device=DEV)
+        stats, rs = torch.full((B, C, 2), 7.0, device=DEV), torch.full((B, C, 2), 5.0, device=DEV)
+        ops.asp_pool_fwd_len(x.view(B * T, C), s.view(B * T, C), out, stats, lens, B, T, C)
+        ops.asp_pool_fwd(x.view(B * T, C), s.view(B * T, C), ro, rs, B, T, C)
+        assert torch.equal(out, ro) and torch.equal(stats, rs), dtype
+        B, T, C, k, dil = 2, 23, 32, 3, 2                     # more than one workgroup, the last one partial
+        lens = _i32([T] * B)
+        x = torch.randn(B * T, C, generator=g).to(DEV).to(dtype)
+        x2 = torch.randn(B * T, C, generator=g).to(DEV).to(dtype)
+        for second in (None, x2):
+            col = torch.full((B * T, k * C), 7.0, device=DEV, dtype=dtype)
+            ref = torch.full_like(col, 5.0)
+            ops.im2col_reflect_len(x, C, col, lens, B, T, C, k, dil, second, C if second is not None else 0)
+            ops.im2col_reflect(x, C, ref, B, T, C, k, dil, second, C if second is not None else 0)
+            assert torch.equal(col, ref), (dtype, second is not None)
+
+
 # ------------------------------------------------------------------------------------------------ ECAPA engine
 def _running(name, C, seed=20211):
     """Seeded, non-trivial BatchNorm running statistics {mean[C], var[C]}."""

@@ -166,6 +166,67 @@ def test_attention_len_bit_identical_under_forced_geometry(geom, dtype, monkeypa
         assert torch.equal(lse.view(B, heads, T)[b, :, :L], rl.view(heads, L))
 
 
+def test_len_entries_at_full_lengths_equal_the_fixed_length_entries(monkeypatch):
+    """The two forms of an operation are instantiations of one kernel body: with lens = [T] * B the variable-length
+    entry must give the bits of the fixed-length entry, on shapes that cross the kernels' internal boundaries."""
+    from w2v2_speaker_amd import _lib, ops
+    g = torch.Generator().manual_seed(7)
+    # layer-0 statistics, exact and window-moment route: five whole 128-frame chunks and a ragged one (two 640-frame
+    # window-moment blocks, the second ragged)
+    C, k, stride, B = 512, 10, 5, 2
+    N = 5 * (128 * stride) + 37 * stride + k
+    wav = torch.randn(B, N, generator=g).to(DEV)
+    w = (0.3 * torch.randn(C, k, generator=g)).to(DEV)
+    for mfma in (False, True):
+        work = ops.conv0_workspace(B, N, C, k, stride, DEV)
+        mr = ops.conv0_stats_len(wav, w, work, _i32([(N - k) // stride + 1] * B), k, stride, mfma).clone()
+        wk = ops.conv0_workspace(B, N, C, k, stride, DEV)
+        ref = wk[wk.numel() - B * C * 2:]
+        fn = ops.lib().w2v2_conv0_stats_mfma if mfma else ops.lib().w2v2_conv0_stats
+        _lib.check(fn(wav.data_ptr(), w.data_ptr(), wk.data_ptr(), ref.data_ptr(), B, N, C, k, stride, 1e-5,
+                      ops.stream()), "conv0_stats")
+        assert torch.equal(mr, ref.view(B, C, 2)), mfma
+    for dtype in DTYPES:
+        B, T, H, G, K = 2, 21, 64, 4, 8
+        x = torch.randn(B, T, H, generator=g).to(DEV).to(dtype)
+        xg = torch.full((B, G, T + K - 1, H // G), 7.0, device=DEV, dtype=dtype)
+        ref = torch.full_like(xg, 5.0)
+        ops.posconv_regroup_len(x, xg, _i32([T] * B), B, T, H, G, K, K // 2)
+        ops.posconv_regroup(x, ref, B, T, H, G, K, K // 2)
+        assert torch.equal(xg, ref), dtype
+        # pooling: a partial 128-channel block, T no multiple of the 16 time lanes
+        B, T, H = 3, 37, 136
+        x = torch.randn(B, T, H, generator=g).to(DEV).to(dtype)
+        for m in range(6):
+            W = ops.POOL_WIDTH.get(m, 1) * H
+            out, ref = torch.full((B, W), 7.0, device=DEV), torch.full((B, W), 5.0, device=DEV)
+            ops.pool_fwd_len(x, out, _i32([T] * B), m)
+            ops.pool_fwd(x, ref, m)
+            assert torch.equal(out, ref), (dtype, m)
+        # softmax without dropout: more than one 64-lane pass
+        B, heads, T = 2, 2, 70
+        ld = (T + 7) // 8 * 8
+        s = (3 * torch.randn(B * heads * T, ld, generator=g)).to(DEV)
+        p = torch.full((B * heads * T, ld), 7.0, device=DEV).to(dtype)
+        ref = p.clone()
+        ops.softmax_fwd_len(s, p, _i32([T] * B), B, heads, T, ld)
+        ops.softmax_fwd(s, ref, None, B * heads * T, T, ld, 0.0, 0)
+        assert torch.equal(p, ref), dtype
+    # fused attention without dropout, every row valid: all of ctx and lse
+    B, heads, d = 2, 2, 64
+    for geom in ("32", "64"):
+        monkeypatch.setenv("W2V2_ATTN_GEOM", geom)
+        for dtype in (torch.float16, torch.bfloat16):
+            for T in (70, 149):
+                qkv = torch.randn(B, T, 3 * heads * d, generator=g).to(DEV).to(dtype)
+                ctx = torch.full((B, T, heads * d), 7.0, device=DEV, dtype=dtype)
+                ref = torch.full_like(ctx, 5.0)
+                lse, rl = torch.full((B * heads * T,), 7.0, device=DEV), torch.full((B * heads * T,), 5.0, device=DEV)
+                ops.attention_fwd_len(qkv, ctx, lse, _i32([T] * B), B, T, heads, d, d ** -0.5)
+                ops.attention_fwd(qkv, ref, rl, B, T, heads, d, d ** -0.5, 0.0, 0)
+                assert torch.equal(ctx, ref) and torch.equal(lse, rl), (geom, dtype, T)
+
+
 # ------------------------------------------------------------------------------------------------ engine
 def _golden_batch():
     """g2_base's two 3 s utterances and g13_long's 20 s one, in one batch padded to 20 s (weights seed 20211)."""

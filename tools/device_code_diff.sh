@@ -4,7 +4,8 @@
 # instruction streams are identical.  What a host-side refactor has to show (the kernels did not move) --
 #     bash tools/device_code_diff.sh gemm_ring.hip /path/to/parent/tree [/path/to/this/tree] [-v]
 # -v prints a unified diff of every differing kernel.  Kernels present in one tree only are listed as such; the
-# instantiations of a template that gained ONE parameter are compared with the old kernel of the remaining parameters.
+# instantiations of a template that gained ONE parameter (and, with it, trailing kernel arguments) are paired with the
+# old kernel of the remaining parameters: the nearest of them is compared with it, the others are listed as new.
 f=$1; old=$2; new=${3:-$(dirname "$(dirname "$(realpath "$0")")")}; verbose=0
 for a in "$@"; do [ "$a" = "-v" ] && verbose=1; done
 [ "$new" = "-v" ] && new=$(dirname "$(dirname "$(realpath "$0")")")
@@ -45,12 +46,19 @@ verbose = sys.argv[3] == '1'
 # a kernel template that GAINED one parameter: its instantiations are compared with the old kernel of the remaining ones
 # (listed under the new name)
 for n in [k for k in new if k not in old]:
-    for m in re.finditer(r'L[bi]\d+E', n):
-        o = n[:m.start()] + n[m.end():]
-        if o in old and o not in new:
-            old[n] = old[o]
+    for m in reversed(list(re.finditer(r'L[bi]\d+E', n))):      # a trailing parameter first
+        o = (n[:m.start()] + n[m.end():]).replace('IEv', '', 1)    # (its only parameter: the old kernel was no template)
+        # the new parameter may bring kernel arguments with it, appended to the old list: the old name is a prefix then
+        c = max((k for k in old if k not in new and o.startswith(k)), key=len, default=None)
+        if c is not None and o not in new:
+            old[n] = old[c]
             break
 for o in [k for k in old if k not in new and any(old[k] is old.get(n) for n in new)]:
+    # several instantiations of the new template: the old kernel is compared with the nearest, the others are new code
+    pairs = [n for n in new if old.get(n) is old[o]]
+    near = max(pairs, key=lambda n: difflib.SequenceMatcher(None, old[o], new[n], autojunk=False).ratio())
+    for n in pairs:
+        if n != near: del old[n]
     del old[o]
 same = [k for k in old if k in new and old[k] == new[k]]
 diff = [k for k in old if k in new and old[k] != new[k]]

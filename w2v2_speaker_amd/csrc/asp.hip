@@ -46,39 +46,16 @@ __device__ __forceinline__ float asp_block_max(float v, float (*red)[64]) {
 }
 
 // ------------------------------------------------------------------------------------------ global context
-template <typename T>
-__global__ void asp_context_kernel(const T* __restrict__ x, float* __restrict__ ctx, int Tn, int C) {
+// LEN: variable-length batch, the first lens[b] frames of utterance b (rows keep the padded stride).  The same time lanes
+// and the same fold order: bit-identical to the fixed-length form on the [1, lens[b], C] slice.
+template <typename T, bool LEN>
+__global__ void asp_context_kernel(const T* __restrict__ x, float* __restrict__ ctx, int Tn, int C,
+                                   LensArg<LEN> lens) {
   __shared__ float red[ASP_TL][64];
   const int b = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x;
   const bool ok = c < C;
   const T* xp = x + (int64_t)b * Tn * C + (ok ? c : 0);
-  float s = 0.f;
-  if (ok)
-    for (int t = threadIdx.y; t < Tn; t += ASP_TL) s += to_f32<T>(xp[(int64_t)t * C]);
-  const float mu = asp_block_sum(s, red) / (float)Tn;
-  float q = 0.f;
-  if (ok)
-    for (int t = threadIdx.y; t < Tn; t += ASP_TL) {
-      const float d = to_f32<T>(xp[(int64_t)t * C]) - mu;
-      q = fmaf(d, d, q);
-    }
-  q = asp_block_sum(q, red);
-  if (ok && threadIdx.y == 0) {
-    ctx[(int64_t)b * 2 * C + c] = mu;
-    ctx[(int64_t)b * 2 * C + C + c] = sqrtf(fmaxf(q / (float)Tn, ASP_EPS));
-  }
-}
-
-// Variable-length batch: asp_context_kernel over the first lens[b] frames of utterance b (rows keep the padded stride).
-// The same time lanes and the same fold order: bit-identical to asp_context_kernel on the [1, lens[b], C] slice.
-template <typename T>
-__global__ void asp_context_len_kernel(const T* __restrict__ x, float* __restrict__ ctx, const int* __restrict__ lens,
-                                       int Tn, int C) {
-  __shared__ float red[ASP_TL][64];
-  const int b = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x;
-  const bool ok = c < C;
-  const T* xp = x + (int64_t)b * Tn * C + (ok ? c : 0);
-  Tn = min(lens[b], Tn);                                  // frames that enter the statistics
+  if constexpr (LEN) Tn = min(lens[b], Tn);               // frames that enter the statistics
   float s = 0.f;
   if (ok)
     for (int t = threadIdx.y; t < Tn; t += ASP_TL) s += to_f32<T>(xp[(int64_t)t * C]);
@@ -240,54 +217,17 @@ __global__ void asp_bn_bwd_apply_kernel(const T* __restrict__ dh, const T* __res
 
 // ------------------------------------------------------------------------------------------ weighted statistics
 // per (b, c): w = softmax_t(s);  out = [sum w x, sqrt(clamp(sum w (x - mean)^2))];  stats = {max_t s, sum_t exp(s - max)}
-template <typename T>
+// LEN: variable-length batch, the first lens[b] frames of utterance b -- the scores of the frames past them enter neither
+// the maximum, nor the sum, nor the statistics (skipped, not weighted by zero).  Bit-identical to the fixed-length form on
+// the [1, lens[b], C] slices of x and s.
+template <typename T, bool LEN>
 __global__ void asp_pool_fwd_kernel(const T* __restrict__ x, const T* __restrict__ s, float* __restrict__ out,
-                                    float* __restrict__ stats, int Tn, int C) {
+                                    float* __restrict__ stats, int Tn, int C, LensArg<LEN> lens) {
   __shared__ float red[ASP_TL][64];
   const int b = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x;
   const bool ok = c < C;
   const int64_t base = (int64_t)b * Tn * C + (ok ? c : 0);
-  float mx = -INFINITY;
-  if (ok)
-    for (int t = threadIdx.y; t < Tn; t += ASP_TL) mx = fmaxf(mx, to_f32<T>(s[base + (int64_t)t * C]));
-  mx = asp_block_max(mx, red);
-  float z = 0.f, m1 = 0.f;
-  if (ok)
-    for (int t = threadIdx.y; t < Tn; t += ASP_TL) {
-      const float e = __expf(to_f32<T>(s[base + (int64_t)t * C]) - mx);
-      z += e;
-      m1 = fmaf(e, to_f32<T>(x[base + (int64_t)t * C]), m1);
-    }
-  z = asp_block_sum(z, red);
-  m1 = asp_block_sum(m1, red);
-  const float inv = 1.0f / z, mean = m1 * inv;
-  float v = 0.f;
-  if (ok)
-    for (int t = threadIdx.y; t < Tn; t += ASP_TL) {
-      const float e = __expf(to_f32<T>(s[base + (int64_t)t * C]) - mx);
-      const float d = to_f32<T>(x[base + (int64_t)t * C]) - mean;
-      v = fmaf(e * d, d, v);
-    }
-  v = asp_block_sum(v, red);
-  if (ok && threadIdx.y == 0) {
-    out[(int64_t)b * 2 * C + c] = mean;
-    out[(int64_t)b * 2 * C + C + c] = sqrtf(fmaxf(v * inv, ASP_EPS));
-    stats[((int64_t)b * C + c) * 2] = mx;
-    stats[((int64_t)b * C + c) * 2 + 1] = z;
-  }
-}
-
-// Variable-length batch: asp_pool_fwd_kernel over the first lens[b] frames of utterance b -- the scores of the frames past
-// them enter neither the maximum, nor the sum, nor the statistics (skipped, not weighted by zero).  Bit-identical to
-// asp_pool_fwd_kernel on the [1, lens[b], C] slices of x and s.
-template <typename T>
-__global__ void asp_pool_fwd_len_kernel(const T* __restrict__ x, const T* __restrict__ s, float* __restrict__ out,
-                                        float* __restrict__ stats, const int* __restrict__ lens, int Tn, int C) {
-  __shared__ float red[ASP_TL][64];
-  const int b = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x;
-  const bool ok = c < C;
-  const int64_t base = (int64_t)b * Tn * C + (ok ? c : 0);
-  Tn = min(lens[b], Tn);
+  if constexpr (LEN) Tn = min(lens[b], Tn);
   float mx = -INFINITY;
   if (ok)
     for (int t = threadIdx.y; t < Tn; t += ASP_TL) mx = fmaxf(mx, to_f32<T>(s[base + (int64_t)t * C]));
@@ -405,25 +345,26 @@ __global__ void asp_context_bwd_kernel(const T* __restrict__ x, const float* __r
 
 // ------------------------------------------------------------------------------------------ C ABI
 
-extern "C" int w2v2_asp_context(const void* x, float* ctx, int B, int T, int C, int dtype, void* stream) {
-  W2V2_REQUIRE(x && ctx && B > 0 && T > 0 && C > 0, "asp_context: bad arguments");
+// lens: device int32 [B] for the variable-length form, null for fixed length
+static int asp_context_launch(const char* name, const void* x, float* ctx, const int* lens, int B, int T, int C,
+                              int dtype, void* stream) {
   dim3 grid((unsigned)cdiv(C, 64), B), blk(64, ASP_TL);
   hipStream_t st = as_stream(stream);
-  W2V2_DISPATCH_ACT(dtype, "asp_context",
-    hipLaunchKernelGGL(asp_context_kernel<AT>, grid, blk, 0, st, (const AT*)x, ctx, T, C););
-  W2V2_CHECK_LAUNCH("asp_context");
+  W2V2_DISPATCH_LEN(lens, W2V2_DISPATCH_ACT(dtype, name,
+    hipLaunchKernelGGL((asp_context_kernel<AT, LEN>), grid, blk, 0, st, (const AT*)x, ctx, T, C, lens);));
+  W2V2_CHECK_LAUNCH(name);
   return 0;
+}
+
+extern "C" int w2v2_asp_context(const void* x, float* ctx, int B, int T, int C, int dtype, void* stream) {
+  W2V2_REQUIRE(x && ctx && B > 0 && T > 0 && C > 0, "asp_context: bad arguments");
+  return asp_context_launch("asp_context", x, ctx, nullptr, B, T, C, dtype, stream);
 }
 
 extern "C" int w2v2_asp_context_len(const void* x, float* ctx, const int* lens, int B, int T, int C, int dtype,
                                     void* stream) {
   W2V2_REQUIRE(x && ctx && lens && B > 0 && T > 0 && C > 0, "asp_context_len: bad arguments");
-  dim3 grid((unsigned)cdiv(C, 64), B), blk(64, ASP_TL);
-  hipStream_t st = as_stream(stream);
-  W2V2_DISPATCH_ACT(dtype, "asp_context_len",
-    hipLaunchKernelGGL(asp_context_len_kernel<AT>, grid, blk, 0, st, (const AT*)x, ctx, lens, T, C););
-  W2V2_CHECK_LAUNCH("asp_context_len");
-  return 0;
+  return asp_context_launch("asp_context_len", x, ctx, lens, B, T, C, dtype, stream);
 }
 
 extern "C" int w2v2_asp_context_bias(const float* ctx, const float* w1, const float* b1, float* cb, int B, int A,
@@ -495,28 +436,27 @@ extern "C" int w2v2_asp_bn_bwd(const void* dh, const void* a_pre, const float* m
   return 0;
 }
 
+static int asp_pool_fwd_launch(const char* name, const void* x, const void* s, float* out, float* stats,
+                               const int* lens, int B, int T, int C, int dtype, void* stream) {
+  dim3 grid((unsigned)cdiv(C, 64), B), blk(64, ASP_TL);
+  hipStream_t st = as_stream(stream);
+  W2V2_DISPATCH_LEN(lens, W2V2_DISPATCH_ACT(dtype, name,
+    hipLaunchKernelGGL((asp_pool_fwd_kernel<AT, LEN>), grid, blk, 0, st, (const AT*)x, (const AT*)s, out, stats, T, C,
+                       lens);));
+  W2V2_CHECK_LAUNCH(name);
+  return 0;
+}
+
 extern "C" int w2v2_asp_pool_fwd(const void* x, const void* s, float* out, float* stats, int B, int T, int C, int dtype,
                                  void* stream) {
   W2V2_REQUIRE(x && s && out && stats && B > 0 && T > 0 && C > 0, "asp_pool_fwd: bad arguments");
-  dim3 grid((unsigned)cdiv(C, 64), B), blk(64, ASP_TL);
-  hipStream_t st = as_stream(stream);
-  W2V2_DISPATCH_ACT(dtype, "asp_pool_fwd",
-    hipLaunchKernelGGL(asp_pool_fwd_kernel<AT>, grid, blk, 0, st, (const AT*)x, (const AT*)s,
-                            out, stats, T, C););
-  W2V2_CHECK_LAUNCH("asp_pool_fwd");
-  return 0;
+  return asp_pool_fwd_launch("asp_pool_fwd", x, s, out, stats, nullptr, B, T, C, dtype, stream);
 }
 
 extern "C" int w2v2_asp_pool_fwd_len(const void* x, const void* s, float* out, float* stats, const int* lens, int B,
                                      int T, int C, int dtype, void* stream) {
   W2V2_REQUIRE(x && s && out && stats && lens && B > 0 && T > 0 && C > 0, "asp_pool_fwd_len: bad arguments");
-  dim3 grid((unsigned)cdiv(C, 64), B), blk(64, ASP_TL);
-  hipStream_t st = as_stream(stream);
-  W2V2_DISPATCH_ACT(dtype, "asp_pool_fwd_len",
-    hipLaunchKernelGGL(asp_pool_fwd_len_kernel<AT>, grid, blk, 0, st, (const AT*)x, (const AT*)s,
-                            out, stats, lens, T, C););
-  W2V2_CHECK_LAUNCH("asp_pool_fwd_len");
-  return 0;
+  return asp_pool_fwd_launch("asp_pool_fwd_len", x, s, out, stats, lens, B, T, C, dtype, stream);
 }
 
 extern "C" int w2v2_asp_pool_bwd(const void* x, const void* s, const float* out, const float* stats, const float* dout,

@@ -278,10 +278,17 @@ __device__ __forceinline__ AttnBlock attn_block(int ntile_rows, int heads) {
   return o;
 }
 
-template <typename TE, int NW, int KT, typename IDX>
+// LEN: variable-length batch (eval, no dropout): the per-utterance bound Lv = lens[b] stands in place of Tn wherever it
+// masks or counts (ntile, nfj, FULL, the -inf key mask, active, the tile_load / reg_frag row bounds); buffers keep the row
+// stride of the padded Tn.  A valid query row therefore computes exactly what it computes in a launch on the utterance
+// alone at T = Lv.  Key / value rows >= Lv are zero-filled by the loads (the padding may hold anything and never enters
+// the arithmetic), query rows >= Lv of ctx are written as zeros, and a workgroup whose row tile starts at or past Lv
+// writes its zero rows and leaves before the first barrier (uniform per workgroup).
+template <typename TE, int NW, int KT, typename IDX, bool LEN>
 __global__ __launch_bounds__(64 * NW, 4) void attn_fwd_tiled_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
                                                              float* __restrict__ lse, int Tn, int heads_s, float scale,
-                                                             float dp, float inv_keep, uint64_t seed) {
+                                                             float dp, float inv_keep, uint64_t seed,
+                                                             LensArg<LEN> lens) {
   static_assert(KT * 8 == 2 * 64 * NW, "a tile is staged as two 16-byte chunks per thread");
   constexpr int NT = 64 * NW, RW = 16 * NW, AT_TILE = KT;
   __shared__ __attribute__((aligned(16))) bf16_t Ks[2][AT_TILE * 64];
@@ -295,13 +302,22 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_fwd_tiled_kernel(const bf16_t
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
   const int q = row_tile * RW + wave * 16 + (lane & 15);
   const int64_t bh = (int64_t)b * heads + h;
+  int Lv = Tn;                                        // rows / keys that exist
+  if constexpr (LEN) {
+    Lv = lens[b];
+    if (row_tile * RW >= Lv) {                        // the whole row tile is padding: zero rows, no barrier taken
+      const f32x4 z[4] = {};
+      store_row4x4<TE>(ctx + ((int64_t)b * Tn + q) * H + h * HD, g, q < Tn, z);
+      return;
+    }
+  }
   frag8_t qf[2];
-  reg_frag(qf, qb, gs, q, Tn, lane);
+  reg_frag(qf, qb, gs, q, Lv, lane);
   const TrOff troff = tr_offsets(lane);
-  const int ntile = (Tn + AT_TILE - 1) / AT_TILE;
+  const int ntile = (Lv + AT_TILE - 1) / AT_TILE;
   TileRegs rk, rv;
-  tile_load<NT>(rk, qb + H, gs, 0, Tn);
-  tile_load<NT>(rv, qb + 2 * H, gs, 0, Tn);
+  tile_load<NT>(rk, qb + H, gs, 0, Lv);
+  tile_load<NT>(rv, qb + 2 * H, gs, 0, Lv);
   tile_store<NT>(rk, Ks[0]);
   tile_store<NT>(rv, Vs[0]);
   __syncthreads();
@@ -313,17 +329,17 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_fwd_tiled_kernel(const bf16_t
   f32x4 o[4];
 #pragma unroll
   for (int df = 0; df < 4; ++df) o[df] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const bool active = row_tile * RW + wave * 16 < Tn;       // wave-uniform: any of this wave's 16 rows valid
+  const bool active = row_tile * RW + wave * 16 < Lv;       // wave-uniform: any of this wave's 16 rows valid
 #pragma unroll 1
   for (int t = 0; t < ntile; ++t) {
     const int cur = t & 1;
     if (t + 1 < ntile) {                              // next tile's loads fly under this tile's arithmetic
-      tile_load<NT>(rk, qb + H, gs, (t + 1) * AT_TILE, Tn);
-      tile_load<NT>(rv, qb + 2 * H, gs, (t + 1) * AT_TILE, Tn);
+      tile_load<NT>(rk, qb + H, gs, (t + 1) * AT_TILE, Lv);
+      tile_load<NT>(rv, qb + 2 * H, gs, (t + 1) * AT_TILE, Lv);
     }
     // 16-key blocks of this tile that hold a valid key (uniform): the blocks past the end of the sequence are skipped
     // outright -- at T = 149 that is two of the twelve blocks a query tile walks
-    const int nfj = min(AT_TILE / 16, (Tn - t * AT_TILE + 15) >> 4);
+    const int nfj = min(AT_TILE / 16, (Lv - t * AT_TILE + 15) >> 4);
     if (active) {
       // One body, two instantiations: FULL = a tile with four valid 16-key blocks and no key past T (every tile but the
       // last): straight-line code, no per-block branches, no masks
@@ -340,7 +356,7 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_fwd_tiled_kernel(const bf16_t
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               float v = acc[j] * scale2;
-              if constexpr (!FULL) v = (t * AT_TILE + fj * 16 + g * 4 + j < Tn) ? v : -INFINITY;
+              if constexpr (!FULL) v = (t * AT_TILE + fj * 16 + g * 4 + j < Lv) ? v : -INFINITY;
               s[fj][j] = v;
               tmax = fmaxf(tmax, v);
             }
@@ -379,8 +395,8 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_fwd_tiled_kernel(const bf16_t
           }
         }
       };
-      const bool full = (t + 1) * AT_TILE <= Tn;
-      if (dp > 0.f) {
+      const bool full = (t + 1) * AT_TILE <= Lv;
+      if (!LEN && dp > 0.f) {
         if (full) body(std::true_type{}, std::true_type{}); else body(std::false_type{}, std::true_type{});
       } else {
         if (full) body(std::true_type{}, std::false_type{}); else body(std::false_type{}, std::false_type{});
@@ -392,130 +408,15 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_fwd_tiled_kernel(const bf16_t
     }
     __syncthreads();
   }
-  const float inv = q < Tn ? 1.0f / l : 0.f;
+  if constexpr (LEN) {
+    const float inv = 1.0f / l;
 #pragma unroll
-  for (int df = 0; df < 4; ++df) o[df] *= inv;
-  store_row4x4<TE>(ctx + ((int64_t)b * Tn + q) * H + h * HD, g, q < Tn, o);
-  if (q < Tn && g == 0) lse[bh * Tn + q] = m * 0.6931471805599453f + __logf(l);
-}
-
-// Variable-length batch (eval, no dropout): attn_fwd_tiled_kernel with the per-utterance bound Lv = lens[b] in place of
-// Tn wherever it masks or counts (ntile, nfj, FULL, the -inf key mask, active, the tile_load / reg_frag row bounds);
-// buffers keep the row stride of the padded Tn.  A valid query row therefore computes exactly what it computes in a launch
-// on the utterance alone at T = Lv.  Key / value rows >= Lv are zero-filled by the loads (the padding may hold anything
-// and never enters the arithmetic), query rows >= Lv of ctx are written as zeros, and a workgroup whose row tile starts at
-// or past Lv writes its zero rows and leaves before the first barrier (uniform per workgroup).  A separate kernel, so the
-// training / fixed-length instantiations above keep their code.
-template <typename TE, int NW, int KT, typename IDX>
-__global__ __launch_bounds__(64 * NW, 4) void attn_fwd_len_tiled_kernel(const bf16_t* __restrict__ qkv,
-                                                                 bf16_t* __restrict__ ctx, float* __restrict__ lse,
-                                                                 const int* __restrict__ lens, int Tn, int heads_s,
-                                                                 float scale) {
-  static_assert(KT * 8 == 2 * 64 * NW, "a tile is staged as two 16-byte chunks per thread");
-  constexpr int NT = 64 * NW, RW = 16 * NW, AT_TILE = KT;
-  __shared__ __attribute__((aligned(16))) bf16_t Ks[2][AT_TILE * 64];
-  __shared__ __attribute__((aligned(16))) bf16_t Vs[2][AT_TILE * 64];
-  const AttnBlock blk = attn_block((Tn + RW - 1) / RW, heads_s);
-  const int heads = heads_s < 0 ? -heads_s : heads_s;
-  const int b = blk.b, h = blk.h, row_tile = blk.tile;
-  const int H = heads * HD;
-  const int64_t gs = 3 * (int64_t)H;
-  const bf16_t* qb = qkv + (int64_t)b * Tn * gs + h * HD;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
-  const int q = row_tile * RW + wave * 16 + (lane & 15);
-  const int64_t bh = (int64_t)b * heads + h;
-  const int Lv = lens[b];
-  if (row_tile * RW >= Lv) {                          // the whole row tile is padding: zero rows, no barrier taken
-    const f32x4 z[4] = {};
-    store_row4x4<TE>(ctx + ((int64_t)b * Tn + q) * H + h * HD, g, q < Tn, z);
-    return;
+    for (int df = 0; df < 4; ++df) o[df] = q < Lv ? o[df] * inv : f32x4{0.f, 0.f, 0.f, 0.f};   // padded rows: zeros
+  } else {
+    const float inv = q < Tn ? 1.0f / l : 0.f;
+#pragma unroll
+    for (int df = 0; df < 4; ++df) o[df] *= inv;
   }
-  frag8_t qf[2];
-  reg_frag(qf, qb, gs, q, Lv, lane);
-  const TrOff troff = tr_offsets(lane);
-  const int ntile = (Lv + AT_TILE - 1) / AT_TILE;
-  TileRegs rk, rv;
-  tile_load<NT>(rk, qb + H, gs, 0, Lv);
-  tile_load<NT>(rv, qb + 2 * H, gs, 0, Lv);
-  tile_store<NT>(rk, Ks[0]);
-  tile_store<NT>(rv, Vs[0]);
-  __syncthreads();
-  float m = -INFINITY, l = 0.f;                       // running maximum in the log2 domain
-  const float scale2 = scale * 1.4426950408889634f;
-  f32x4 o[4];
-#pragma unroll
-  for (int df = 0; df < 4; ++df) o[df] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const bool active = row_tile * RW + wave * 16 < Lv;       // wave-uniform: any of this wave's 16 rows valid
-#pragma unroll 1
-  for (int t = 0; t < ntile; ++t) {
-    const int cur = t & 1;
-    if (t + 1 < ntile) {                              // next tile's loads fly under this tile's arithmetic
-      tile_load<NT>(rk, qb + H, gs, (t + 1) * AT_TILE, Lv);
-      tile_load<NT>(rv, qb + 2 * H, gs, (t + 1) * AT_TILE, Lv);
-    }
-    const int nfj = min(AT_TILE / 16, (Lv - t * AT_TILE + 15) >> 4);
-    if (active) {
-      auto body = [&](auto full_c) {
-        constexpr bool FULL = decltype(full_c)::value;
-        float s[AT_TILE / 16][4];
-        float tmax = -INFINITY;
-        // scores in the LOG2 domain (scale * log2(e) folded into one multiply, v_exp_f32 is 2^x)
-#pragma unroll
-        for (int fj = 0; fj < AT_TILE / 16; ++fj) {
-          if (FULL || fj < nfj) {
-            f32x4 acc = mfma16<TE>(lds_frag(Ks[cur], fj * 16, 0, lane), qf[0], f32x4{0.f, 0.f, 0.f, 0.f});
-            acc = mfma16<TE>(lds_frag(Ks[cur], fj * 16, 1, lane), qf[1], acc);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float v = acc[j] * scale2;
-              if constexpr (!FULL) v = (t * AT_TILE + fj * 16 + g * 4 + j < Lv) ? v : -INFINITY;
-              s[fj][j] = v;
-              tmax = fmaxf(tmax, v);
-            }
-          }
-        }
-        tmax = quad_max(tmax);
-        const float mn = fmaxf(m, tmax);                  // finite: every tile holds at least one valid key
-        const float alpha = __builtin_amdgcn_exp2f(m - mn);   // first tile: 2^(-inf) = 0
-        m = mn;
-        float psum = 0.f;
-#pragma unroll
-        for (int fj = 0; fj < AT_TILE / 16; ++fj) {
-          if (FULL || fj < nfj) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const float p = __builtin_amdgcn_exp2f(s[fj][j] - mn);
-              psum += p;
-              s[fj][j] = p;
-            }
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s[fj][j] = 0.f;
-          }
-        }
-        l = l * alpha + quad_sum(psum);
-#pragma unroll
-        for (int df = 0; df < 4; ++df) o[df] *= alpha;
-#pragma unroll
-        for (int kb = 0; kb < AT_TILE / 32; ++kb) {
-          if (FULL || 2 * kb < nfj) {
-            const frag8_t pf = pack_frag<TE>(s[2 * kb], s[2 * kb + 1]);
-#pragma unroll
-            for (int df = 0; df < 4; ++df) o[df] = mfma16<TE>(lds_frag_tr(Vs[cur], troff, df, kb), pf, o[df]);
-          }
-        }
-      };
-      if ((t + 1) * AT_TILE <= Lv) body(std::true_type{}); else body(std::false_type{});
-    }   // active
-    if (t + 1 < ntile) {
-      tile_store<NT>(rk, Ks[cur ^ 1]);                    // last read in iteration t-1, behind that iteration's barrier
-      tile_store<NT>(rv, Vs[cur ^ 1]);
-    }
-    __syncthreads();
-  }
-  const float inv = 1.0f / l;
-#pragma unroll
-  for (int df = 0; df < 4; ++df) o[df] = q < Lv ? o[df] * inv : f32x4{0.f, 0.f, 0.f, 0.f};   // padded rows: zeros
   store_row4x4<TE>(ctx + ((int64_t)b * Tn + q) * H + h * HD, g, q < Tn, o);
   if (q < Lv && g == 0) lse[bh * Tn + q] = m * 0.6931471805599453f + __logf(l);
 }
@@ -798,26 +699,29 @@ static bool attn_idx32(int B, int T, int heads) {
   return (uint64_t)B * heads * T * (uint64_t)(((T + 1) & ~1) >> 1) < (1ull << 32);
 }
 
+// lens: device int32 [B] for the variable-length form (no dropout), null for fixed length
 template <typename TE, int NW, int KT, typename IDX>
-static int attention_fwd_g(const void* qkv, void* ctx, float* lse, int B, int T, int heads, float scale, float drop_p,
-                           uint64_t seed, void* stream) {
+static int attention_fwd_g(const char* name, const void* qkv, void* ctx, float* lse, const int* lens, int B, int T,
+                           int heads, float scale, float drop_p, uint64_t seed, void* stream) {
   const float ik = 1.0f / (1.0f - drop_p);
   hipStream_t st = as_stream(stream);
   dim3 grid((unsigned)(cdiv(T, 16 * NW) * heads * B));       // see attn_block
-  hipLaunchKernelGGL((attn_fwd_tiled_kernel<TE, NW, KT, IDX>), grid, dim3(64 * NW), 0, st, (const bf16_t*)qkv, (bf16_t*)ctx, lse, T,
-                     g_attn_no_remap ? -heads : heads, scale, drop_p, ik, seed);
-  W2V2_CHECK_LAUNCH("attention_fwd");
+  W2V2_DISPATCH_LEN(lens,
+    hipLaunchKernelGGL((attn_fwd_tiled_kernel<TE, NW, KT, IDX, LEN>), grid, dim3(64 * NW), 0, st, (const bf16_t*)qkv,
+                       (bf16_t*)ctx, lse, T, g_attn_no_remap ? -heads : heads, scale, drop_p, ik, seed, lens));
+  W2V2_CHECK_LAUNCH(name);
   return 0;
 }
+// the geometry is that of the padded T (W2V2_ATTN_GEOM forces it for both forms)
 template <typename TE>
-static int attention_fwd_t(const void* qkv, void* ctx, float* lse, int B, int T, int heads, float scale, float drop_p,
-                           uint64_t seed, void* stream) {
+static int attention_fwd_t(const char* name, const void* qkv, void* ctx, float* lse, const int* lens, int B, int T,
+                           int heads, float scale, float drop_p, uint64_t seed, void* stream) {
   const bool i32 = attn_idx32(B, T, heads);
   if (attn_small_geom(T))
-    return i32 ? attention_fwd_g<TE, 2, 32, uint32_t>(qkv, ctx, lse, B, T, heads, scale, drop_p, seed, stream)
-               : attention_fwd_g<TE, 2, 32, uint64_t>(qkv, ctx, lse, B, T, heads, scale, drop_p, seed, stream);
-  return i32 ? attention_fwd_g<TE, 4, 64, uint32_t>(qkv, ctx, lse, B, T, heads, scale, drop_p, seed, stream)
-             : attention_fwd_g<TE, 4, 64, uint64_t>(qkv, ctx, lse, B, T, heads, scale, drop_p, seed, stream);
+    return i32 ? attention_fwd_g<TE, 2, 32, uint32_t>(name, qkv, ctx, lse, lens, B, T, heads, scale, drop_p, seed, stream)
+               : attention_fwd_g<TE, 2, 32, uint64_t>(name, qkv, ctx, lse, lens, B, T, heads, scale, drop_p, seed, stream);
+  return i32 ? attention_fwd_g<TE, 4, 64, uint32_t>(name, qkv, ctx, lse, lens, B, T, heads, scale, drop_p, seed, stream)
+             : attention_fwd_g<TE, 4, 64, uint64_t>(name, qkv, ctx, lse, lens, B, T, heads, scale, drop_p, seed, stream);
 }
 
 extern "C" int w2v2_attention_fwd(const void* qkv, void* ctx, float* lse, int B, int T, int heads, int d, float scale,
@@ -825,29 +729,9 @@ extern "C" int w2v2_attention_fwd(const void* qkv, void* ctx, float* lse, int B,
   if (attn_check("attention_fwd", B, T, heads, d, dtype, drop_p)) return -1;
   W2V2_REQUIRE(qkv && ctx && lse, "attention_fwd: null pointer");
   W2V2_DISPATCH_16(dtype, "attention_fwd",
-                   return attention_fwd_t<AT>(qkv, ctx, lse, B, T, heads, scale, drop_p, seed, stream););
+                   return attention_fwd_t<AT>("attention_fwd", qkv, ctx, lse, nullptr, B, T, heads, scale, drop_p, seed,
+                                              stream););
   return 0;
-}
-
-template <typename TE, int NW, int KT, typename IDX>
-static int attention_fwd_len_g(const void* qkv, void* ctx, float* lse, const int* lens, int B, int T, int heads,
-                               float scale, void* stream) {
-  dim3 grid((unsigned)(cdiv(T, 16 * NW) * heads * B));       // see attn_block
-  hipLaunchKernelGGL((attn_fwd_len_tiled_kernel<TE, NW, KT, IDX>), grid, dim3(64 * NW), 0, as_stream(stream),
-                     (const bf16_t*)qkv, (bf16_t*)ctx, lse, lens, T, g_attn_no_remap ? -heads : heads, scale);
-  W2V2_CHECK_LAUNCH("attention_fwd_len");
-  return 0;
-}
-// the geometry is that of the padded T (W2V2_ATTN_GEOM forces it like for the plain entry)
-template <typename TE>
-static int attention_fwd_len_t(const void* qkv, void* ctx, float* lse, const int* lens, int B, int T, int heads,
-                               float scale, void* stream) {
-  const bool i32 = attn_idx32(B, T, heads);
-  if (attn_small_geom(T))
-    return i32 ? attention_fwd_len_g<TE, 2, 32, uint32_t>(qkv, ctx, lse, lens, B, T, heads, scale, stream)
-               : attention_fwd_len_g<TE, 2, 32, uint64_t>(qkv, ctx, lse, lens, B, T, heads, scale, stream);
-  return i32 ? attention_fwd_len_g<TE, 4, 64, uint32_t>(qkv, ctx, lse, lens, B, T, heads, scale, stream)
-             : attention_fwd_len_g<TE, 4, 64, uint64_t>(qkv, ctx, lse, lens, B, T, heads, scale, stream);
 }
 
 extern "C" int w2v2_attention_fwd_len(const void* qkv, void* ctx, float* lse, const int* lens, int B, int T, int heads,
@@ -855,7 +739,8 @@ extern "C" int w2v2_attention_fwd_len(const void* qkv, void* ctx, float* lse, co
   if (attn_check("attention_fwd_len", B, T, heads, d, dtype, 0.f)) return -1;
   W2V2_REQUIRE(qkv && ctx && lse && lens, "attention_fwd_len: null pointer");
   W2V2_DISPATCH_16(dtype, "attention_fwd_len",
-                   return attention_fwd_len_t<AT>(qkv, ctx, lse, lens, B, T, heads, scale, stream););
+                   return attention_fwd_t<AT>("attention_fwd_len", qkv, ctx, lse, lens, B, T, heads, scale, 0.f, 0,
+                                              stream););
   return 0;
 }
 

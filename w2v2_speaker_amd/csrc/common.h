@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <math.h>
+#include <type_traits>
 
 #include "../../include/w2v2_hip.h"
 
@@ -338,6 +339,19 @@ template <typename TC> __device__ __forceinline__ uint4 pack8(const float* v) {
     case W2V2_F16: { using AT = f16_t; __VA_ARGS__; } break;                    \
     default: W2V2_FAIL("%s: needs a 16-bit activation dtype (got %d)", NAME, (int)(DT)); \
   }
+
+// Variable-length forms are the LEN instantiation of the fixed-length kernel template (one body per operation).
+// LensArg<LEN> is the kernel's trailing `lens` argument: the device lengths (int32 [B]) when LEN, and NO argument in the
+// fixed-length instantiation -- a zero-size placeholder, so that instantiation keeps its kernel-argument layout (the
+// launch dimensions a kernel reads as blockDim / gridDim sit behind the arguments) and with it, instruction for
+// instruction, the code it had before it gained the parameter (tools/device_code_diff.sh shows it).  A launch site passes
+// `lens` to either: the placeholder is constructible from the pointer.
+struct NoLens { int none[0]; NoLens(const int*) {} };
+template <bool LEN> using LensArg = std::conditional_t<LEN, const int*, NoLens>;
+// LEN = (lens != null) for the statement(s)
+#define W2V2_DISPATCH_LEN(LENS, ...)                       \
+  if (LENS) { constexpr bool LEN = true; __VA_ARGS__; }    \
+  else { constexpr bool LEN = false; __VA_ARGS__; }
 
 // ---------------------------------------------------------------- math
 // erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, i.e. f32 round-off class): 1 rcp + 1 exp + 7 fma

@@ -18,16 +18,24 @@
 constexpr int C0_FRAMES = 128;   // frames per block
 constexpr int C0_MAXK = 16;
 
-template <typename T, bool APPLY>
+// LEN (statistics pass only): variable-length batch, utterance b has frames[b] valid frames.  Chunks past its end are
+// skipped and the chunk that straddles it counts its valid frames only; the chunking starts at frame 0 as for the
+// utterance alone.
+template <typename T, bool APPLY, bool LEN>
 __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ wav, const float* __restrict__ w,
                                                     float* __restrict__ partial, const float* __restrict__ mr,
                                                     const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, T* __restrict__ y, int N,
-                                                    int L, int C, int k, int stride, float eps) {
+                                                    int L, int C, int k, int stride, float eps,
+                                                    LensArg<LEN> frames) {
+  static_assert(!(APPLY && LEN), "the apply pass has no variable-length form");
   extern __shared__ float xs[];
   const int b = blockIdx.y;
   const int l0 = blockIdx.x * C0_FRAMES;
+  if constexpr (LEN) L = frames[b];
   const int nf = min(C0_FRAMES, L - l0);
+  if constexpr (LEN)
+    if (nf <= 0) return;                             // uniform: the whole chunk lies past the end of the utterance
   const int nsamp = (nf - 1) * stride + k;
   const float* src = wav + (int64_t)b * N + (int64_t)l0 * stride;
   for (int i = threadIdx.x; i < nsamp; i += 256) xs[i] = src[i];
@@ -69,65 +77,19 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ wa
 }
 
 // fold the per-chunk partials of one (b, c) in chunk order (f64) -> {mean, rstd}
+// LEN: the first cdiv(frames[b], C0_FRAMES) partials, divided by frames[b]: the same sums in the same order as on the
+// utterance alone
+template <bool LEN>
 __global__ void conv0_finalize_kernel(const float* __restrict__ partial, float* __restrict__ mr, int B, int C,
-                                      int nchunk, int L, float eps) {
+                                      int nchunk, int L, float eps, LensArg<LEN> frames) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * C) return;
   const int b = i / C, c = i - b * C;
-  double s1 = 0.0, s2 = 0.0;
-  for (int j = 0; j < nchunk; ++j) {
-    const float* pt = partial + (((int64_t)b * nchunk + j) * C + c) * 2;
-    s1 += (double)pt[0];
-    s2 += (double)pt[1];
+  int nc = nchunk;
+  if constexpr (LEN) {
+    L = frames[b];
+    nc = (L + C0_FRAMES - 1) / C0_FRAMES;
   }
-  const double mu = s1 / (double)L;
-  const double var = s2 / (double)L - mu * mu;
-  mr[(int64_t)i * 2] = (float)mu;
-  mr[(int64_t)i * 2 + 1] = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps));
-}
-
-// Variable-length batch: utterance b has frames[b] valid frames.  Chunks past its end are skipped, the chunk that
-// straddles it counts its valid frames only, and the finalize folds the first cdiv(frames[b], C0_FRAMES) partials in
-// chunk order and divides by frames[b]: the same sums in the same order as conv0_kernel<float, false> + finalize on the
-// utterance alone, because the chunking starts at frame 0 in both.
-__global__ __launch_bounds__(256) void conv0_stats_len_kernel(const float* __restrict__ wav, const float* __restrict__ w,
-                                                              float* __restrict__ partial, const int* __restrict__ frames,
-                                                              int N, int C, int k, int stride) {
-  extern __shared__ float xs[];
-  const int b = blockIdx.y;
-  const int l0 = blockIdx.x * C0_FRAMES;
-  const int nf = min(C0_FRAMES, frames[b] - l0);
-  if (nf <= 0) return;                               // uniform: the whole chunk lies past the end of the utterance
-  const int nsamp = (nf - 1) * stride + k;
-  const float* src = wav + (int64_t)b * N + (int64_t)l0 * stride;
-  for (int i = threadIdx.x; i < nsamp; i += 256) xs[i] = src[i];
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    float wr[C0_MAXK];
-#pragma unroll
-    for (int j = 0; j < C0_MAXK; ++j) wr[j] = j < k ? w[c * k + j] : 0.f;
-    float s1 = 0.f, s2 = 0.f;
-    for (int f = 0; f < nf; ++f) {
-      const float* xp = xs + f * stride;
-      float acc = 0.f;
-#pragma unroll
-      for (int j = 0; j < C0_MAXK; ++j)
-        if (j < k) acc = fmaf(wr[j], xp[j], acc);
-      s1 += acc;
-      s2 = fmaf(acc, acc, s2);
-    }
-    float* pt = partial + (((int64_t)b * gridDim.x + blockIdx.x) * C + c) * 2;
-    pt[0] = s1;
-    pt[1] = s2;
-  }
-}
-
-__global__ void conv0_finalize_len_kernel(const float* __restrict__ partial, float* __restrict__ mr,
-                                          const int* __restrict__ frames, int B, int C, int nchunk, float eps) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * C) return;
-  const int b = i / C, c = i - b * C;
-  const int L = frames[b], nc = (L + C0_FRAMES - 1) / C0_FRAMES;
   double s1 = 0.0, s2 = 0.0;
   for (int j = 0; j < nc; ++j) {
     const float* pt = partial + (((int64_t)b * nchunk + j) * C + c) * 2;
@@ -323,15 +285,22 @@ static bool conv0_mfma_ok(int C, int k) { return C % 128 == 0 && 3 * k <= 32 && 
 // pass drops from 100 us to a few.  Products of two f32 are exact in f64 and everything is accumulated in f64 in a fixed
 // order (per thread over its frames, the 64 lanes in lane order, blocks in order): deterministic, independent of the
 // batch, and more accurate than summing the split-bf16 convolution itself.
-template <int K>
+// LEN: variable-length batch, utterance b has frames[b] valid frames.  Blocks past its end are skipped, the block that
+// straddles it counts its valid frames, the finalize folds the first cdiv(frames[b], fpb) partials and divides by
+// frames[b] -- the same sums in the same order as on the utterance alone.
+template <int K, bool LEN>
 __global__ __launch_bounds__(64) void conv0_gram_kernel(const float* __restrict__ wav, double* __restrict__ partial,
-                                                        int N, int L, int stride, int fpb) {
+                                                        int N, int L, int stride, int fpb,
+                                                        LensArg<LEN> frames) {
   constexpr int NR = K * (K + 1) / 2, NV = K + NR;
   extern __shared__ float xs[];                      // the block's samples: (fpb - 1) * stride + K floats
   __shared__ double red[NV][65];                     // (pitch 65: the fold below reads a row per lane)
   const int b = blockIdx.y;
   const int f0 = blockIdx.x * fpb;                   // frames [f0, f0 + nf) of utterance b; one wave per block
+  if constexpr (LEN) L = frames[b];
   const int nf = min(fpb, L - f0);
+  if constexpr (LEN)
+    if (nf <= 0) return;                             // uniform: a block past the end writes nothing (never read)
   const float* src = wav + (int64_t)b * N + (int64_t)f0 * stride;
   const int nsamp = nf > 0 ? (nf - 1) * stride + K : 0;
   for (int i = threadIdx.x; i < nsamp; i += 64) xs[i] = src[i];
@@ -362,91 +331,19 @@ __global__ __launch_bounds__(64) void conv0_gram_kernel(const float* __restrict_
   }
 }
 
-template <int K>
+template <int K, bool LEN>
 __global__ __launch_bounds__(256) void conv0_gram_finalize_kernel(const double* __restrict__ partial,
                                                                   const float* __restrict__ w, float* __restrict__ mr,
-                                                                  int C, int nblk, int L, float eps) {
+                                                                  int C, int nblk, int L, float eps,
+                                                                  LensArg<LEN> frames, int fpb) {
   constexpr int NR = K * (K + 1) / 2, NV = K + NR;
   __shared__ double G[NV];
   const int b = blockIdx.x;
-  if (threadIdx.x < NV) {
-    double v = 0.0;
-    for (int j = 0; j < nblk; ++j) v += partial[((int64_t)b * nblk + j) * NV + threadIdx.x];
-    G[threadIdx.x] = v;
+  int nb = nblk;
+  if constexpr (LEN) {
+    L = frames[b];
+    nb = (L + fpb - 1) / fpb;                         // the first nb partials of the utterance, in block order
   }
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    double wr[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) wr[j] = (double)w[c * K + j];
-    double s1 = 0.0, s2 = 0.0;
-    int idx = K;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      s1 += wr[j] * G[j];
-#pragma unroll
-      for (int j2 = j; j2 < K; ++j2) s2 += (j2 == j ? 1.0 : 2.0) * wr[j] * wr[j2] * G[idx++];
-    }
-    const double mu = s1 / (double)L;
-    const double var = s2 / (double)L - mu * mu;
-    mr[((int64_t)b * C + c) * 2] = (float)mu;
-    mr[((int64_t)b * C + c) * 2 + 1] = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps));
-  }
-}
-// Variable-length forms of the two window-moment kernels: blocks past the end of utterance b are skipped, the block that
-// straddles it counts its valid frames, the finalize folds the first cdiv(frames[b], fpb) partials and divides by
-// frames[b] -- the same sums in the same order as the two kernels above on the utterance alone.
-template <int K>
-__global__ __launch_bounds__(64) void conv0_gram_len_kernel(const float* __restrict__ wav, double* __restrict__ partial,
-                                                            const int* __restrict__ frames, int N, int stride,
-                                                            int fpb) {
-  constexpr int NR = K * (K + 1) / 2, NV = K + NR;
-  extern __shared__ float xs[];                      // the block's samples: (fpb - 1) * stride + K floats
-  __shared__ double red[NV][65];                     // (pitch 65: the fold below reads a row per lane)
-  const int b = blockIdx.y;
-  const int f0 = blockIdx.x * fpb;                   // frames [f0, f0 + nf) of utterance b; one wave per block
-  const int nf = min(fpb, frames[b] - f0);
-  if (nf <= 0) return;                               // uniform: a block past the end writes nothing (never read)
-  const float* src = wav + (int64_t)b * N + (int64_t)f0 * stride;
-  const int nsamp = (nf - 1) * stride + K;
-  for (int i = threadIdx.x; i < nsamp; i += 64) xs[i] = src[i];
-  __syncthreads();
-  double acc[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) acc[i] = 0.0;
-  for (int f = threadIdx.x; f < nf; f += 64) {       // lanes `stride` floats apart: conflict-free LDS reads for odd strides
-    float x[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) x[j] = xs[f * stride + j];
-    int idx = K;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      acc[j] += (double)x[j];
-#pragma unroll
-      for (int j2 = j; j2 < K; ++j2) acc[idx++] += (double)x[j] * (double)x[j2];
-    }
-  }
-  // fold over the 64 lanes in lane order through LDS (a shuffle tree costs 2 x 6 ds_bpermute per value: 780 per wave)
-#pragma unroll
-  for (int i = 0; i < NV; ++i) red[i][threadIdx.x] = acc[i];
-  __syncthreads();
-  for (int i = threadIdx.x; i < NV; i += 64) {
-    double v = 0.0;
-    for (int j = 0; j < 64; ++j) v += red[i][j];
-    partial[((int64_t)b * gridDim.x + blockIdx.x) * NV + i] = v;
-  }
-}
-
-template <int K>
-__global__ __launch_bounds__(256) void conv0_gram_finalize_len_kernel(const double* __restrict__ partial,
-                                                                      const float* __restrict__ w,
-                                                                      float* __restrict__ mr,
-                                                                      const int* __restrict__ frames, int C, int nblk,
-                                                                      int fpb, float eps) {
-  constexpr int NR = K * (K + 1) / 2, NV = K + NR;
-  __shared__ double G[NV];
-  const int b = blockIdx.x;
-  const int L = frames[b], nb = (L + fpb - 1) / fpb;  // the first nb partials of the utterance, in block order
   if (threadIdx.x < NV) {
     double v = 0.0;
     for (int j = 0; j < nb; ++j) v += partial[((int64_t)b * nblk + j) * NV + threadIdx.x];
@@ -480,21 +377,48 @@ static int conv0_check(const char* nm, int B, int N, int C, int k, int stride) {
   return 0;
 }
 
-extern "C" int w2v2_conv0_stats(const float* wav, const float* w, float* partial, float* mean_rstd, int B, int N,
-                                int C, int k, int stride, float eps, void* stream) {
-  if (conv0_check("conv0_stats", B, N, C, k, stride)) return -1;
-  W2V2_REQUIRE(wav && w && partial && mean_rstd, "conv0_stats: null pointer");
+// The two statistics routes; frames: device int32 [B] for the variable-length form, null for fixed length.
+static int conv0_stats_launch(const char* name, const float* wav, const float* w, float* partial, float* mean_rstd,
+                              const int* frames, int B, int N, int C, int k, int stride, float eps, void* stream) {
   const int L = (N - k) / stride + 1;
   const int nchunk = (int)cdiv(L, C0_FRAMES);
   dim3 grid((unsigned)nchunk, B);
   const size_t lds = ((size_t)(C0_FRAMES - 1) * stride + k) * sizeof(float);
-  hipLaunchKernelGGL((conv0_kernel<float, false>), grid, dim3(256), lds, as_stream(stream), wav, w, partial,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, N, L, C, k,
-                     stride, 0.f);
-  hipLaunchKernelGGL(conv0_finalize_kernel, dim3((unsigned)cdiv((int64_t)B * C, 256)), dim3(256), 0,
-                     as_stream(stream), partial, mean_rstd, B, C, nchunk, L, eps);
-  W2V2_CHECK_LAUNCH("conv0_stats");
+  W2V2_DISPATCH_LEN(frames,
+    hipLaunchKernelGGL((conv0_kernel<float, false, LEN>), grid, dim3(256), lds, as_stream(stream), wav, w, partial,
+                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, N, L, C, k,
+                       stride, 0.f, frames);
+    hipLaunchKernelGGL(conv0_finalize_kernel<LEN>, dim3((unsigned)cdiv((int64_t)B * C, 256)), dim3(256), 0,
+                       as_stream(stream), partial, mean_rstd, B, C, nchunk, L, eps, frames));
+  W2V2_CHECK_LAUNCH(name);
   return 0;
+}
+
+// statistics from the window moments of the waveform (see conv0_gram_kernel); the workspace (>= 8 floats per frame)
+// holds the f64 partials: 130 floats per block of C0_GRAM_FRAMES frames
+static int conv0_gram_stats_launch(const char* name, const float* wav, const float* w, float* partial, float* mean_rstd,
+                                   const int* frames, int B, int N, int C, int stride, float eps, void* stream) {
+  const int L = (N - 10) / stride + 1;
+  const int nblk = (int)cdiv(L, C0_GRAM_FRAMES);
+  double* gp = reinterpret_cast<double*>(partial);
+  const size_t lds = ((size_t)(C0_GRAM_FRAMES - 1) * stride + 10) * sizeof(float);
+  W2V2_REQUIRE(lds <= 64 * 1024, "%s: stride %d too large for the window-moment kernel", name, stride);
+  W2V2_REQUIRE((int64_t)nblk * 130 <= (int64_t)w2v2_conv0_workspace_floats(N, C, 10, stride),
+               "%s: workspace too small for %d window-moment blocks", name, nblk);
+  W2V2_DISPATCH_LEN(frames,
+    hipLaunchKernelGGL((conv0_gram_kernel<10, LEN>), dim3((unsigned)nblk, B), dim3(64), lds, as_stream(stream), wav, gp,
+                       N, L, stride, C0_GRAM_FRAMES, frames);
+    hipLaunchKernelGGL((conv0_gram_finalize_kernel<10, LEN>), dim3(B), dim3(256), 0, as_stream(stream),
+                       (const double*)gp, w, mean_rstd, C, nblk, L, eps, frames, C0_GRAM_FRAMES));
+  W2V2_CHECK_LAUNCH(name);
+  return 0;
+}
+
+extern "C" int w2v2_conv0_stats(const float* wav, const float* w, float* partial, float* mean_rstd, int B, int N,
+                                int C, int k, int stride, float eps, void* stream) {
+  if (conv0_check("conv0_stats", B, N, C, k, stride)) return -1;
+  W2V2_REQUIRE(wav && w && partial && mean_rstd, "conv0_stats: null pointer");
+  return conv0_stats_launch("conv0_stats", wav, w, partial, mean_rstd, nullptr, B, N, C, k, stride, eps, stream);
 }
 
 // Same contract as w2v2_conv0_stats, statistics of the split-bf16 matrix-core convolution (what
@@ -506,30 +430,16 @@ extern "C" int w2v2_conv0_stats_mfma(const float* wav, const float* w, float* pa
   W2V2_REQUIRE(wav && w && partial && mean_rstd, "conv0_stats_mfma: null pointer");
   const int L = (N - k) / stride + 1;
   static const bool no_gram = getenv("W2V2_CONV0_NO_GRAM") != nullptr;        // A/B switch
-  if (k == 10 && !no_gram) {
-    // statistics from the window moments of the waveform (see conv0_gram_kernel); the workspace (>= 8 floats per frame)
-    // holds the f64 partials: 130 floats per block of C0_GRAM_FRAMES frames
-    const int nblk = (int)cdiv(L, C0_GRAM_FRAMES);
-    double* gp = reinterpret_cast<double*>(partial);
-    const size_t lds = ((size_t)(C0_GRAM_FRAMES - 1) * stride + 10) * sizeof(float);
-    W2V2_REQUIRE(lds <= 64 * 1024, "conv0_stats_mfma: stride %d too large for the window-moment kernel", stride);
-    W2V2_REQUIRE((int64_t)nblk * 130 <= (int64_t)w2v2_conv0_workspace_floats(N, C, k, stride),
-                 "conv0_stats_mfma: workspace too small for %d window-moment blocks", nblk);
-    hipLaunchKernelGGL((conv0_gram_kernel<10>), dim3((unsigned)nblk, B), dim3(64), lds, as_stream(stream), wav, gp, N, L,
-                       stride, C0_GRAM_FRAMES);
-    hipLaunchKernelGGL((conv0_gram_finalize_kernel<10>), dim3(B), dim3(256), 0, as_stream(stream), (const double*)gp, w,
-                       mean_rstd, C, nblk, L, eps);
-    W2V2_CHECK_LAUNCH("conv0_stats_mfma");
-    return 0;
-  }
+  if (k == 10 && !no_gram)
+    return conv0_gram_stats_launch("conv0_stats_mfma", wav, w, partial, mean_rstd, nullptr, B, N, C, stride, eps, stream);
   const int nchunk = (int)cdiv(cdiv(L, C0_FRAMES), C0_CPB);      // one partial per workgroup (C0_CPB chunks)
   dim3 grid((unsigned)nchunk, B);
   const size_t lds2 = (2 * ((size_t)(C0_FRAMES - 1) * stride + k) + 8) * sizeof(bf16_t);
   hipLaunchKernelGGL((conv0_mfma_kernel<false, bf16_t>), grid, dim3(256), lds2, as_stream(stream), wav, w, partial,
                      (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (bf16_t*)nullptr, N, L, C, k,
                      stride);
-  hipLaunchKernelGGL(conv0_finalize_kernel, dim3((unsigned)cdiv((int64_t)B * C, 256)), dim3(256), 0,
-                     as_stream(stream), partial, mean_rstd, B, C, nchunk, L, eps);
+  hipLaunchKernelGGL(conv0_finalize_kernel<false>, dim3((unsigned)cdiv((int64_t)B * C, 256)), dim3(256), 0,
+                     as_stream(stream), partial, mean_rstd, B, C, nchunk, L, eps, (const int*)nullptr);
   W2V2_CHECK_LAUNCH("conv0_stats_mfma");
   return 0;
 }
@@ -541,15 +451,7 @@ extern "C" int w2v2_conv0_stats_len(const float* wav, const float* w, float* par
                                     const int* frames, int B, int N, int C, int k, int stride, float eps, void* stream) {
   if (conv0_check("conv0_stats_len", B, N, C, k, stride)) return -1;
   W2V2_REQUIRE(wav && w && partial && mean_rstd && frames, "conv0_stats_len: null pointer");
-  const int L = (N - k) / stride + 1;
-  const int nchunk = (int)cdiv(L, C0_FRAMES);
-  const size_t lds = ((size_t)(C0_FRAMES - 1) * stride + k) * sizeof(float);
-  hipLaunchKernelGGL(conv0_stats_len_kernel, dim3((unsigned)nchunk, B), dim3(256), lds, as_stream(stream), wav, w,
-                     partial, frames, N, C, k, stride);
-  hipLaunchKernelGGL(conv0_finalize_len_kernel, dim3((unsigned)cdiv((int64_t)B * C, 256)), dim3(256), 0,
-                     as_stream(stream), partial, mean_rstd, frames, B, C, nchunk, eps);
-  W2V2_CHECK_LAUNCH("conv0_stats_len");
-  return 0;
+  return conv0_stats_launch("conv0_stats_len", wav, w, partial, mean_rstd, frames, B, N, C, k, stride, eps, stream);
 }
 
 extern "C" int w2v2_conv0_stats_mfma_len(const float* wav, const float* w, float* partial, float* mean_rstd,
@@ -562,19 +464,8 @@ extern "C" int w2v2_conv0_stats_mfma_len(const float* wav, const float* w, float
   static const bool no_gram = getenv("W2V2_CONV0_NO_GRAM") != nullptr;
   W2V2_REQUIRE(k == 10 && !no_gram,
                "conv0_stats_mfma_len: variable lengths need the window-moment statistics (k = 10, W2V2_CONV0_NO_GRAM unset)");
-  const int L = (N - k) / stride + 1;
-  const int nblk = (int)cdiv(L, C0_GRAM_FRAMES);
-  double* gp = reinterpret_cast<double*>(partial);
-  const size_t lds = ((size_t)(C0_GRAM_FRAMES - 1) * stride + 10) * sizeof(float);
-  W2V2_REQUIRE(lds <= 64 * 1024, "conv0_stats_mfma_len: stride %d too large for the window-moment kernel", stride);
-  W2V2_REQUIRE((int64_t)nblk * 130 <= (int64_t)w2v2_conv0_workspace_floats(N, C, k, stride),
-               "conv0_stats_mfma_len: workspace too small for %d window-moment blocks", nblk);
-  hipLaunchKernelGGL((conv0_gram_len_kernel<10>), dim3((unsigned)nblk, B), dim3(64), lds, as_stream(stream), wav, gp,
-                     frames, N, stride, C0_GRAM_FRAMES);
-  hipLaunchKernelGGL((conv0_gram_finalize_len_kernel<10>), dim3(B), dim3(256), 0, as_stream(stream), (const double*)gp,
-                     w, mean_rstd, frames, C, nblk, C0_GRAM_FRAMES, eps);
-  W2V2_CHECK_LAUNCH("conv0_stats_mfma_len");
-  return 0;
+  return conv0_gram_stats_launch("conv0_stats_mfma_len", wav, w, partial, mean_rstd, frames, B, N, C, stride, eps,
+                                 stream);
 }
 
 extern "C" int w2v2_conv0_workspace_floats(int N, int C, int k, int stride) {
@@ -601,8 +492,9 @@ extern "C" int w2v2_conv0_apply(const float* wav, const float* w, const float* m
       hipLaunchKernelGGL((conv0_mfma_kernel<true, AT>), grid2, dim3(256), lds2, as_stream(stream), wav, w,
                          (float*)nullptr, mean_rstd, gamma, beta, (AT*)y, N, L, C, k, stride););
   } else W2V2_DISPATCH_ACT(dtype, "conv0_apply",
-    hipLaunchKernelGGL((conv0_kernel<AT, true>), grid, dim3(256), lds, as_stream(stream), wav, w,
-                       (float*)nullptr, mean_rstd, gamma, beta, (AT*)y, N, L, C, k, stride, 0.f););
+    hipLaunchKernelGGL((conv0_kernel<AT, true, false>), grid, dim3(256), lds, as_stream(stream), wav, w,
+                       (float*)nullptr, mean_rstd, gamma, beta, (AT*)y, N, L, C, k, stride, 0.f,
+                       (const int*)nullptr););
   W2V2_CHECK_LAUNCH("conv0_apply");
   return 0;
 }

@@ -5,9 +5,10 @@
 // Two passes over the (L2-resident) slab: mean, then centred sum of squares -> torch.std_mean parity.
 #include "common.h"
 
-template <typename T>
+// LEN: variable-length batch, the same kernel over the first lens[b] frames of utterance b
+template <typename T, bool LEN>
 __global__ __launch_bounds__(256) void pool_meanstd_kernel(const T* __restrict__ x, float* __restrict__ out, int Tn,
-                                                           int H, int with_std) {
+                                                           int H, int with_std, LensArg<LEN> lens) {
   __shared__ float red[4][16][8];
   __shared__ float meanv[16][8];
   const int b = blockIdx.y;
@@ -16,80 +17,7 @@ __global__ __launch_bounds__(256) void pool_meanstd_kernel(const T* __restrict__
   const int col = (blockIdx.x * 16 + cl) * 8;
   const bool active = col < H;
   const T* xb = x + (int64_t)b * Tn * H + col;
-  float acc[8] = {};
-  if (active)
-    for (int t = tl; t < Tn; t += 16) {
-      Vec8<T> v;
-      v.load(xb + (int64_t)t * H);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] += v.v[e];
-    }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    acc[e] += __shfl_xor(acc[e], 16, 64);
-    acc[e] += __shfl_xor(acc[e], 32, 64);
-  }
-  if (lane < 16)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[wave][cl][e] = acc[e];
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    const int c = threadIdx.x >> 3, e = threadIdx.x & 7;
-    meanv[c][e] = (red[0][c][e] + red[1][c][e] + red[2][c][e] + red[3][c][e]) / (float)Tn;
-  }
-  __syncthreads();
-  float mu[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) mu[e] = meanv[cl][e];
-  const int mean_off = with_std ? H : 0;
-  const int ostride = with_std ? 2 * H : H;
-  if (active && wave == 0 && lane < 16)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) out[(int64_t)b * ostride + mean_off + col + e] = mu[e];
-  if (!with_std) return;
-  float sq[8] = {};
-  if (active)
-    for (int t = tl; t < Tn; t += 16) {
-      Vec8<T> v;
-      v.load(xb + (int64_t)t * H);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const float d = v.v[e] - mu[e]; sq[e] = fmaf(d, d, sq[e]); }
-    }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    sq[e] += __shfl_xor(sq[e], 16, 64);
-    sq[e] += __shfl_xor(sq[e], 32, 64);
-  }
-  __syncthreads();
-  if (lane < 16)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[wave][cl][e] = sq[e];
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    const int c = threadIdx.x >> 3, e = threadIdx.x & 7;
-    const int cc = (blockIdx.x * 16 + c) * 8 + e;
-    if (cc < H) {
-      const float m2 = red[0][c][e] + red[1][c][e] + red[2][c][e] + red[3][c][e];
-      out[(int64_t)b * ostride + cc] = sqrtf(m2 / (float)(Tn - 1));  // unbiased; T == 1 -> NaN like torch
-    }
-  }
-}
-
-// Variable-length batch: pool_meanstd_kernel over the first lens[b] frames of utterance b
-template <typename T>
-__global__ __launch_bounds__(256) void pool_meanstd_len_kernel(const T* __restrict__ x, float* __restrict__ out,
-                                                               const int* __restrict__ lens, int Tn, int H,
-                                                               int with_std) {
-  __shared__ float red[4][16][8];
-  __shared__ float meanv[16][8];
-  const int b = blockIdx.y;
-  const T* xb = x + (int64_t)b * Tn * H;
-  Tn = lens[b];                                           // frames pooled; rows keep the padded stride
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int cl = lane & 15, tl = (lane >> 4) + 4 * wave;  // column lane, time lane (0..15)
-  const int col = (blockIdx.x * 16 + cl) * 8;
-  const bool active = col < H;
-  xb += col;
+  if constexpr (LEN) Tn = lens[b];                        // frames pooled; rows keep the padded stride
   float acc[8] = {};
   if (active)
     for (int t = tl; t < Tn; t += 16) {
@@ -182,14 +110,21 @@ __global__ void pool_meanstd_bwd_kernel(const T* __restrict__ x, const float* __
 }
 
 // max / first / last: one thread per (b, c); coalesced over c.
-template <typename T>
-__global__ void pool_select_kernel(const T* __restrict__ x, float* __restrict__ out, int B, int Tn, int H, int mode) {
+// LEN: over the first lens[b] frames (middle = last, ref: pooling.py), in the same order; no frame-index mode.
+template <typename T, bool LEN>
+__global__ void pool_select_kernel(const T* __restrict__ x, float* __restrict__ out, int B, int Tn, int H, int mode,
+                                   LensArg<LEN> lens) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= (int64_t)B * H) return;
   const int b = (int)(i / H), c = (int)(i - (int64_t)b * H);
   const T* xb = x + (int64_t)b * Tn * H + c;
   float r;
-  if (mode == 2) {
+  if constexpr (LEN) {
+    const int Lb = lens[b];
+    r = to_f32<T>(xb[mode == 4 ? (int64_t)(Lb - 1) * H : 0]);
+    if (mode == 2)
+      for (int t = 1; t < Lb; ++t) r = fmaxf(r, to_f32<T>(xb[(int64_t)t * H]));
+  } else if (mode == 2) {
     r = to_f32<T>(xb[0]);
     for (int t = 1; t < Tn; ++t) r = fmaxf(r, to_f32<T>(xb[(int64_t)t * H]));
   } else if (mode == 3) {
@@ -199,21 +134,6 @@ __global__ void pool_select_kernel(const T* __restrict__ x, float* __restrict__ 
   } else {
     r = to_f32<T>(xb[(int64_t)(Tn - 1) * H]);
   }
-  out[i] = r;
-}
-
-// max / first / last over the first lens[b] frames (middle = last, ref: pooling.py), same order as pool_select_kernel
-template <typename T>
-__global__ void pool_select_len_kernel(const T* __restrict__ x, float* __restrict__ out, const int* __restrict__ lens,
-                                       int B, int Tn, int H, int mode) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= (int64_t)B * H) return;
-  const int b = (int)(i / H), c = (int)(i - (int64_t)b * H);
-  const int Lb = lens[b];
-  const T* xb = x + (int64_t)b * Tn * H + c;
-  float r = to_f32<T>(xb[mode == 4 ? (int64_t)(Lb - 1) * H : 0]);
-  if (mode == 2)
-    for (int t = 1; t < Lb; ++t) r = fmaxf(r, to_f32<T>(xb[(int64_t)t * H]));
   out[i] = r;
 }
 
@@ -307,12 +227,15 @@ __device__ __forceinline__ float lerp_torch(float a, float b, float w) {
   return w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.0f - w);       // at::lerp
 }
 
-template <typename T>
-__global__ void pool_quantile_kernel(const T* __restrict__ x, float* __restrict__ out, int B, int Tn, int H) {
+// LEN: the order statistics of the first lens[b] frames
+template <typename T, bool LEN>
+__global__ void pool_quantile_kernel(const T* __restrict__ x, float* __restrict__ out, int B, int Tn, int H,
+                                     LensArg<LEN> lens) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= (int64_t)B * H) return;
   const int b = (int)(i / H), c = (int)(i - (int64_t)b * H);
   const T* xb = x + (int64_t)b * Tn * H + c;
+  if constexpr (LEN) Tn = lens[b];
   const QRanks r = quantile_ranks(Tn);
   uint32_t key[QN];
   select_keys<T>(xb, Tn, H, r.k, key);
@@ -323,26 +246,6 @@ __global__ void pool_quantile_kernel(const T* __restrict__ x, float* __restrict_
     ob[(int64_t)(q + 1) * H] = lerp_torch(key_value(key[1 + 2 * q]), key_value(key[2 + 2 * q]), r.w[q]);
   ob[(int64_t)4 * H] = key_value(key[7]);
 }
-
-template <typename T>
-__global__ void pool_quantile_len_kernel(const T* __restrict__ x, float* __restrict__ out, const int* __restrict__ lens,
-                                         int B, int Tn, int H) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= (int64_t)B * H) return;
-  const int b = (int)(i / H), c = (int)(i - (int64_t)b * H);
-  const int Lb = lens[b];
-  const T* xb = x + (int64_t)b * Tn * H + c;
-  const QRanks r = quantile_ranks(Lb);
-  uint32_t key[QN];
-  select_keys<T>(xb, Lb, H, r.k, key);
-  float* ob = out + (int64_t)b * 5 * H + c;
-  ob[0] = key_value(key[0]);
-#pragma unroll
-  for (int q = 0; q < 3; ++q)
-    ob[(int64_t)(q + 1) * H] = lerp_torch(key_value(key[1 + 2 * q]), key_value(key[2 + 2 * q]), r.w[q]);
-  ob[(int64_t)4 * H] = key_value(key[7]);
-}
-
 template <typename T>
 __global__ void pool_quantile_bwd_kernel(const T* __restrict__ x, const float* __restrict__ dout, T* __restrict__ dx,
                                          int B, int Tn, int H) {
@@ -394,26 +297,34 @@ __global__ void pool_quantile_bwd_kernel(const T* __restrict__ x, const float* _
   }
 }
 
-extern "C" int w2v2_pool_fwd(const void* x, float* out, int B, int T, int H, int mode, int dtype, void* stream) {
-  W2V2_REQUIRE(x && out && B > 0 && T > 0 && H > 0 && mode >= 0 && (mode <= 5 || (mode >= 16 && mode - 16 < T)),
-               "pool_fwd: bad arguments (mode %d, T %d)", mode, T);
+// lens: device int32 [B] for the variable-length form, null for fixed length
+static int pool_fwd_launch(const char* name, const void* x, float* out, const int* lens, int B, int T, int H, int mode,
+                           int dtype, void* stream) {
   hipStream_t st = as_stream(stream);
   if (mode == 5) {
     dim3 grid((unsigned)cdiv((int64_t)B * H, 64));
-    W2V2_DISPATCH_ACT(dtype, "pool_fwd",
-      hipLaunchKernelGGL(pool_quantile_kernel<AT>, grid, dim3(64), 0, st, (const AT*)x, out, B, T, H););
+    W2V2_DISPATCH_LEN(lens, W2V2_DISPATCH_ACT(dtype, name,
+      hipLaunchKernelGGL((pool_quantile_kernel<AT, LEN>), grid, dim3(64), 0, st, (const AT*)x, out, B, T, H, lens);));
   } else if (mode <= 1) {
-    W2V2_REQUIRE(H % 8 == 0, "pool_fwd: H must be a multiple of 8");
+    W2V2_REQUIRE(H % 8 == 0, "%s: H must be a multiple of 8", name);
     dim3 grid((unsigned)cdiv(H, 128), B);
-    W2V2_DISPATCH_ACT(dtype, "pool_fwd",
-      hipLaunchKernelGGL(pool_meanstd_kernel<AT>, grid, dim3(256), 0, st, (const AT*)x, out, T, H, mode == 0););
+    W2V2_DISPATCH_LEN(lens, W2V2_DISPATCH_ACT(dtype, name,
+      hipLaunchKernelGGL((pool_meanstd_kernel<AT, LEN>), grid, dim3(256), 0, st, (const AT*)x, out, T, H, mode == 0,
+                         lens);));
   } else {
     dim3 grid((unsigned)cdiv((int64_t)B * H, 256));
-    W2V2_DISPATCH_ACT(dtype, "pool_fwd",
-      hipLaunchKernelGGL(pool_select_kernel<AT>, grid, dim3(256), 0, st, (const AT*)x, out, B, T, H, mode););
+    W2V2_DISPATCH_LEN(lens, W2V2_DISPATCH_ACT(dtype, name,
+      hipLaunchKernelGGL((pool_select_kernel<AT, LEN>), grid, dim3(256), 0, st, (const AT*)x, out, B, T, H, mode,
+                         lens);));
   }
-  W2V2_CHECK_LAUNCH("pool_fwd");
+  W2V2_CHECK_LAUNCH(name);
   return 0;
+}
+
+extern "C" int w2v2_pool_fwd(const void* x, float* out, int B, int T, int H, int mode, int dtype, void* stream) {
+  W2V2_REQUIRE(x && out && B > 0 && T > 0 && H > 0 && mode >= 0 && (mode <= 5 || (mode >= 16 && mode - 16 < T)),
+               "pool_fwd: bad arguments (mode %d, T %d)", mode, T);
+  return pool_fwd_launch("pool_fwd", x, out, nullptr, B, T, H, mode, dtype, stream);
 }
 
 extern "C" int w2v2_pool_bwd(const void* x, const float* out, const float* dout, void* dx, int B, int T, int H,
@@ -446,22 +357,5 @@ extern "C" int w2v2_pool_fwd_len(const void* x, float* out, const int* lens, int
                                  void* stream) {
   W2V2_REQUIRE(x && out && lens && B > 0 && T > 0 && H > 0 && mode >= 0 && mode <= 5,
                "pool_fwd_len: bad arguments (mode %d, T %d; the frame-index mode has no length-aware form)", mode, T);
-  hipStream_t st = as_stream(stream);
-  if (mode == 5) {
-    dim3 grid((unsigned)cdiv((int64_t)B * H, 64));
-    W2V2_DISPATCH_ACT(dtype, "pool_fwd_len",
-      hipLaunchKernelGGL(pool_quantile_len_kernel<AT>, grid, dim3(64), 0, st, (const AT*)x, out, lens, B, T, H););
-  } else if (mode <= 1) {
-    W2V2_REQUIRE(H % 8 == 0, "pool_fwd_len: H must be a multiple of 8");
-    dim3 grid((unsigned)cdiv(H, 128), B);
-    W2V2_DISPATCH_ACT(dtype, "pool_fwd_len",
-      hipLaunchKernelGGL(pool_meanstd_len_kernel<AT>, grid, dim3(256), 0, st, (const AT*)x, out, lens, T, H,
-                         mode == 0););
-  } else {
-    dim3 grid((unsigned)cdiv((int64_t)B * H, 256));
-    W2V2_DISPATCH_ACT(dtype, "pool_fwd_len",
-      hipLaunchKernelGGL(pool_select_len_kernel<AT>, grid, dim3(256), 0, st, (const AT*)x, out, lens, B, T, H, mode););
-  }
-  W2V2_CHECK_LAUNCH("pool_fwd_len");
-  return 0;
+  return pool_fwd_launch("pool_fwd_len", x, out, lens, B, T, H, mode, dtype, stream);
 }

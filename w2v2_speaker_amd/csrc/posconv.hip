@@ -7,9 +7,11 @@
 // x [B,T,H] -> xg [B,G,Tp,Cg], Tp = T+K-1, xg[b,g,tp,c] = x[b, tp-pad_left, g*Cg+c] (0 outside).
 // A row of the implicit GEMM for output frame t of group g is the contiguous K*Cg run starting at
 // xg[b,g,t,0]:  lda = Cg, seg_len = T, seg_stride = G*Tp*Cg.
-template <typename T>
+// LEN: variable-length batch, frames t >= lens[b] are written as zeros, the padding Conv1d(padding = K/2) gives the
+// utterance alone -- its first lens[b] + K - 1 regrouped rows equal those of the fixed-length form at T = lens[b]
+template <typename T, bool LEN>
 __global__ void regroup_kernel(const T* __restrict__ x, T* __restrict__ xg, int B, int Tn, int H, int G, int K,
-                               int pad_left) {
+                               int pad_left, LensArg<LEN> lens) {
   const int Cg = H / G, Tp = Tn + K - 1, nch = Cg >> 3;
   const int64_t total = (int64_t)B * G * Tp * nch;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -19,8 +21,10 @@ __global__ void regroup_kernel(const T* __restrict__ x, T* __restrict__ xg, int 
     const int g = (int)(r % G);
     const int b = (int)(r / G);
     const int t = tp - pad_left;
+    int L = Tn;
+    if constexpr (LEN) L = lens[b];
     Vec8<T> v;
-    if (t >= 0 && t < Tn) {
+    if (t >= 0 && t < L) {
       v.load(x + ((int64_t)b * Tn + t) * H + g * Cg + ch * 8);
     } else {
 #pragma unroll
@@ -30,55 +34,30 @@ __global__ void regroup_kernel(const T* __restrict__ x, T* __restrict__ xg, int 
   }
 }
 
-// Variable-length batch: frames t >= lens[b] are written as zeros, the padding Conv1d(padding = K/2) gives the utterance
-// alone -- its first lens[b] + K - 1 regrouped rows equal those of regroup_kernel at T = lens[b]
-template <typename T>
-__global__ void regroup_len_kernel(const T* __restrict__ x, T* __restrict__ xg, const int* __restrict__ lens, int B,
-                                   int Tn, int H, int G, int K, int pad_left) {
-  const int Cg = H / G, Tp = Tn + K - 1, nch = Cg >> 3;
-  const int64_t total = (int64_t)B * G * Tp * nch;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int ch = (int)(i % nch);
-    int64_t r = i / nch;
-    const int tp = (int)(r % Tp); r /= Tp;
-    const int g = (int)(r % G);
-    const int b = (int)(r / G);
-    const int t = tp - pad_left;
-    Vec8<T> v;
-    if (t >= 0 && t < lens[b]) {
-      v.load(x + ((int64_t)b * Tn + t) * H + g * Cg + ch * 8);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v.v[e] = 0.f;
-    }
-    v.store(xg + (((int64_t)b * G + g) * Tp + tp) * Cg + ch * 8);
-  }
+// lens: device int32 [B] for the variable-length form, null for fixed length
+static int regroup_launch(const char* name, const void* x, void* xg, const int* lens, int B, int T, int H, int G, int K,
+                          int pad_left, int dtype, void* stream) {
+  const int64_t total = (int64_t)B * G * (T + K - 1) * ((H / G) >> 3);
+  int nb = (int)(cdiv(total, 256) > 8192 ? 8192 : cdiv(total, 256));
+  W2V2_DISPATCH_LEN(lens, W2V2_DISPATCH_ACT(dtype, name,
+    hipLaunchKernelGGL((regroup_kernel<AT, LEN>), dim3(nb), dim3(256), 0, as_stream(stream), (const AT*)x,
+                       (AT*)xg, B, T, H, G, K, pad_left, lens);));
+  W2V2_CHECK_LAUNCH(name);
+  return 0;
 }
 
 extern "C" int w2v2_posconv_regroup(const void* x, void* xg, int B, int T, int H, int G, int K, int pad_left,
                                     int dtype, void* stream) {
   W2V2_REQUIRE(x && xg && B > 0 && T > 0 && G > 0 && H % G == 0 && (H / G) % 8 == 0 && K > 0,
                "posconv_regroup: bad arguments (H/G must be a multiple of 8)");
-  const int64_t total = (int64_t)B * G * (T + K - 1) * ((H / G) >> 3);
-  int nb = (int)(cdiv(total, 256) > 8192 ? 8192 : cdiv(total, 256));
-  W2V2_DISPATCH_ACT(dtype, "posconv_regroup",
-    hipLaunchKernelGGL(regroup_kernel<AT>, dim3(nb), dim3(256), 0, as_stream(stream), (const AT*)x,
-                       (AT*)xg, B, T, H, G, K, pad_left););
-  W2V2_CHECK_LAUNCH("posconv_regroup");
-  return 0;
+  return regroup_launch("posconv_regroup", x, xg, nullptr, B, T, H, G, K, pad_left, dtype, stream);
 }
 
 extern "C" int w2v2_posconv_regroup_len(const void* x, void* xg, const int* lens, int B, int T, int H, int G, int K,
                                         int pad_left, int dtype, void* stream) {
   W2V2_REQUIRE(x && xg && lens && B > 0 && T > 0 && G > 0 && H % G == 0 && (H / G) % 8 == 0 && K > 0,
                "posconv_regroup_len: bad arguments (H/G must be a multiple of 8)");
-  const int64_t total = (int64_t)B * G * (T + K - 1) * ((H / G) >> 3);
-  int nb = (int)(cdiv(total, 256) > 8192 ? 8192 : cdiv(total, 256));
-  W2V2_DISPATCH_ACT(dtype, "posconv_regroup_len",
-    hipLaunchKernelGGL(regroup_len_kernel<AT>, dim3(nb), dim3(256), 0, as_stream(stream), (const AT*)x,
-                       (AT*)xg, lens, B, T, H, G, K, pad_left););
-  W2V2_CHECK_LAUNCH("posconv_regroup_len");
-  return 0;
+  return regroup_launch("posconv_regroup_len", x, xg, lens, B, T, H, G, K, pad_left, dtype, stream);
 }
 
 // per-tap reductions over v [H][Cg][K] (K fastest): out[k] = sum_{o,i} a*b, in a FIXED order

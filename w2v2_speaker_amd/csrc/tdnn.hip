@@ -342,19 +342,46 @@ __device__ __forceinline__ int reflect(int p, int Tn) {
   return p;
 }
 // col[(b,t)][j*Cin + c] = x[b][reflect(t + off_j)][c];   one 16-byte vector per thread (8 / 4 channels)
-template <typename T>
+// LEN: variable-length batch (evaluation), utterance b has lens[b] valid frames out of Tn.  Taps reflect about the
+// utterance's OWN last frame lens[b] - 1, so a valid row reads rows < lens[b] only and equals the row of the fixed-length
+// form on the [1, lens[b], Cin] slice; rows t >= lens[b] are written as zeros (the products behind them then see no
+// padding content).  A workgroup whose 256 vectors all lie in padded rows of one utterance stores its zeros without
+// decoding or loading.
+template <typename T, bool LEN>
 __global__ void im2col_reflect_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ x2, int64_t ldx2,
-                                      T* __restrict__ col, int B, int Tn, int Cin, int k, int dil) {
+                                      T* __restrict__ col, int B, int Tn, int Cin, int k, int dil, LensArg<LEN> lens) {
   constexpr int EPT = BnGeom<T>::EPT;              // one 16-byte vector per thread (BnGeom)
   const int nch = Cin / EPT;
   const int64_t total = (int64_t)B * Tn * k * nch;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    typename BnGeom<T>::Vec zero;                    // (LEN only)
+    if constexpr (LEN) {
+#pragma unroll
+      for (int e = 0; e < EPT; ++e) zero.v[e] = 0.f;
+      const int64_t per_row = (int64_t)k * nch, i0 = i - threadIdx.x;     // i0: first vector of this workgroup's pass
+      const int64_t r0 = i0 / per_row, r1 = (min(i0 + (int64_t)blockDim.x, total) - 1) / per_row;   // first / last row here
+      const int b0 = (int)(r0 / Tn);
+      if (b0 == (int)(r1 / Tn) && (int)(r0 % Tn) >= lens[b0]) {     // (workgroup-uniform) nothing but padding
+        zero.store(col + i * EPT);                                 // col is dense: vector i sits at element i * EPT
+        continue;
+      }
+    }
     const int ch = (int)(i % nch);
     int64_t r = i / nch;
     const int j = (int)(r % k);
     r /= k;
     const int t = (int)(r % Tn), b = (int)(r / Tn);
-    const int src = reflect(t + (j - (k - 1) / 2) * dil, Tn);
+    int L = Tn;
+    if constexpr (LEN) {
+      L = min(lens[b], Tn);
+      if (t >= L) {
+        zero.store(col + ((int64_t)b * Tn + t) * ((int64_t)k * Cin) + (int64_t)j * Cin + ch * EPT);
+        continue;
+      }
+    }
+    int src = reflect(t + (j - (k - 1) / 2) * dil, L);
+    // (the host guarantees padding < lens[b]; the clamp keeps a bad table inside the utterance's rows)
+    if constexpr (LEN) src = min(max(src, 0), L - 1);
     typename BnGeom<T>::Vec v;
     v.load(x + ((int64_t)b * Tn + src) * ldx + ch * EPT);
     if (x2 != nullptr) {                   // taps of x + x2 (Res2Net: chunk input + previous chunk's output), summed here
@@ -364,54 +391,6 @@ __global__ void im2col_reflect_kernel(const T* __restrict__ x, int64_t ldx, cons
       for (int e = 0; e < EPT; ++e) v.v[e] += w.v[e];
     }
     v.store(col + ((int64_t)b * Tn + t) * ((int64_t)k * Cin) + (int64_t)j * Cin + ch * EPT);
-  }
-}
-// Variable-length batch (evaluation): utterance b has lens[b] valid frames out of Tn.  Taps reflect about the utterance's
-// OWN last frame lens[b] - 1, so a valid row reads rows < lens[b] only and equals the row of im2col_reflect_kernel on the
-// [1, lens[b], Cin] slice; rows t >= lens[b] are written as zeros (the products behind them then see no padding content).
-// A workgroup whose 256 vectors all lie in padded rows of one utterance stores its zeros without decoding or loading.
-template <typename T>
-__global__ void im2col_reflect_len_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ x2, int64_t ldx2,
-                                          T* __restrict__ col, const int* __restrict__ lens, int B, int Tn, int Cin, int k,
-                                          int dil) {
-  constexpr int EPT = BnGeom<T>::EPT;              // one 16-byte vector per thread (BnGeom)
-  const int nch = Cin / EPT;
-  const int64_t per_row = (int64_t)k * nch;
-  const int64_t total = (int64_t)B * Tn * per_row;
-  typename BnGeom<T>::Vec zero;
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) zero.v[e] = 0.f;
-  for (int64_t i0 = blockIdx.x * (int64_t)blockDim.x; i0 < total; i0 += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = i0 + threadIdx.x;
-    const int64_t r0 = i0 / per_row, r1 = (min(i0 + (int64_t)blockDim.x, total) - 1) / per_row;   // first / last row here
-    const int b0 = (int)(r0 / Tn);
-    if (b0 == (int)(r1 / Tn) && (int)(r0 % Tn) >= lens[b0]) {     // (workgroup-uniform) nothing but padding
-      if (i < total) zero.store(col + i * EPT);                  // col is dense: vector i sits at element i * EPT
-      continue;
-    }
-    if (i >= total) continue;
-    const int ch = (int)(i % nch);
-    int64_t r = i / nch;
-    const int j = (int)(r % k);
-    r /= k;
-    const int t = (int)(r % Tn), b = (int)(r / Tn);
-    const int L = min(lens[b], Tn);
-    T* dst = col + ((int64_t)b * Tn + t) * ((int64_t)k * Cin) + (int64_t)j * Cin + ch * EPT;
-    if (t >= L) {
-      zero.store(dst);
-      continue;
-    }
-    // (the host guarantees padding < lens[b]; the clamp keeps a bad table inside the utterance's rows)
-    const int src = min(max(reflect(t + (j - (k - 1) / 2) * dil, L), 0), L - 1);
-    typename BnGeom<T>::Vec v;
-    v.load(x + ((int64_t)b * Tn + src) * ldx + ch * EPT);
-    if (x2 != nullptr) {
-      typename BnGeom<T>::Vec w;
-      w.load(x2 + ((int64_t)b * Tn + src) * ldx2 + ch * EPT);
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) v.v[e] += w.v[e];
-    }
-    v.store(dst);
   }
 }
 // dx[b][s][c] (+)= sum over (t, j) with reflect(t + off_j) == s of dcol[(b,t)][j*Cin + c]   (gather: deterministic)
@@ -636,53 +615,42 @@ extern "C" int w2v2_bn_bwd_sum(const void* dy, int64_t lddy, const void* dy2, in
                      colsum_partial, dtype, stream);
 }
 
-static int im2col_reflect_impl(const void* x, int64_t ldx, const void* x2, int64_t ldx2, void* col, int B, int T, int Cin,
-                               int k, int dilation, int dtype, void* stream) {
+// lens: device int32 [B] for the variable-length form (dilation * (k - 1) / 2 < lens[b] <= T, checked by the caller on
+// the host), null for fixed length
+static int im2col_reflect_impl(const char* name, const void* x, int64_t ldx, const void* x2, int64_t ldx2, void* col,
+                               const int* lens, int B, int T, int Cin, int k, int dilation, int dtype, void* stream) {
   W2V2_REQUIRE(x && col && B > 0 && T > 0 && Cin % 8 == 0 && k % 2 == 1 && dilation >= 1 && ldx % 8 == 0 &&
                    (x2 == nullptr || ldx2 % 8 == 0) && dilation * (k - 1) / 2 < T,
-               "im2col_reflect: bad arguments (odd k, Cin %% 8 == 0, padding < T)");
+               "%s: bad arguments (odd k, Cin %% 8 == 0, padding < T)", name);
   const int nb = td_blocks((int64_t)B * T * k * (Cin >> (dtype == W2V2_F32 ? 2 : 3)));   // one 16-byte vector per thread
   hipStream_t st = as_stream(stream);
-  W2V2_DISPATCH_ACT(dtype, "im2col_reflect",
-    hipLaunchKernelGGL(im2col_reflect_kernel<AT>, dim3(nb), dim3(256), 0, st, (const AT*)x, ldx, (const AT*)x2, ldx2,
-                           (AT*)col, B, T, Cin, k, dilation););
-  W2V2_CHECK_LAUNCH("im2col_reflect");
+  W2V2_DISPATCH_LEN(lens, W2V2_DISPATCH_ACT(dtype, name,
+    hipLaunchKernelGGL((im2col_reflect_kernel<AT, LEN>), dim3(nb), dim3(256), 0, st, (const AT*)x, ldx, (const AT*)x2,
+                       ldx2, (AT*)col, B, T, Cin, k, dilation, lens);));
+  W2V2_CHECK_LAUNCH(name);
   return 0;
 }
 extern "C" int w2v2_im2col_reflect(const void* x, int64_t ldx, void* col, int B, int T, int Cin, int k, int dilation,
                                    int dtype, void* stream) {
-  return im2col_reflect_impl(x, ldx, nullptr, 0, col, B, T, Cin, k, dilation, dtype, stream);
+  return im2col_reflect_impl("im2col_reflect", x, ldx, nullptr, 0, col, nullptr, B, T, Cin, k, dilation, dtype, stream);
 }
 // the taps of x + x2 (same shape, own row strides): the Res2Net chunk input x_i + y_{i-1} without materialising the sum
 extern "C" int w2v2_im2col_reflect_sum(const void* x, int64_t ldx, const void* x2, int64_t ldx2, void* col, int B, int T,
                                        int Cin, int k, int dilation, int dtype, void* stream) {
   W2V2_REQUIRE(x2 != nullptr, "im2col_reflect_sum: null second operand");
-  return im2col_reflect_impl(x, ldx, x2, ldx2, col, B, T, Cin, k, dilation, dtype, stream);
-}
-
-// Variable-length forms: lens = device int32 [B], dilation * (k - 1) / 2 < lens[b] <= T (checked by the caller on the host)
-static int im2col_reflect_len_impl(const void* x, int64_t ldx, const void* x2, int64_t ldx2, void* col, const int* lens,
-                                   int B, int T, int Cin, int k, int dilation, int dtype, void* stream) {
-  W2V2_REQUIRE(x && col && lens && B > 0 && T > 0 && Cin % 8 == 0 && k % 2 == 1 && dilation >= 1 && ldx % 8 == 0 &&
-                   (x2 == nullptr || ldx2 % 8 == 0) && dilation * (k - 1) / 2 < T,
-               "im2col_reflect_len: bad arguments (odd k, Cin %% 8 == 0, padding < T)");
-  const int nb = td_blocks((int64_t)B * T * k * (Cin >> (dtype == W2V2_F32 ? 2 : 3)));   // one 16-byte vector per thread
-  hipStream_t st = as_stream(stream);
-  W2V2_DISPATCH_ACT(dtype, "im2col_reflect_len",
-    hipLaunchKernelGGL(im2col_reflect_len_kernel<AT>, dim3(nb), dim3(256), 0, st, (const AT*)x, ldx, (const AT*)x2, ldx2,
-                           (AT*)col, lens, B, T, Cin, k, dilation););
-  W2V2_CHECK_LAUNCH("im2col_reflect_len");
-  return 0;
+  return im2col_reflect_impl("im2col_reflect", x, ldx, x2, ldx2, col, nullptr, B, T, Cin, k, dilation, dtype, stream);
 }
 extern "C" int w2v2_im2col_reflect_len(const void* x, int64_t ldx, void* col, const int* lens, int B, int T, int Cin,
                                        int k, int dilation, int dtype, void* stream) {
-  return im2col_reflect_len_impl(x, ldx, nullptr, 0, col, lens, B, T, Cin, k, dilation, dtype, stream);
+  W2V2_REQUIRE(lens != nullptr, "im2col_reflect_len: bad arguments (null lens)");
+  return im2col_reflect_impl("im2col_reflect_len", x, ldx, nullptr, 0, col, lens, B, T, Cin, k, dilation, dtype, stream);
 }
 extern "C" int w2v2_im2col_reflect_sum_len(const void* x, int64_t ldx, const void* x2, int64_t ldx2, void* col,
                                            const int* lens, int B, int T, int Cin, int k, int dilation, int dtype,
                                            void* stream) {
   W2V2_REQUIRE(x2 != nullptr, "im2col_reflect_sum_len: null second operand");
-  return im2col_reflect_len_impl(x, ldx, x2, ldx2, col, lens, B, T, Cin, k, dilation, dtype, stream);
+  W2V2_REQUIRE(lens != nullptr, "im2col_reflect_len: bad arguments (null lens)");
+  return im2col_reflect_impl("im2col_reflect_len", x, ldx, x2, ldx2, col, lens, B, T, Cin, k, dilation, dtype, stream);
 }
 
 extern "C" int w2v2_col2im_reflect(const void* dcol, void* dx, int64_t lddx, int B, int T, int Cin, int k, int dilation,
