@@ -1577,6 +1577,50 @@ def test_grouped_weight_gradient_phased_kernel_ragged_problems(lp):
             assert float((db.double() - refb).norm() / refb.norm()) < 2e-6
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("lp", LP16)
+def test_grouped_weight_gradient_forced_families_small_ragged_group(lp):
+    """Every forced family of w2v2_tune_wgrad_kernel (1 = 128x128, 2 = 256x128 ring, 3 = 256x256x32 ring, 4 = phased) on
+    one small ragged group, which the library's own choice would send to one of them only.  tokens = 261 pads to 320 =
+    five 64-token K tiles: the 3-stage ring wraps, the 4-stage ring runs ten stages, the phased kernel uses both buffers
+    and both tail branches.  Problems with edges in both dimensions, one narrower than any tile and without bias.
+    Checked: every dW / dbias against the float64 product over the first 261 rows (rel-L2 < 1e-5, the bound of
+    test_grouped_weight_gradient_gemm), no NaN of the pre-fill left, family 4 bit-equal to family 3 (wgrad_phased.hip)."""
+    o = ops()
+    tokens, Mp = 261, 320
+    g = torch.Generator(device="cpu").manual_seed(261)
+
+    def mk(c):
+        t = torch.zeros(Mp, c, dtype=lp, device=DEV)
+        t[:tokens] = (torch.randn(tokens, c, generator=g) * 0.5).to(lp).to(DEV)
+        return t
+    shapes = [(264, 136, True), (72, 40, False), (520, 264, True)]
+    probs = [(mk(no), mk(ni)) for no, ni, _ in shapes]
+    refs = [(dy[:tokens].double().t() @ x[:tokens].double(), dy[:tokens].double().sum(0)) for dy, x in probs]
+    res = {}
+    try:
+        for fam in (1, 2, 3, 4):
+            outs = [(torch.full((no, ni), float("nan"), device=DEV),
+                     torch.full((no,), float("nan"), device=DEV) if hb else None) for no, ni, hb in shapes]
+            wg = o.WgradGroup([(dy, x, dw, db) for (dy, x), (dw, db) in zip(probs, outs)], tokens, Mp)
+            o.lib().w2v2_tune_wgrad_kernel(fam)
+            wg()
+            torch.cuda.synchronize()
+            res[fam] = outs
+    finally:
+        o.lib().w2v2_tune_wgrad_kernel(0)
+    for fam, outs in res.items():
+        for (dw, db), (rw, rb), shp in zip(outs, refs, shapes):
+            assert not bool(torch.isnan(dw).any()), (fam, shp)
+            assert rel_l2(dw.cpu(), rw.cpu()) < 1e-5, (fam, shp)
+            if db is not None:
+                assert not bool(torch.isnan(db).any()), (fam, shp)
+                assert rel_l2(db.cpu(), rb.cpu()) < 1e-5, (fam, shp)
+    for (dw4, db4), (dw3, db3) in zip(res[4], res[3]):
+        assert torch.equal(dw4, dw3)
+        assert db4 is None or torch.equal(db4, db3)
+
+
 # ----------------------------------------------------------------------------------------------- round-5 small kernels
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("B,C,E", [(66, 5994, 1536), (7, 37, 192), (150, 1211, 768), (3, 16, 520)])

@@ -2,6 +2,9 @@
 # Device code of one .hip file in two source trees, kernel by kernel: compiles both to gfx950 assembly with the flags of
 # _build.FLAGS, drops comments / directives / metadata, renumbers the local labels and says per kernel whether the
 # instruction streams are identical.  What a host-side refactor has to show (the kernels did not move) --
+# a differing kernel is listed with the index of its first differing instruction and of its last v_mfma: a difference
+# behind the last v_mfma left the K loop alone.  The offset of an LDS read is compared as a number: an explicit `offset:0`
+# counts as none and `offset:0x800` as `offset:2048` (inline assembly prints what its author or the compiler spelled).
 #     bash tools/device_code_diff.sh gemm_ring.hip /path/to/parent/tree [/path/to/this/tree] [-v]
 # -v prints a unified diff of every differing kernel.  Kernels present in one tree only are listed as such; the
 # instantiations of a template that gained ONE parameter (and, with it, trailing kernel arguments) are paired with the
@@ -31,6 +34,8 @@ def kernels(path):
         s = l.split(';')[0].strip()               # comments carry line numbers and register statistics
         if not s or s.startswith('.') and not s.startswith(('.LBB', '.Lpost_getpc')):
             continue
+        if s.startswith('ds_read'):                  # one encoding, three spellings: none / offset:0, offset:2048 / offset:0x800
+            s = re.sub(r'\s+offset:(0x[0-9a-f]+|\d+)$', lambda m: ' offset:%d' % int(m.group(1), 0) if int(m.group(1), 0) else '', s)
         body.append(s)
         if s == 's_endpgm':
             # local labels are numbered per translation unit: renumber in order of appearance
@@ -68,7 +73,10 @@ for k in diff:
     d = list(difflib.unified_diff(old[k], new[k], lineterm='', n=2))
     plus = sum(1 for x in d if x.startswith('+') and not x.startswith('+++'))
     minus = sum(1 for x in d if x.startswith('-') and not x.startswith('---'))
-    print(f"  DIFFERS {k}: {len(old[k])} -> {len(new[k])} instructions (-{minus} +{plus})")
+    first = next((i for i, (x, y) in enumerate(zip(old[k], new[k])) if x != y), min(len(old[k]), len(new[k])))
+    last_mfma = [max((i for i, x in enumerate(v) if x.startswith('v_mfma')), default=-1) for v in (old[k], new[k])]
+    print(f"  DIFFERS {k}: {len(old[k])} -> {len(new[k])} instructions (-{minus} +{plus}); first difference at "
+          f"instruction {first}, last v_mfma at {last_mfma[0]} -> {last_mfma[1]}")
     if verbose:
         print('\n'.join('      ' + x for x in d))
 for k in old:

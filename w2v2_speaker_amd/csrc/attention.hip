@@ -20,7 +20,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int HD = 64;  // head dim
 
@@ -172,8 +171,6 @@ __device__ __forceinline__ void store_row4x4(bf16_t* row, int g, bool valid, con
 // The products that contract over the streamed axis (P V, dS K, P^T dO, dS^T Q) need their LDS operand transposed.
 // The images stay ROW-MAJOR and the operand comes from the hardware transpose read ds_read_b64_tr_b16 (16 lanes x 8 B =
 // a 4(row) x 16(col) block, lane i receives column i): no transposed copies in LDS.
-typedef __attribute__((ext_vector_type(4))) short short4v_t;
-typedef __attribute__((address_space(3))) short4v_t lds_s4v_t;
 
 // MFMA operand fragment "columns d0..d0+15 x k-slots of 32-row block blk" from a row-major swizzled image.
 // The swizzle of the rows a lane touches depends on the lane only (16-row periodic, blocks of 32 rows), so the
@@ -191,9 +188,9 @@ __device__ __forceinline__ TrOff tr_offsets(int lane) {
 }
 __device__ __forceinline__ frag8_t lds_frag_tr(const bf16_t* img, const TrOff& t, int df, int blk) {
   const bf16_t* p0 = img + t.o[df] + blk * 2048;
-  const short4v_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v_t*)p0);
-  const short4v_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v_t*)(p0 + 1024));
-  union { struct { short4v_t a, b; } s; frag8_t v; } u;
+  const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)p0);
+  const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(p0 + 1024));
+  TrFrag u;
   u.s.a = lo;
   u.s.b = hi;
   return u.v;
@@ -245,8 +242,6 @@ __device__ __forceinline__ void tile_store(const TileRegs& r, bf16_t* lds) {
 // applied on the SOURCE side (the lane fetches chunk (l & 7) ^ aswz(row)).  The DMA cannot write zeros: rows past
 // n_valid are CLAMPED onto the last valid row (finite data) and the caller makes their contribution vanish
 // (dK / dV kernel: lse = +inf for those query rows -> p = 0).  KT / (8 NW) instructions per wave and operand.
-typedef __attribute__((address_space(1))) const void attn_gvoid_t;
-typedef __attribute__((address_space(3))) void attn_lvoid_t;
 template <int NW, int KT>
 __device__ __forceinline__ void tile_dma(const bf16_t* g, int64_t gs, int row0, int n_valid, bf16_t* lds, int wave, int lane) {
 #pragma unroll
@@ -255,7 +250,7 @@ __device__ __forceinline__ void tile_dma(const bf16_t* g, int64_t gs, int row0, 
     const int row = piece * 8 + (lane >> 3);
     const int src_row = min(row0 + row, n_valid - 1);
     const int ch = (lane & 7) ^ aswz(row);
-    __builtin_amdgcn_global_load_lds((attn_gvoid_t*)(g + (int64_t)src_row * gs + ch * 8), (attn_lvoid_t*)(lds + piece * 8 * 64), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gvoid_t*)(g + (int64_t)src_row * gs + ch * 8), (lvoid_t*)(lds + piece * 8 * 64), 16, 0, 0);
   }
 }
 
@@ -266,10 +261,8 @@ __device__ __forceinline__ void tile_dma(const bf16_t* g, int64_t gs, int row0, 
 // fetched the operands from HBM itself: 121 / 152 / 155 MB per launch against ~60 algorithmic at T = 149 (PMC, round 2).
 struct AttnBlock { int tile, h, b; };
 __device__ __forceinline__ AttnBlock attn_block(int ntile_rows, int heads) {
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  if (heads < 0) { logical = bid; heads = -heads; }       // A/B switch (W2V2_ATTN_NO_XCD_REMAP): dispatch order
+  int logical = xcd_remap(blockIdx.x, gridDim.x);
+  if (heads < 0) { logical = blockIdx.x; heads = -heads; }       // A/B switch (W2V2_ATTN_NO_XCD_REMAP): dispatch order
   AttnBlock o;
   o.tile = logical % ntile_rows;
   const int bh = logical / ntile_rows;
@@ -579,7 +572,7 @@ __global__ __launch_bounds__(64 * NW, DMA ? 4 : 3) void attn_bwd_kv_tiled_kernel
     tile_dma<NW, KT>(dob, H, 0, Tn, Os[0], wave, lane);
     row_load(0);
     row_store(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
   } else {
     tile_load<NT>(rq, qb, gs, 0, Tn);
     tile_load<NT>(ro, dob, H, 0, Tn);
@@ -660,7 +653,7 @@ __global__ __launch_bounds__(64 * NW, DMA ? 4 : 3) void attn_bwd_kv_tiled_kernel
         tile_store<NT>(ro, Os[cur ^ 1]);
       }
       row_store(cur ^ 1);
-      if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if constexpr (DMA) wait_vmcnt<0>();
     }
     __syncthreads();
   }

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <math.h>
 #include <type_traits>
+#include <utility>
 
 #include "../../include/w2v2_hip.h"
 
@@ -287,6 +288,78 @@ template <> __device__ __forceinline__ float pair_sum_add<bf16_t>(uint32_t w, ui
 }
 template <> __device__ __forceinline__ float pair_sum_add<f16_t>(uint32_t w, uint32_t ones, float acc) {
   return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2_hw, w), __builtin_bit_cast(f16x2_hw, ones), acc, false);
+}
+
+// ---------------------------------------------------------------- what the LDS-DMA kernel families share
+// (16-bit GEMMs, exact-f32 DMA GEMM, grouped weight gradients, attention, positional convolution)
+typedef f32x4_hw f32x4;
+typedef __attribute__((ext_vector_type(4))) short short4v;
+typedef __attribute__((address_space(1))) const void gvoid_t;   // operands of __builtin_amdgcn_global_load_lds
+typedef __attribute__((address_space(3))) void lvoid_t;
+typedef __attribute__((address_space(3))) short4v lds_s4_t;     // operand of __builtin_amdgcn_ds_read_tr16_b64_v4i16
+
+// XCD-aware tile order: consecutive workgroup ids land on different XCDs (id % 8); remap so each
+// XCD owns a contiguous run of tiles (neighbouring tiles share the A row panel in its private L2).
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+}
+
+// `s_waitcnt vmcnt(N)` in front of a barrier: all but the N most recent vector-memory operations of this wave (its
+// LDS-DMA pieces) have landed
+template <int N> __device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// the same with a run-time count (phased kernels: at most 8 pieces of a wave are in flight)
+__device__ __forceinline__ void wait_pieces(int n) {
+  switch (n) {
+    case 0: wait_vmcnt<0>(); break;
+    case 1: wait_vmcnt<1>(); break;
+    case 2: wait_vmcnt<2>(); break;
+    case 3: wait_vmcnt<3>(); break;
+    case 4: wait_vmcnt<4>(); break;
+    case 5: wait_vmcnt<5>(); break;
+    case 6: wait_vmcnt<6>(); break;
+    case 7: wait_vmcnt<7>(); break;
+    default: wait_vmcnt<8>(); break;
+  }
+}
+// ... counted in quarters of a K-tile buffer (2 DMA pieces per wave each)
+__device__ __forceinline__ void wait_quarters(int newer) {
+  if (newer >= 4) wait_vmcnt<8>();
+  else if (newer == 3) wait_vmcnt<6>();
+  else if (newer == 2) wait_vmcnt<4>();
+  else if (newer == 1) wait_vmcnt<2>();
+  else wait_vmcnt<0>();
+}
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): loop bodies that need their index at compile time
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
+  static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// One MFMA fragment out of a K-major LDS image = two hardware transposing reads (ds_read_b64_tr_b16: 16 lanes x 8 B = a
+// 4 (k) x 16 (m) block, lane i receives column i) at byte offsets OFF0 / OFF1 from the per-lane address.  Inline assembly
+// on purpose: the compiler treats the ds_read_tr builtin as possibly aliasing the LDS-DMA pieces in flight and puts
+// `s_waitcnt vmcnt(0)` in front of every group of reads, which drains the ring.  Which stage is read and which written is
+// the kernel's protocol (counted wait + barrier); landed() is the matching wait -- LDS returns in order, so all but the N
+// most recently issued reads have arrived behind it, and the "+v" ties the fragment's registers to it.
+union TrFrag { struct { short4v a, b; } s; frag8_t v; };
+template <int OFF0, int OFF1> __device__ __forceinline__ void tr_read(TrFrag& f, uint32_t addr) {
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.s.a) : "v"(addr), "n"(OFF0) : "memory");
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.s.b) : "v"(addr), "n"(OFF1) : "memory");
+}
+template <int N = 0> __device__ __forceinline__ void landed(TrFrag& f) {
+  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f.s.a), "+v"(f.s.b) : "n"(N));
+}
+template <int N = 0, int K> __device__ __forceinline__ void landed(TrFrag (&f)[K]) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) landed<N>(f[i]);
 }
 
 // ---------------------------------------------------------------- full-line stores of MFMA-layout tiles

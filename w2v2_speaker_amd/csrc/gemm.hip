@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void gemm16_dma_128_kernel(const GemmArgs g) {
     for (int j = 0; j < NB; ++j) w2v2_dma16(bp[j] + kt * 64, bd + j * 8 * 64);
   };
   auto landed = [&]() {                           // this wave's pieces are in; the barrier then makes every wave's visible
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
   };
   const int frow = lane & 15, fk = lane >> 4;

@@ -11,8 +11,6 @@
 #include <type_traits>
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 struct OpDev {
   const void* ptr;
   int64_t ld, seg_len, seg_stride;
@@ -513,24 +511,6 @@ __device__ __forceinline__ void tile_ptrs(const OpDev& o, const bf16_t* base, in
 #pragma unroll
     for (int j = 0; j < NP; ++j) out[j] = base + outer_off(o, min(t0 + row0 + j * step, bound - 1)) + col[j];
   }
-}
-
-// XCD-aware tile order: consecutive workgroup ids land on different XCDs (id % 8); remap so each
-// XCD owns a contiguous run of tiles (neighbouring tiles share the A row panel in its private L2).
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-
-
-typedef __attribute__((address_space(1))) const void gvoid_t;
-typedef __attribute__((address_space(3))) void lvoid_t;
-
-// `s_waitcnt vmcnt(N)` in front of a barrier: all but the N most recent vector-memory operations of this wave (its
-// LDS-DMA pieces) have landed
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // CUs the persistent grids may fill: w2v2_device_cus() (common.h) minus W2V2_RESERVE_CUS, which keeps some out for RCCL's

@@ -23,18 +23,8 @@
 // Host side: w2v2_launch_gemm_f32 (gemm_f32.hip) sends a product here when both operands are plain 16-byte aligned
 // matrices with K % 4 == 0 (and M % 4 / N % 4 for K-major ones); anything else stays on the register-staged kernel.
 #include "gemm_common.h"
-#include <utility>
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): loop bodies that need their index at compile time
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 __device__ __attribute__((aligned(16))) float g_f32_zero16[4] = {0.f, 0.f, 0.f, 0.f};
 

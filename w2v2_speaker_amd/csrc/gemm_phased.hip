@@ -17,36 +17,6 @@
 //     is re-issued two phases after its last read (strictly after BOTH groups' reads have returned): a quarter is in
 //     flight for 5-6 phases (~1.5 us), four quarters at a time, `s_waitcnt vmcnt(8)`, never vmcnt(0) in steady state.
 //   * same register epilogue as the 256x256 ring kernel (B rows permuted so a lane owns 16 consecutive columns).
-template <int N> __device__ __forceinline__ void wait_vm() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-}
-// wait until all but the n most recently issued DMA pieces of this wave have landed
-__device__ __forceinline__ void wait_pieces(int n) {
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-  }
-}
-// wait until all but the `newer` most recently issued quarters (2 DMA pieces each) of this wave have landed
-__device__ __forceinline__ void wait_quarters(int newer) {
-  if (newer >= 4) wait_vm<8>();
-  else if (newer == 3) wait_vm<6>();
-  else if (newer == 2) wait_vm<4>();
-  else if (newer == 1) wait_vm<2>();
-  else wait_vm<0>();
-}
-
 // DBG (tools only, w2v2_tune_gemm_debug): time attribution / placement experiments on the SAME kernel body --
 //   1 = no DMA in the steady-state loop, 2 = no fragment reads, 4 = no MFMAs, 8 = no epilogue,
 //   16 / 32 = one / both of the two DMA pieces of a phase are issued BETWEEN its MFMAs instead of in its read segment,

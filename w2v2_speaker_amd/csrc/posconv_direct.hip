@@ -17,10 +17,6 @@
 // data gradient (the same convolution over the regrouped dY with the flipped weights): + aux.
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(1))) const void gvoid_t;
-typedef __attribute__((address_space(3))) void lvoid_t;
-
 constexpr int PD_MB = 160;                     // frames per workgroup (ten 16-row fragments)
 // Two geometries (template parameter CG = channels per group): 48 (w2v2-base, H = 768 / 16 groups) and 64 (wav2vec2-large,
 // H = 1024 / 16 groups; round 6).  CG = 64: a frame row of the image is exactly one 128-byte line = one 64-wide K tile (one
@@ -108,10 +104,10 @@ __global__ __launch_bounds__(256) void posconv_direct_kernel(const bf16_t* __res
   for (int kt = 0; kt < nk; ++kt) {
     // stage kt (and, the first time, the image) landed: at most the pieces of stage kt + 1 stay in flight
     if (loader) {
-      if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (kt + 1 < nk) wait_vmcnt<2>();
+      else wait_vmcnt<0>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
     }
     __builtin_amdgcn_s_barrier();
     if (kt + 2 < nk) issue(kt + 2);              // into the buffer every wave finished reading before this barrier

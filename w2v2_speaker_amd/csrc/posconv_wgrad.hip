@@ -18,37 +18,9 @@
 #include "common.h"
 #include <type_traits>
 
-typedef __attribute__((ext_vector_type(4))) short short4v;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((address_space(1))) const void gvoid_t;
-typedef __attribute__((address_space(3))) void lvoid_t;
-
 namespace {
 
 constexpr int PW_TC = 160;                 // time rows per work item (5 MFMA k steps)
-
-union PwFrag {
-  struct { short4v a, b; } s;
-  frag8_t v;
-};
-
-template <int OFF0, int OFF1>
-__device__ __forceinline__ void pw_tr_read(PwFrag& f, uint32_t addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.s.a) : "v"(addr), "n"(OFF0) : "memory");
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.s.b) : "v"(addr), "n"(OFF1) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void pw_wait(PwFrag& f) {
-  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f.s.a), "+v"(f.s.b) : "n"(N));
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void pw_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    pw_static_for<I + 1, N>(f);
-  }
-}
 
 // NF = Cg / 16 fragments per channel dimension, TW = taps per wave (4 waves -> 4 TW taps per workgroup)
 template <typename TE, int NF, int TW>
@@ -114,39 +86,39 @@ __global__ __launch_bounds__(256) void posconv_wgrad_kernel(const bf16_t* __rest
 #pragma unroll 1
   for (int it = 0; it < items; ++it) {
     const int s = it & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();                                    // item `it` landed everywhere; buffer s^1 is free again
     if (it + 1 < items) load_item(it + 1, s ^ 1);
     const uint32_t dyb = lds0 + (uint32_t)(s * bufbytes) + lane_off;
     const uint32_t xb0 = dyb + (uint32_t)(PW_TC * ROWB) + (uint32_t)(wave * TW * ROWB);
 
-    PwFrag af[KS][NF];                                   // dY fragments of the item: shared by the taps of the wave
-    pw_static_for<0, KS>([&](auto ks) {
-      pw_static_for<0, NF>([&](auto fo) {
+    TrFrag af[KS][NF];                                   // dY fragments of the item: shared by the taps of the wave
+    static_for<KS>([&](auto ks) {
+      static_for<NF>([&](auto fo) {
         constexpr int off = decltype(ks)::value * 32 * ROWB + decltype(fo)::value * 32;
-        pw_tr_read<off, off + 16 * ROWB>(af[decltype(ks)::value][decltype(fo)::value], dyb);
+        tr_read<off, off + 16 * ROWB>(af[decltype(ks)::value][decltype(fo)::value], dyb);
       });
     });
     // taps x k steps, software-pipelined TWO steps deep (three fragment sets): with one wave per SIMD a transposing
     // read has to cover its ~200-clock latency under the nine MFMAs (144 clocks) of a step, which one step does not
-    PwFrag xf[3][NF];
-    auto read_x = [&](auto step, PwFrag (&dst)[NF]) {
+    TrFrag xf[3][NF];
+    auto read_x = [&](auto step, TrFrag (&dst)[NF]) {
       constexpr int tw = decltype(step)::value / KS, ks = decltype(step)::value % KS;
-      pw_static_for<0, NF>([&](auto fc) {
+      static_for<NF>([&](auto fc) {
         constexpr int off = (tw + ks * 32) * ROWB + decltype(fc)::value * 32;
-        pw_tr_read<off, off + 16 * ROWB>(dst[decltype(fc)::value], xb0);
+        tr_read<off, off + 16 * ROWB>(dst[decltype(fc)::value], xb0);
       });
     };
     read_x(std::integral_constant<int, 0>{}, xf[0]);
     if constexpr (TW * KS > 1) read_x(std::integral_constant<int, 1>{}, xf[1]);
-    pw_static_for<0, KS>([&](auto ks) {
-      pw_static_for<0, NF>([&](auto fo) { pw_wait<0>(af[decltype(ks)::value][decltype(fo)::value]); });
+    static_for<KS>([&](auto ks) {
+      static_for<NF>([&](auto fo) { landed<0>(af[decltype(ks)::value][decltype(fo)::value]); });
     });
-    pw_static_for<0, TW * KS>([&](auto step) {
+    static_for<TW * KS>([&](auto step) {
       constexpr int st = decltype(step)::value, tw = st / KS, ks = st % KS, cur = st % 3;
       // LDS returns in order: all but the 2 NF reads of step st+1 (if there is one) must have landed
-      pw_static_for<0, NF>([&](auto fc) {
-        pw_wait<(st + 1 < TW * KS) ? 2 * NF : 0>(xf[cur][decltype(fc)::value]);
+      static_for<NF>([&](auto fc) {
+        landed<(st + 1 < TW * KS) ? 2 * NF : 0>(xf[cur][decltype(fc)::value]);
       });
       if constexpr (st + 2 < TW * KS) read_x(std::integral_constant<int, st + 2>{}, xf[(st + 2) % 3]);
       __builtin_amdgcn_sched_barrier(0);

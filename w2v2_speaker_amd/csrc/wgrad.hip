@@ -14,8 +14,6 @@
 // (tokens_padded = tokens rounded up to 64); n_out, n_in multiples of 8; 16-byte aligned rows.
 #include "wgrad_common.h"
 
-__device__ __forceinline__ int wg_f(int r) { return (r & 3) | ((r >> 1) & 4); }
-
 __device__ __forceinline__ frag8_t tr_frag(const bf16_t* tile, int kk, int seg, int lane) {
   // k-slots of lane group g: rows kk*32 + g*8 + {0..7}; two 4x16 transposing reads
   const int i = lane & 15, g = lane >> 4;
@@ -24,7 +22,7 @@ __device__ __forceinline__ frag8_t tr_frag(const bf16_t* tile, int kk, int seg, 
   const bf16_t* p = tile + r * 128 + ((seg ^ f) << 4) + ((i & 3) << 2);
   const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)p);
   const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(p + 4 * 128));
-  union { struct { short4v a, b; } s; frag8_t v; } u;
+  TrFrag u;
   u.s.a = lo;
   u.s.b = hi;
   return u.v;
@@ -40,17 +38,8 @@ __global__ __launch_bounds__(256) void wgrad_grouped_kernel(const WgArgs a) {
   const int wm = wave >> 1, wn = wave & 1;
 
   // tile -> (problem, tm, tn); XCD-aware order as in gemm.hip
-  int tile;
-  {
-    const int nwg = a.total_tiles, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < WG_MAXP; ++i)
-    if (i < a.n_problems && tile >= a.p[i].tile_begin) pi = i;
-  const WgProblem& P = a.p[pi];
+  const int tile = xcd_remap(blockIdx.x, a.total_tiles);
+  WG_PROBLEM_OF_TILE(P, a, tile);
   const int t = tile - P.tile_begin;
   const int tm = t / P.tiles_n, tn = t - tm * P.tiles_n;
   const int m0 = tm * 128, n0 = tn * 128;
@@ -101,12 +90,7 @@ __global__ __launch_bounds__(256) void wgrad_grouped_kernel(const WgArgs a) {
       for (int j = 0; j < 4; ++j) bfr[j] = tr_frag(Bc, kk, wn * 4 + j, lane);
       if (do_bias) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          union { frag8_t v; uint32_t p[4]; } u;
-          u.v = af[i];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) bsum[i] = pair_sum_add<TE>(u.p[e], one2, bsum[i]);
-        }
+        for (int i = 0; i < 4; ++i) bsum[i] = wg_dbias_add<TE>(af[i], one2, bsum[i]);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -132,13 +116,7 @@ __global__ __launch_bounds__(256) void wgrad_grouped_kernel(const WgArgs a) {
 
   if (do_bias) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float s = bsum[i];
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      const int m = m0 + wm * 64 + i * 16 + (lane & 15);
-      if ((lane >> 4) == 0 && m < P.n_out) P.dbias[m] = s;
-    }
+    for (int i = 0; i < 4; ++i) WG_DBIAS_STORE(P, bsum[i], m0 + wm * 64 + i * 16 + (lane & 15), lane)
   }
   // coalesced f32 tile store through LDS (two 64-row halves, as in gemm.hip)
   float* stagef = reinterpret_cast<float*>(smem_raw);
@@ -156,14 +134,7 @@ __global__ __launch_bounds__(256) void wgrad_grouped_kernel(const WgArgs a) {
               make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
     }
     __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int c = tid + 256 * it;                 // 64 rows x 32 float4 chunks
-      const int r = c >> 5, ch = c & 31;
-      const int m = m0 + pass * 64 + r, n = n0 + ch * 4;
-      if (m < P.n_out && n + 4 <= P.n_in)
-        store16_wt(P.dW + (int64_t)m * P.ld_dw + n, *reinterpret_cast<const uint4*>(stagef + r * PITCH + ch * 4));
-    }
+    WG_STORE_ROWS(256, 64, 128, P, stagef, m0 + pass * 64, n0, tid)
   }
 }
 
@@ -173,11 +144,6 @@ __global__ __launch_bounds__(256) void wgrad_grouped_kernel(const WgArgs a) {
 // gemm16_ring_256x128_kernel: while tile t is multiplied, tiles t+1 and t+2 are in flight; per K tile one raw
 // s_barrier and `s_waitcnt vmcnt(6)` (6 = this wave's DMA pieces per stage: 4 x [2 rows x 512 B] of dY,
 // 2 x [4 rows x 256 B] of X).  The four Linear layers of a w2v2-base block are 216 tiles = one round on 256 CUs.
-template <int S> __device__ __forceinline__ void wg_wait_vmcnt() {
-  if constexpr (S == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-}
-
 template <typename TE>
 __global__ __launch_bounds__(512) void wgrad_grouped_ring_kernel(const WgArgs a) {
   constexpr int BM = 256, BN = 128;
@@ -188,17 +154,8 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring_kernel(const WgArgs a)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // 0..7
   const int wm = wave >> 1, wn = wave & 1;
 
-  int tile;
-  {
-    const int nwg = a.total_tiles, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < WG_MAXP; ++i)
-    if (i < a.n_problems && tile >= a.p[i].tile_begin) pi = i;
-  const WgProblem& P = a.p[pi];
+  const int tile = xcd_remap(blockIdx.x, a.total_tiles);
+  WG_PROBLEM_OF_TILE(P, a, tile);
   const int t = tile - P.tile_begin;
   const int tm = t / P.tiles_n, tn = t - tm * P.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -228,8 +185,7 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring_kernel(const WgArgs a)
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // dbias[m] = sum_t dY[t][m]: the waves of n-tile 0 / wn 0 add up the dY fragments they hold anyway, two bf16 per
-  // v_dot2c_f32_bf16 against (1, 1) -- 4 VALU ops per fragment instead of 16 converts+adds
+  // dbias: the waves of n-tile 0 / wn 0 add up the dY fragments they hold anyway (wg_dbias_add)
   float bsum[4] = {0.f, 0.f, 0.f, 0.f};
   const bool do_bias = (P.dbias != nullptr) && tn == 0 && wn == 0;
   const uint32_t one2 = ones_pair<TE>();
@@ -246,9 +202,8 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring_kernel(const WgArgs a)
   };
   // per-lane fragment byte offsets: row (g*8 + i/4), 8-byte piece (i%4), physical segment (seg ^ f) with
   // seg = w*4 + x (x = 0..3 compile time) and f = (i/4) | ((g&1) << 2)  ->  ((w ^ f>>2) << 2) | (x ^ (f&3)).
-  // The transposing reads are issued as inline asm: the compiler treats the ds_read_tr builtin as possibly
-  // aliasing the LDS-DMA writes in flight and would put `s_waitcnt vmcnt(0)` in front of every group of
-  // reads, draining the ring.  Which stage is being read vs written is guaranteed by the ring protocol.
+  // The reads are tr_read (common.h: inline assembly, so that the compiler does not drain the ring in front of them);
+  // which stage is being read vs written is guaranteed by the ring protocol.
   const int li = lane & 15, lg = lane >> 4;
   const int fr = lg * 8 + (li >> 2);
   const int flo = (li >> 2), fhi = lg & 1;
@@ -259,29 +214,12 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring_kernel(const WgArgs a)
     aoff[x] = lds0 + 2u * (fr * BM + (((((wm ^ fhi) & 3) << 2) | (x ^ flo)) << 4) + ((li & 3) << 2));
     boff[x] = lds0 + 2u * (64 * BM + fr * BN + (((((wn ^ fhi) & 1) << 2) | (x ^ flo)) << 4) + ((li & 3) << 2));
   }
-  union Frag { struct { short4v a, b; } s; frag8_t v; };
-#define W2V2_TR_READ(dst, addr, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr) : "memory")
-#define W2V2_FRAG_A(f, addr, KK)                                   \
-  if (KK == 0) { W2V2_TR_READ(f.s.a, addr, 0);     W2V2_TR_READ(f.s.b, addr, 2048); }  \
-  else         { W2V2_TR_READ(f.s.a, addr, 16384); W2V2_TR_READ(f.s.b, addr, 18432); }
-#define W2V2_FRAG_B(f, addr, KK)                                   \
-  if (KK == 0) { W2V2_TR_READ(f.s.a, addr, 0);    W2V2_TR_READ(f.s.b, addr, 1024); }   \
-  else         { W2V2_TR_READ(f.s.a, addr, 8192); W2V2_TR_READ(f.s.b, addr, 9216); }
-  static_assert(4 * BM * 2 == 2048 && 32 * BM * 2 == 16384 && 4 * BN * 2 == 1024 && 32 * BN * 2 == 8192, "offsets");
-  auto landed = [&](Frag (&f)[4]) {   // LDS returns in order: all reads issued so far have landed after this
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[i].s.a), "+v"(f[i].s.b));
-  };
-  auto mma = [&](Frag (&af)[4], Frag (&bfr)[4]) {
+  // second transposing read of a fragment = + 4 token rows; k-step 1 = + 32 token rows
+  constexpr int A4 = 4 * BM * 2, AK = 32 * BM * 2, B4 = 4 * BN * 2, BK1 = 32 * BN * 2;
+  auto mma = [&](TrFrag (&af)[4], TrFrag (&bfr)[4]) {
     if (do_bias) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        union { frag8_t v; uint32_t p[4]; } u;
-        u.v = af[i].v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) bsum[i] = pair_sum_add<TE>(u.p[e], one2, bsum[i]);
-      }
+      for (int i = 0; i < 4; ++i) bsum[i] = wg_dbias_add<TE>(af[i].v, one2, bsum[i]);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -293,17 +231,17 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring_kernel(const WgArgs a)
     uint32_t aa[4], ba[4];
 #pragma unroll
     for (int x = 0; x < 4; ++x) { aa[x] = aoff[x] + sbytes; ba[x] = boff[x] + sbytes; }
-    Frag a0[4], b0[4], a1[4], b1[4];
+    TrFrag a0[4], b0[4], a1[4], b1[4];
 #pragma unroll
-    for (int x = 0; x < 4; ++x) { W2V2_FRAG_A(a0[x], aa[x], 0) }
+    for (int x = 0; x < 4; ++x) tr_read<0, A4>(a0[x], aa[x]);
 #pragma unroll
-    for (int x = 0; x < 4; ++x) { W2V2_FRAG_B(b0[x], ba[x], 0) }
+    for (int x = 0; x < 4; ++x) tr_read<0, B4>(b0[x], ba[x]);
     landed(a0);
     landed(b0);
 #pragma unroll
-    for (int x = 0; x < 4; ++x) { W2V2_FRAG_A(a1[x], aa[x], 1) }
+    for (int x = 0; x < 4; ++x) tr_read<AK, AK + A4>(a1[x], aa[x]);
 #pragma unroll
-    for (int x = 0; x < 4; ++x) { W2V2_FRAG_B(b1[x], ba[x], 1) }
+    for (int x = 0; x < 4; ++x) tr_read<BK1, BK1 + B4>(b1[x], ba[x]);
     __builtin_amdgcn_sched_barrier(0);   // k-step 1 reads are in flight under the MFMAs of k-step 0 ...
     mma(a0, b0);
     __builtin_amdgcn_sched_barrier(0);   // ... and their wait comes after those MFMAs
@@ -314,7 +252,7 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring_kernel(const WgArgs a)
   const int nk = a.ktiles;
 #define W2V2_WG_RING_STEP(cur, nxt)                                      \
   {                                                                      \
-    if (kt + 1 < nk) wg_wait_vmcnt<6>(); else wg_wait_vmcnt<0>();        \
+    if (kt + 1 < nk) wait_vmcnt<6>(); else wait_vmcnt<0>();              \
     __builtin_amdgcn_s_barrier();                                        \
     if (kt + 2 < nk) stage(smem + (nxt) * STAGE, kt + 2);                \
     compute((cur) * STAGE * 2u);                                         \
@@ -331,19 +269,10 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring_kernel(const WgArgs a)
     W2V2_WG_RING_STEP(2, 1)
   }
 #undef W2V2_WG_RING_STEP
-#undef W2V2_FRAG_A
-#undef W2V2_FRAG_B
-#undef W2V2_TR_READ
 
   if (do_bias) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float s = bsum[i];
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      const int m = m0 + wm * 64 + i * 16 + (lane & 15);
-      if ((lane >> 4) == 0 && m < P.n_out) P.dbias[m] = s;
-    }
+    for (int i = 0; i < 4; ++i) WG_DBIAS_STORE(P, bsum[i], m0 + wm * 64 + i * 16 + (lane & 15), lane)
   }
   // coalesced f32 tile store through LDS: two passes of 128 rows
   float* stagef = reinterpret_cast<float*>(smem_raw);
@@ -361,14 +290,7 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring_kernel(const WgArgs a)
               make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
     }
     __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int c = tid + 512 * it;                 // 128 rows x 32 float4 chunks
-      const int r = c >> 5, ch = c & 31;
-      const int m = m0 + pass * 128 + r, n = n0 + ch * 4;
-      if (m < P.n_out && n + 4 <= P.n_in)
-        store16_wt(P.dW + (int64_t)m * P.ld_dw + n, *reinterpret_cast<const uint4*>(stagef + r * PITCH + ch * 4));
-    }
+    WG_STORE_ROWS(512, 128, BN, P, stagef, m0 + pass * 128, n0, tid)
   }
 }
 
@@ -393,19 +315,10 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring4_kernel(const WgArgs a
   const int wm = wave >> 2, wn = wave & 3;
   const int nk_tile = a.ktiles * 2;                  // stages of 32 tokens per tile
 
-  int tile;
-  {
-    const int nwg = a.total_tiles, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  const int tile = xcd_remap(blockIdx.x, a.total_tiles);
   const int nk = nk_tile;
   constexpr int k_first = 0;
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < WG_MAXP; ++i)
-    if (i < a.n_problems && tile >= a.p[i].tile_begin) pi = i;
-  const WgProblem& P = a.p[pi];
+  WG_PROBLEM_OF_TILE(P, a, tile);
   const int t = tile - P.tile_begin;
   const int tm = t / P.tiles_n, tn = t - tm * P.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -452,11 +365,8 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring4_kernel(const WgArgs a
   for (int x = 0; x < 8; ++x) aoff[x] = lds0 + 2u * (fr * BM + (((wm * 8 + x) ^ ff) << 4) + ((li & 3) << 2));
 #pragma unroll
   for (int x = 0; x < 4; ++x) boff[x] = lds0 + 2u * (BK * BM + fr * BN + (((wn * 4 + x) ^ ff) << 4) + ((li & 3) << 2));
-  union Frag { struct { short4v a, b; } s; frag8_t v; };
-#define W2V2_TR4(f, addr)                                                                              \
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.s.a) : "v"(addr) : "memory");                      \
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "=v"(f.s.b) : "v"(addr) : "memory")
-  static_assert(4 * BM * 2 == 2048 && 4 * BN * 2 == 2048, "second transposing read = +4 token rows");
+  constexpr int R4 = 4 * BM * 2;                     // second transposing read of a fragment = + 4 token rows
+  static_assert(BM == BN, "one row pitch for both operands");
 
   __builtin_amdgcn_s_barrier();
   if (nk > 0) stage(0, 0);
@@ -464,32 +374,26 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring4_kernel(const WgArgs a
   if (nk > 2) stage(2, 2);
 #pragma unroll 1
   for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (kt + 2 < nk) wait_vmcnt<8>();
+    else if (kt + 1 < nk) wait_vmcnt<4>();
+    else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (kt + 3 < nk) stage((kt + 3) & 3, kt + 3);
     const uint32_t sb = (uint32_t)(kt & 3) * (STAGE * 2u);
-    Frag bf_[4], af[8];
+    TrFrag bf_[4], af[8];
 #pragma unroll
-    for (int x = 0; x < 4; ++x) { const uint32_t ad = boff[x] + sb; W2V2_TR4(bf_[x], ad); }
+    for (int x = 0; x < 4; ++x) tr_read<0, R4>(bf_[x], boff[x] + sb);
 #pragma unroll
-    for (int x = 0; x < 4; ++x) { const uint32_t ad = aoff[x] + sb; W2V2_TR4(af[x], ad); }
+    for (int x = 0; x < 4; ++x) tr_read<0, R4>(af[x], aoff[x] + sb);
+    landed(bf_);
 #pragma unroll
-    for (int x = 0; x < 4; ++x) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bf_[x].s.a), "+v"(bf_[x].s.b));
+    for (int x = 0; x < 4; ++x) landed(af[x]);
 #pragma unroll
-    for (int x = 0; x < 4; ++x) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[x].s.a), "+v"(af[x].s.b));
-#pragma unroll
-    for (int x = 4; x < 8; ++x) { const uint32_t ad = aoff[x] + sb; W2V2_TR4(af[x], ad); }
+    for (int x = 4; x < 8; ++x) tr_read<0, R4>(af[x], aoff[x] + sb);
     __builtin_amdgcn_sched_barrier(0);     // the second half of the dY fragments lands under the first 16 MFMAs
     if (do_bias) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        union { frag8_t v; uint32_t p[4]; } u;
-        u.v = af[i].v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) bsum[i] = pair_sum_add<TE>(u.p[e], one2, bsum[i]);
-      }
+      for (int i = 0; i < 4; ++i) bsum[i] = wg_dbias_add<TE>(af[i].v, one2, bsum[i]);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -498,15 +402,10 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring4_kernel(const WgArgs a
         acc[i][j] = mfma16<TE>(bf_[j].v, af[i].v, acc[i][j]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int x = 4; x < 8; ++x) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[x].s.a), "+v"(af[x].s.b));
+    for (int x = 4; x < 8; ++x) landed(af[x]);
     if (do_bias) {
 #pragma unroll
-      for (int i = 4; i < 8; ++i) {
-        union { frag8_t v; uint32_t p[4]; } u;
-        u.v = af[i].v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) bsum[i] = pair_sum_add<TE>(u.p[e], one2, bsum[i]);
-      }
+      for (int i = 4; i < 8; ++i) bsum[i] = wg_dbias_add<TE>(af[i].v, one2, bsum[i]);
     }
 #pragma unroll
     for (int i = 4; i < 8; ++i)
@@ -514,17 +413,10 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring4_kernel(const WgArgs a
       for (int j = 0; j < 4; ++j)
         acc[i][j] = mfma16<TE>(bf_[j].v, af[i].v, acc[i][j]);
   }
-#undef W2V2_TR4
 
   if (do_bias) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float s = bsum[i];
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      const int m = m0 + wm * 128 + i * 16 + (lane & 15);
-      if ((lane >> 4) == 0 && m < P.n_out) P.dbias[m] = s;
-    }
+    for (int i = 0; i < 8; ++i) WG_DBIAS_STORE(P, bsum[i], m0 + wm * 128 + i * 16 + (lane & 15), lane)
   }
   // coalesced f32 tile store through LDS: four passes of 64 rows (fragments (p & 1) * 4 .. +3 of the waves wm == p >> 1)
   float* stagef = reinterpret_cast<float*>(smem_raw);
@@ -545,14 +437,7 @@ __global__ __launch_bounds__(512) void wgrad_grouped_ring4_kernel(const WgArgs a
       }
     }
     __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int c = tid + 512 * it;                 // 64 rows x 64 float4 chunks
-      const int r = c >> 6, ch = c & 63;
-      const int m = m0 + pass * 64 + r, n = n0 + ch * 4;
-      if (m < P.n_out && n + 4 <= P.n_in)
-        store16_wt(P.dW + (int64_t)m * P.ld_dw + n, *reinterpret_cast<const uint4*>(stagef + r * PITCH + ch * 4));
-    }
+    WG_STORE_ROWS(512, 64, BN, P, stagef, m0 + pass * 64, n0, tid)
   }
 }
 

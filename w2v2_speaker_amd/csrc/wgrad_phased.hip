@@ -31,46 +31,8 @@
 // multiples of 8; 16-byte aligned rows.
 #include "wgrad_common.h"
 
-template <int N> __device__ __forceinline__ void wgp_wait_vm() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-}
-__device__ __forceinline__ void wgp_wait_pieces(int n) {     // all but the n most recently issued DMA pieces have landed
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-  }
-}
-// wait until all but the `newer` most recently issued quarters (2 DMA pieces each) of this wave have landed
-__device__ __forceinline__ void wgp_wait_quarters(int newer) {
-  if (newer >= 4) wgp_wait_vm<8>();
-  else if (newer == 3) wgp_wait_vm<6>();
-  else if (newer == 2) wgp_wait_vm<4>();
-  else if (newer == 1) wgp_wait_vm<2>();
-  else wgp_wait_vm<0>();
-}
-
-union WgFrag { struct { short4v a, b; } s; frag8_t v; };
-// one MFMA fragment = two transposing reads (token rows r and r + 4 of the lane's 8-row group); OFF = byte offset of the
-// k-step / quarter.  asm: the builtin makes the compiler drain the DMA ring in front of every read (wgrad.hip).
-template <int OFF> __device__ __forceinline__ void wgp_read(WgFrag& f, uint32_t addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.s.a) : "v"(addr), "n"(OFF) : "memory");
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.s.b) : "v"(addr), "n"(OFF + 1024) : "memory");
-}
-__device__ __forceinline__ void wgp_landed(WgFrag& f) {   // LDS returns in order: ties the registers to the wait
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f.s.a), "+v"(f.s.b));
-}
-
+// one MFMA fragment = tr_read<OFF, OFF + 1024> (common.h): token rows r and r + 4 of the lane's 8-row group, OFF = byte
+// offset of the k-step / quarter
 // LATE = how many of the two DMA pieces of a phase are issued between its MFMAs instead of in its read segment
 template <typename TE, int LATE>
 __global__ __launch_bounds__(512) void wgrad_grouped_phased_kernel(const WgArgs a) {
@@ -84,17 +46,8 @@ __global__ __launch_bounds__(512) void wgrad_grouped_phased_kernel(const WgArgs 
   const int wr = wave >> 2, wc = wave & 3;
   const int nk = a.ktiles;                          // K tiles of 64 tokens
 
-  int tile;
-  {
-    const int nwg = a.total_tiles, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < WG_MAXP; ++i)
-    if (i < a.n_problems && tile >= a.p[i].tile_begin) pi = i;
-  const WgProblem& P = a.p[pi];
+  const int tile = xcd_remap(blockIdx.x, a.total_tiles);
+  WG_PROBLEM_OF_TILE(P, a, tile);
   const int t = tile - P.tile_begin;
   const int tm = t / P.tiles_n, tn = t - tm * P.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -186,11 +139,11 @@ __global__ __launch_bounds__(512) void wgrad_grouped_phased_kernel(const WgArgs 
   // ---- prologue: K tile 0 entirely, QA0 / QB0 of K tile 1 (issue order = consumption order)
   issue(0, 0); issue(1, 0); issue(2, 0); issue(3, 0);
   if (nk > 1) { issue(0, 1); issue(1, 1); }
-  wgp_wait_quarters(2 + (nk > 1 ? 2 : 0));           // QA0(0), QB0(0) landed (this wave's pieces)
+  wait_quarters(2 + (nk > 1 ? 2 : 0));               // QA0(0), QB0(0) landed (this wave's pieces)
   __builtin_amdgcn_s_barrier();                      // ... everyone's
   if (wr == 1) __builtin_amdgcn_s_barrier();         // group 1 runs one barrier behind from here on
 
-  WgFrag af[4][2], b0[2][2], b1[2][2];
+  TrFrag af[4][2], b0[2][2], b1[2][2];
   int bufd = BUFB;                                   // + BUFB / - BUFB: the address registers hop between the two buffers
 #pragma unroll 1
   for (int kt = 0; kt < nk; ++kt) {
@@ -198,21 +151,21 @@ __global__ __launch_bounds__(512) void wgrad_grouped_phased_kernel(const WgArgs 
     // ---------------- phase 1: read B0 + A lo; issue QB1(kt+1); MFMA A lo x B0
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      wgp_read<0>(b0[s][0], boff[s]);
-      wgp_read<KSTEP>(b0[s][1], boff[s]);
+      tr_read<0, 1024>(b0[s][0], boff[s]);
+      tr_read<KSTEP, KSTEP + 1024>(b0[s][1], boff[s]);
     }
 #pragma unroll
     for (int x = 0; x < 4; ++x) {
-      wgp_read<0>(af[x][0], aoff[x]);
-      wgp_read<KSTEP>(af[x][1], aoff[x]);
+      tr_read<0, 1024>(af[x][0], aoff[x]);
+      tr_read<KSTEP, KSTEP + 1024>(af[x][1], aoff[x]);
     }
     if (more1) issue_early(2, kt + 1);
-    wgp_wait_pieces(2 + (more1 ? 6 - LATE : 0));     // QB1(kt) for phase 2
+    wait_pieces(2 + (more1 ? 6 - LATE : 0));         // QB1(kt) for phase 2
     __builtin_amdgcn_s_barrier();
 #pragma unroll
-    for (int s = 0; s < 2; ++s) { wgp_landed(b0[s][0]); wgp_landed(b0[s][1]); }
+    for (int s = 0; s < 2; ++s) landed(b0[s]);
 #pragma unroll
-    for (int x = 0; x < 4; ++x) { wgp_landed(af[x][0]); wgp_landed(af[x][1]); }
+    for (int x = 0; x < 4; ++x) landed(af[x]);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
     W2V2_WGP_MFMA(0, 0, b0, more1, 2, kt + 1)
@@ -221,25 +174,20 @@ __global__ __launch_bounds__(512) void wgrad_grouped_phased_kernel(const WgArgs 
 #pragma unroll
       for (int x = 0; x < 4; ++x)
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          union { frag8_t v; uint32_t p[4]; } u;
-          u.v = af[x][kk].v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) bsum[x] = pair_sum_add<TE>(u.p[e], one2, bsum[x]);
-        }
+        for (int kk = 0; kk < 2; ++kk) bsum[x] = wg_dbias_add<TE>(af[x][kk].v, one2, bsum[x]);
     }
     __builtin_amdgcn_s_barrier();
     // ---------------- phase 2: read B1; issue QA1(kt+1); MFMA A lo x B1
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      wgp_read<QB>(b1[s][0], boff[s]);
-      wgp_read<QB + KSTEP>(b1[s][1], boff[s]);
+      tr_read<QB, QB + 1024>(b1[s][0], boff[s]);
+      tr_read<QB + KSTEP, QB + KSTEP + 1024>(b1[s][1], boff[s]);
     }
     if (more1) issue_early(3, kt + 1);
-    wgp_wait_pieces(more1 ? 8 - LATE : 0);           // QA1(kt) for phase 3
+    wait_pieces(more1 ? 8 - LATE : 0);               // QA1(kt) for phase 3
     __builtin_amdgcn_s_barrier();
 #pragma unroll
-    for (int s = 0; s < 2; ++s) { wgp_landed(b1[s][0]); wgp_landed(b1[s][1]); }
+    for (int s = 0; s < 2; ++s) landed(b1[s]);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
     W2V2_WGP_MFMA(0, 2, b1, more1, 3, kt + 1)
@@ -248,13 +196,13 @@ __global__ __launch_bounds__(512) void wgrad_grouped_phased_kernel(const WgArgs 
     // ---------------- phase 3: read A hi; issue QA0(kt+2); MFMA A hi x B1
 #pragma unroll
     for (int x = 0; x < 4; ++x) {
-      wgp_read<QB>(af[x][0], aoff[x]);
-      wgp_read<QB + KSTEP>(af[x][1], aoff[x]);
+      tr_read<QB, QB + 1024>(af[x][0], aoff[x]);
+      tr_read<QB + KSTEP, QB + KSTEP + 1024>(af[x][1], aoff[x]);
     }
     if (more2) issue_early(0, kt + 2);
     __builtin_amdgcn_s_barrier();
 #pragma unroll
-    for (int x = 0; x < 4; ++x) { wgp_landed(af[x][0]); wgp_landed(af[x][1]); }
+    for (int x = 0; x < 4; ++x) landed(af[x]);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
     W2V2_WGP_MFMA(4, 2, b1, more2, 0, kt + 2)
@@ -263,17 +211,12 @@ __global__ __launch_bounds__(512) void wgrad_grouped_phased_kernel(const WgArgs 
 #pragma unroll
       for (int x = 0; x < 4; ++x)
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          union { frag8_t v; uint32_t p[4]; } u;
-          u.v = af[x][kk].v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) bsum[4 + x] = pair_sum_add<TE>(u.p[e], one2, bsum[4 + x]);
-        }
+        for (int kk = 0; kk < 2; ++kk) bsum[4 + x] = wg_dbias_add<TE>(af[x][kk].v, one2, bsum[4 + x]);
     }
     __builtin_amdgcn_s_barrier();
     // ---------------- phase 4: (operands in registers); issue QB0(kt+2); MFMA A hi x B0
     if (more2) issue_early(1, kt + 2);
-    if (more1) wgp_wait_pieces(4 + (more2 ? 4 - LATE : 0));   // QA0(kt+1), QB0(kt+1) for the next K tile's phase 1
+    if (more1) wait_pieces(4 + (more2 ? 4 - LATE : 0));   // QA0(kt+1), QB0(kt+1) for the next K tile's phase 1
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
@@ -292,13 +235,7 @@ __global__ __launch_bounds__(512) void wgrad_grouped_phased_kernel(const WgArgs 
 
   if (do_bias) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float s = bsum[i];
-      s += __shfl_xor(s, 16, 64);
-      s += __shfl_xor(s, 32, 64);
-      const int m = m0 + (i >> 2) * 128 + wr * 64 + (i & 3) * 16 + li;
-      if (lg == 0 && m < P.n_out) P.dbias[m] = s;
-    }
+    for (int i = 0; i < 8; ++i) WG_DBIAS_STORE(P, bsum[i], m0 + (i >> 2) * 128 + wr * 64 + (i & 3) * 16 + li, lane)
   }
   // coalesced f32 tile store through LDS: pass p = rows m0 + 64 p .. + 63 = fragments (p >> 1) * 4 .. + 3 of the waves
   // with wr == (p & 1); a lane holds 4 consecutive n_in of row li per accumulator
@@ -319,14 +256,7 @@ __global__ __launch_bounds__(512) void wgrad_grouped_phased_kernel(const WgArgs 
       }
     }
     __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int c = tid + 512 * it;                  // 64 rows x 64 float4 chunks
-      const int r = c >> 6, ch = c & 63;
-      const int m = m0 + pass * 64 + r, n = n0 + ch * 4;
-      if (m < P.n_out && n + 4 <= P.n_in)
-        store16_wt(P.dW + (int64_t)m * P.ld_dw + n, *reinterpret_cast<const uint4*>(stagef + r * PITCH + ch * 4));
-    }
+    WG_STORE_ROWS(512, 64, BN, P, stagef, m0 + pass * 64, n0, tid)
   }
 }
 
