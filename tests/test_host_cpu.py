@@ -850,3 +850,28 @@ def test_wgrad_routing_table():
         assert len(got) == len(want) == len(g.CASES)
         wrong = [(g.CASES[i][0], got[i], want[i]) for i in range(len(want)) if got[i] != want[i]]
         assert not wrong, (name, wrong)
+
+
+def test_plan_cache_hits_and_least_recently_used_eviction():
+    from w2v2_speaker_amd.eval_batching import PlanCache
+    evicted = []
+    cache = PlanCache(2, on_evict=evicted.append)
+    one = cache.lookup(1, object)
+    assert cache.lookup(1, object) is one and cache.built == 1       # a hit: the same object, not counted as built
+    cache.lookup(2, object)
+    assert cache.lookup(1, object) is one                            # touch key 1: key 2 is now the least recently used
+    cache.lookup(3, object)
+    assert list(cache) == [1, 3] and evicted == [2] and cache.built == 3
+    assert cache.lookup(1, object) is one and cache.built == 3
+    assert cache.lookup(2, object) is not None and evicted == [2, 3] and cache.built == 4      # rebuilt after eviction
+
+
+def test_plan_cache_without_bound_keeps_everything():
+    from w2v2_speaker_amd.eval_batching import PlanCache
+    evicted = []
+    cache = PlanCache(None, on_evict=evicted.append)
+    made = [cache.lookup(k, object) for k in range(100)]
+    assert len(cache) == 100 and cache.built == 100 and not evicted
+    assert all(cache.lookup(k, object) is made[k] for k in range(100)) and cache.built == 100
+    cache.clear()
+    assert len(cache) == 0

@@ -56,6 +56,35 @@ def test_plan_batches_long_utterance_runs_alone_and_defaults():
         plan_batches([0, 5], 16000, 1000, 4)
 
 
+@pytest.mark.parametrize("feature_dims", [(), (3,)])
+def test_padded_batches_fill_the_planned_batches(feature_dims):
+    """1-D waveforms and [T, 3] features: every utterance sits in exactly one (batch, row), zero-padded to the planned
+    length; unused rows are all zero and carry the fill length."""
+    import torch
+    from w2v2_speaker_amd.eval_batching import padded_batches, plan_batches
+    lens, quantum, cap, max_batch, fill = [5, 12, 7, 12, 3], 4, 24, 2, 2
+    g = torch.Generator().manual_seed(11)
+    utts = [torch.rand(n, *feature_dims, generator=g) + 0.5 for n in lens]          # no zero inside an utterance
+    planned = plan_batches(lens, quantum, cap, max_batch)
+    got = list(padded_batches(utts, quantum, cap, max_batch, fill, "cpu"))
+    assert len(got) == len(planned) >= 2
+    placed, unused_rows = [], 0
+    for (idx, padded, row_lens), (pidx, n, batch) in zip(got, planned):
+        assert tuple(idx) == pidx and padded.shape == (batch, n) + feature_dims and padded.dtype == torch.float32
+        assert len(row_lens) == batch == max_batch
+        for j in range(batch):
+            if j < len(idx):
+                u = utts[idx[j]]
+                assert row_lens[j] == lens[idx[j]] == u.shape[0]
+                assert torch.equal(padded[j, :u.shape[0]], u) and not padded[j, u.shape[0]:].any()
+                placed.append(idx[j])
+            else:
+                assert row_lens[j] == fill and not padded[j].any()
+                unused_rows += 1
+    assert sorted(placed) == list(range(5)) and len(placed) == 5        # a permutation of the inputs
+    assert unused_rows == 1                                             # the bucket of the 3-sample utterance
+
+
 def test_length_validation_errors():
     import torch
     from w2v2_speaker_amd.config import W2V2Config

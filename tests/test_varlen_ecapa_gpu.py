@@ -397,7 +397,7 @@ def test_ecapa_evaluate_trials_matches_per_utterance_path():
     keys, feats, pairs = _trial_set(lambda w, n: w[:n * F_].view(n, F_), 20, 400)     # frames cut out of the waveform
     got = mod.evaluate_trials(pairs, feats, quantum=50, max_batch_frames=4 * 400, max_batch=4)
     outs = [{"embedding": mod.compute_speaker_embedding(feats[k]).cpu(), "sample_id": [k]} for k in keys]
-    _assert_same_scores(got, mod._evaluate(outs, pairs), len(pairs))
+    _assert_same_scores(got, mod._evaluate_embeddings(outs, pairs), len(pairs))
 
 
 def _attentive_module(dtype):

@@ -14,6 +14,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .trainer import GradBucketReducer
 
 
 class RcclComm:
@@ -110,29 +111,20 @@ def signature_agrees(summed, world: int) -> bool:
     return all(world * int(summed[h + i]) == int(summed[i]) ** 2 for i in range(h))
 
 
-class CAbiBucketAllReducer:
+class CAbiBucketAllReducer(GradBucketReducer):
     """Drop-in for trainer.BucketAllReducer (same ``bucket_ready`` / ``wait`` / ``world`` / ``ranges`` / ``members``)
     whose collective is w2v2_allreduce_async on a side HIP stream."""
 
     def __init__(self, store, comm: RcclComm, bucket_merge: int = 2):
-        from .trainer import BucketAllReducer
-        self.comm, self.store, self.world = comm, store, comm.world
-        self.ranges, self.members = BucketAllReducer.merge_buckets(store.grad_buckets(), bucket_merge)
-        self.comm_stream = torch.cuda.Stream()
+        super().__init__(store, comm.world, bucket_merge)
+        self.comm = comm
         self._issued = False
-        self.buffer = None         # the arena bucket_ready() reduces; None = store.grad (see trainer.BucketAllReducer)
 
     def bucket_ready(self, name: str) -> None:
-        if self.world == 1 or name not in self.ranges:
-            return
-        s, e = self.ranges[name]
-        if e <= s:
-            return
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self.comm_stream.wait_event(ev)
-        self.comm.all_reduce_((self.buffer if self.buffer is not None else self.store.grad)[s:e], self.comm_stream)
-        self._issued = True
+        view = self.ready_slice(name)
+        if view is not None:
+            self.comm.all_reduce_(view, self.comm_stream)
+            self._issued = True
 
     def broadcast_parameters(self, root: int = 0, host_counters=None):
         """Same contract as trainer.BucketAllReducer.broadcast_parameters (device state + the host-side step counters),

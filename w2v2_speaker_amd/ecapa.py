@@ -21,7 +21,6 @@ import math
 from collections import OrderedDict
 from typing import Dict, List, Optional, Tuple
 
-import numpy as np
 import torch
 
 from . import ops
@@ -29,10 +28,10 @@ from .asp import AttentivePool
 from .heads import ClassifierHead
 from .ops import EPI_ADD, EPI_BIAS, EPI_NONE, Gemm
 from .optim import OptimConfig, fused
+from .params import ALIGN, FlatArena
 
 FE = "feature_extractor."          # reference attribute name of the ECAPA_TDNN module (ecapa_tdnn.py:75)
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
-ALIGN = 64
 
 
 @dataclasses.dataclass
@@ -143,28 +142,22 @@ def ecapa_param_shapes(cfg: EcapaConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     return s
 
 
-class EcapaStore:
-    """Flat parameter arena (f32 master, gradient, Adam moments, bf16 operand copy) of the ECAPA model + AAM head;
-    the subset of ParamStore's interface that AttentivePool / ClassifierHead / the plan below use."""
+class EcapaStore(FlatArena):
+    """Flat parameter arena (f32 master, gradient, Adam moments, bf16 operand copy) of the ECAPA model + AAM head: the
+    whole arena trains, and there is no loss-scale record."""
+    PREFIX = FE
+    BATCHES_TRACKED = "bn_batches_tracked"
 
     def __init__(self, cfg: EcapaConfig, device, act_dtype: torch.dtype = torch.bfloat16, num_speakers: int = 5994):
         assert act_dtype in (torch.bfloat16, torch.float32), "ECAPA: bf16 or f32 (the reference runs it in fp32; no loss scaler here)"
-        self.cfg, self.device, self.act_dtype, self.num_speakers = cfg, torch.device(device), act_dtype, num_speakers
+        self.cfg, self.act_dtype, self.num_speakers = cfg, act_dtype, num_speakers
         self.embed_dim = cfg.lin_neurons
         shapes: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
         shapes["loss_fn.fc_weights"] = (num_speakers, cfg.lin_neurons)
         shapes.update(ecapa_param_shapes(cfg))
-        self.shapes, self.offsets = shapes, {}
-        off = 0
-        for n, s in shapes.items():
-            self.offsets[n] = off
-            off += (int(np.prod(s)) + ALIGN - 1) // ALIGN * ALIGN
-        self.n_total = self.n_train = off
+        super().__init__(shapes, device)
         dev = self.device
-        self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.exp_avg = self.exp_avg_sq = None
-        self.flat_lp = torch.zeros(off, dtype=act_dtype, device=dev) if ops.is16(act_dtype) else None
+        self.flat_lp = torch.zeros(self.n_total, dtype=act_dtype, device=dev) if ops.is16(act_dtype) else None
         # BatchNorm1d buffers of EVERY norm layer live in the store (shared by the training and the evaluation plans,
         # saved / loaded under the speechbrain names ``...norm.running_mean`` / ``running_var``): one f32 record
         # {running_mean[C], running_var[C]} per layer, keyed by the name of its ``.weight``
@@ -174,32 +167,18 @@ class EcapaStore:
                 self.bn_running[n] = torch.cat([torch.zeros(shp[0]), torch.ones(shp[0])]).to(dev)
         self.asp_running = self.bn_running[FE + "asp.tdnn.norm.norm.weight"]
         self.bn_batches_tracked = 0
-        self.version, self.step_count = 0, 0
-        self.optim_algo: Optional[str] = None          # see ParamStore
-        self.grad_norm = torch.zeros(2, dtype=torch.float32, device=dev)
-        self.track_grad_norm = False
-        self.grad_acc: Optional[torch.Tensor] = None   # see ParamStore
-        self.accum_count = 0
 
     def running(self, weight_name: str) -> torch.Tensor:
         """{running_mean, running_var} record of the BatchNorm whose scale parameter is ``weight_name``."""
         return self.bn_running[weight_name]
 
-    def _buffer_views(self) -> "OrderedDict[str, torch.Tensor]":
+    def _buffers(self) -> "OrderedDict[str, torch.Tensor]":
         out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
         for n, r in self.bn_running.items():
             C = r.numel() // 2
             base = n[:-len("weight")]
             out[base + "running_mean"], out[base + "running_var"] = r[:C], r[C:]
         return out
-
-    def _view(self, buf, name):
-        s, o = self.shapes[name], self.offsets[name]
-        return buf[o:o + int(np.prod(s))].view(*s)
-
-    def p(self, name): return self._view(self.flat, name)
-    def g(self, name): return self._view(self.grad, name)
-    def w(self, name): return self._view(self.flat_lp if self.flat_lp is not None else self.flat, name)
 
     def sync_lowp(self) -> None:
         if self.flat_lp is not None:
@@ -214,39 +193,6 @@ class EcapaStore:
         else:
             self.grad.zero_()
 
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> None:
-        seen = set()
-        bufs = self._buffer_views()
-        for k, v in sd.items():
-            bk = k if k in bufs else (FE + k if FE + k in bufs else None)
-            if bk is not None:                             # BatchNorm running statistics
-                bufs[bk].copy_(torch.as_tensor(v).to(self.device, torch.float32))
-                continue
-            if k.endswith("num_batches_tracked"):
-                self.bn_batches_tracked = int(v)
-                continue
-            name = k if k in self.shapes else (FE + k if FE + k in self.shapes else None)
-            if name is None:
-                if strict:
-                    raise KeyError(f"unexpected key {k}")
-                continue
-            t = torch.as_tensor(v).to(torch.float32)
-            if tuple(t.shape) != tuple(self.shapes[name]):
-                raise ValueError(f"{name}: shape {tuple(t.shape)} != {self.shapes[name]}")
-            self.p(name).copy_(t.to(self.device))
-            seen.add(name)
-        if strict and len(seen) != len(self.shapes):
-            raise KeyError(f"missing keys: {[n for n in self.shapes if n not in seen][:5]}")
-        self.sync_lowp()
-
-    def state_dict(self):
-        sd = OrderedDict((n, self.p(n).detach().clone().cpu()) for n in self.shapes)
-        for n, b in self._buffer_views().items():
-            sd[n] = b.detach().clone().cpu()
-            if n.endswith("running_var"):
-                sd[n[:-len("running_var")] + "num_batches_tracked"] = torch.tensor(self.bn_batches_tracked)
-        return sd
-
     def init_weights(self, seed: int = 20211) -> None:
         g = torch.Generator(device="cpu").manual_seed(seed)
         for n, s in self.shapes.items():
@@ -260,11 +206,6 @@ class EcapaStore:
                 t = (torch.rand(s, generator=g) * 2 - 1) / math.sqrt(s[1] * s[2])
             self.p(n).copy_(t.to(self.device))
         self.sync_lowp()
-
-    def adam_step(self, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
-                  grad_scale: float = 1.0) -> None:
-        """Fused Adam without weight decay or clipping: optimizer_step() with the default description."""
-        self.optimizer_step(lr, beta1, OptimConfig(beta2=beta2, eps=eps), grad_scale)
 
     def optimizer_step(self, lr: float, momentum_or_beta1: float = 0.9, cfg: Optional[OptimConfig] = None,
                        grad_scale: float = 1.0, gradient_clip_val: float = 0.0, head_only: bool = False,
@@ -788,7 +729,7 @@ class EcapaPlan:
                 t.finish_weight_grad()
 
 
-class EcapaTrainer:
+class EcapaTrainer(fused.WindowedTrainer):
     """One training step: forward, AAM head, backward, fused Adam (ref: speaker_recognition_module.py:207-220)."""
 
     def __init__(self, store: EcapaStore, plan: EcapaPlan, schedule, process_group=None,
@@ -796,17 +737,13 @@ class EcapaTrainer:
                  accumulate_grad_batches: int = 1):
         """optimizer (None = Adam, beta2 0.999, eps 1e-8, no weight decay) / gradient_clip_val / accumulate_grad_batches:
         see SpeakerTrainer."""
-        if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
-            raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {accumulate_grad_batches!r}")
-        self.accumulate_grad_batches = int(accumulate_grad_batches)
-        self.stepped = False               # whether the last train_step / flush call ran the optimiser
-        self.store, self.plan, self.schedule, self.step = store, plan, schedule, 0
-        self.optimizer, self.gradient_clip_val = optimizer, float(gradient_clip_val)
         self.pg = process_group                      # data parallel: ONE all-reduce of the flat gradient arena (25 MB)
-        self.world = 1
+        world = 1
         if process_group is not None:
             import torch.distributed as dist
-            self.world = dist.get_world_size(process_group)
+            world = dist.get_world_size(process_group)
+        super().__init__(store, schedule, optimizer, gradient_clip_val, accumulate_grad_batches, world)
+        self.plan = plan
 
     def _embed(self, x: torch.Tensor) -> None:
         """[B, T, n_mels] filterbank features, or [B, N] waveforms through the device front-end."""
@@ -815,6 +752,11 @@ class EcapaTrainer:
         else:
             self.plan.embed(x)
 
+    def _all_reduce(self, arena: torch.Tensor) -> None:
+        if self.world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(arena, group=self.pg)
+
     def train_step(self, feat: torch.Tensor, label: torch.Tensor):
         if self.accumulate_grad_batches > 1:
             return self._micro_batch(feat, label)
@@ -822,19 +764,15 @@ class EcapaTrainer:
         self._embed(feat)
         loss, softmax = self.plan.head_forward_backward(label)
         self.plan.backward()
-        if self.world > 1:
-            import torch.distributed as dist
-            dist.all_reduce(self.store.grad, group=self.pg)
-        lr, second = self.schedule.at(self.step)           # beta1 under Adam, the momentum under SGD
-        self.store.optimizer_step(lr, second, self.optimizer, 1.0 / self.world, self.gradient_clip_val)
-        self.step += 1
+        self._all_reduce(self.store.grad)
+        self._optimizer_step()
         self.stepped = True
         return loss, softmax
 
     def _micro_batch(self, feat: torch.Tensor, label: torch.Tensor):
-        """One micro-batch of an accumulation window (SpeakerTrainer's protocol with the single all-reduce): the gradient
-        is added into store.grad_acc, the N-th call all-reduces that arena and steps.  The BatchNorm running statistics
-        move on every micro-batch, as in torch."""
+        """One micro-batch of an accumulation window: the gradient is added into store.grad_acc, the N-th call all-reduces
+        that arena (one synchronous collective on the compute stream) and steps.  The BatchNorm running statistics move
+        on every micro-batch, as in torch."""
         store = self.store
         store.zero_grad()
         self._embed(feat)
@@ -844,24 +782,9 @@ class EcapaTrainer:
         store.accum_count += 1
         self.stepped = store.accum_count == self.accumulate_grad_batches
         if self.stepped:
+            self._reduce_window()
             self._close_window()
         return loss, softmax
 
-    def _close_window(self) -> None:
-        store = self.store
-        if self.world > 1:
-            import torch.distributed as dist
-            dist.all_reduce(store.grad_acc, group=self.pg)
-        lr, second = self.schedule.at(self.step)
-        store.optimizer_step(lr, second, self.optimizer, 1.0 / (self.world * self.accumulate_grad_batches),
-                             self.gradient_clip_val, grad=store.grad_acc)
-        self.step += 1
-        store.accum_count = 0
-
-    def flush(self) -> None:
-        """Close a partial window: step on what has been accumulated, still divided by world * N (see SpeakerTrainer)."""
-        self.stepped = False
-        if self.accumulate_grad_batches == 1 or self.store.accum_count == 0:
-            return
-        self._close_window()
-        self.stepped = True
+    def _reduce_window(self) -> None:
+        self._all_reduce(self.store.grad_acc)

@@ -1,4 +1,5 @@
-"""Length bucketing for batched variable-length evaluation (host only: no device work, testable on the CPU).
+"""Length bucketing for batched variable-length evaluation, the padded batches cut by it and the cache of the static
+plans that run them (no kernels: testable on the CPU).
 
 Utterances are sorted by length, each is given a padded length (its length rounded up to ``quantum`` samples; all
 utterances with the same padded length form a bucket) and every bucket is cut into batches of at most
@@ -8,7 +9,10 @@ with dummy audio and drops their outputs), so one static plan serves the whole b
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from collections import OrderedDict
+from typing import Callable, Iterator, List, Optional, Sequence, Tuple
+
+import torch
 
 DEFAULT_QUANTUM = 32000                      # 2 s at 16 kHz
 DEFAULT_MAX_BATCH_SAMPLES = 66 * 48000       # the benchmark's training batch: an eval plan never holds more audio
@@ -45,6 +49,43 @@ def plan_batches(lengths: Sequence[int], quantum: int = DEFAULT_QUANTUM,
             out.append((tuple(order[k:min(k + batch, j)]), padded, batch))
         i = j
     return out
+
+
+def padded_batches(utterances: Sequence[torch.Tensor], quantum: int, max_batch_samples: int, max_batch: int, fill: int,
+                   device) -> Iterator[Tuple[Tuple[int, ...], torch.Tensor, List[int]]]:
+    """The batches of plan_batches over ``utterances`` (1-D waveforms [N], or [T, F] features: the length is dim 0, in
+    the unit of ``quantum`` and ``max_batch_samples``), filled: -> (indices, padded, lens) per batch, ``padded`` the zero
+    f32 batch [batch, padded_n, ...] on ``device`` with utterance indices[j] copied into row j, ``lens`` its valid
+    length per row.  Unused rows of a bucket's last batch stay zero and get ``fill``, the shortest length the model
+    takes; the caller drops their outputs."""
+    for idx, n, batch in plan_batches([x.shape[0] for x in utterances], quantum, max_batch_samples, max_batch):
+        padded = torch.zeros(batch, n, *utterances[idx[0]].shape[1:], dtype=torch.float32, device=device)
+        lens = [fill] * batch
+        for j, i in enumerate(idx):
+            padded[j, :utterances[i].shape[0]].copy_(utterances[i])
+            lens[j] = utterances[i].shape[0]
+        yield idx, padded, lens
+
+
+class PlanCache(OrderedDict):
+    """Static plans by shape key, least recently used first.  ``bound``: how many are kept (None: all of them);
+    ``on_evict(key)`` is told which plan went; ``built`` counts the misses."""
+
+    def __init__(self, bound: Optional[int] = None, on_evict: Optional[Callable] = None):
+        super().__init__()
+        self.bound, self.on_evict, self.built = bound, on_evict, 0
+
+    def lookup(self, key, build: Callable):
+        if key in self:
+            self.move_to_end(key)
+            return self[key]
+        plan = self[key] = build()
+        self.built += 1
+        while self.bound is not None and len(self) > self.bound:
+            old, _ = self.popitem(last=False)
+            if self.on_evict is not None:
+                self.on_evict(old)
+        return plan
 
 
 def plan_pair_batches(left_frames: Sequence[int], right_frames: Sequence[int], quantum: int = DEFAULT_PAIR_QUANTUM,

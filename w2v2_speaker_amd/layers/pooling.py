@@ -9,6 +9,7 @@ import random
 import torch
 
 from .. import ops
+from ..params import FlatArena
 
 
 class _PoolFn(torch.autograd.Function):
@@ -102,34 +103,16 @@ class QuantilePool1D(torch.nn.Module):
         return _PoolFn.apply(_btf(tensor, self.dim_to_reduce), ops.POOL_MODES["quantile"])
 
 
-class _AspStore:
-    """The slice of ParamStore's interface that asp.AttentivePool needs, over the parameters of ONE pooling module."""
+class _AspStore(FlatArena):
+    """The arena of ONE pooling module: what asp.AttentivePool needs of a store."""
 
     def __init__(self, channels: int, attention_channels: int, device, act_dtype: torch.dtype):
         from ..asp import ASP_PREFIX, asp_param_shapes
-        self.prefix = ASP_PREFIX
-        self.shapes = asp_param_shapes(channels, attention_channels)
-        self.device, self.act_dtype = torch.device(device), act_dtype
-        self.offsets, off = {}, 0
-        for n, shp in self.shapes.items():
-            self.offsets[n] = off
-            off += (int(torch.tensor(shp).prod()) + 63) // 64 * 64
-        self.flat = torch.zeros(off, dtype=torch.float32, device=device)
-        self.grad = torch.zeros(off, dtype=torch.float32, device=device)
-        self.flat_lp = torch.zeros(off, dtype=act_dtype, device=device) if ops.is16(act_dtype) else None
+        super().__init__(asp_param_shapes(channels, attention_channels), device)
+        self.prefix, self.act_dtype = ASP_PREFIX, act_dtype
+        self.flat_lp = torch.zeros(self.n_total, dtype=act_dtype, device=device) if ops.is16(act_dtype) else None
         self.asp_running = torch.cat([torch.zeros(attention_channels), torch.ones(attention_channels)]).to(device)
         self.asp_batches_tracked = 0
-
-    def _view(self, buf, name):
-        shp, o = self.shapes[name], self.offsets[name]
-        n = 1
-        for d in shp:
-            n *= d
-        return buf[o:o + n].view(*shp)
-
-    def p(self, name): return self._view(self.flat, name)
-    def g(self, name): return self._view(self.grad, name)
-    def w(self, name): return self._view(self.flat_lp if self.flat_lp is not None else self.flat, name)
 
     def sync_lowp(self):
         if self.flat_lp is not None:

@@ -3,15 +3,28 @@ src/lightning_modules/base_lightning_module.py:58-62,70-75), shared by the three
 torch optimiser and scheduler over ``network.parameters()`` from its configuration and hands them to the module (ref:
 src/main.py:323-335); here the two objects are READ -- class and first param group through ``OptimConfig.from_torch``,
 the scheduler through ``schedule.from_torch_scheduler`` -- and the fused step runs what they describe.  The torch
-optimiser itself is never stepped (manual optimisation, see Wav2vec2FCModule)."""
+optimiser itself is never stepped (manual optimisation, see Wav2vec2FCModule).
+
+Next to it the other pieces the modules share: the trainer-per-plan-shape step of ``training_step``, the waveform
+input forms, and (EmbeddingEvaluation) the evaluation surface of the two modules that score trials by embeddings."""
 from __future__ import annotations
 
-from typing import Optional
+from typing import Callable, List, Optional
 
 import torch
 
+from ...evaluation.speaker.cosine_distance import EmbeddingSample
 from ...optim import OptimConfig
 from ...optim.schedule import from_torch_scheduler
+
+
+def prep_waveform_input(input_tensor: torch.Tensor) -> torch.Tensor:
+    # ref: wav2vec2_fc.py:414-421 -- [BS,1,N] or [1,N] or [N] -> [BS,N]
+    if len(input_tensor.shape) == 3 and input_tensor.shape[1] == 1:
+        input_tensor = input_tensor[:, 0, :]
+    if len(input_tensor.shape) == 1:
+        input_tensor = torch.stack([input_tensor])
+    return input_tensor
 
 
 class OptimizerSurface:
@@ -55,6 +68,17 @@ class OptimizerSurface:
             raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {n!r}")
         self.accumulate_grad_batches = int(n)
 
+    def _trainer_step(self, key, build: Callable, run: Callable):
+        """One ``training_step`` call on the trainer of plan shape ``key`` (``build()`` makes it on first use; the module
+        keeps one per shape over its one store): ``run(trainer)`` at the module's schedule position."""
+        tr = self._trainers.get(key)
+        if tr is None:
+            tr = self._trainers[key] = build()
+        tr.step = self.schedule_step
+        out = run(tr)
+        self._after_micro_batch(tr)
+        return out
+
     def _after_micro_batch(self, trainer) -> None:
         """``training_step`` bookkeeping: the schedule advances only when the trainer ran the optimiser (every call at
         ``accumulate_grad_batches`` = 1)."""
@@ -74,9 +98,9 @@ class OptimizerSurface:
         tr.flush()
         self._after_micro_batch(tr)
 
-    def parameters(self, recurse: bool = True):
-        """One ``nn.Parameter`` view of the flat arena per parameter (``.grad`` = the matching gradient view), so that
-        the reference's ``instantiate(cfg.optim.algo, params=network.parameters())`` has something to hold."""
+    def _parameter_views(self) -> dict:
+        """name -> one ``nn.Parameter`` view of the flat arena per parameter (``.grad`` = the matching gradient view), so
+        that the reference's ``instantiate(cfg.optim.algo, params=network.parameters())`` has something to hold."""
         if getattr(self, "_param_views", None) is None:
             store = self.store
             # reference registration order where the store knows it (the speaker heads of ParamStore), arena order else
@@ -88,4 +112,46 @@ class OptimizerSurface:
                 if store.offsets[n] < store.n_train:
                     p.grad = store.g(n)
                 self._param_views[n] = p
-        yield from self._param_views.values()
+        return self._param_views
+
+    def parameters(self, recurse: bool = True):
+        yield from self._parameter_views().values()
+
+
+class EmbeddingEvaluation:
+    """Validation / test surface of the modules whose trials are scored by the cosine of two speaker embeddings
+    (Wav2vec2FCModule, EcapaTdnnModule; ref: speaker_recognition_module.py:451-519) over their
+    ``compute_speaker_embedding(s)``, ``evaluator`` and ``validation_pairs`` / ``test_pairs``."""
+
+    def validation_step(self, batch, batch_idx: int = 0):
+        emb = self.compute_speaker_embedding(batch.network_input)
+        return {"embedding": emb.detach().to("cpu"), "sample_id": batch.keys}
+
+    def test_step(self, batch, batch_idx: int = 0):
+        if batch.batch_size != 1:
+            raise ValueError("expecting a batch size of 1 for evaluating speaker embeddings")   # ref: :468-469
+        return self.validation_step(batch, batch_idx)
+
+    def _evaluate_embeddings(self, outputs: List[dict], pairs):
+        samples = [EmbeddingSample(sample_id=k, embedding=o["embedding"][i]) for o in outputs
+                   for i, k in enumerate(o["sample_id"])]
+        return self.evaluator.evaluate(pairs, samples)
+
+    def validation_epoch_end(self, outputs: List[dict]):
+        return self._evaluate_embeddings(outputs, self.validation_pairs)
+
+    def test_epoch_end(self, outputs: List[dict]):
+        return self._evaluate_embeddings(outputs, self.test_pairs)
+
+    def evaluate_trials(self, pairs, input_by_key, **batching) -> dict:
+        """Score a trial list: every utterance the pairs name (key -> one input of compute_speaker_embeddings in
+        ``input_by_key``) is embedded once with compute_speaker_embeddings (``batching``: its keyword arguments) and the
+        module's evaluator scores the pairs -- the same dict as test_epoch_end over the batch-size-1 test loop."""
+        keys = sorted({k for p in pairs for k in (p.sample1_id, p.sample2_id)})
+        embs = self.compute_speaker_embeddings([input_by_key[k] for k in keys], **batching)
+        return self._evaluate_embeddings([{"embedding": torch.cat(embs).detach().to("cpu"), "sample_id": keys}], pairs)
+
+    @property
+    def bucket_plans_built(self) -> int:
+        """Plans compute_speaker_embeddings has built for its length buckets."""
+        return self._bucket_plans.built

@@ -2,18 +2,18 @@
 on the HIP path (w2v2_speaker_amd/ecapa.py).  Same config field names, same method names and argument meaning."""
 from __future__ import annotations
 
-from collections import OrderedDict
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
 from ...ecapa import EcapaConfig, EcapaPlan, EcapaStore, EcapaTrainer, ecapa_min_frames, fbank_frames
-from ...eval_batching import DEFAULT_FRAME_QUANTUM, DEFAULT_MAX_BATCH, DEFAULT_MAX_BATCH_FRAMES, plan_batches
+from ...eval_batching import (DEFAULT_FRAME_QUANTUM, DEFAULT_MAX_BATCH, DEFAULT_MAX_BATCH_FRAMES, PlanCache,
+                              padded_batches)
 from ...optim.schedule import OneCycle
-from ._optim_surface import OptimizerSurface
+from ._optim_surface import EmbeddingEvaluation, OptimizerSurface, prep_waveform_input
 from ...ops import FBANK_HOP
-from .wav2vec2_fc import SpeakerClassificationDataBatch, Wav2vec2FCModule
+from .wav2vec2_fc import SpeakerClassificationDataBatch
 
 MAX_BUCKET_PLANS = 12     # plans of compute_speaker_embeddings' length buckets (LRU, one per bucket shape)
 
@@ -35,7 +35,7 @@ class EcapaTDNNModuleConfig:
     explicit_num_speakers: Optional[int] = None
 
 
-class EcapaTdnnModule(OptimizerSurface):
+class EcapaTdnnModule(OptimizerSurface, EmbeddingEvaluation):
     def __init__(self, hyperparameters_to_save, cfg: EcapaTDNNModuleConfig, num_speakers: int,
                  loss_fn_constructor: Callable[[], object], validation_pairs=None, test_pairs=None, evaluator=None, *,
                  device="cuda", act_dtype: torch.dtype = torch.bfloat16, max_lr: float = 1e-3,
@@ -83,10 +83,9 @@ class EcapaTdnnModule(OptimizerSurface):
         self._set_accumulate_grad_batches(accumulate_grad_batches)     # PL ``trainer.accumulate_grad_batches``
         self.skip_classifier = True                        # AAM owns the classifier weight (ref :93-95, :129-131)
         self.device = torch.device(device)
-        self._plans: Dict[Tuple, EcapaPlan] = {}
+        self._plans = PlanCache()                          # one per (batch, frames, train) shape, all kept
         self._trainers: Dict[Tuple, EcapaTrainer] = {}
-        self._bucket_plans: "OrderedDict[Tuple, EcapaPlan]" = OrderedDict()
-        self.bucket_plans_built = 0
+        self._bucket_plans = PlanCache(MAX_BUCKET_PLANS)
         self.steps = 0              # backward passes (micro-batches)
         self.schedule_step = 0      # optimiser steps = position in the learning-rate schedule
 
@@ -102,11 +101,8 @@ class EcapaTdnnModule(OptimizerSurface):
                    kw.pop("evaluator", None), **kw)
 
     def _plan(self, batch: int, frames: int, train: bool) -> EcapaPlan:
-        key = (batch, frames, train)
-        if key not in self._plans:
-            self._plans[key] = EcapaPlan(self.store, batch, frames, train=train, aam_margin=self.margin,
-                                         aam_scale=self.scale)
-        return self._plans[key]
+        return self._plans.lookup((batch, frames, train), lambda: EcapaPlan(
+            self.store, batch, frames, train=train, aam_margin=self.margin, aam_scale=self.scale))
 
     def generate_example_input(self, include_batch_dimension: bool, batch_size: Optional[int] = None):
         # ref :97-108: [BATCH_SIZE, NUMBER_OF_WINDOWS, NUMBER_OF_MEL_COEFFICIENTS]
@@ -125,22 +121,14 @@ class EcapaTdnnModule(OptimizerSurface):
 
     def _prep_waveform(self, input_tensor: torch.Tensor) -> torch.Tensor:
         """[B, 1, N], [B, N] or [N] audio -> [B, N] f32 on the device (Wav2vec2FCModule's input forms)."""
-        x = Wav2vec2FCModule._prep_input(input_tensor)
+        x = prep_waveform_input(input_tensor)
         if x.dim() != 2:
             raise ValueError(f"expected [B, 1, N], [B, N] or [N] audio, got {tuple(input_tensor.shape)}")
         return x.to(self.device, torch.float32).contiguous()
 
     def _bucket_plan(self, batch: int, frames: int) -> EcapaPlan:
-        key = (batch, frames)
-        if key in self._bucket_plans:
-            self._bucket_plans.move_to_end(key)
-            return self._bucket_plans[key]
-        plan = EcapaPlan(self.store, batch, frames, train=False, aam_margin=self.margin, aam_scale=self.scale)
-        self.bucket_plans_built += 1
-        self._bucket_plans[key] = plan
-        while len(self._bucket_plans) > MAX_BUCKET_PLANS:
-            self._bucket_plans.popitem(last=False)
-        return plan
+        return self._bucket_plans.lookup((batch, frames), lambda: EcapaPlan(
+            self.store, batch, frames, train=False, aam_margin=self.margin, aam_scale=self.scale))
 
     def compute_speaker_embeddings(self, feats, *, quantum: int = DEFAULT_FRAME_QUANTUM,
                                    max_batch_frames: int = DEFAULT_MAX_BATCH_FRAMES,
@@ -164,14 +152,8 @@ class EcapaTdnnModule(OptimizerSurface):
             xs.append(x)
         out: List[Optional[torch.Tensor]] = [None] * len(xs)
         fill = ecapa_min_frames(self.model_cfg)
-        for idx, n, batch in plan_batches([x.shape[0] for x in xs], quantum, max_batch_frames, max_batch):
-            plan = self._bucket_plan(batch, n)
-            feat = torch.zeros(batch, n, F_, dtype=torch.float32, device=self.device)
-            lens = [fill] * batch           # unused rows of a bucket's last batch: zeros of the minimum length
-            for j, i in enumerate(idx):
-                feat[j, :xs[i].shape[0]].copy_(xs[i])
-                lens[j] = xs[i].shape[0]
-            emb = plan.embed(feat, lengths=lens)
+        for idx, feat, lens in padded_batches(xs, quantum, max_batch_frames, max_batch, fill, self.device):
+            emb = self._bucket_plan(*feat.shape[:2]).embed(feat, lengths=lens)
             for j, i in enumerate(idx):
                 out[i] = emb[j:j + 1].clone()
         return out
@@ -185,26 +167,12 @@ class EcapaTdnnModule(OptimizerSurface):
             xs.append(x)
         out: List[Optional[torch.Tensor]] = [None] * len(xs)
         fill = (ecapa_min_frames(self.model_cfg) - 1) * FBANK_HOP      # fewest samples with the minimum frame count
-        for idx, n, batch in plan_batches([x.shape[0] for x in xs], quantum * FBANK_HOP, max_batch_frames * FBANK_HOP,
-                                          max_batch):
-            plan = self._bucket_plan(batch, fbank_frames(n))
-            wav = torch.zeros(batch, n, dtype=torch.float32, device=self.device)
-            lens = [fill] * batch           # unused rows of a bucket's last batch: silence of the minimum length
-            for j, i in enumerate(idx):
-                wav[j, :xs[i].shape[0]].copy_(xs[i])
-                lens[j] = xs[i].shape[0]
-            emb = plan.embed_waveform(wav, lengths=lens)
+        for idx, wav, lens in padded_batches(xs, quantum * FBANK_HOP, max_batch_frames * FBANK_HOP, max_batch, fill,
+                                             self.device):
+            emb = self._bucket_plan(wav.shape[0], fbank_frames(wav.shape[1])).embed_waveform(wav, lengths=lens)
             for j, i in enumerate(idx):
                 out[i] = emb[j:j + 1].clone()
         return out
-
-    def evaluate_trials(self, pairs, feats_by_key, **batching) -> dict:
-        """Score a trial list: every utterance the pairs name (key -> filterbank tensor in ``feats_by_key``, or key ->
-        waveform under ``input_features="waveform"``) is embedded once with compute_speaker_embeddings (``batching``: its keyword arguments) and the module's evaluator scores the pairs --
-        the same dict as test_epoch_end over the batch-size-1 test loop."""
-        keys = sorted({k for p in pairs for k in (p.sample1_id, p.sample2_id)})
-        embs = self.compute_speaker_embeddings([feats_by_key[k] for k in keys], **batching)
-        return self._evaluate([{"embedding": torch.cat(embs).detach().to("cpu"), "sample_id": keys}], pairs)
 
     def compute_speaker_prediction(self, embedding_tensor: torch.Tensor) -> torch.Tensor:
         return embedding_tensor.squeeze()                  # ref :120-122 under AAM
@@ -224,36 +192,12 @@ class EcapaTdnnModule(OptimizerSurface):
             x = batch.network_input.to(self.device, torch.float32)
             key = (x.shape[0], x.shape[1])
         label = batch.ground_truth.to(self.device)
-        if key not in self._trainers:
-            self._trainers[key] = EcapaTrainer(self.store, self._plan(key[0], key[1], True), self.schedule,
-                                               **self._trainer_options())
-        tr = self._trainers[key]
-        tr.step = self.schedule_step
-        loss, pred = tr.train_step(x, label)
+        loss, pred = self._trainer_step(
+            key, lambda: EcapaTrainer(self.store, self._plan(key[0], key[1], True), self.schedule,
+                                      **self._trainer_options()),
+            lambda tr: tr.train_step(x, label))
         self.steps += 1
-        self._after_micro_batch(tr)
         return {"loss": loss, "prediction": pred}
-
-    def validation_step(self, batch: SpeakerClassificationDataBatch, batch_idx: int = 0):
-        return {"embedding": self.compute_speaker_embedding(batch.network_input).detach().to("cpu"),
-                "sample_id": batch.keys}
-
-    def test_step(self, batch: SpeakerClassificationDataBatch, batch_idx: int = 0):
-        if batch.batch_size != 1:
-            raise ValueError("expecting a batch size of 1 for evaluating speaker embeddings")
-        return self.validation_step(batch, batch_idx)
-
-    def _evaluate(self, outputs, pairs):
-        from ...evaluation.speaker.cosine_distance import EmbeddingSample
-        samples = [EmbeddingSample(sample_id=k, embedding=o["embedding"][i]) for o in outputs
-                   for i, k in enumerate(o["sample_id"])]
-        return self.evaluator.evaluate(pairs, samples)
-
-    def validation_epoch_end(self, outputs):
-        return self._evaluate(outputs, self.validation_pairs)
-
-    def test_epoch_end(self, outputs):
-        return self._evaluate(outputs, self.test_pairs)
 
     def state_dict(self):
         return self.store.state_dict()

@@ -26,16 +26,16 @@ import torch
 from ... import ops
 from ...config import W2V2Config, Wav2Vec2RegularisationConfig
 from ...engine import Plan
-from ...eval_batching import (DEFAULT_MAX_BATCH, DEFAULT_MAX_BATCH_SAMPLES, DEFAULT_QUANTUM, min_samples,
-                              plan_batches)
-from ...evaluation.speaker.cosine_distance import CosineDistanceEvaluator, EmbeddingSample, EvaluationPair
+from ...eval_batching import (DEFAULT_MAX_BATCH, DEFAULT_MAX_BATCH_SAMPLES, DEFAULT_QUANTUM, PlanCache, min_samples,
+                              padded_batches)
+from ...evaluation.speaker.cosine_distance import CosineDistanceEvaluator, EvaluationPair
 from ...models.handles import ModelHandle
 from ...optim.loss import AngularAdditiveMarginSoftMaxLoss, CrossEntropyLoss
 from ...optim import OptimConfig
 from ...optim.schedule import OneCycle
 from ...params import ParamStore
 from ...trainer import SpeakerTrainer
-from ._optim_surface import OptimizerSurface
+from ._optim_surface import EmbeddingEvaluation, OptimizerSurface, prep_waveform_input
 
 from ...params import _WN_OLD as _WN_LEGACY
 
@@ -135,7 +135,7 @@ def _pool_width(pooling: str) -> int:
     raise ValueError(f"unknown value for stat_pooling_type={pooling!r}")
 
 
-class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
+class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
     """A ``torch.nn.Module`` (the reference's is a LightningModule): ``parameters()`` / ``named_parameters()`` yield one
     ``nn.Parameter`` per reference parameter, in the reference's order and under its names, each a VIEW of the flat f32
     arena (``.grad`` = the matching view of the flat gradient buffer, scaled by the loss scale in the fp16 mode);
@@ -227,10 +227,9 @@ class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
         self.evaluator = evaluator or CosineDistanceEvaluator(False, False, 0)
         self.schedule = OneCycle(max_lr=max_lr, total_steps=max_steps)
         self.process_group = process_group
-        self._plans: "OrderedDict[Tuple, Plan]" = OrderedDict()
-        self._bucket_plans: "OrderedDict[Tuple, Plan]" = OrderedDict()
-        self.bucket_plans_built = 0
         self._trainers: Dict[Tuple, SpeakerTrainer] = {}
+        self._plans = PlanCache(MAX_PLANS, on_evict=lambda key: self._trainers.pop(key, None))
+        self._bucket_plans = PlanCache(MAX_BUCKET_PLANS)
         self.steps = 0              # ref: counts backward calls since on_train_start (the freeze schedule)
         self.schedule_step = 0      # position in the learning-rate schedule (restored from a checkpoint)
         self._is_wav2vec_frozen = False
@@ -256,19 +255,8 @@ class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
 
     # ------------------------------------------------------------------ nn.Module surface over the flat arena
     def named_parameters(self, prefix: str = "", recurse: bool = True, remove_duplicate: bool = True):
-        if getattr(self, "_param_views", None) is None:
-            self._param_views = {}
-            for n in self.store.reference_parameter_order():
-                p = torch.nn.Parameter(self.store.p(n), requires_grad=False)        # a view: shares the arena's memory
-                if self.store.is_trainable(n):
-                    p.grad = self.store.g(n)
-                self._param_views[n] = p
-        for n, p in self._param_views.items():
+        for n, p in self._parameter_views().items():            # (``parameters()``: OptimizerSurface's, the same views)
             yield (prefix + "." if prefix else "") + n, p       # same keys as state_dict() (save_checkpoint maps to the torch-1.9 names)
-
-    def parameters(self, recurse: bool = True):
-        for _, p in self.named_parameters(recurse=recurse):
-            yield p
 
     def _apply(self, fn, recurse: bool = True):
         return self            # .to() / .cuda() / .half() / .float(): the engine keeps its device and precision
@@ -296,38 +284,18 @@ class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
             if self.cfg.completely_freeze_feature_extractor:
                 self.wav2vec.model.feature_extractor.requires_grad_(False)
 
-    # ------------------------------------------------------------------ plans (bounded LRU cache)
-    def _cached_plan(self, key: Tuple, build: Callable[[], Plan]) -> Plan:
-        if key in self._plans:
-            self._plans.move_to_end(key)
-            return self._plans[key]
-        plan = build()
-        self._plans[key] = plan
-        while len(self._plans) > MAX_PLANS:
-            old, _ = self._plans.popitem(last=False)
-            self._trainers.pop(old, None)
-        return plan
-
+    # ------------------------------------------------------------------ plans (bounded LRU caches: eval_batching.PlanCache)
     def _plan(self, batch: int, n: int, train: bool) -> Plan:
         pooling = self.cfg.stat_pooling_type if train else self.cfg.test_stat_pooling_type
-        return self._cached_plan((batch, n, train, pooling), lambda: Plan(
+        return self._plans.lookup((batch, n, train, pooling), lambda: Plan(
             self.store, batch, n, train=train, reg=self.reg, pooling=pooling,
             insert_cls_token=(pooling == "first+cls"), aam_margin=self.margin, aam_scale=self.scale))
-
-    @staticmethod
-    def _prep_input(input_tensor: torch.Tensor) -> torch.Tensor:
-        # ref: wav2vec2_fc.py:414-421 -- [BS,1,N] or [1,N] or [N] -> [BS,N]
-        if len(input_tensor.shape) == 3 and input_tensor.shape[1] == 1:
-            input_tensor = input_tensor[:, 0, :]
-        if len(input_tensor.shape) == 1:
-            input_tensor = torch.stack([input_tensor])
-        return input_tensor
 
     # ------------------------------------------------------------------ reference surface
     def compute_speaker_embedding(self, input_tensor: torch.Tensor) -> torch.Tensor:
         """ref: :414-431 -- wav2vec2 -> statistics pooling -> (identity masker) -> hidden FC layers up to
         ``embedding_layer_idx``."""
-        x = self._prep_input(input_tensor).to(self.device, torch.float32)
+        x = prep_waveform_input(input_tensor).to(self.device, torch.float32)
         plan = self._plan(x.shape[0], x.shape[1], False)
         plan.embed(x)
         emb = plan.speaker_embedding(self.cfg.embedding_layer_idx).clone()
@@ -337,17 +305,9 @@ class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
 
     def _bucket_plan(self, batch: int, n: int) -> Plan:
         pooling = self.cfg.test_stat_pooling_type
-        key = (batch, n, pooling)
-        if key in self._bucket_plans:
-            self._bucket_plans.move_to_end(key)
-            return self._bucket_plans[key]
-        plan = Plan(self.store, batch, n, train=False, reg=self.reg, pooling=pooling,
-                    insert_cls_token=(pooling == "first+cls"), aam_margin=self.margin, aam_scale=self.scale)
-        self.bucket_plans_built += 1
-        self._bucket_plans[key] = plan
-        while len(self._bucket_plans) > MAX_BUCKET_PLANS:
-            self._bucket_plans.popitem(last=False)
-        return plan
+        return self._bucket_plans.lookup((batch, n, pooling), lambda: Plan(
+            self.store, batch, n, train=False, reg=self.reg, pooling=pooling,
+            insert_cls_token=(pooling == "first+cls"), aam_margin=self.margin, aam_scale=self.scale))
 
     def compute_speaker_embeddings(self, waveforms, *, quantum: int = DEFAULT_QUANTUM,
                                    max_batch_samples: int = DEFAULT_MAX_BATCH_SAMPLES,
@@ -358,32 +318,19 @@ class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
         cross-frame reduction sees each utterance's own frames only."""
         xs = []
         for w in waveforms:
-            x = self._prep_input(w)
+            x = prep_waveform_input(w)
             if x.dim() != 2 or x.shape[0] != 1:
                 raise ValueError(f"compute_speaker_embeddings: expected one utterance per waveform, got {tuple(w.shape)}")
             xs.append(x[0])
         out: List[Optional[torch.Tensor]] = [None] * len(xs)
         fill = min_samples(self.store.cfg.conv_kernel, self.store.cfg.conv_stride)
-        for idx, n, batch in plan_batches([x.shape[0] for x in xs], quantum, max_batch_samples, max_batch):
-            plan = self._bucket_plan(batch, n)
-            wav = torch.zeros(batch, n, dtype=torch.float32, device=self.device)
-            lens = [fill] * batch           # unused rows of a bucket's last batch: silence of the minimum length
-            for j, i in enumerate(idx):
-                wav[j, :xs[i].shape[0]].copy_(xs[i])
-                lens[j] = xs[i].shape[0]
+        for idx, wav, lens in padded_batches(xs, quantum, max_batch_samples, max_batch, fill, self.device):
+            plan = self._bucket_plan(*wav.shape)
             plan.embed(wav, lengths=lens)
             emb = plan.speaker_embedding(self.cfg.embedding_layer_idx)
             for j, i in enumerate(idx):
                 out[i] = emb[j:j + 1].clone()
         return out
-
-    def evaluate_trials(self, pairs: List[EvaluationPair], audio_by_key, **batching) -> dict:
-        """Score a trial list: every utterance the pairs name (key -> waveform in ``audio_by_key``) is embedded once with
-        compute_speaker_embeddings (``batching``: its keyword arguments) and the module's evaluator scores the pairs --
-        the same dict as test_epoch_end over the batch-size-1 test loop."""
-        keys = sorted({k for p in pairs for k in (p.sample1_id, p.sample2_id)})
-        embs = self.compute_speaker_embeddings([audio_by_key[k] for k in keys], **batching)
-        return self._evaluate_embeddings([{"embedding": torch.cat(embs).detach().to("cpu"), "sample_id": keys}], pairs)
 
     def _linear(self, x: torch.Tensor, i: int, relu: bool) -> torch.Tensor:
         W, b = self.store.p(f"fc_list.{i}.0.weight"), self.store.p(f"fc_list.{i}.0.bias")
@@ -435,20 +382,23 @@ class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
         """forward + backward (+ all-reduce) + fused Adam; returns {"loss", "prediction", "train_acc"} (device
         tensors; train_acc = fraction of the batch whose arg-max prediction is the label, the quantity the
         reference feeds torchmetrics.Accuracy, ref: speaker_recognition_module.py:296-307)."""
-        x = self._prep_input(batch.network_input).to(self.device, torch.float32)
+        x = prep_waveform_input(batch.network_input).to(self.device, torch.float32)
         label = batch.ground_truth.to(self.device)
         pkey = (x.shape[0], x.shape[1], True, self.cfg.stat_pooling_type)
         plan = self._plan(x.shape[0], x.shape[1], True)
-        if pkey not in self._trainers:
-            self._trainers[pkey] = SpeakerTrainer(self.store, plan, self.schedule, process_group=self.process_group,
-                                                  **self._trainer_options())
-        tr = self._trainers[pkey]
-        tr.step = self.schedule_step
+        loss, pred = self._trainer_step(
+            pkey, lambda: SpeakerTrainer(self.store, plan, self.schedule, process_group=self.process_group,
+                                         **self._trainer_options()),
+            lambda tr: self._run_step(tr, plan, x, label))
+        self.on_after_backward()
+        return {"loss": loss, "prediction": pred, "train_acc": self.train_acc}
+
+    def _run_step(self, tr: SpeakerTrainer, plan: Plan, x: torch.Tensor, label: torch.Tensor):
         if self._is_wav2vec_frozen:
             # frozen network = eval-mode forward (PL freeze()), head-only backward + Adam
             noreg = Wav2Vec2RegularisationConfig(activation_dropout=0.0, attention_dropout=0.0, feat_proj_dropout=0.0,
                                                  hidden_dropout=0.0, layerdrop=0.0, mask_time_prob=0.0)
-            fplan = self._cached_plan((x.shape[0], x.shape[1], "frozen"), lambda: Plan(
+            fplan = self._plans.lookup((x.shape[0], x.shape[1], "frozen"), lambda: Plan(
                 self.store, x.shape[0], x.shape[1], train=True, reg=noreg, pooling=self.cfg.stat_pooling_type,
                 insert_cls_token=(self.cfg.stat_pooling_type == "first+cls"), aam_margin=self.margin,
                 aam_scale=self.scale))
@@ -458,38 +408,14 @@ class Wav2vec2FCModule(OptimizerSurface, torch.nn.Module):
             loss, pred = tr.train_step(x, label)
             head = plan.head
         self.train_acc = head.correct.mean()
-        self._after_micro_batch(tr)
-        self.on_after_backward()
-        return {"loss": loss, "prediction": pred, "train_acc": self.train_acc}
-
-    def validation_step(self, batch: SpeakerClassificationDataBatch, batch_idx: int = 0):
-        emb = self.compute_speaker_embedding(batch.network_input)
-        return {"embedding": emb.detach().to("cpu"), "sample_id": batch.keys}
-
-    def test_step(self, batch: SpeakerClassificationDataBatch, batch_idx: int = 0):
-        if batch.batch_size != 1:
-            raise ValueError("expecting a batch size of 1 for evaluating speaker embeddings")   # ref: :468-469
-        return self.validation_step(batch, batch_idx)
-
-    def _evaluate_embeddings(self, outputs: List[dict], pairs: List[EvaluationPair]):
-        samples = []
-        for o in outputs:
-            for i, key in enumerate(o["sample_id"]):
-                samples.append(EmbeddingSample(sample_id=key, embedding=o["embedding"][i]))
-        return self.evaluator.evaluate(pairs, samples)
-
-    def validation_epoch_end(self, outputs: List[dict]):
-        return self._evaluate_embeddings(outputs, self.validation_pairs)
-
-    def test_epoch_end(self, outputs: List[dict]):
-        return self._evaluate_embeddings(outputs, self.test_pairs)
+        return loss, pred
 
     def compute_ensemble_embedding(self, input_tensor: torch.Tensor):
         """ref: wav2vec2_fc.py:440-463 -- list of ``num_ensembles`` pooled embeddings, one per hidden state of the
         last transformer layers (``use_transformers_as_ensembles``); scored by CosineDistanceEvaluator as the mean
         of the per-layer cosine scores."""
-        x = self._prep_input(input_tensor)
-        plan = self._cached_plan(("ensemble", x.shape[0], x.shape[1]), lambda: Plan(
+        x = prep_waveform_input(input_tensor)
+        plan = self._plans.lookup(("ensemble", x.shape[0], x.shape[1]), lambda: Plan(
             self.store, x.shape[0], x.shape[1], train=False, reg=self.reg, pooling=self.cfg.stat_pooling_type,
             keep_hidden_states=True, insert_cls_token=(self.cfg.stat_pooling_type == "first+cls")))
         return plan.ensemble_embeddings(x.to(self.device), self.cfg.num_ensembles)

@@ -9,7 +9,6 @@ Evaluation (ref: paired_speaker_recognition_module.py:115-248): the step hooks a
 from __future__ import annotations
 
 import dataclasses
-from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Tuple
 
@@ -19,7 +18,7 @@ import torch
 from ...config import W2V2Config, Wav2Vec2RegularisationConfig
 from ...engine import Plan
 from ...eval_batching import (DEFAULT_MAX_BATCH, DEFAULT_MAX_PAIR_BATCH_FRAMES, DEFAULT_PAIR_QUANTUM, DEFAULT_QUANTUM,
-                              min_samples, plan_batches, plan_pair_batches)
+                              PlanCache, min_samples, padded_batches, plan_pair_batches)
 from ...eval_metrics import calculate_eer, calculate_mdc
 from ...optim.schedule import OneCycle
 from ._optim_surface import OptimizerSurface
@@ -104,12 +103,11 @@ class Wav2vec2PairedSpeakerModule(OptimizerSurface):
         self._set_accumulate_grad_batches(accumulate_grad_batches)     # PL ``trainer.accumulate_grad_batches``
         self.process_group = process_group
         self.device = torch.device(device)
-        self._plans: Dict[Tuple, Plan] = {}
+        self._plans = PlanCache()                          # one per (batch, samples, train) shape, all kept
         self._trainers: Dict[Tuple, SpeakerTrainer] = {}
         # evaluation plans, one bounded LRU each: variable-length equality plans (batch, samples), feature plans of
         # score_trials (batch, samples), encoder-only trial plans (batch, frames)
-        self._lru: Dict[str, "OrderedDict[Tuple, Plan]"] = {k: OrderedDict() for k in ("equality", "features", "pairs")}
-        self.bucket_plans_built = 0
+        self._lru: Dict[str, PlanCache] = {k: PlanCache(n) for k, n in MAX_BUCKET_PLANS.items()}
         self.last_bank_bytes = 0
         self.steps = 0              # backward passes (micro-batches)
         self.schedule_step = 0      # optimiser steps = position in the learning-rate schedule
@@ -122,23 +120,14 @@ class Wav2vec2PairedSpeakerModule(OptimizerSurface):
         return torch.rand(size=shape), torch.rand(size=shape)
 
     def _plan(self, batch: int, n: int, train: bool) -> Plan:
-        key = (batch, n, train)
-        if key not in self._plans:
-            self._plans[key] = Plan(self.store, batch, n, train=train, reg=self.reg, pooling="first", paired=True,
-                                    cls_token_constant=self.cfg.cls_token_constant,
-                                    sep_token_constant=self.cfg.sep_token_constant)
-        return self._plans[key]
+        return self._plans.lookup((batch, n, train), lambda: Plan(
+            self.store, batch, n, train=train, reg=self.reg, pooling="first", paired=True,
+            cls_token_constant=self.cfg.cls_token_constant, sep_token_constant=self.cfg.sep_token_constant))
 
-    def _lru_plan(self, kind: str, key: Tuple, build: Callable[[], Plan]) -> Plan:
-        plans = self._lru[kind]
-        if key in plans:
-            plans.move_to_end(key)
-            return plans[key]
-        plans[key] = build()
-        self.bucket_plans_built += 1
-        while len(plans) > MAX_BUCKET_PLANS[kind]:
-            plans.popitem(last=False)
-        return plans[key]
+    @property
+    def bucket_plans_built(self) -> int:
+        """Plans built by the three evaluation caches together."""
+        return sum(c.built for c in self._lru.values())
 
     @staticmethod
     def _sq(x: torch.Tensor) -> torch.Tensor:
@@ -180,7 +169,7 @@ class Wav2vec2PairedSpeakerModule(OptimizerSurface):
         wav = torch.zeros(2 * B, n, dtype=torch.float32, device=self.device)
         wav[:B, :a.shape[1]].copy_(a)
         wav[B:, :b.shape[1]].copy_(b)
-        plan = self._lru_plan("equality", (B, n), lambda: self._make_plan(B, n))
+        plan = self._lru["equality"].lookup((B, n), lambda: self._make_plan(B, n))
         return self._logits(plan.embed(wav, pair_lengths=lengths))
 
     def _make_plan(self, batch: int, n: int, **kw) -> Plan:
@@ -198,14 +187,11 @@ class Wav2vec2PairedSpeakerModule(OptimizerSurface):
         wav = self._stack(batch.primary_network_input, batch.secondary_network_input).to(self.device, torch.float32)
         label = batch.ground_truth.to(self.device).to(torch.int64)
         key = (wav.shape[0] // 2, wav.shape[1])
-        if key not in self._trainers:
-            self._trainers[key] = SpeakerTrainer(self.store, self._plan(key[0], key[1], True), self.schedule,
-                                                 process_group=self.process_group, **self._trainer_options())
-        tr = self._trainers[key]
-        tr.step = self.schedule_step
-        loss, pred = tr.train_step(wav, label)
+        loss, pred = self._trainer_step(
+            key, lambda: SpeakerTrainer(self.store, self._plan(key[0], key[1], True), self.schedule,
+                                        process_group=self.process_group, **self._trainer_options()),
+            lambda tr: tr.train_step(wav, label))
         self.steps += 1
-        self._after_micro_batch(tr)
         return {"loss": loss, "prediction": pred}
 
     # ------------------------------------------------------------------ evaluation
@@ -259,21 +245,17 @@ class Wav2vec2PairedSpeakerModule(OptimizerSurface):
         bank = torch.empty(offset[-1], H, dtype=adt, device=self.device)
         self.last_bank_bytes = nbytes
         hop = int(np.prod(cfg.conv_stride))
-        for idx, n, batch in plan_batches([w.shape[0] for w in wavs], quantum * hop, max_batch_frames * hop, max_batch):
-            plan = self._lru_plan("features", (batch, n),
-                                  lambda: Plan(self.store, batch, n, train=False, reg=self.reg, pooling="first"))
-            wav = torch.zeros(batch, n, dtype=torch.float32, device=self.device)
-            lens = [fill] * batch           # unused rows of a bucket's last batch: silence of the minimum length
-            for j, i in enumerate(idx):
-                wav[j, :wavs[i].shape[0]].copy_(wavs[i])
-                lens[j] = wavs[i].shape[0]
+        for idx, wav, lens in padded_batches(wavs, quantum * hop, max_batch_frames * hop, max_batch, fill, self.device):
+            batch, n = wav.shape
+            plan = self._lru["features"].lookup(
+                (batch, n), lambda: Plan(self.store, batch, n, train=False, reg=self.reg, pooling="first"))
             feat, _ = plan.features(wav, lengths=lens)
             for j, i in enumerate(idx):
                 bank[offset[i]:offset[i + 1]].copy_(feat[j, :frames[i]])
         lf, rf = [frames[a] for a, _ in sides], [frames[b] for _, b in sides]
         parts = []
         for idx, t, batch in plan_pair_batches(lf, rf, quantum, max_batch_frames, max_batch):
-            plan = self._lru_plan("pairs", (batch, t), lambda: Plan.pair_encoder(
+            plan = self._lru["pairs"].lookup((batch, t), lambda: Plan.pair_encoder(
                 self.store, batch, t, reg=self.reg, cls_token_constant=self.cfg.cls_token_constant,
                 sep_token_constant=self.cfg.sep_token_constant))
             rows = [[0] * batch, [1] * batch, [0] * batch, [1] * batch]      # unused rows: dummy one-frame pairs

@@ -7,14 +7,14 @@ the engine's hand-written backward."""
 from __future__ import annotations
 
 import warnings
-from collections import OrderedDict
-from typing import Optional, Tuple
+from typing import Optional
 
 import numpy as np
 import torch
 
 from ..config import W2V2Config, Wav2Vec2RegularisationConfig  # noqa: F401  (re-exported like the reference)
 from ..engine import Plan
+from ..eval_batching import PlanCache
 from ..params import ParamStore, W2V_PREFIX
 from ..spec_augment import compute_mask_indices
 from .handles import ModelHandle
@@ -69,7 +69,7 @@ class Wav2Vec2WrapperModule(torch.nn.Module):
                 warnings.warn(f"Wav2Vec2WrapperModule: reset_weights=False asks for the pretrained "
                               f"{wav2vec2_huggingface_id!r} weights but no pretrained_state_dict was given (there is "
                               "no network access): the model starts from a RANDOM initialisation", stacklevel=2)
-        self._plans: "OrderedDict[Tuple[int, int, bool], Plan]" = OrderedDict()
+        self._plans = PlanCache(MAX_PLANS)              # bounded: one static plan per (batch, length, mode)
         self._anchor = torch.nn.Parameter(torch.zeros((), device=self.store.device))
         self._step = 0
         self._ld_rng = np.random.RandomState(regularisation_seed)
@@ -82,15 +82,9 @@ class Wav2Vec2WrapperModule(torch.nn.Module):
         return self.num_features
 
     def _plan(self, batch: int, n_samples: int, train: bool) -> Plan:
-        key = (batch, n_samples, train)
-        if key in self._plans:
-            self._plans.move_to_end(key)
-            return self._plans[key]
-        self._plans[key] = Plan(self.store, batch, n_samples, train=train, reg=self.reg_cfg,
-                                insert_cls_token=self.insert_cls_token, cls_token_constant=self.cls_token_constant)
-        while len(self._plans) > MAX_PLANS:             # bounded: one static plan per (batch, length, mode)
-            self._plans.popitem(last=False)
-        return self._plans[key]
+        return self._plans.lookup((batch, n_samples, train), lambda: Plan(
+            self.store, batch, n_samples, train=train, reg=self.reg_cfg, insert_cls_token=self.insert_cls_token,
+            cls_token_constant=self.cls_token_constant))
 
     def _publish_grads(self) -> None:
         pass            # gradients live in store.grad (flat arena); optimisers use ParamStore.adam_step
@@ -175,7 +169,7 @@ class Wav2vecLiteWrapperModule(torch.nn.Module):
             elif not reset_weights:
                 warnings.warn("Wav2vecLiteWrapperModule: reset_weights=False asks for pretrained weights but no "
                               "pretrained_state_dict was given (no network access): RANDOM initialisation", stacklevel=2)
-        self._plans: "OrderedDict[Tuple[int, int, bool], Plan]" = OrderedDict()
+        self._plans = PlanCache(MAX_PLANS)              # bounded: one static plan per (batch, length, mode)
         self._anchor = torch.nn.Parameter(torch.zeros((), device=self.store.device))
         self.model = ModelHandle(self.store)
 
@@ -184,13 +178,8 @@ class Wav2vecLiteWrapperModule(torch.nn.Module):
         return self.num_features
 
     def _plan(self, batch: int, n_samples: int, train: bool) -> Plan:
-        key = (batch, n_samples, train)
-        if key not in self._plans:
-            self._plans[key] = Plan(self.store, batch, n_samples, train=train, reg=Wav2Vec2RegularisationConfig())
-            while len(self._plans) > MAX_PLANS:
-                self._plans.popitem(last=False)
-        self._plans.move_to_end(key)
-        return self._plans[key]
+        return self._plans.lookup((batch, n_samples, train), lambda: Plan(
+            self.store, batch, n_samples, train=train, reg=Wav2Vec2RegularisationConfig()))
 
     def forward(self, wav_input: torch.Tensor) -> torch.Tensor:
         # wav_input has shape [BATCH_SIZE, NUM_SAMPLES]

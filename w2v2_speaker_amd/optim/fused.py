@@ -1,5 +1,6 @@
 """Host side of the fused optimiser step, shared by ParamStore and EcapaStore: state arenas, the gradient-norm
-pair and the choice of entry point.  Everything here only enqueues launches; nothing reads the device."""
+pair and the choice of entry point; and WindowedTrainer, the step / accumulation-window protocol shared by their trainers.
+Everything here only enqueues launches; nothing reads the device."""
 from __future__ import annotations
 
 from typing import Optional
@@ -62,3 +63,44 @@ def accumulate(store, start: int, end: int) -> None:
         store.grad_acc = torch.empty_like(store.grad)
     if end > start:
         ops.grad_accumulate(store.grad_acc[start:end], store.grad[start:end], end - start, store.accum_count == 0)
+
+
+class WindowedTrainer:
+    """``accumulate_grad_batches`` = N (PL's ``trainer.accumulate_grad_batches``): at N > 1 one ``train_step`` call is one
+    micro-batch whose gradient the trainer adds into ``store.grad_acc``; the N-th call of a window reduces that arena over
+    the ranks, steps on the mean over world * N micro-batches and advances the schedule.  ``stepped`` tells which kind
+    the last call was, ``flush()`` closes a partial window.  A trainer supplies its ``train_step`` and ``_reduce_window()``,
+    the all-reduce of what the open window holds in store.grad_acc (nothing on one rank)."""
+
+    def __init__(self, store, schedule, optimizer: Optional[OptimConfig], gradient_clip_val: float,
+                 accumulate_grad_batches: int, world: int):
+        if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {accumulate_grad_batches!r}")
+        self.accumulate_grad_batches = int(accumulate_grad_batches)
+        self.stepped = False               # whether the last train_step / flush call ran the optimiser
+        self.store, self.schedule, self.step, self.world = store, schedule, 0, world
+        self.optimizer, self.gradient_clip_val = optimizer, float(gradient_clip_val)
+
+    def _optimizer_step(self, grad: Optional[torch.Tensor] = None, n_micro: int = 1, head_only: bool = False) -> None:
+        """Step on the mean of ``grad`` (None = store.grad), the rank-summed gradient of ``n_micro`` micro-batches per rank,
+        with the schedule's values of this step; then advance the schedule."""
+        lr, second = self.schedule.at(self.step)           # beta1 under Adam, the momentum under SGD
+        self.store.optimizer_step(lr, second, self.optimizer, 1.0 / (self.world * n_micro), self.gradient_clip_val,
+                                  head_only=head_only, grad=grad)
+        self.step += 1
+
+    def _close_window(self, head_only: bool = False) -> None:
+        """Step on the (already reduced) accumulated arena, still divided by world * N when the window is partial -- PL
+        divides every micro-batch's loss by N, also those of a short last window."""
+        self._optimizer_step(self.store.grad_acc, self.accumulate_grad_batches, head_only)
+        self.store.accum_count = 0
+
+    def flush(self) -> None:
+        """Close a partial window (the end of an epoch): all-reduce what has been accumulated and step on it.  Nothing
+        happens when no window is open."""
+        self.stepped = False
+        if self.accumulate_grad_batches == 1 or self.store.accum_count == 0:
+            return
+        self._reduce_window()
+        self._close_window()
+        self.stepped = True

@@ -79,7 +79,129 @@ _WN_OLD = {"encoder.pos_conv_embed.conv.weight_g": "encoder.pos_conv_embed.conv.
            "encoder.pos_conv_embed.conv.weight_v": "encoder.pos_conv_embed.conv.parametrizations.weight.original1"}
 
 
-class ParamStore:
+class FlatArena:
+    """Flat f32 parameter arena: every parameter of ``shapes`` (name -> shape, in arena order) at an ALIGN-ed offset of one
+    master buffer ``flat``, the gradient arena ``grad`` over its trainable head [0, n_train), and the host side of the
+    optimiser and accumulation state that optim.fused works on.  Base of ParamStore, ecapa.EcapaStore and the pooling
+    layer's own store.  A subclass sets ``flat_lp`` (the operand copy in a 16-bit activation dtype, or None), supplies
+    ``optimizer_step`` / ``zero_grad`` / ``sync_lowp`` and, for checkpoints, ``_buffers`` / ``_canonical`` / ``PREFIX`` /
+    ``BATCHES_TRACKED``."""
+    PREFIX = ""                    # what ``load_state_dict(prefix_model=True)`` may put in front of a bare key
+    BATCHES_TRACKED = ""           # attribute that the ``num_batches_tracked`` keys of the BatchNorm buffers save and load
+
+    def __init__(self, shapes: "OrderedDict[str, Tuple[int, ...]]", device, frozen_from: Optional[str] = None):
+        """frozen_from: name prefix of the first frozen parameter -- it and everything behind it in the arena have no
+        gradient (None: the whole arena trains)."""
+        self.shapes, self.device = shapes, torch.device(device)
+        self.offsets: Dict[str, int] = {}
+        off = 0
+        self.n_train = None
+        for n, s in shapes.items():
+            if self.n_train is None and frozen_from is not None and n.startswith(frozen_from):
+                self.n_train = off
+            self.offsets[n] = off
+            off += (int(np.prod(s)) + ALIGN - 1) // ALIGN * ALIGN
+        self.n_total = off
+        if self.n_train is None:
+            self.n_train = off
+        dev = self.device
+        self.flat = torch.zeros(self.n_total, dtype=torch.float32, device=dev)
+        self.grad = torch.zeros(self.n_train, dtype=torch.float32, device=dev)
+        self.exp_avg: Optional[torch.Tensor] = None
+        self.exp_avg_sq: Optional[torch.Tensor] = None
+        self.version = 0          # bumped whenever weights change (derived packs are re-made lazily)
+        self.step_count = 0
+        # optimiser: the algorithm the moment arenas belong to (set by the first step or by a loaded state), and the
+        # {global gradient norm, clip coefficient} record of the last step that clipped or tracked the norm
+        self.optim_algo: Optional[str] = None
+        self.grad_norm = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.track_grad_norm = False
+        # gradient accumulation (``trainer.accumulate_grad_batches`` > 1): the f32 sum over the open window, allocated by
+        # the first accumulating step (optim.fused.accumulate) and never at N = 1, and the number of micro-batches already
+        # in it.  The window position lives here because a module keeps one trainer per plan shape over this one store.
+        self.grad_acc: Optional[torch.Tensor] = None
+        self.accum_count = 0
+
+    # ------------------------------------------------------------------ views
+    def _view(self, buf: torch.Tensor, name: str) -> torch.Tensor:
+        s = self.shapes[name]
+        o = self.offsets[name]
+        return buf[o:o + int(np.prod(s))].view(*s)
+
+    def p(self, name: str) -> torch.Tensor:
+        """f32 master view."""
+        return self._view(self.flat, name)
+
+    def g(self, name: str) -> torch.Tensor:
+        """f32 gradient view (trainable parameters only)."""
+        if self.offsets[name] >= self.n_train:
+            raise KeyError(f"{name} is frozen: no gradient")
+        return self._view(self.grad, name)
+
+    def w(self, name: str) -> torch.Tensor:
+        """GEMM-operand view in the activation dtype."""
+        return self._view(self.flat_lp if self.flat_lp is not None else self.flat, name)
+
+    def adam_step(self, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                  grad_scale: float = 1.0, head_only: bool = False) -> None:
+        """Fused Adam without weight decay or clipping: optimizer_step() with the default description."""
+        self.optimizer_step(lr, beta1, OptimConfig(beta2=beta2, eps=eps), grad_scale, 0.0, head_only)
+
+    # ------------------------------------------------------------------ state
+    def _buffers(self) -> "OrderedDict[str, torch.Tensor]":
+        """Non-parameter state under the reference's key names: views of the BatchNorm1d running statistics."""
+        return OrderedDict()
+
+    def _canonical(self, key: str) -> str:
+        """A state-dict key under the name this arena uses for it."""
+        return key
+
+    def _resolve(self, key: str, names, prefix_model: bool) -> Optional[str]:
+        key = self._canonical(key)
+        if key in names:
+            return key
+        return self.PREFIX + key if prefix_model and self.PREFIX + key in names else None
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True, prefix_model: bool = True) -> None:
+        """Accepts the reference's keys or, with ``prefix_model``, keys without the model's ``PREFIX``."""
+        seen = set()
+        buffers = self._buffers()
+        for k, v in sd.items():
+            name = self._resolve(k, buffers, prefix_model)
+            if name is not None:                           # BatchNorm running statistics
+                buffers[name].copy_(torch.as_tensor(v).to(self.device, torch.float32))
+                continue
+            if k.endswith("num_batches_tracked") and buffers:
+                setattr(self, self.BATCHES_TRACKED, int(v))
+                continue
+            name = self._resolve(k, self.shapes, prefix_model)
+            if name is None:
+                if strict:
+                    raise KeyError(f"unexpected key {k}")
+                continue
+            t = torch.as_tensor(v).to(torch.float32)
+            if tuple(t.shape) != tuple(self.shapes[name]):
+                raise ValueError(f"{name}: shape {tuple(t.shape)} != {self.shapes[name]}")
+            self.p(name).copy_(t.to(self.device))
+            seen.add(name)
+        if strict and len(seen) != len(self.shapes):
+            missing = [n for n in self.shapes if n not in seen]
+            raise KeyError(f"missing keys: {missing[:5]}{'...' if len(missing) > 5 else ''}")
+        self.sync_lowp()
+
+    def state_dict(self) -> "OrderedDict[str, torch.Tensor]":
+        sd = OrderedDict((n, self.p(n).detach().clone().cpu()) for n in self.shapes)
+        for n, b in self._buffers().items():
+            sd[n] = b.detach().clone().cpu()
+            if n.endswith("running_var"):
+                sd[n[:-len("running_var")] + "num_batches_tracked"] = torch.tensor(getattr(self, self.BATCHES_TRACKED))
+        return sd
+
+
+class ParamStore(FlatArena):
+    PREFIX = W2V_PREFIX
+    BATCHES_TRACKED = "asp_batches_tracked"
+
     def __init__(self, cfg: W2V2Config, device, act_dtype: torch.dtype = torch.bfloat16,
                  head: Optional[str] = "aam", num_speakers: int = 5994, embed_dim: Optional[int] = None,
                  freeze_cnn: bool = True, attentive_pool: bool = False, attention_channels: int = 128,
@@ -90,7 +212,7 @@ class ParamStore:
         reference (wav2vec2_fc.py:212-224)."""
         assert act_dtype in (torch.bfloat16, torch.float16, torch.float32)
         assert head in (None, "aam", "ce", "bce")
-        self.cfg, self.device, self.act_dtype = cfg, torch.device(device), act_dtype
+        self.cfg, self.act_dtype = cfg, act_dtype
         self.head, self.num_speakers, self.freeze_cnn = head, num_speakers, freeze_cnn
         self.embed_dim = embed_dim if embed_dim is not None else 2 * cfg.hidden_size
         shapes: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
@@ -124,27 +246,12 @@ class ParamStore:
             shapes.update(asp_param_shapes(cfg.hidden_size, attention_channels))
         for n, s in hf_param_shapes(cfg).items():
             shapes[W2V_PREFIX + n] = s
-        self.shapes = shapes
-        self.offsets: Dict[str, int] = {}
-        off = 0
-        self.n_train = None
-        for n, s in shapes.items():
-            if self.n_train is None and freeze_cnn and n.startswith(W2V_PREFIX + "feature_extractor."):
-                self.n_train = off
-            self.offsets[n] = off
-            off += (int(np.prod(s)) + ALIGN - 1) // ALIGN * ALIGN
-        self.n_total = off
-        if self.n_train is None:
-            self.n_train = off
+        super().__init__(shapes, device, W2V_PREFIX + "feature_extractor." if freeze_cnn else None)
         # first arena element of the conv feature extractor; `cnn_runtime_frozen` is the run-time form of
         # ``feature_extractor.requires_grad_(False)`` for a store that owns CNN gradient buffers
         self.n_body = self.offsets[W2V_PREFIX + f"feature_extractor.conv_layers.{len(cfg.conv_dim) - 1}.conv.weight"]
         self.cnn_runtime_frozen = False
         dev = self.device
-        self.flat = torch.zeros(self.n_total, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros(self.n_train, dtype=torch.float32, device=dev)
-        self.exp_avg: Optional[torch.Tensor] = None
-        self.exp_avg_sq: Optional[torch.Tensor] = None
         # fp16: a second plane holds the residuals fp16(W - fp16(W)) of the weights whose products run with two-term
         # weights (value and output projections of every attention block, see Plan._build_gemms / DESIGN "precision")
         self.two_term = (act_dtype == torch.float16 and two_term_weights and not os.environ.get("W2V2_NO_TWO_TERM"))
@@ -186,43 +293,12 @@ class ParamStore:
             ent.append((self.offsets[n], self.offsets[n], shapes[n][0], shapes[n][1]))
             self.flat_lp_t = torch.zeros(self.n_total, dtype=act_dtype, device=dev)
             self._t_table = torch.tensor(ent, dtype=torch.int64, device=dev)
-        self.version = 0          # bumped whenever weights change (derived packs are re-made lazily)
         self.cnn_version = 0      # bumped whenever the CNN weights change
-        self.step_count = 0
         self.step_head = 0
         self.step_body = 0
-        # optimiser: the algorithm the moment arenas belong to (set by the first step or by a loaded state), and the
-        # {global gradient norm, clip coefficient} record of the last step that clipped or tracked the norm
-        self.optim_algo: Optional[str] = None
-        self.grad_norm = torch.zeros(2, dtype=torch.float32, device=dev)
-        self.track_grad_norm = False
-        # gradient accumulation (``trainer.accumulate_grad_batches`` > 1): the f32 sum over the open window, allocated by
-        # the first accumulating step (optim.fused.accumulate) and never at N = 1, and the number of micro-batches already
-        # in it.  The window position lives here because a module keeps one trainer per plan shape over this one store.
-        self.grad_acc: Optional[torch.Tensor] = None
-        self.accum_count = 0
         self.accum_head_only = False      # the open window's micro-batches ran with the encoder frozen
 
     # ------------------------------------------------------------------ views
-    def _view(self, buf: torch.Tensor, name: str) -> torch.Tensor:
-        s = self.shapes[name]
-        o = self.offsets[name]
-        return buf[o:o + int(np.prod(s))].view(*s)
-
-    def p(self, name: str) -> torch.Tensor:
-        """f32 master view."""
-        return self._view(self.flat, name)
-
-    def g(self, name: str) -> torch.Tensor:
-        """f32 gradient view (trainable parameters only)."""
-        if self.offsets[name] >= self.n_train:
-            raise KeyError(f"{name} is frozen: no gradient")
-        return self._view(self.grad, name)
-
-    def w(self, name: str) -> torch.Tensor:
-        """GEMM-operand view in the activation dtype."""
-        return self._view(self.flat_lp if self.flat_lp is not None else self.flat, name)
-
     def wt(self, name: str) -> torch.Tensor:
         """Pre-transposed bf16 operand view [in, out] of a 2-D weight [out, in] (bf16 mode only)."""
         r, c = self.shapes[name]
@@ -302,41 +378,17 @@ class ParamStore:
         del names
         return out
 
-    # ------------------------------------------------------------------ state
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True, prefix_model: bool = True) -> None:
-        """Accepts reference-style keys (``wav2vec.model.*``) or bare HF keys (prefix_model adds the prefix),
-        and both weight-norm namings."""
-        seen = set()
-        buffers = self._buffers()
-        for k, v in sd.items():
-            if k in buffers:                               # BatchNorm running statistics of the attentive pooling
-                buffers[k].copy_(torch.as_tensor(v).to(self.device, torch.float32))
-                continue
-            if k.endswith("num_batches_tracked") and self.asp_running is not None:
-                self.asp_batches_tracked = int(v)
-                continue
-            k = _WN_OLD.get(k, k)
-            for old, new in _WN_OLD.items():
-                if k.endswith(old):
-                    k = k[: -len(old)] + new
-            name = k if k in self.shapes else (W2V_PREFIX + k if prefix_model and W2V_PREFIX + k in self.shapes else None)
-            if name is None:
-                if strict:
-                    raise KeyError(f"unexpected key {k}")
-                continue
-            t = torch.as_tensor(v).to(torch.float32)
-            if tuple(t.shape) != tuple(self.shapes[name]):
-                raise ValueError(f"{name}: shape {tuple(t.shape)} != {self.shapes[name]}")
-            self.p(name).copy_(t.to(self.device))
-            seen.add(name)
-        if strict and len(seen) != len(self.shapes):
-            missing = [n for n in self.shapes if n not in seen]
-            raise KeyError(f"missing keys: {missing[:5]}{'...' if len(missing) > 5 else ''}")
-        self.sync_lowp()
+    # ------------------------------------------------------------------ state (FlatArena.load_state_dict / state_dict)
+    def _canonical(self, key: str) -> str:
+        """Both weight-norm namings are accepted."""
+        for old, new in _WN_OLD.items():
+            if key.endswith(old):
+                key = key[: -len(old)] + new
+        return key
 
     def _buffers(self) -> "OrderedDict[str, torch.Tensor]":
-        """Non-parameter state under the reference's key names: the BatchNorm1d buffers of the attentive pooling
-        (speechbrain ``stat_pooling.pooling_layer.tdnn.norm.norm.running_{mean,var}``)."""
+        """The BatchNorm1d buffers of the attentive pooling (speechbrain
+        ``stat_pooling.pooling_layer.tdnn.norm.norm.running_{mean,var}``)."""
         out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
         if self.asp_running is not None:
             from .asp import ASP_PREFIX
@@ -344,15 +396,6 @@ class ParamStore:
             out[ASP_PREFIX + "tdnn.norm.norm.running_mean"] = self.asp_running[:A]
             out[ASP_PREFIX + "tdnn.norm.norm.running_var"] = self.asp_running[A:]
         return out
-
-    def state_dict(self) -> "OrderedDict[str, torch.Tensor]":
-        sd = OrderedDict((n, self.p(n).detach().clone().cpu()) for n in self.shapes)
-        for n, b in self._buffers().items():
-            sd[n] = b.detach().clone().cpu()
-        if self.asp_running is not None:
-            from .asp import ASP_PREFIX
-            sd[ASP_PREFIX + "tdnn.norm.norm.num_batches_tracked"] = torch.tensor(self.asp_batches_tracked)
-        return sd
 
     # ------------------------------------------------------------------ reference-facing names / order
     def reference_parameter_order(self) -> List[str]:
@@ -621,11 +664,6 @@ class ParamStore:
     def stepped_size(self) -> int:
         """Number of leading arena elements a full (not head-only) optimiser step updates."""
         return min(self.n_train, self.n_body) if self.cnn_runtime_frozen else self.n_train
-
-    def adam_step(self, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
-                  grad_scale: float = 1.0, head_only: bool = False) -> None:
-        """Fused Adam without weight decay or clipping: optimizer_step() with the default description."""
-        self.optimizer_step(lr, beta1, OptimConfig(beta2=beta2, eps=eps), grad_scale, 0.0, head_only)
 
     def optimizer_step(self, lr: float, momentum_or_beta1: float = 0.9, cfg: Optional[OptimConfig] = None,
                        grad_scale: float = 1.0, gradient_clip_val: float = 0.0, head_only: bool = False,

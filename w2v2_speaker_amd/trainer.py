@@ -25,18 +25,14 @@ from .params import ParamStore
 from .spec_augment import compute_mask_indices
 
 
-class BucketAllReducer:
-    """All-reduce contiguous slices of the flat gradient buffer on a side stream as they become final."""
+class GradBucketReducer:
+    """What the bucket reducers share (BucketAllReducer below, comm.CAbiBucketAllReducer): which contiguous slice of the
+    flat gradient arena each firing bucket covers, and the side stream its collective runs on."""
 
-    def __init__(self, store: ParamStore, process_group=None, bucket_merge: int = 2):
-        import torch.distributed as dist
-        self.dist = dist
-        self.pg = process_group
-        self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
-        self.store = store
+    def __init__(self, store: ParamStore, world: int, bucket_merge: int):
+        self.store, self.world = store, world
         self.ranges, self.members = self.merge_buckets(store.grad_buckets(), bucket_merge)
         self.comm_stream = torch.cuda.Stream() if store.device.type == "cuda" else None
-        self.works = []
         self.buffer = None         # the arena bucket_ready() reduces; None = store.grad (a trainer that accumulates over
                                    # several micro-batches points it at store.grad_acc)
 
@@ -59,20 +55,37 @@ class BucketAllReducer:
             i = j + 1
         return ranges, members
 
-    def bucket_ready(self, name: str) -> None:
+    def ready_slice(self, name: str) -> Optional[torch.Tensor]:
+        """The arena slice to all-reduce now that bucket ``name`` is final on the compute stream, with the side stream
+        already ordered behind that stream; None when nothing is to be sent (one rank, a bucket that does not fire, an
+        empty range)."""
         if self.world == 1 or name not in self.ranges:
-            return
+            return None
         s, e = self.ranges[name]
         if e <= s:
+            return None
+        if self.comm_stream is not None:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream())
+            self.comm_stream.wait_event(ev)
+        return (self.buffer if self.buffer is not None else self.store.grad)[s:e]
+
+
+class BucketAllReducer(GradBucketReducer):
+    """All-reduce contiguous slices of the flat gradient buffer on a side stream as they become final."""
+
+    def __init__(self, store: ParamStore, process_group=None, bucket_merge: int = 2):
+        import torch.distributed as dist
+        self.dist = dist
+        self.pg = process_group
+        super().__init__(store, dist.get_world_size(process_group) if dist.is_initialized() else 1, bucket_merge)
+        self.works = []
+
+    def bucket_ready(self, name: str) -> None:
+        view = self.ready_slice(name)
+        if view is None:
             return
-        view = (self.buffer if self.buffer is not None else self.store.grad)[s:e]
-        if self.comm_stream is None:       # CPU / gloo test path
-            self.works.append(self.dist.all_reduce(view, op=self.dist.ReduceOp.SUM, group=self.pg, async_op=True))
-            return
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self.comm_stream.wait_event(ev)
-        with torch.cuda.stream(self.comm_stream):
+        with torch.cuda.stream(self.comm_stream):          # (no stream on the CPU / gloo test path: a no-op)
             self.works.append(self.dist.all_reduce(view, op=self.dist.ReduceOp.SUM, group=self.pg, async_op=True))
 
     def broadcast_parameters(self, root: int = 0, host_counters: Optional[Sequence[int]] = None) -> List[int]:
@@ -112,7 +125,7 @@ class BucketAllReducer:
             torch.cuda.current_stream().wait_stream(self.comm_stream)
 
 
-class SpeakerTrainer:
+class SpeakerTrainer(fused.WindowedTrainer):
     def __init__(self, store: ParamStore, plan: Plan, schedule, process_group=None, beta2: float = 0.999,
                  eps: float = 1e-8, layerdrop_seed: int = 1234, mask_seed: int = 7, reducer=None,
                  optimizer: Optional[OptimConfig] = None, gradient_clip_val: float = 0.0,
@@ -123,22 +136,13 @@ class SpeakerTrainer:
         ``beta2`` / ``eps`` and no weight decay.  The schedule's second value is beta1 under Adam and the momentum under
         SGD (what torch's OneCycleLR cycles for each).  gradient_clip_val: PL's ``trainer.gradient_clip_val`` (global
         norm; 0 = off), applied to the all-reduced, unscaled gradient inside the optimiser launch.
-        accumulate_grad_batches: PL's ``trainer.accumulate_grad_batches`` = N (ref: config/trainer/trainer.yaml:33).  At
-        N > 1 one ``train_step`` call is one micro-batch: its gradient is added into ``store.grad_acc``, and only the N-th
-        call of a window all-reduces (PL's ``no_sync`` on the others), steps on the mean over world * N micro-batches and
-        advances the schedule; ``stepped`` tells which kind the last call was, ``flush()`` closes a partial window."""
+        accumulate_grad_batches: PL's ``trainer.accumulate_grad_batches`` = N (ref: config/trainer/trainer.yaml:33), see
+        optim.fused.WindowedTrainer; only the N-th call of a window all-reduces (PL's ``no_sync`` on the others)."""
         assert plan.train
-        if int(accumulate_grad_batches) != accumulate_grad_batches or accumulate_grad_batches < 1:
-            raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {accumulate_grad_batches!r}")
-        self.accumulate_grad_batches = int(accumulate_grad_batches)
-        self.stepped = False               # whether the last train_step / flush call ran the optimiser
-        self.store, self.plan, self.schedule = store, plan, schedule
-        self.beta2, self.eps = beta2, eps
-        self.optimizer = optimizer if optimizer is not None else OptimConfig(beta2=beta2, eps=eps)
-        self.gradient_clip_val = float(gradient_clip_val)
-        self.step = 0
         self.reducer = reducer if reducer is not None else BucketAllReducer(store, process_group)
-        self.world = self.reducer.world
+        super().__init__(store, schedule, optimizer if optimizer is not None else OptimConfig(beta2=beta2, eps=eps),
+                         gradient_clip_val, accumulate_grad_batches, self.reducer.world)
+        self.plan, self.beta2, self.eps = plan, beta2, eps
         if self.accumulate_grad_batches > 1 and self.world > 1:
             if not hasattr(self.reducer, "buffer"):
                 raise TypeError("accumulate_grad_batches > 1 on several ranks needs a reducer with a `buffer` attribute "
@@ -196,9 +200,7 @@ class SpeakerTrainer:
         loss, softmax = frozen_plan.head_forward_backward(label)
         self.reducer.bucket_ready("head")
         self.reducer.wait()
-        lr, second = self.schedule.at(self.step)
-        store.optimizer_step(lr, second, self.optimizer, 1.0 / self.world, self.gradient_clip_val, head_only=True)
-        self.step += 1
+        self._optimizer_step(head_only=True)
         self.stepped = True
         return loss, softmax
 
@@ -220,9 +222,7 @@ class SpeakerTrainer:
         loss, softmax = plan.head_forward_backward(label)
         plan.backward(on_bucket_ready=self.reducer.bucket_ready)
         self.reducer.wait()
-        lr, second = self.schedule.at(self.step)
-        store.optimizer_step(lr, second, self.optimizer, 1.0 / self.world, self.gradient_clip_val)
-        self.step += 1
+        self._optimizer_step()
         self.stepped = True
         return loss, softmax
 
@@ -250,7 +250,7 @@ class SpeakerTrainer:
         store.accum_head_only = False
         self.stepped = last
         if last:
-            self._close_window(False)
+            self._close_window()
         return loss, softmax
 
     def _accumulate_and_reduce(self, name: str) -> None:
@@ -275,32 +275,18 @@ class SpeakerTrainer:
         store.accum_head_only = True
         self.stepped = last
         if last:
-            if self.world > 1:
-                self.reducer.buffer = store.grad_acc
-                self.reducer.bucket_ready("head")
-            self._close_window(True)
+            self._reduce_window()
+            self._close_window()
         return loss, softmax
 
-    def _close_window(self, head_only: bool) -> None:
-        store = self.store
+    def _close_window(self) -> None:
         self.reducer.wait()
-        lr, second = self.schedule.at(self.step)
-        store.optimizer_step(lr, second, self.optimizer, 1.0 / (self.world * self.accumulate_grad_batches),
-                             self.gradient_clip_val, head_only=head_only, grad=store.grad_acc)
-        self.step += 1
-        store.accum_count = 0
+        super()._close_window(self.store.accum_head_only)
 
-    def flush(self) -> None:
-        """Close a partial window (the end of an epoch): all-reduce what has been accumulated and step on it, still
-        divided by world * N -- PL divides every micro-batch's loss by N, also those of a short last window.  Nothing
-        happens when no window is open."""
-        store = self.store
-        self.stepped = False
-        if self.accumulate_grad_batches == 1 or store.accum_count == 0:
-            return
+    def _reduce_window(self) -> None:
+        """Hand every bucket of the open window's arena (the head's alone when its micro-batches ran with the encoder
+        frozen) to the reducer."""
         if self.world > 1:
-            self.reducer.buffer = store.grad_acc
-            for name in (("head",) if store.accum_head_only else tuple(self.reducer.ranges)):
+            self.reducer.buffer = self.store.grad_acc
+            for name in (("head",) if self.store.accum_head_only else tuple(self.reducer.ranges)):
                 self.reducer.bucket_ready(name)
-        self._close_window(store.accum_head_only)
-        self.stepped = True
