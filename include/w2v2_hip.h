@@ -460,6 +460,19 @@ int w2v2_bce_head_fwd_bwd(const float* emb, const float* w, const float* b, cons
                           float* loss_rows, float* dlogit, float* demb, float* dw, float* db, int B, int H,
                           const float* loss_scale, void* stream);
 
+/* Triplet margin head (ref: src/optim/loss/triplet_loss.py:21-107 -> F.triplet_margin_loss, p = 2, eps = 1e-6 added to
+ * the difference, no swap; mean taken by the caller): emb [B][E] f32 with row stride ld; pos / neg [B] int64 (device)
+ * name the positive and negative ROW of every anchor row.  d_ap / d_an [B] = ||a - p + eps|| / ||a - n + eps||,
+ * loss_rows [B] = max(margin + d_ap - d_an, 0), unweighted.  demb [B][E] (contiguous; may be NULL: forward only)
+ * = coef * *loss_scale / B * d(sum of loss rows)/d(emb), a row being active when margin + d_ap - d_an >= 0 (torch's
+ * clamp_min backward); written when accumulate == 0 (rows nobody names and inactive rows: exact zeros), added to what
+ * demb holds when accumulate != 0.  One writer per element and a fixed summation order (ascending anchor, its
+ * positive term before its negative term): no atomics, bitwise reproducible.  An index outside [0, B) is not
+ * dereferenced: NaN loss and distances for that row, no gradient.  d == 0 gives a zero unit vector.  Two launches. */
+int w2v2_triplet_fwd_bwd(const float* emb, int64_t ld, const int64_t* pos, const int64_t* neg, float* d_ap,
+                         float* d_an, float* loss_rows, float* demb, int B, int E, float margin, float coef,
+                         int accumulate, const float* loss_scale, void* stream);
+
 /* ------------------------------------------------------------------------------ ECAPA-TDNN pieces
  * ref: src/lightning_modules/speaker/ecapa_tdnn.py:75-85 -> speechbrain 0.5.x ECAPA_TDNN (not part of the reference
  * tree; restated in oracle/ecapa_oracle.py).  Channels-last [B*T][C] activations; `ld*` = row stride in elements so

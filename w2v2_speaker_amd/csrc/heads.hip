@@ -436,3 +436,139 @@ extern "C" int w2v2_bce_head_fwd_bwd(const float* emb, const float* w, const flo
   W2V2_CHECK_LAUNCH("bce_head");
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------ triplet margin head
+// ref: src/optim/loss/triplet_loss.py:21-107 -> F.triplet_margin_loss(anchor, positive, negative, margin) with torch's
+// defaults (p = 2, eps = 1e-6 added to the DIFFERENCE, swap off, mean): d(x, y) = ||x - y + eps||,
+// loss_i = max(margin + d(a_i, p_i) - d(a_i, n_i), 0) with p_i = emb[pos[i]], n_i = emb[neg[i]] rows of the same batch.
+// Row kernel (one workgroup per anchor): both distances and the loss row.  An index outside [0, B) is not
+// dereferenced: NaN distances and loss for the row, no gradient (the bad_label convention of the kernels above).
+constexpr float TRIPLET_EPS = 1e-6f;
+__global__ __launch_bounds__(256) void triplet_row_kernel(const float* __restrict__ emb, int64_t ld,
+                                                          const int64_t* __restrict__ pos, const int64_t* __restrict__ neg,
+                                                          float* __restrict__ d_ap, float* __restrict__ d_an,
+                                                          float* __restrict__ loss_rows, int B, int E, float margin) {
+  __shared__ float sh[4], sh2[4];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const int64_t pi = pos[row], ni = neg[row];
+  if (pi < 0 || pi >= B || ni < 0 || ni >= B) {         // (block-uniform)
+    if (tid == 0) d_ap[row] = d_an[row] = loss_rows[row] = __builtin_nanf("");
+    return;
+  }
+  const float* a = emb + (int64_t)row * ld;
+  const float* p = emb + pi * ld;
+  const float* n = emb + ni * ld;
+  float sp = 0.f, sn = 0.f;
+  int tail = 0;
+  if ((ld & 3) == 0 && (reinterpret_cast<uintptr_t>(emb) & 15) == 0) {
+    const float4 *a4 = reinterpret_cast<const float4*>(a), *p4 = reinterpret_cast<const float4*>(p),
+                 *n4 = reinterpret_cast<const float4*>(n);
+    for (int c = tid; c < (E >> 2); c += 256) {
+      const float4 av = a4[c], pv = p4[c], nv = n4[c];
+      const float dp[4] = {av.x - pv.x + TRIPLET_EPS, av.y - pv.y + TRIPLET_EPS, av.z - pv.z + TRIPLET_EPS,
+                           av.w - pv.w + TRIPLET_EPS};
+      const float dn[4] = {av.x - nv.x + TRIPLET_EPS, av.y - nv.y + TRIPLET_EPS, av.z - nv.z + TRIPLET_EPS,
+                           av.w - nv.w + TRIPLET_EPS};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { sp = fmaf(dp[k], dp[k], sp); sn = fmaf(dn[k], dn[k], sn); }
+    }
+    tail = E & ~3;
+  }
+  for (int c = tail + tid; c < E; c += 256) {           // the whole row when it is not 16-byte addressable, else E % 4
+    const float av = a[c], dp = av - p[c] + TRIPLET_EPS, dn = av - n[c] + TRIPLET_EPS;
+    sp = fmaf(dp, dp, sp);
+    sn = fmaf(dn, dn, sn);
+  }
+  block_reduce_sum2<4>(sp, sn, sh, sh2);
+  if (tid == 0) {
+    const float dap = sqrtf(sp), dan = sqrtf(sn), v = margin + dap - dan;
+    d_ap[row] = dap;
+    d_an[row] = dan;
+    loss_rows[row] = v > 0.f ? v : (v <= 0.f ? 0.f : v);      // (a NaN stays a NaN)
+  }
+}
+
+// Gradient kernel: one writer per demb element (workgroup = output row j, thread = column), no atomics.  With
+// g_i = coef * loss_scale / B where row i is active (margin + d_ap - d_an >= 0, torch's clamp_min backward) and 0
+// otherwise, u_ap = (a - p + eps) / d_ap, u_an = (a - n + eps) / d_an (zero vector when d == 0):
+//   demb[j] = g_j (u_ap_j - u_an_j) - sum_{i: pos[i] = j} g_i u_ap_i + sum_{i: neg[i] = j} g_i u_an_i
+// in ascending i, the pos term of an i before its neg term: a fixed order, bitwise reproducible.  The rows i that name
+// j are found 256 at a time by wave ballots; only those are visited.
+__global__ __launch_bounds__(256) void triplet_grad_kernel(const float* __restrict__ emb, int64_t ld,
+                                                           const int64_t* __restrict__ pos, const int64_t* __restrict__ neg,
+                                                           const float* __restrict__ d_ap, const float* __restrict__ d_an,
+                                                           float* __restrict__ demb, int B, int E, float margin, float coef,
+                                                           const float* __restrict__ loss_scale, int accumulate) {
+  __shared__ unsigned long long mpos[4], mneg[4];
+  const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int e = blockIdx.y * 256 + tid;
+  const bool live = e < E;
+  const float g = coef * (loss_scale ? loss_scale[0] : 1.0f) / (float)B;
+  const float aj = live ? emb[(int64_t)j * ld + e] : 0.f;
+  float acc = 0.f;
+  {
+    const int64_t pj = pos[j], nj = neg[j];
+    if (pj >= 0 && pj < B && nj >= 0 && nj < B) {
+      const float dap = d_ap[j], dan = d_an[j];
+      if (margin + dap - dan >= 0.f && live) {
+        const float ip = dap > 0.f ? 1.0f / dap : 0.f, in = dan > 0.f ? 1.0f / dan : 0.f;
+        const float uap = (aj - emb[pj * ld + e] + TRIPLET_EPS) * ip, uan = (aj - emb[nj * ld + e] + TRIPLET_EPS) * in;
+        acc = g * (uap - uan);
+      }
+    }
+  }
+  for (int c0 = 0; c0 < B; c0 += 256) {
+    const int i = c0 + tid;
+    bool fp = false, fn = false;
+    if (i < B) {
+      const int64_t pi = pos[i], ni = neg[i];
+      if (pi >= 0 && pi < B && ni >= 0 && ni < B && margin + d_ap[i] - d_an[i] >= 0.f) {
+        fp = pi == j;
+        fn = ni == j;
+      }
+    }
+    const unsigned long long bp = __ballot(fp), bn = __ballot(fn);
+    __syncthreads();                                     // (the previous chunk's masks have been read)
+    if (lane == 0) { mpos[wave] = bp; mneg[wave] = bn; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const unsigned long long mp = mpos[w], mn = mneg[w];
+      unsigned long long m = mp | mn;                    // block-uniform: no divergence
+      while (m) {
+        const int b = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const int r = c0 + w * 64 + b;
+        if (live) {
+          const float ar = emb[(int64_t)r * ld + e];
+          if ((mp >> b) & 1) {                           // j is the positive of anchor r: d/dp = -u_ap
+            const float d = d_ap[r], iv = d > 0.f ? 1.0f / d : 0.f;
+            acc -= g * ((ar - aj + TRIPLET_EPS) * iv);
+          }
+          if ((mn >> b) & 1) {                           // j is the negative of anchor r: d/dn = +u_an
+            const float d = d_an[r], iv = d > 0.f ? 1.0f / d : 0.f;
+            acc += g * ((ar - aj + TRIPLET_EPS) * iv);
+          }
+        }
+      }
+    }
+  }
+  if (live) {
+    float* o = demb + (int64_t)j * E + e;
+    *o = accumulate ? *o + acc : acc;
+  }
+}
+
+extern "C" int w2v2_triplet_fwd_bwd(const float* emb, int64_t ld, const int64_t* pos, const int64_t* neg, float* d_ap,
+                                    float* d_an, float* loss_rows, float* demb, int B, int E, float margin, float coef,
+                                    int accumulate, const float* loss_scale, void* stream) {
+  W2V2_REQUIRE(emb && pos && neg && d_ap && d_an && loss_rows && B > 0 && E > 0 && ld >= E, "triplet: bad arguments");
+  W2V2_REQUIRE(demb != nullptr || !accumulate, "triplet: accumulate needs the gradient output");
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(triplet_row_kernel, dim3(B), dim3(256), 0, st, emb, ld, pos, neg, d_ap, d_an, loss_rows, B, E, margin);
+  if (demb != nullptr)
+    hipLaunchKernelGGL(triplet_grad_kernel, dim3(B, (unsigned)cdiv(E, 256)), dim3(256), 0, st, emb, ld, pos, neg, d_ap,
+                       d_an, demb, B, E, margin, coef, loss_scale, accumulate);
+  W2V2_CHECK_LAUNCH("triplet");
+  return 0;
+}

@@ -12,19 +12,29 @@ from typing import Iterable, Iterator, List, Optional, Sequence
 
 import torch
 
-from .pipeline import (AudioChunkSelector, BatchProcessor, InputNormalizer2D, default_collate_fn, to_sample)
+from .pipeline import (AudioChunkSelector, BatchProcessor, InputNormalizer2D, TripletSpeakerBatchProcessor,
+                       default_collate_fn, to_sample)
 from .shards import iter_shard
 
 
 class ShardDataset:
     """One pass over the shards: decode -> SpeakerClassificationDataSample -> preprocessors (each may return one
-    sample or a list, ref ``_pipe_preprocessors`` :586-600) -> BatchProcessor."""
+    sample or a list, ref ``_pipe_preprocessors`` :586-600) -> BatchProcessor, or with
+    ``batch_processing_mode="categorical_triplets"`` (ref: voxceleb.py:449-466) the TripletSpeakerBatchProcessor, whose
+    batches hold two utterances of every speaker in them."""
 
     def __init__(self, shard_paths: Sequence[str], batch_size: int, queue_size: int = 1024,
-                 preprocessors: Optional[List] = None, collate_fn=default_collate_fn):
+                 preprocessors: Optional[List] = None, collate_fn=default_collate_fn,
+                 batch_processing_mode: str = "categorical", ensure_all_samples_seen: bool = False):
         self.shard_paths = list(shard_paths)
         self.preprocessors = preprocessors if preprocessors is not None else self.train_pipeline()
-        self.batcher = BatchProcessor(batch_size, max(queue_size, batch_size), collate_fn)
+        if batch_processing_mode == "categorical":
+            self.batcher = BatchProcessor(batch_size, max(queue_size, batch_size), collate_fn)
+        elif batch_processing_mode == "categorical_triplets":
+            self.batcher = TripletSpeakerBatchProcessor(batch_size, max(queue_size, batch_size), collate_fn,
+                                                        ensure_all_samples_seen)
+        else:
+            raise ValueError(f"unknown batch_processing_mode {batch_processing_mode!r}")
 
     @staticmethod
     def train_pipeline(chunk_seconds: float = 3.0):

@@ -138,3 +138,109 @@ class BatchProcessor:
         while len(batch) < self.max_batch_size and len(self.queue) >= 1:
             batch.append(self.queue.pop(random.randint(0, len(self.queue) - 1)))
         return self.collate_fn(batch)
+
+
+class TripletSpeakerBatchProcessor:
+    """ref: voxceleb.py:888-1062 (``batch_processing_mode: categorical_triplets``): every batch holds two utterances
+    (anchor, positive) of up to ``max_batch_size // 2`` speakers, so the triplet losses find a positive for every row.
+    Samples wait in a per-speaker map; a speaker is *valid* while it holds two or more.  A batch is possible once two
+    speakers are valid: the speakers are drawn with ``random.sample`` over the valid set, and per drawn speaker two
+    utterances are popped at ``random.randint`` positions -- the reference's calls of the ``random`` module in the
+    reference's order (it hands the *set* to ``random.sample``, which Python 3.10 turns into ``tuple(set)`` and 3.11
+    refuses; the tuple is made here).  With ``ensure_all_samples_seen`` the left-overs (speakers with one utterance, or a
+    single valid speaker) are drained in batches without the pair structure, as validation needs every sample."""
+
+    def __init__(self, max_batch_size: int, max_queue_size: int,
+                 collate_fn: Callable[[List[SpeakerClassificationDataSample]], SpeakerClassificationDataBatch]
+                 = default_collate_fn, ensure_all_samples_seen: bool = False):
+        if max_batch_size % 2 == 1:
+            raise ValueError("batch size needs to be even to allow for triplets")
+        self.max_batch_size, self.max_queue_size, self.collate_fn = max_batch_size, max_queue_size, collate_fn
+        self.ensure_all_samples_seen = ensure_all_samples_seen
+        self.sample_keys = set()
+        self._reset()
+
+    def _reset(self) -> None:
+        self.map_size = 0
+        self.by_speaker = {}               # speaker -> its waiting samples, in arrival order
+        self.valid_keys, self.invalid_keys = set(), set()        # speakers holding >= 2 / exactly 1 samples
+        self.sample_keys.clear()
+
+    def is_triplet_batch_possible(self) -> bool:
+        return len(self.valid_keys) >= 2
+
+    def __call__(self, sample_iterator: Iterable[SpeakerClassificationDataSample]
+                 ) -> Iterator[SpeakerClassificationDataBatch]:
+        self._reset()
+        for sample in sample_iterator:
+            if not isinstance(sample, SpeakerClassificationDataSample):
+                raise ValueError(f"batch is expected to be of type {SpeakerClassificationDataSample}")
+            self._add(sample)
+            if self.is_triplet_batch_possible():
+                yield self._get_batch()
+            if self.map_size == 2 * self.max_queue_size:
+                raise ValueError("queue size has exceeded its limit while no triplet batch could be formed")
+        while self.is_triplet_batch_possible():
+            yield self._get_batch()
+        if self.ensure_all_samples_seen:
+            while self.map_size >= 1:
+                yield self._get_batch()
+        self._reset()
+
+    def _add(self, sample: SpeakerClassificationDataSample) -> None:
+        if sample.key in self.sample_keys:
+            raise ValueError("this sample has already been loaded")
+        self.sample_keys.add(sample.key)
+        self.map_size += 1
+        spk = sample.ground_truth
+        waiting = self.by_speaker.setdefault(spk, [])
+        waiting.append(sample)
+        if len(waiting) >= 2:
+            self.invalid_keys.discard(spk)
+            self.valid_keys.add(spk)
+        else:
+            self.invalid_keys.add(spk)
+
+    def _took_from(self, spk) -> None:
+        """Book-keeping after samples of speaker ``spk`` left the map."""
+        left = len(self.by_speaker[spk])
+        if left < 2:
+            self.valid_keys.discard(spk)
+            self.invalid_keys.add(spk)
+        if left == 0:
+            self.invalid_keys.discard(spk)
+            del self.by_speaker[spk]
+
+    def _get_batch(self) -> SpeakerClassificationDataBatch:
+        if not self.is_triplet_batch_possible():
+            if not self.ensure_all_samples_seen:
+                raise ValueError("cannot get a batch while state does not allow for triplets")
+            return self.collate_fn(self._drain())
+        if not self.ensure_all_samples_seen and self.map_size <= 3:
+            raise ValueError("cannot get a batch with less than 4 samples")
+        speakers = random.sample(tuple(self.valid_keys), min(self.max_batch_size // 2, len(self.valid_keys)))
+        batch = []
+        for spk in speakers:
+            waiting = self.by_speaker[spk]
+            batch.append(waiting.pop(random.randint(0, len(waiting) - 1)))      # anchor
+            batch.append(waiting.pop(random.randint(0, len(waiting) - 1)))      # positive
+            self.map_size -= 2
+            self._took_from(spk)
+        return self.collate_fn(batch)
+
+    def _drain(self) -> List[SpeakerClassificationDataSample]:
+        """Up to max_batch_size left-over samples, oldest of a speaker first: from the valid speaker the set iterates to
+        last, else from the first single-sample speaker."""
+        batch = []
+        while len(batch) < self.max_batch_size and self.map_size >= 1:
+            spk = None
+            for k in self.valid_keys:
+                spk = k
+            if spk is None:
+                spk = next((k for k in self.invalid_keys if len(self.by_speaker[k]) >= 1), None)
+            if spk is None:
+                raise ValueError("no valid sample")
+            batch.append(self.by_speaker[spk].pop(0))
+            self.map_size -= 1
+            self._took_from(spk)
+        return batch

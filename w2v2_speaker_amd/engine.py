@@ -177,8 +177,10 @@ class Plan:
                  insert_cls_token: bool = False, cls_token_constant: float = 1.0,
                  aam_margin: float = 0.2, aam_scale: float = 30.0, fused_attention: Optional[bool] = None,
                  seed: int = 7, keep_hidden_states: bool = False, paired: bool = False,
-                 sep_token_constant: float = -1.0, encoder_frames: Optional[int] = None):
+                 sep_token_constant: float = -1.0, encoder_frames: Optional[int] = None,
+                 triplet_margin: float = 1.0, triplet_coef: float = 1.0):
         cfg = store.cfg
+        self.triplet_margin, self.triplet_coef = float(triplet_margin), float(triplet_coef)
         self.store, self.cfg, self.B, self.N, self.train = store, cfg, batch, n_samples, train
         # paired input (ref: wav2vec2_paired_input.py:163-207): the conv stack and projection run on 2B waveforms (first
         # B = left, last B = right utterance of each pair); the encoder sees B sequences [CLS] left [SEP] right [SEP]
@@ -241,7 +243,7 @@ class Plan:
         self.grouped = train and store.flat_lp_t is not None
         self.wg_group = self._wgrad_group_size() if train else 2
         self.g_wgrad_pair, self._wgrad_cache = {}, {}
-        self.head, self.fc, self._lnfold = None, None, None
+        self.head, self.fc, self._lnfold, self.triplet = None, None, None, None
         # variable-length evaluation (forward(..., lengths=)): device int32 table [conv-0 frames | encoder frames] of the
         # current forward, or None on the fixed-length path
         self._len_dev, self._len = None, None
@@ -393,7 +395,7 @@ class Plan:
                                 w_grad=st.g("linear.weight") if self.train else None,
                                 b_grad=st.g("linear.bias") if self.train else None, emb=self.emb, train=self.train,
                                 loss_scale=st.scaler)
-        elif st.head is not None:
+        elif st.head is not None and st.head != "triplet":
             from .heads import ClassifierHead, FcStack
             aam = st.head == "aam"
             nh = len(st.hidden_fc)
@@ -402,8 +404,8 @@ class Plan:
             head_in = self.fc.x[-1] if self.fc is not None else self.emb
             wname = "loss_fn.fc_weights" if aam else f"fc_list.{nh}.0.weight"
             bname = f"fc_list.{nh}.0.bias"
-            self.head = ClassifierHead(st.head, self.head_rows, st.head_in_dim, st.num_speakers, w_master=st.p(wname),
-                                       w_operand=st.w(wname), w_grad=st.g(wname) if self.train else None,
+            self.head = ClassifierHead("aam" if aam else "ce", self.head_rows, st.head_in_dim, st.num_speakers,
+                                       w_master=st.p(wname), w_operand=st.w(wname), w_grad=st.g(wname) if self.train else None,
                                        bias=None if aam else st.p(bname),
                                        bias_grad=None if (aam or not self.train) else st.g(bname),
                                        emb=head_in, act_dtype=self.adt, train=self.train, margin=self.margin,
@@ -433,6 +435,18 @@ class Plan:
             else:
                 self.dS = torch.zeros(B * heads * T, self.Tl, dtype=self.adt, device=self.dev)
             self._lnfold = ops.LnFoldGroup(H, self.dev)
+        if st.head in ("triplet", "triplet_ce"):
+            # ref: speaker_recognition_module.py:85-93,269-294: the triplet term acts on the pooled embedding; alone it
+            # writes self.demb, next to the CE head it is added to the gradient the CE path has left there
+            if self.no_pool:
+                raise ValueError("triplet loss does not support no_pooling")
+            from .heads import TripletHead
+            self.triplet = TripletHead(self.head_rows, E, emb=self.emb, margin=self.triplet_margin,
+                                       coef=self.triplet_coef, train=self.train, loss_scale=st.scaler,
+                                       demb=self.demb if self.train else None,
+                                       accumulate=self.train and st.head == "triplet_ce")
+            if st.head == "triplet":
+                self.head = self.triplet
 
     # ------------------------------------------------------------------------------------------ descriptors
     def _build_gemms(self) -> None:
@@ -1008,10 +1022,16 @@ class Plan:
         return self._asp_cur
 
     # ------------------------------------------------------------------------------------------ head
-    def head_forward_backward(self, label: torch.Tensor):
+    def head_forward_backward(self, label: torch.Tensor, triplets=None):
         """Loss head on self.emb (hidden FC layers, then heads.ClassifierHead): returns (loss scalar tensor,
         softmax [B,C]); a training plan also leaves d(loss)/d(pooled embedding) in self.demb and the head gradients
-        in the flat buffer."""
+        in the flat buffer.  Triplet heads: ``triplets`` = (pos, neg) row indices of every anchor row (None: heads.TripletHead
+        draws them from ``label.tolist()``, a host synchronisation); "triplet" returns (loss, None), "triplet_ce" returns
+        (CE + triplet_coef * triplet, softmax) with the sum taken on the device."""
+        if triplets is not None and self.triplet is None:
+            raise ValueError(f"triplets were given, but the head is {self.store.head!r}")
+        if self.store.head == "triplet":
+            return self.triplet.forward_backward(label, triplets)
         if self.no_pool:                 # one prediction per frame: the utterance label for each of its T frames
             label = torch.repeat_interleave(label, self.T)
         if self.fc is not None:
@@ -1019,6 +1039,9 @@ class Plan:
         out = self.head.forward_backward(label)
         if self.fc is not None and self.train:
             self.demb.copy_(self.fc.backward(self.head.demb))
+        if self.triplet is not None:     # "triplet_ce": the triplet term is added to the gradient the CE path has left
+            tl, _ = self.triplet.forward_backward(label, triplets)
+            return torch.add(out[0], tl, alpha=self.triplet_coef), out[1]
         return out
 
     def speaker_embedding(self, embedding_layer_idx: int = -1) -> torch.Tensor:
@@ -1029,7 +1052,7 @@ class Plan:
         nh = len(self.store.hidden_fc)
         if embedding_layer_idx < nh:
             return self.fc.forward(upto=embedding_layer_idx)
-        if embedding_layer_idx == nh and self.store.head == "ce":
+        if embedding_layer_idx == nh and self.store.head in ("ce", "triplet_ce"):
             if self.fc is not None:
                 self.fc.forward()
             h = self.head

@@ -4,7 +4,9 @@ src/optim/loss/cross_entropy.py:15-33).  One object = fixed buffers + prebuilt G
 given (batch, embedding dim, classes); used by engine.Plan and by the nn.Module surface."""
 from __future__ import annotations
 
-from typing import Optional
+import random
+from collections import Counter
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -146,6 +148,84 @@ class BceHead:
         ops.mean(self.loss_rows, loss)
         return loss, self.prob
 
+
+def sample_triplets(labels: Sequence[int], rng=random) -> Tuple[List[int], List[int]]:
+    """(pos, neg): for every batch row the row of its positive (another row with the same label) and of its negative
+    (a row with another label), drawn like ref: src/optim/loss/triplet_loss.py:45-99 -- row by row, the positive then
+    the negative, each ``rng.choice`` over the candidate rows in ascending order -- so the same ``random.seed`` gives
+    the reference's triplets.  ValueError when a label occurs once (the reference's ``verify_labels`` assertion) or when
+    the batch holds one speaker (no negative exists)."""
+    labels = [int(l) for l in labels]
+    count = Counter(labels)
+    single = sorted(l for l, c in count.items() if c < 2)
+    if single:
+        raise ValueError(f"triplet loss: every label of a batch must occur at least twice, labels {single} occur once")
+    if len(count) < 2:
+        raise ValueError("triplet loss: a batch with a single speaker has no negative")
+    pos, neg = [], []
+    for i, l in enumerate(labels):
+        pos.append(rng.choice([j for j, m in enumerate(labels) if m == l and j != i]))
+        neg.append(rng.choice([j for j, m in enumerate(labels) if m != l]))
+    return pos, neg
+
+
+class TripletHead:
+    """ref: src/optim/loss/triplet_loss.py (F.triplet_margin_loss over one sampled triplet per batch row) on
+    w2v2_triplet_fwd_bwd: two launches + the mean.  The host never waits for the step it enqueues: the index upload goes
+    through two pinned staging buffers used in turn, and the only wait is for the upload of two steps ago.  ``emb`` [B, E] f32 is read in place;
+    ``demb`` (given, or allocated) is written, or added to with ``accumulate`` (the triplet + CE head, whose CE part has
+    filled it).  ``coef`` weighs the gradient (``c_triplet``); ``loss_rows`` and the returned loss stay unweighted."""
+
+    def __init__(self, batch: int, embed_dim: int, emb: torch.Tensor, margin: float = 1.0, coef: float = 1.0,
+                 train: bool = True, loss_scale: Optional[torch.Tensor] = None, demb: Optional[torch.Tensor] = None,
+                 accumulate: bool = False):
+        dev, f32 = emb.device, torch.float32
+        assert emb.dtype == f32 and emb.shape == (batch, embed_dim) and emb.stride(1) == 1
+        assert not accumulate or demb is not None, "accumulate adds to a gradient somebody else wrote"
+        self.B, self.E, self.emb, self.train = batch, embed_dim, emb, train
+        self.margin, self.coef, self.loss_scale, self.accumulate = float(margin), float(coef), loss_scale, accumulate
+        self.d_ap = torch.empty(batch, dtype=f32, device=dev)
+        self.d_an = torch.empty(batch, dtype=f32, device=dev)
+        self.loss_rows = torch.empty(batch, dtype=f32, device=dev)
+        self.demb = (demb if demb is not None else torch.empty(batch, embed_dim, dtype=f32, device=dev)) if train else None
+        # fixed device index buffers [2, B], fed from a pinned staging buffer by one non-blocking copy per step
+        self._idx = torch.zeros(2, batch, dtype=torch.int64, device=dev)
+        # two pinned staging buffers, used in turn: before one is rewritten the host waits for the upload that read it
+        # TWO steps ago (an event that has long fired), so the host may run one whole step ahead of the device
+        self._stage = [torch.zeros(2, batch, dtype=torch.int64, pin_memory=dev.type == "cuda") for _ in range(2)]
+        self._copied = [None, None]
+        self._turn = 0
+
+    def set_triplets(self, pos: Sequence[int], neg: Sequence[int]) -> None:
+        B = self.B
+        pos, neg = [int(v) for v in pos], [int(v) for v in neg]
+        if len(pos) != B or len(neg) != B:
+            raise ValueError(f"triplets: {len(pos)} positives and {len(neg)} negatives for a batch of {B}")
+        if min(pos + neg) < 0 or max(pos + neg) >= B:
+            raise ValueError(f"triplets: row indices must lie in [0, {B})")
+        t = self._turn
+        self._turn = 1 - t
+        if self._copied[t] is not None:
+            self._copied[t].synchronize()     # the upload of two steps ago has left this staging buffer
+        self._stage[t].copy_(torch.tensor([pos, neg], dtype=torch.int64))
+        self._idx.copy_(self._stage[t], non_blocking=True)
+        if self._stage[t].is_pinned():
+            self._copied[t] = torch.cuda.Event()
+            self._copied[t].record()
+
+    def forward_backward(self, label: Optional[torch.Tensor] = None, triplets=None):
+        """-> (loss, None).  ``triplets`` = (pos, neg) row indices (validated on the host); None draws them with
+        ``sample_triplets`` from ``label.tolist()`` -- a host synchronisation when the label is on the device."""
+        if triplets is None:
+            triplets = sample_triplets(label.tolist())
+        self.set_triplets(*triplets)
+        tr = self.train
+        ops.triplet_fwd_bwd(self.emb, self._idx[0], self._idx[1], self.d_ap, self.d_an, self.loss_rows,
+                            self.demb if tr else None, self.B, self.E, self.margin, self.coef, self.accumulate and tr,
+                            self.loss_scale if tr else None, ld=self.emb.stride(0))
+        loss = torch.empty((), dtype=torch.float32, device=self.loss_rows.device)
+        ops.mean(self.loss_rows, loss)
+        return loss, None
 
 
 class FcStack:

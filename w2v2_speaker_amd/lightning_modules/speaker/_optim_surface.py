@@ -104,7 +104,7 @@ class OptimizerSurface:
         if getattr(self, "_param_views", None) is None:
             store = self.store
             # reference registration order where the store knows it (the speaker heads of ParamStore), arena order else
-            names = (store.reference_parameter_order() if getattr(store, "head", None) in ("aam", "ce")
+            names = (store.reference_parameter_order() if getattr(store, "head", None) in ("aam", "ce", "triplet", "triplet_ce")
                      else list(store.shapes))
             self._param_views = {}
             for n in names:

@@ -30,7 +30,9 @@ from ...eval_batching import (DEFAULT_MAX_BATCH, DEFAULT_MAX_BATCH_SAMPLES, DEFA
                               padded_batches)
 from ...evaluation.speaker.cosine_distance import CosineDistanceEvaluator, EvaluationPair
 from ...models.handles import ModelHandle
-from ...optim.loss import AngularAdditiveMarginSoftMaxLoss, CrossEntropyLoss
+from ...heads import sample_triplets
+from ...optim.loss import (AngularAdditiveMarginSoftMaxLoss, CrossEntropyLoss, TripletCrossEntropyLoss,
+                           TripletLoss)
 from ...optim import OptimConfig
 from ...optim.schedule import OneCycle
 from ...params import ParamStore
@@ -178,13 +180,39 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
         # the channel mask on ``timestep_mask_prob``, which Wav2vec2FCModule hard-wires to 0 (quirk Q3,
         # ref: src/layers/embedding_masking.py:79, wav2vec2_fc.py:162-169)
         loss_fn = loss_fn_constructor()
+        self.triplet_margin, self.c_triplet = 1.0, 1.0
         if isinstance(loss_fn, AngularAdditiveMarginSoftMaxLoss):
             loss, margin, scale = "aam", float(loss_fn.margin), float(loss_fn.scale)
+        elif isinstance(loss_fn, TripletCrossEntropyLoss):        # (before CrossEntropyLoss, which it derives from)
+            loss, margin, scale = "triplet_ce", 0.2, 30.0
+            self.triplet_margin, self.c_triplet = float(loss_fn.margin), float(loss_fn.c_triplet)
+            if loss_fn.c_ce != 1:
+                raise NotImplementedError(f"TripletCrossEntropyLoss(c_ce={loss_fn.c_ce}): the CE row kernel has no loss "
+                                          "weight; only c_ce = 1 (the reference's configuration) is built")
+        elif isinstance(loss_fn, TripletLoss):
+            loss, margin, scale = "triplet", 0.2, 30.0
+            self.triplet_margin = float(loss_fn.margin)
         elif isinstance(loss_fn, CrossEntropyLoss):
             loss, margin, scale = "ce", 0.2, 30.0
         else:
-            raise NotImplementedError(f"loss {type(loss_fn).__name__}: only AngularAdditiveMarginSoftMaxLoss and "
-                                      "CrossEntropyLoss are on the hot path (w2v2_speaker_amd.optim.loss)")
+            raise NotImplementedError(f"loss {type(loss_fn).__name__}: only AngularAdditiveMarginSoftMaxLoss, "
+                                      "CrossEntropyLoss, TripletLoss and TripletCrossEntropyLoss are on the hot path "
+                                      "(w2v2_speaker_amd.optim.loss)")
+        if loss in ("triplet", "triplet_ce"):
+            # ref: speaker_recognition_module.py:85-93
+            if "none" in (cfg.stat_pooling_type.lower(), cfg.test_stat_pooling_type.lower()):
+                raise ValueError("triplet loss does not support no_pooling")
+            if cfg.embedding_layer_idx >= 0:
+                raise NotImplementedError(f"embedding_layer_idx = {cfg.embedding_layer_idx} under a triplet loss: the "
+                                          "triplet term would act on a hidden FC output; only the pooled embedding "
+                                          "(embedding_layer_idx < 0) is built")
+            if loss == "triplet" and cfg.wav2vec_initially_frozen and (cfg.num_frozen_steps is None
+                                                                       or cfg.num_frozen_steps > 0):
+                raise ValueError("TripletLoss with wav2vec_initially_frozen and num_frozen_steps > 0: the loss has no "
+                                 "parameters of its own, so nothing would be trainable while the network is frozen")
+            if loss == "triplet" and cfg.hidden_fc_layers_out:
+                raise NotImplementedError("TripletLoss with hidden_fc_layers_out: the loss acts on the pooled embedding, "
+                                          "the hidden layers would never receive a gradient")
         del loss_fn            # its sizes are placeholders (ref: config/optim/loss/aam_softmax.yaml), see module docstring
         self.model_cfg = W2V2Config.from_huggingface_id(cfg.wav2vec_hunggingface_id)
         self.num_speakers = num_speakers
@@ -204,7 +232,7 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
             self.embedding_size = self.stat_pool_dimension
         elif cfg.embedding_layer_idx < len(hidden):
             self.embedding_size = hidden[cfg.embedding_layer_idx]
-        elif cfg.embedding_layer_idx == len(hidden) and loss == "ce":
+        elif cfg.embedding_layer_idx == len(hidden) and loss in ("ce", "triplet_ce"):
             self.embedding_size = num_speakers
         else:
             raise ValueError("could not determine size of speaker embeddings")
@@ -240,15 +268,22 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
 
     @classmethod
     def from_config(cls, cfg: Wav2vec2FCModuleConfig, num_speakers: int, loss: str = "aam", aam_margin: float = 0.2,
-                    aam_scale: float = 30.0, **kw) -> "Wav2vec2FCModule":
+                    aam_scale: float = 30.0, triplet_margin: float = 1.0, c_triplet: float = 1.0,
+                    **kw) -> "Wav2vec2FCModule":
         """Short form for scripts and tests: the loss by name instead of a constructor."""
-        assert loss in ("aam", "ce")
+        assert loss in ("aam", "ce", "triplet", "triplet_ce")
         dev = kw.get("device", "cuda")
 
         def ctor():
             if loss == "aam":      # placeholder sizes, like config/optim/loss/aam_softmax.yaml
                 return AngularAdditiveMarginSoftMaxLoss(2, 2, margin=aam_margin, scale=aam_scale, device=dev,
                                                         act_dtype=torch.float32)
+            if loss == "triplet":
+                return TripletLoss(margin=triplet_margin)
+            if loss == "triplet_ce":      # (the reference's class has no margin argument: its triplet part runs at 1)
+                both = TripletCrossEntropyLoss(c_ce=1, c_triplet=c_triplet)
+                both.margin = triplet_margin
+                return both
             return CrossEntropyLoss()
         return cls(None, cfg, num_speakers, ctor, kw.pop("validation_pairs", None), kw.pop("test_pairs", None),
                    kw.pop("evaluator", None), **kw)
@@ -289,7 +324,10 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
         pooling = self.cfg.stat_pooling_type if train else self.cfg.test_stat_pooling_type
         return self._plans.lookup((batch, n, train, pooling), lambda: Plan(
             self.store, batch, n, train=train, reg=self.reg, pooling=pooling,
-            insert_cls_token=(pooling == "first+cls"), aam_margin=self.margin, aam_scale=self.scale))
+            insert_cls_token=(pooling == "first+cls"), aam_margin=self.margin, aam_scale=self.scale, **self._triplet_kw()))
+
+    def _triplet_kw(self) -> dict:
+        return {"triplet_margin": self.triplet_margin, "triplet_coef": self.c_triplet}
 
     # ------------------------------------------------------------------ reference surface
     def compute_speaker_embedding(self, input_tensor: torch.Tensor) -> torch.Tensor:
@@ -307,7 +345,7 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
         pooling = self.cfg.test_stat_pooling_type
         return self._bucket_plans.lookup((batch, n, pooling), lambda: Plan(
             self.store, batch, n, train=False, reg=self.reg, pooling=pooling,
-            insert_cls_token=(pooling == "first+cls"), aam_margin=self.margin, aam_scale=self.scale))
+            insert_cls_token=(pooling == "first+cls"), aam_margin=self.margin, aam_scale=self.scale, **self._triplet_kw()))
 
     def compute_speaker_embeddings(self, waveforms, *, quantum: int = DEFAULT_QUANTUM,
                                    max_batch_samples: int = DEFAULT_MAX_BATCH_SAMPLES,
@@ -351,7 +389,7 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
         nh = len(self.cfg.hidden_fc_layers_out)
         for i in range(self.cfg.embedding_layer_idx + 1, nh):
             x = self._linear(x, i, relu=True)
-        if self.loss == "ce" and self.cfg.embedding_layer_idx < nh:
+        if self.loss in ("ce", "triplet_ce") and self.cfg.embedding_layer_idx < nh:
             x = self._linear(x, nh, relu=False)
         if lead is not None:
             x = x.view(*lead, -1)
@@ -359,6 +397,8 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
 
     def forward(self, input_tensor: torch.Tensor):
         embedding = self.compute_speaker_embedding(input_tensor)
+        if self.loss == "triplet":         # ref: speaker_recognition_module.py:121-130 -- no prediction in this mode
+            return embedding, None
         return embedding, self.compute_speaker_prediction(embedding)
 
     def generate_example_input(self, include_batch_dimension: bool, batch_size: Optional[int] = None):
@@ -381,19 +421,24 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
                       optimizer_idx: Optional[int] = None):
         """forward + backward (+ all-reduce) + fused Adam; returns {"loss", "prediction", "train_acc"} (device
         tensors; train_acc = fraction of the batch whose arg-max prediction is the label, the quantity the
-        reference feeds torchmetrics.Accuracy, ref: speaker_recognition_module.py:296-307)."""
+        reference feeds torchmetrics.Accuracy, ref: speaker_recognition_module.py:296-307).  Triplet losses (ref:
+        :269-294): the triplets are drawn from ``batch.ground_truth`` before it goes to the device (no synchronisation
+        when the batch is still on the host); "triplet" returns prediction None and train_acc None."""
         x = prep_waveform_input(batch.network_input).to(self.device, torch.float32)
+        triplets = None
+        if self.loss in ("triplet", "triplet_ce"):
+            triplets = sample_triplets(batch.ground_truth.tolist())
         label = batch.ground_truth.to(self.device)
         pkey = (x.shape[0], x.shape[1], True, self.cfg.stat_pooling_type)
         plan = self._plan(x.shape[0], x.shape[1], True)
         loss, pred = self._trainer_step(
             pkey, lambda: SpeakerTrainer(self.store, plan, self.schedule, process_group=self.process_group,
                                          **self._trainer_options()),
-            lambda tr: self._run_step(tr, plan, x, label))
+            lambda tr: self._run_step(tr, plan, x, label, triplets))
         self.on_after_backward()
         return {"loss": loss, "prediction": pred, "train_acc": self.train_acc}
 
-    def _run_step(self, tr: SpeakerTrainer, plan: Plan, x: torch.Tensor, label: torch.Tensor):
+    def _run_step(self, tr: SpeakerTrainer, plan: Plan, x: torch.Tensor, label: torch.Tensor, triplets=None):
         if self._is_wav2vec_frozen:
             # frozen network = eval-mode forward (PL freeze()), head-only backward + Adam
             noreg = Wav2Vec2RegularisationConfig(activation_dropout=0.0, attention_dropout=0.0, feat_proj_dropout=0.0,
@@ -401,13 +446,13 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
             fplan = self._plans.lookup((x.shape[0], x.shape[1], "frozen"), lambda: Plan(
                 self.store, x.shape[0], x.shape[1], train=True, reg=noreg, pooling=self.cfg.stat_pooling_type,
                 insert_cls_token=(self.cfg.stat_pooling_type == "first+cls"), aam_margin=self.margin,
-                aam_scale=self.scale))
-            loss, pred = tr.train_step_frozen_encoder(fplan, x, label)
+                aam_scale=self.scale, **self._triplet_kw()))
+            loss, pred = tr.train_step_frozen_encoder(fplan, x, label, triplets=triplets)
             head = fplan.head
         else:
-            loss, pred = tr.train_step(x, label)
+            loss, pred = tr.train_step(x, label, triplets=triplets)
             head = plan.head
-        self.train_acc = head.correct.mean()
+        self.train_acc = head.correct.mean() if self.loss != "triplet" else None
         return loss, pred
 
     def compute_ensemble_embedding(self, input_tensor: torch.Tensor):

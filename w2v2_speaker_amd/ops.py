@@ -1060,3 +1060,20 @@ def bce_head_fwd_bwd(emb, w, b, label, prob, loss_rows, dlogit, demb, dw, db, B:
                                            loss_rows.data_ptr(), _p(dlogit), _p(demb), _p(dw), _p(db), B, H,
                                            _p(loss_scale), stream()), "bce_head")
 
+
+
+def triplet_fwd_bwd(emb, pos, neg, d_ap, d_an, loss_rows, demb, B: int, E: int, margin: float, coef: float = 1.0,
+                    accumulate: bool = False, loss_scale=None, ld: Optional[int] = None) -> None:
+    """Triplet margin head (w2v2_triplet_fwd_bwd): emb [B, E] f32 with row stride ``ld`` (default emb.stride(0)), pos / neg [B] int64
+    row indices on the device -> d_ap, d_an, loss_rows [B]; demb [B, E] (None = forward only) written, or added to with
+    ``accumulate``, scaled by coef * loss_scale[0] / B."""
+    _dev(emb, pos, neg, d_ap, d_an, loss_rows, demb, loss_scale)
+    assert emb.dtype == torch.float32 and pos.dtype == torch.int64 and neg.dtype == torch.int64
+    assert pos.numel() == B and neg.numel() == B and min(d_ap.numel(), d_an.numel(), loss_rows.numel()) >= B
+    assert emb.dim() == 2 and emb.shape == (B, E) and emb.stride(1) == 1
+    ld = emb.stride(0) if ld is None else ld
+    assert ld == emb.stride(0) or B == 1, "ld must be the row stride of emb"
+    assert demb is None or (demb.dtype == torch.float32 and demb.is_contiguous() and demb.numel() >= B * E)
+    _lib.check(lib().w2v2_triplet_fwd_bwd(emb.data_ptr(), ld, pos.data_ptr(), neg.data_ptr(), d_ap.data_ptr(),
+                                          d_an.data_ptr(), loss_rows.data_ptr(), _p(demb), B, E, float(margin), float(coef),
+                                          int(bool(accumulate)), _p(loss_scale), stream()), "triplet")

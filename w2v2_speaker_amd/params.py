@@ -211,7 +211,7 @@ class ParamStore(FlatArena):
         the CE head's Linear is fc_list.{len(hidden_fc)}.0, the AAM weight keeps input size embed_dim like the
         reference (wav2vec2_fc.py:212-224)."""
         assert act_dtype in (torch.bfloat16, torch.float16, torch.float32)
-        assert head in (None, "aam", "ce", "bce")
+        assert head in (None, "aam", "ce", "bce", "triplet", "triplet_ce")
         self.cfg, self.act_dtype = cfg, act_dtype
         self.head, self.num_speakers, self.freeze_cnn = head, num_speakers, freeze_cnn
         self.embed_dim = embed_dim if embed_dim is not None else 2 * cfg.hidden_size
@@ -224,11 +224,16 @@ class ParamStore(FlatArena):
                 raise ValueError("AAM head: the reference builds the AAM weight with input_features = the pooled "
                                  f"embedding size ({self.embed_dim}); the last hidden layer must have that size")
             shapes["loss_fn.fc_weights"] = (num_speakers, self.embed_dim)
-        elif head == "ce":
+        elif head in ("ce", "triplet_ce"):            # triplet + CE owns exactly what CE owns
             n = len(self.hidden_fc)
             shapes[f"fc_list.{n}.0.weight"] = (num_speakers, dims[-1])
             shapes[f"fc_list.{n}.0.bias"] = (num_speakers,)
-        if head in ("aam", "ce"):
+        if head == "triplet" and self.hidden_fc:
+            raise NotImplementedError("triplet head: the loss acts on the pooled embedding; hidden FC layers would never "
+                                      "receive a gradient")
+        # "triplet" owns no head parameter: the reference's fc_list[-1] Linear exists there but is never part of the
+        # loss, so it is left out of the arena (its checkpoint keys are ignored on load and omitted on save)
+        if head in ("aam", "ce", "triplet_ce"):
             for i, h in enumerate(self.hidden_fc):
                 shapes[f"fc_list.{i}.0.weight"] = (h, dims[i])
                 shapes[f"fc_list.{i}.0.bias"] = (h,)
@@ -379,6 +384,13 @@ class ParamStore(FlatArena):
         return out
 
     # ------------------------------------------------------------------ state (FlatArena.load_state_dict / state_dict)
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True, prefix_model: bool = True) -> None:
+        if self.head == "triplet":
+            # the reference's module keeps its fc_list[-1] Linear under TripletLoss although the loss never reaches it;
+            # this arena has no such tensor, so a reference checkpoint's keys for it are not "unexpected"
+            sd = {k: v for k, v in sd.items() if not k.startswith("fc_list.")}
+        super().load_state_dict(sd, strict=strict, prefix_model=prefix_model)
+
     def _canonical(self, key: str) -> str:
         """Both weight-norm namings are accepted."""
         for old, new in _WN_OLD.items():

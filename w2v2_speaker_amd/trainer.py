@@ -189,15 +189,15 @@ class SpeakerTrainer(fused.WindowedTrainer):
                                  getattr(plan.cfg, "mask_feature_min_masks", 0), rng=self._mask_rng)
         return torch.from_numpy(m.astype(np.uint8)).to(plan.dev, non_blocking=True)
 
-    def train_step_frozen_encoder(self, frozen_plan: Plan, wav: torch.Tensor, label: torch.Tensor):
-        """Step while the whole wav2vec2 network is frozen (ref: wav2vec2_fc.py:339-347 + PL ``freeze()`` =
+    def train_step_frozen_encoder(self, frozen_plan: Plan, wav: torch.Tensor, label: torch.Tensor, triplets=None):
+        """``triplets``: see train_step.  Step while the whole wav2vec2 network is frozen (ref: wav2vec2_fc.py:339-347 + PL ``freeze()`` =
         requires_grad False AND eval mode): eval-mode forward, head forward/backward, Adam on the head only."""
         store = self.store
         if self.accumulate_grad_batches > 1:
-            return self._micro_batch_frozen_encoder(frozen_plan, wav, label)
+            return self._micro_batch_frozen_encoder(frozen_plan, wav, label, triplets=triplets)
         store.zero_grad()
         frozen_plan.embed(wav, None, (), self.step)
-        loss, softmax = frozen_plan.head_forward_backward(label)
+        loss, softmax = self._head(frozen_plan, label, triplets)
         self.reducer.bucket_ready("head")
         self.reducer.wait()
         self._optimizer_step(head_only=True)
@@ -205,9 +205,15 @@ class SpeakerTrainer(fused.WindowedTrainer):
         return loss, softmax
 
     def train_step(self, wav: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor] = None,
-                   skip_layers: Optional[Sequence[int]] = None, feature_mask: Optional[torch.Tensor] = None):
+                   skip_layers: Optional[Sequence[int]] = None, feature_mask: Optional[torch.Tensor] = None,
+                   triplets=None):
         """ref: speaker_recognition_module.py:207-220 (_train_step_ce_loss) + PL backward/optimizer step.
-        Returns (loss, softmax) as device tensors; no host sync."""
+        Returns (loss, softmax) as device tensors; no host sync.  Triplet heads (store.head "triplet" / "triplet_ce",
+        ref: :269-294): ``triplets`` = (pos, neg), the positive and negative batch row of every row
+        (heads.sample_triplets); None lets the head draw them from ``label.tolist()`` (heads.TripletHead, the one place
+        that draws) -- a host synchronisation when the label is on the device, which a caller that still holds the labels
+        on the host avoids by passing them.  "triplet"
+        returns (loss, None)."""
         plan, store = self.plan, self.store
         if skip_layers is None:
             skip_layers = self.sample_layerdrop()
@@ -216,10 +222,10 @@ class SpeakerTrainer(fused.WindowedTrainer):
         if feature_mask is None:
             feature_mask = self.sample_feature_mask()
         if self.accumulate_grad_batches > 1:
-            return self._micro_batch(wav, label, mask, skip_layers, feature_mask)
+            return self._micro_batch(wav, label, mask, skip_layers, feature_mask, triplets=triplets)
         store.zero_grad(tuple(skip_layers) if plan.grouped else None)
         plan.embed(wav, mask, skip_layers, self.step, feature_mask)
-        loss, softmax = plan.head_forward_backward(label)
+        loss, softmax = self._head(plan, label, triplets)
         plan.backward(on_bucket_ready=self.reducer.bucket_ready)
         self.reducer.wait()
         self._optimizer_step()
@@ -232,7 +238,15 @@ class SpeakerTrainer(fused.WindowedTrainer):
     # is zeroed), unscaled -- 1 / (world * N) rides in the optimiser's grad_scale, next to the loss scale and the clip
     # coefficient, so the clip sees the averaged gradient as torch's clip_grad_norm_ does.  The loss-scale record is only
     # touched by optimizer_step, i.e. constant over a window like torch's GradScaler between update() calls.
-    def _micro_batch(self, wav, label, mask, skip_layers, feature_mask):
+    @staticmethod
+    def _head(plan: Plan, label: torch.Tensor, triplets):
+        """The head of every step function.  Without triplets the call is ``head_forward_backward(label)``, the form it
+        has always had (callers replace that method with one-argument functions of their own)."""
+        if triplets is None:
+            return plan.head_forward_backward(label)
+        return plan.head_forward_backward(label, triplets=triplets)
+
+    def _micro_batch(self, wav, label, mask, skip_layers, feature_mask, triplets=None):
         plan, store, N = self.plan, self.store, self.accumulate_grad_batches
         if store.accum_count > 0 and store.accum_head_only:
             raise RuntimeError("this accumulation window was opened by a frozen-encoder micro-batch; a window cannot mix "
@@ -240,7 +254,7 @@ class SpeakerTrainer(fused.WindowedTrainer):
         last = store.accum_count == N - 1
         store.zero_grad(tuple(skip_layers) if plan.grouped else None)
         plan.embed(wav, mask, skip_layers, self.step * N + store.accum_count, feature_mask)    # a dropout seed per micro-batch
-        loss, softmax = plan.head_forward_backward(label)
+        loss, softmax = self._head(plan, label, triplets)
         if last and self.world > 1:
             plan.backward(on_bucket_ready=self._accumulate_and_reduce)     # the all-reduce of grad_acc overlaps backward
         else:
@@ -261,7 +275,7 @@ class SpeakerTrainer(fused.WindowedTrainer):
             self.reducer.buffer = self.store.grad_acc
         self.reducer.bucket_ready(name)
 
-    def _micro_batch_frozen_encoder(self, frozen_plan: Plan, wav, label):
+    def _micro_batch_frozen_encoder(self, frozen_plan: Plan, wav, label, triplets=None):
         store, N = self.store, self.accumulate_grad_batches
         if store.accum_count > 0 and not store.accum_head_only:
             raise RuntimeError("this accumulation window was opened by an unfrozen micro-batch; a window cannot mix frozen "
@@ -269,7 +283,7 @@ class SpeakerTrainer(fused.WindowedTrainer):
         last = store.accum_count == N - 1
         store.zero_grad()
         frozen_plan.embed(wav, None, (), self.step * N + store.accum_count)
-        loss, softmax = frozen_plan.head_forward_backward(label)
+        loss, softmax = self._head(frozen_plan, label, triplets)
         fused.accumulate(store, 0, store.head_size())
         store.accum_count += 1
         store.accum_head_only = True
