@@ -473,6 +473,28 @@ int w2v2_triplet_fwd_bwd(const float* emb, int64_t ld, const int64_t* pos, const
                          float* d_an, float* loss_rows, float* demb, int B, int E, float margin, float coef,
                          int accumulate, const float* loss_scale, void* stream);
 
+/* CTC loss on the device (ref: src/optim/loss/ctc_loss.py:36-58 -> F.ctc_loss(log_softmax(logits), blank,
+ * reduction="mean", zero_infinity=True); src/lightning_modules/speaker/speaker_recognition_module.py:222-244).
+ * logits [B*T][ldc] f32, utterance-major rows (row b * T + t), C classes of which `blank` is the blank.  targets: int64
+ * (device), row b at targets + b * target_stride, `target_width` readable labels per row (0 <= width <= 31: the 2L + 1
+ * <= 63 extended states of an utterance are one wavefront); the class of a label is label + target_offset (1 on the
+ * speaker path, which leaves the caller's labels as they are; 0 for the generic loss).  input_lengths / target_lengths:
+ * int32 [B] (device).  Outputs: loss_rows [B] = -log P(target | input) / max(L_b, 1), 0 where infinite (the mean over B
+ * is the caller's); dlogits [B*T][ldc] in `dtype` (may be NULL: forward only, no gradient output is touched) =
+ *   (softmax_t[c] - sum_{s: class(s) = c} gamma_t(s)) * *loss_scale / (B * max(L_b, 1))
+ * for c < C (the padding columns are not written): exact zeros for the frames t >= input_lengths[b] and for every frame
+ * of an utterance whose loss is infinite.  Repeated labels are merged before the subtraction; one writer per element, no
+ * atomics, bitwise reproducible.  loss_scale (device pointer, may be NULL = 1) multiplies the gradient only.  A bad row --
+ * a class outside [0, C) or equal to blank after the offset, a target length outside [0, target_width], an input length
+ * outside [0, T] -- gives a NaN loss row and a zero gradient, and nothing out of range is read.  workspace: f32, 16-byte
+ * aligned, at least w2v2_ctc_workspace_floats(B, T, target_width) elements (-1: bad arguments); the library allocates
+ * nothing.  Three launches (two when forward only). */
+int64_t w2v2_ctc_workspace_floats(int B, int T, int target_width);
+int w2v2_ctc_fwd_bwd(const float* logits, int64_t ldc, const int64_t* targets, int64_t target_stride, int target_width,
+                     int target_offset, const int* input_lengths, const int* target_lengths, int blank, float* loss_rows,
+                     void* dlogits, const float* loss_scale, float* workspace, int64_t workspace_floats, int B, int T, int C,
+                     int dtype, void* stream);
+
 /* ------------------------------------------------------------------------------ ECAPA-TDNN pieces
  * ref: src/lightning_modules/speaker/ecapa_tdnn.py:75-85 -> speechbrain 0.5.x ECAPA_TDNN (not part of the reference
  * tree; restated in oracle/ecapa_oracle.py).  Channels-last [B*T][C] activations; `ld*` = row stride in elements so

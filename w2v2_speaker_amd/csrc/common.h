@@ -526,6 +526,37 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// a workgroup of NW waves (the row kernels of heads.hip and ctc.hip), folded in wave order (fixed order: bitwise
+// reproducible); sh: NW floats of LDS
+template <int NW>
+__device__ __forceinline__ float block_reduce_n(float v, float* sh, bool is_max) {
+  v = is_max ? wave_max(v) : wave_sum(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  float r = sh[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) r = is_max ? fmaxf(r, sh[w]) : r + sh[w];
+  return r;
+}
+
+// two sums at once (the same two barriers and the same wave order as block_reduce_n)
+template <int NW>
+__device__ __forceinline__ void block_reduce_sum2(float& a, float& b, float* sha, float* shb) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) { sha[wave] = a; shb[wave] = b; }
+  __syncthreads();
+  float ra = sha[0], rb = shb[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) { ra += sha[w]; rb += shb[w]; }
+  a = ra;
+  b = rb;
+}
+
 // ---------------------------------------------------------------- fixed-order fold of per-workgroup column partials
 // (norm.hip) partial [nblk][nslot * C] f32 -> ADDED to the targets in a fixed order, no atomics: slot s < kdw is tap s of a
 // convolution weight gradient dw[c][kdw], the three slots after them go to d0 / d1 / d2 [C] (NULL: skipped).

@@ -53,35 +53,7 @@ __device__ __forceinline__ float block_reduce(float v, float* sh, bool is_max) {
   return is_max ? fmaxf(fmaxf(a, b), fmaxf(c, d)) : (a + b + c + d);
 }
 
-// the same over NW waves, folded in wave order (fixed order: bitwise reproducible)
-template <int NW>
-__device__ __forceinline__ float block_reduce_n(float v, float* sh, bool is_max) {
-  v = is_max ? wave_max(v) : wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  float r = sh[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) r = is_max ? fmaxf(r, sh[w]) : r + sh[w];
-  return r;
-}
-
-// two sums at once (the same two barriers and the same wave order as block_reduce_n)
-template <int NW>
-__device__ __forceinline__ void block_reduce_sum2(float& a, float& b, float* sha, float* shb) {
-  a = wave_sum(a);
-  b = wave_sum(b);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) { sha[wave] = a; shb[wave] = b; }
-  __syncthreads();
-  float ra = sha[0], rb = shb[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) { ra += sha[w]; rb += shb[w]; }
-  a = ra;
-  b = rb;
-}
+// (block_reduce_n / block_reduce_sum2, which the row kernels below fold with, are in common.h: ctc.hip uses them too)
 
 // One workgroup per utterance row.  z_c = s*cos_c (c != y), z_y = s*phi(cos_y); loss = lse(z) - z_y.
 // dLoss/dcos_c = s * (softmax_c - [c==y]) / B * (c == y ? dphi/dcos : 1).

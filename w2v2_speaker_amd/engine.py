@@ -196,6 +196,10 @@ class Plan:
         self.pooling, self.pool_mode = pooling, POOL_MODES.get(pooling, -1)
         assert pooling in ("attentive", "random", "none") or pooling in POOL_MODES, pooling
         self.no_pool = pooling == "none"
+        if train and store.head == "ctc" and not self.no_pool:
+            raise ValueError(f"a training plan of a \"ctc\" store needs pooling=\"none\" (got {pooling!r}): the CTC loss acts "
+                             "on the logits of every frame (ref: config/experiment/speaker_wav2vec2_ctc.yaml "
+                             "stat_pooling_type: none)")
         self._rand_idx = 0
         self.cls, self.cls_c = insert_cls_token, cls_token_constant
         self.margin, self.scale = aam_margin, aam_scale
@@ -395,6 +399,21 @@ class Plan:
                                 w_grad=st.g("linear.weight") if self.train else None,
                                 b_grad=st.g("linear.bias") if self.train else None, emb=self.emb, train=self.train,
                                 loss_scale=st.scaler)
+        elif st.head == "ctc" and not self.no_pool:
+            pass      # an evaluation plan under test_stat_pooling_type (mean+std in the experiment): embeddings, no loss
+        elif st.head == "ctc":
+            # ref: config/experiment/speaker_wav2vec2_ctc.yaml (stat_pooling_type: none, optim/loss: ctc) +
+            # speaker_recognition_module.py:222-244: one label per utterance over the logits of all its T frames
+            from .heads import CtcHead, FcStack
+            nh = len(st.hidden_fc)
+            self.fc = FcStack(st, self.head_rows, E, st.hidden_fc, self.emb, self.train) if nh else None
+            self.head = CtcHead(B, T, st.head_in_dim, st.num_speakers + 1,
+                                w_master=st.p(f"fc_list.{nh}.0.weight"), w_operand=st.w(f"fc_list.{nh}.0.weight"),
+                                w_grad=st.g(f"fc_list.{nh}.0.weight") if self.train else None,
+                                bias=st.p(f"fc_list.{nh}.0.bias"),
+                                bias_grad=st.g(f"fc_list.{nh}.0.bias") if self.train else None,
+                                emb=self.fc.x[-1] if self.fc is not None else self.emb, act_dtype=self.adt,
+                                train=self.train, loss_scale=st.scaler)
         elif st.head is not None and st.head != "triplet":
             from .heads import ClassifierHead, FcStack
             aam = st.head == "aam"
@@ -1032,8 +1051,8 @@ class Plan:
             raise ValueError(f"triplets were given, but the head is {self.store.head!r}")
         if self.store.head == "triplet":
             return self.triplet.forward_backward(label, triplets)
-        if self.no_pool:                 # one prediction per frame: the utterance label for each of its T frames
-            label = torch.repeat_interleave(label, self.T)
+        if self.no_pool and self.store.head != "ctc":    # one prediction per frame: the utterance label for each of its
+            label = torch.repeat_interleave(label, self.T)   # T frames (CTC: one label per utterance, passed through)
         if self.fc is not None:
             self.fc.forward()
         out = self.head.forward_backward(label)

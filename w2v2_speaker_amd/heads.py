@@ -20,7 +20,7 @@ class ClassifierHead:
                  bias_grad: Optional[torch.Tensor] = None, emb: torch.Tensor, act_dtype: torch.dtype,
                  train: bool, margin: float = 0.2, scale: float = 30.0, loss_scale: Optional[torch.Tensor] = None,
                  easy_margin: bool = False):
-        assert kind in ("aam", "ce")
+        assert kind in ("aam", "ce", "ctc")      # "ctc" (CtcHead): the Linear of "ce" under another row kernel
         self.loss_scale = loss_scale          # device record of the dynamic loss scale (fp16 activations) or None
         self.kind, self.B, self.E, self.C, self.train = kind, batch, embed_dim, classes, train
         self.margin, self.scale, self.easy_margin = margin, scale, bool(easy_margin)
@@ -30,7 +30,7 @@ class ClassifierHead:
         self.ldc = (Cn + 7) // 8 * 8
         self.emb_lp = torch.empty(B, E, dtype=act_dtype, device=dev) if act_dtype != f32 else emb
         self.logits = torch.zeros(B, self.ldc, dtype=f32, device=dev)
-        self.softmax = torch.zeros(B, self.ldc, dtype=f32, device=dev)
+        self.softmax = torch.zeros(B, self.ldc, dtype=f32, device=dev) if kind != "ctc" else None
         self.loss_rows = torch.empty(B, dtype=f32, device=dev)
         self.correct = torch.zeros(B, dtype=f32, device=dev)      # 1 where argmax(prediction) == label (train_acc)
         aam = kind == "aam"
@@ -81,17 +81,10 @@ class ClassifierHead:
     def forward_backward(self, label: torch.Tensor):
         """(loss, softmax[B,C]); in training also d(loss)/d(emb) -> self.demb and the head gradients
         (dW written for AAM, accumulated for CE; dbias accumulated) into the tensors given at build."""
-        B, E, Cn = self.B, self.E, self.C
+        B, Cn = self.B, self.C
         assert label.dtype == torch.int64 and label.is_cuda and label.shape == (B,)
         aam, tr = self.kind == "aam", self.train
-        if self.emb_lp is not self.emb:
-            ops.cast(self.emb, self.emb_lp)
-        if aam:
-            ops.row_invnorm(self.emb, self.inv_x, B, E)
-            ops.row_invnorm(self.w_master, self.inv_w, Cn, E)
-        self.g_fwd()
-        if tr:
-            ops.zero_ranges(self._zbuf, self._ztab, blocks_per_range=16)
+        self._forward_logits()
         ops.aam_softmax_fwd_bwd(self.logits, label, self.softmax, self.loss_rows,
                                 self.dcos_w if tr else None, (self.dcos_x if aam else None) if tr else None,
                                 self.inv_x if aam else None, self.inv_w if aam else None,
@@ -101,23 +94,77 @@ class ClassifierHead:
         loss = torch.empty((), dtype=torch.float32, device=self.loss_rows.device)     # (allocator only: no kernel)
         ops.mean(self.loss_rows, loss)
         if tr:
-            for g in self.g_dx:
-                g()
-            ops.colsum(self.dx_parts, self.G1.view(-1), self.dx_parts.shape[0], B * E)    # <= 128 rows: one writer
-            if aam:
-                ops.normalize_bwd(self.G1, self.emb, self.inv_x, self.rowdot, self.demb, B, E)
-                if self.fused_dw:
-                    ops.aam_dw(self.dcos_x, self.emb_lp, self.colprod, self.w_master, self.inv_w, self.w_grad, B, Cn, E,
-                               self.ldc)
-                else:
-                    self.g_dw()
-                    ops.colsum(self.colprod, self.coldot, B, Cn)
-                    ops.normalize_bwd(self.H1, self.w_master, self.inv_w, self.coldot, self.w_grad, Cn, E)
-            else:
-                self.demb.copy_(self.G1)
-                self.g_dw()
-                ops.colsum(self.dcos_w, self.bias_grad, B, Cn, self.ldc)
+            self._backward_from_dlogits()
         return loss, self.softmax[:, :Cn]
+
+    def _forward_logits(self) -> None:
+        """The launches in front of the row kernel: operand cast, (AAM) row norms, the logit GEMM, the accumulators' zeroing."""
+        B, E, Cn = self.B, self.E, self.C
+        aam, tr = self.kind == "aam", self.train
+        if self.emb_lp is not self.emb:
+            ops.cast(self.emb, self.emb_lp)
+        if aam:
+            ops.row_invnorm(self.emb, self.inv_x, B, E)
+            ops.row_invnorm(self.w_master, self.inv_w, Cn, E)
+        self.g_fwd()
+        if tr:
+            ops.zero_ranges(self._zbuf, self._ztab, blocks_per_range=16)
+
+    def _backward_from_dlogits(self) -> None:
+        """The launches behind the row kernel: d(emb) and the head's parameter gradients from dcos_w / dcos_x."""
+        B, E, Cn = self.B, self.E, self.C
+        aam = self.kind == "aam"
+        for g in self.g_dx:
+            g()
+        ops.colsum(self.dx_parts, self.G1.view(-1), self.dx_parts.shape[0], B * E)    # <= 128 rows: one writer
+        if aam:
+            ops.normalize_bwd(self.G1, self.emb, self.inv_x, self.rowdot, self.demb, B, E)
+            if self.fused_dw:
+                ops.aam_dw(self.dcos_x, self.emb_lp, self.colprod, self.w_master, self.inv_w, self.w_grad, B, Cn, E,
+                           self.ldc)
+            else:
+                self.g_dw()
+                ops.colsum(self.colprod, self.coldot, B, Cn)
+                ops.normalize_bwd(self.H1, self.w_master, self.inv_w, self.coldot, self.w_grad, Cn, E)
+        else:
+            self.demb.copy_(self.G1)
+            self.g_dw()
+            ops.colsum(self.dcos_w, self.bias_grad, B, Cn, self.ldc)
+
+
+class CtcHead(ClassifierHead):
+    """ref: src/lightning_modules/speaker/speaker_recognition_module.py:222-244 (_train_step_ctc_loss) +
+    src/optim/loss/ctc_loss.py:36-58: per-frame Linear (``classes`` = speakers + 1 outputs, class 0 the blank) and the CTC
+    loss of ONE label per utterance over all ``frames`` frames.  ClassifierHead("ce")'s forward GEMM and gradient GEMMs over
+    the ``batch * frames`` rows of the no-pooling embedding, with w2v2_ctc_fwd_bwd in the row kernel's place.  The
+    reference adds 1 to the batch's label tensor in place; here the label stays as it is and the kernel adds
+    ``target_offset``.  The length tensors (``frames`` and 1 per utterance) are built once: a step uploads nothing and
+    synchronises nothing.  Returns (loss, None): no softmax and no accuracy in this mode (ref: :458)."""
+
+    def __init__(self, batch: int, frames: int, embed_dim: int, classes: int, *, blank: int = 0, target_offset: int = 1,
+                 **kw):
+        super().__init__("ctc", batch * frames, embed_dim, classes, **kw)
+        dev = self.emb.device
+        self.U, self.T, self.blank, self.target_offset = batch, frames, int(blank), int(target_offset)
+        self.loss_rows = torch.empty(batch, dtype=torch.float32, device=dev)
+        self.correct = None
+        self.in_len = torch.full((batch,), frames, dtype=torch.int32, device=dev)
+        self.tgt_len = torch.ones(batch, dtype=torch.int32, device=dev)
+        self.workspace = torch.empty(ops.ctc_workspace_floats(batch, frames, 1), dtype=torch.float32, device=dev)
+
+    def forward_backward(self, label: torch.Tensor):
+        """label [batch] int64 speaker indices in [0, classes - 1) -> (loss, None)."""
+        assert label.dtype == torch.int64 and label.is_cuda and label.shape == (self.U,) and label.is_contiguous()
+        tr = self.train
+        self._forward_logits()
+        ops.ctc_fwd_bwd(self.logits, label, self.in_len, self.tgt_len, self.loss_rows, self.dcos_w if tr else None,
+                        self.workspace, self.U, self.T, self.C, self.ldc, target_width=1, target_stride=1,
+                        target_offset=self.target_offset, blank=self.blank, loss_scale=self.loss_scale if tr else None)
+        loss = torch.empty((), dtype=torch.float32, device=self.loss_rows.device)
+        ops.mean(self.loss_rows, loss)
+        if tr:
+            self._backward_from_dlogits()
+        return loss, None
 
 
 class BceHead:

@@ -1077,3 +1077,41 @@ def triplet_fwd_bwd(emb, pos, neg, d_ap, d_an, loss_rows, demb, B: int, E: int, 
     _lib.check(lib().w2v2_triplet_fwd_bwd(emb.data_ptr(), ld, pos.data_ptr(), neg.data_ptr(), d_ap.data_ptr(),
                                           d_an.data_ptr(), loss_rows.data_ptr(), _p(demb), B, E, float(margin), float(coef),
                                           int(bool(accumulate)), _p(loss_scale), stream()), "triplet")
+
+
+CTC_MAX_TARGET = 31      # labels per utterance: 2L + 1 <= 63 extended states are one wavefront (csrc/ctc.hip)
+
+
+def ctc_workspace_floats(B: int, T: int, target_width: int) -> int:
+    n = lib().w2v2_ctc_workspace_floats(B, T, target_width)
+    if n < 0:
+        raise ValueError(f"ctc: no workspace for B = {B}, T = {T}, target width {target_width} "
+                         f"(at most {CTC_MAX_TARGET} labels per utterance)")
+    return int(n)
+
+
+def ctc_fwd_bwd(logits, targets, input_lengths, target_lengths, loss_rows, dlogits, workspace, B: int, T: int, C: int,
+                ldc: int, *, target_width: int, target_stride: Optional[int] = None, target_offset: int = 0,
+                blank: int = 0, loss_scale=None) -> None:
+    """CTC loss rows and d(mean loss)/d(logits) (w2v2_ctc_fwd_bwd; ref: src/optim/loss/ctc_loss.py:36-58): logits
+    [B*T, ldc] f32 utterance-major, targets int64 ([B, width] rows ``target_stride`` apart; None when width is 0),
+    input_lengths / target_lengths int32 [B], all on the device.  loss_rows [B] f32 = nll / max(L, 1), 0 where infinite;
+    dlogits [B*T, ldc] f32 / f16 / bf16 or None (forward only).  The class of a label is label + ``target_offset``.
+    workspace: f32, ``ctc_workspace_floats(B, T, target_width)`` elements."""
+    _dev(logits, targets, input_lengths, target_lengths, loss_rows, dlogits, workspace, loss_scale)
+    if not 0 <= target_width <= CTC_MAX_TARGET:
+        raise ValueError(f"ctc: targets of width {target_width}; at most {CTC_MAX_TARGET} labels per utterance are built")
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() >= B * T * ldc and ldc >= C
+    assert targets is None or (targets.dtype == torch.int64 and targets.stride(-1) == 1)
+    assert input_lengths.dtype == torch.int32 and target_lengths.dtype == torch.int32
+    assert input_lengths.numel() == B and target_lengths.numel() == B and loss_rows.numel() >= B
+    assert input_lengths.is_contiguous() and target_lengths.is_contiguous() and loss_rows.dtype == torch.float32
+    assert workspace.dtype == torch.float32 and workspace.is_contiguous()
+    assert dlogits is None or (dlogits.is_contiguous() and dlogits.numel() >= B * T * ldc)
+    if target_stride is None:
+        target_stride = target_width if targets is None or targets.dim() < 2 else targets.stride(0)
+    assert targets is None or target_width == 0 or targets.numel() >= (B - 1) * target_stride + target_width
+    _lib.check(lib().w2v2_ctc_fwd_bwd(logits.data_ptr(), ldc, _p(targets), target_stride, target_width, target_offset,
+                                      input_lengths.data_ptr(), target_lengths.data_ptr(), blank, loss_rows.data_ptr(),
+                                      _p(dlogits), _p(loss_scale), workspace.data_ptr(), workspace.numel(), B, T, C,
+                                      dt(dlogits) if dlogits is not None else F32, stream()), "ctc")

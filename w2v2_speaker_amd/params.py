@@ -211,7 +211,7 @@ class ParamStore(FlatArena):
         the CE head's Linear is fc_list.{len(hidden_fc)}.0, the AAM weight keeps input size embed_dim like the
         reference (wav2vec2_fc.py:212-224)."""
         assert act_dtype in (torch.bfloat16, torch.float16, torch.float32)
-        assert head in (None, "aam", "ce", "bce", "triplet", "triplet_ce")
+        assert head in (None, "aam", "ce", "bce", "triplet", "triplet_ce", "ctc")
         self.cfg, self.act_dtype = cfg, act_dtype
         self.head, self.num_speakers, self.freeze_cnn = head, num_speakers, freeze_cnn
         self.embed_dim = embed_dim if embed_dim is not None else 2 * cfg.hidden_size
@@ -224,16 +224,19 @@ class ParamStore(FlatArena):
                 raise ValueError("AAM head: the reference builds the AAM weight with input_features = the pooled "
                                  f"embedding size ({self.embed_dim}); the last hidden layer must have that size")
             shapes["loss_fn.fc_weights"] = (num_speakers, self.embed_dim)
-        elif head in ("ce", "triplet_ce"):            # triplet + CE owns exactly what CE owns
+        elif head in ("ce", "triplet_ce", "ctc"):     # triplet + CE owns exactly what CE owns
+            # "ctc" too, with one more output: class 0 is the blank (ref: speaker_recognition_module.py:104-107
+            # ``num_speakers += 1``), speaker i is class i + 1
             n = len(self.hidden_fc)
-            shapes[f"fc_list.{n}.0.weight"] = (num_speakers, dims[-1])
-            shapes[f"fc_list.{n}.0.bias"] = (num_speakers,)
+            rows = num_speakers + 1 if head == "ctc" else num_speakers
+            shapes[f"fc_list.{n}.0.weight"] = (rows, dims[-1])
+            shapes[f"fc_list.{n}.0.bias"] = (rows,)
         if head == "triplet" and self.hidden_fc:
             raise NotImplementedError("triplet head: the loss acts on the pooled embedding; hidden FC layers would never "
                                       "receive a gradient")
         # "triplet" owns no head parameter: the reference's fc_list[-1] Linear exists there but is never part of the
         # loss, so it is left out of the arena (its checkpoint keys are ignored on load and omitted on save)
-        if head in ("aam", "ce", "triplet_ce"):
+        if head in ("aam", "ce", "triplet_ce", "ctc"):
             for i, h in enumerate(self.hidden_fc):
                 shapes[f"fc_list.{i}.0.weight"] = (h, dims[i])
                 shapes[f"fc_list.{i}.0.bias"] = (h,)
@@ -590,6 +593,10 @@ class ParamStore(FlatArena):
             else:
                 t = torch.randn(s, generator=g) * 0.02
             self.p(n).copy_(t.to(self.device))
+        if self.head == "ctc":
+            # ref: wav2vec2_fc.py:226-233 -- the bias of the last Linear is zeros with bias[0] = 100, a strong prior for
+            # the blank (the weight keeps the Linear's default initialisation)
+            self.p(f"fc_list.{len(self.hidden_fc)}.0.bias")[0] = 100.0
         # weight-norm: g initialised to ||v|| so that w == v (torch weight_norm semantics)
         v = self.mp("encoder.pos_conv_embed.conv.parametrizations.weight.original1")
         self.mp("encoder.pos_conv_embed.conv.parametrizations.weight.original0").copy_(
