@@ -385,3 +385,132 @@ def test_ecapa_vs_speechbrain_golden():
         if err > 3e-3 * float(_np.linalg.norm(g[k])) + 2e-6 * gmax:
             bad.append((k, err))
     assert not bad, bad[:8]
+
+
+# ------------------------------------------------------------------- direct cases of the csrc/tdnn.hip kernels that only the
+# model reached: the SE gate kernels, the small f32 activations, the strided copy / add and col2im_reflect at the model's
+# own (k, dilation) pairs -- each against f64 torch.  16-bit outputs are held to ecapa_stage_cases.stage_bound with one
+# rounding (every kernel here works in f32 and rounds at its store); f32 outputs of a product, an fma or a sum of at most
+# 15 taps to 1e-6 (a handful of roundings of 2^-24 = 6e-8 each).
+import ecapa_stage_cases as _K
+
+_DTYPES = pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+
+
+def _elementwise_bound(ref, dtype):
+    return 2.0 * _K.rounding_floor(ref, dtype) + 1e-6
+
+
+@_DTYPES
+@pytest.mark.parametrize("B,T,C", [(1, 1, 8), (3, 37, 136), (2, 70, 1024)])
+def test_se_gate_kernels_vs_f64(dtype, B, T, C):
+    """se_scale, se_bwd_gate, se_bwd_x: one vector in all; C = 136 = one 128-channel strip and a single vector of the
+    next, T = 37 against the 8 / 16 time lanes of se_bwd_gate; eight strips."""
+    from w2v2_speaker_amd import ops
+    g_ = torch.Generator().manual_seed(B * 1000 + T * 10 + C)
+    x = torch.randn(B * T, C, generator=g_).to(dtype)
+    dout = torch.randn(B * T, C, generator=g_).to(dtype)
+    gate = torch.rand(B, C, generator=g_)
+    ds = torch.randn(B, C, generator=g_)
+    xd, dd, gd, sd_ = x.to(DEV), dout.to(DEV), gate.to(DEV), ds.to(DEV)
+    x3, d3 = x.double().view(B, T, C), dout.double().view(B, T, C)
+    y = torch.empty(B * T, C, dtype=dtype, device=DEV)
+    ops.se_scale(xd, gd, y, B, T, C)
+    ref = x3 * gate.double()[:, None]
+    assert _K.rel_l2(y.cpu().view(B, T, C), ref) <= _elementwise_bound(ref, dtype)
+    dg = torch.full((B, C), float("nan"), device=DEV)
+    ops.se_bwd_gate(dd, xd, dg, B, T, C)
+    # an f32 dot product over T frames: one fma per frame on a time lane, then the fold of the lanes -- fewer than T + 1
+    # inexact operations on the way to any output, so |error| <= (T + 1) 2^-24 sum |terms|
+    err = _K.sum_scale_error(dg.cpu(), (d3 * x3).sum(1), (d3 * x3).abs().sum(1))
+    assert err <= (T + 1) * 2.0 ** -24, err
+    dx = torch.empty(B * T, C, dtype=dtype, device=DEV)
+    ops.se_bwd_x(dd, gd, sd_, dx, B, T, C)
+    ref = d3 * gate.double()[:, None] + ds.double()[:, None] / T
+    assert _K.rel_l2(dx.cpu().view(B, T, C), ref) <= _elementwise_bound(ref, dtype)
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 100003])
+@pytest.mark.parametrize("mode", [0, 1], ids=["relu", "sigmoid"])
+def test_small_activation_kernels_vs_f64(mode, n):
+    """act_fwd / act_bwd (f32 only: the kernels take no dtype) around their 256-thread blocks, with 0, +-88 and +-104 among
+    the inputs: exp(88) is the last finite f32 power, exp(104) overflows -- the sigmoid stays finite and inside [0, 1]."""
+    from w2v2_speaker_amd import ops
+    g_ = torch.Generator().manual_seed(n + mode)
+    x = torch.randn(n, generator=g_) * 4
+    special = torch.tensor([0.0, 88.0, -88.0, 104.0, -104.0])
+    x[:min(n, 5)] = special[:min(n, 5)]
+    dy = torch.randn(n, generator=g_)
+    xd, dyd = x.to(DEV), dy.to(DEV)
+    y, dx = torch.full((n,), float("nan"), device=DEV), torch.full((n,), float("nan"), device=DEV)
+    ops.act_fwd(xd, y, mode)
+    ops.act_bwd(dyd, y, dx, mode)
+    yc, dxc = y.cpu(), dx.cpu()
+    if mode == 0:
+        assert torch.equal(yc, x.clamp_min(0))
+        assert torch.equal(dxc, torch.where(yc > 0, dy, torch.zeros_like(dy)))
+        assert float(dxc[0]) == 0.0                       # x[0] = 0: y == 0 passes no gradient
+    else:
+        assert bool(torch.isfinite(yc).all()) and float(yc.min()) >= 0.0 and float(yc.max()) <= 1.0
+        # y = 1 / (1 + e), e = exp(-x) with relative error d <= (|x| + 2) 2^-22 (argument scaling of the fast exponential):
+        # |dy| = y (1 - y) d, and |x| y (1 - y) <= 0.23 -- below 3e-7 with the two roundings behind it; held to 1e-6 absolute
+        assert float((yc.double() - torch.sigmoid(x.double())).abs().max()) <= 1e-6
+        ref = dy.double() * yc.double() * (1 - yc.double())                 # from the stored y, as the kernel takes it
+        assert _K.rel_l2(dxc, ref) <= 1e-6
+
+
+@_DTYPES
+def test_strided_copy_and_add_on_column_slices(dtype):
+    """copy_strided / add_strided with both sources and the destination column slices of wider matrices of different
+    row strides: the view bit-equal to the f32 sum rounded once, every column outside it untouched; then the in-place
+    form of the residual (dx += dout)."""
+    from w2v2_speaker_amd import ops
+    M, C = 131, 24
+    g_ = torch.Generator().manual_seed(17)
+    A, Bm = torch.randn(M, 40, generator=g_).to(dtype), torch.randn(M, 56, generator=g_).to(dtype)
+    Y0 = torch.randn(M, 72, generator=g_).to(dtype)
+    Ad, Bd = A.to(DEV), Bm.to(DEV)
+    a, b = Ad[:, 8:8 + C], Bd[:, 16:16 + C]
+    want_sum = (A[:, 8:8 + C].float() + Bm[:, 16:16 + C].float()).to(dtype)
+    for two in (False, True):
+        Y = Y0.to(DEV)
+        if two:
+            ops.add_strided(a, 40, b, 56, Y[:, 24:24 + C], 72, M, C)
+        else:
+            ops.copy_strided(a, 40, Y[:, 24:24 + C], 72, M, C)
+        Yc = Y.cpu()
+        assert torch.equal(Yc[:, 24:24 + C], want_sum if two else A[:, 8:8 + C])
+        assert torch.equal(Yc[:, :24], Y0[:, :24]) and torch.equal(Yc[:, 24 + C:], Y0[:, 24 + C:])
+    Y = Y0.to(DEV)
+    dxv = Y[:, 24:24 + C]
+    ops.add_strided(dxv, 72, b, 56, dxv, 72, M, C)
+    Yc = Y.cpu()
+    assert torch.equal(Yc[:, 24:24 + C], (Y0[:, 24:24 + C].float() + Bm[:, 16:16 + C].float()).to(dtype))
+    assert torch.equal(Yc[:, :24], Y0[:, :24]) and torch.equal(Yc[:, 24 + C:], Y0[:, 24 + C:])
+    assert torch.equal(Ad.cpu(), A) and torch.equal(Bd.cpu(), Bm)                         # sources unchanged
+
+
+@_DTYPES
+@pytest.mark.parametrize("accumulate", [False, True])
+@pytest.mark.parametrize("short", [True, False], ids=["T=pad+1", "T=37"])
+@pytest.mark.parametrize("k,d", [(5, 1), (3, 2), (3, 3), (3, 4)])
+def test_col2im_reflect_at_the_model_geometries(dtype, k, d, short, accumulate):
+    """col2im_reflect at the (k, dilation) pairs of the model, at the smallest legal T (padding + 1: every tap but the
+    centre one reflects) and T = 37, writing or accumulating into a column slice (lddx > Cin) of a non-zero matrix,
+    against the autograd adjoint of the reflect im2col."""
+    from w2v2_speaker_amd import ops
+    B, Cin, ld, c0 = 3, 16, 40, 8
+    T = d * (k - 1) // 2 + 1 if short else 37
+    g_ = torch.Generator().manual_seed(k * 100 + d * 10 + T)
+    dcol = torch.randn(B * T, k * Cin, generator=g_).to(dtype)
+    D0 = torch.randn(B * T, ld, generator=g_).to(dtype)
+    Dd = D0.to(DEV)
+    ops.col2im_reflect(dcol.to(DEV), Dd[:, c0:c0 + Cin], ld, B, T, Cin, k, d, accumulate)
+    Dc = Dd.cpu()
+    ref = _K.col2im_reflect(dcol.double(), B, T, Cin, k, d)
+    if accumulate:
+        ref = ref + D0[:, c0:c0 + Cin].double()
+    err = _K.rel_l2(Dc[:, c0:c0 + Cin], ref)
+    # r = 1: the taps (and the old value) are summed in f32 and stored once; f32 at 1e-6
+    assert err <= _elementwise_bound(ref, dtype), (err, _K.rounding_floor(ref, dtype))
+    assert torch.equal(Dc[:, :c0], D0[:, :c0]) and torch.equal(Dc[:, c0 + Cin:], D0[:, c0 + Cin:])
