@@ -499,28 +499,32 @@ int w2v2_ctc_fwd_bwd(const float* logits, int64_t ldc, const int64_t* targets, i
  * ref: src/lightning_modules/speaker/ecapa_tdnn.py:75-85 -> speechbrain 0.5.x ECAPA_TDNN (not part of the reference
  * tree; restated in oracle/ecapa_oracle.py).  Channels-last [B*T][C] activations; `ld*` = row stride in elements so
  * Res2Net channel slices and the MFA concatenation are views of their parent tensors.
- * BatchNorm1d over the M rows of a channels-last [M][C] view (C, strides multiples of 8), optionally on relu(a)
- * (TDNNBlock = conv -> ReLU -> BatchNorm).  train = 1: batch statistics (biased variance) through `workspace`
+ * BatchNorm1d over the M rows of a channels-last [M][C] view (C, strides multiples of 8; of 4 for f32), on act(a):
+ * act = W2V2_BN_ACT_NONE, W2V2_BN_ACT_RELU (ECAPA's TDNNBlock = conv -> ReLU -> BatchNorm) or W2V2_BN_ACT_LEAKY
+ * (LeakyReLU with slope 0.01: the x-vector's conv -> LeakyReLU -> BatchNorm; the backward uses slope 0.01 at a == 0).  train = 1: batch statistics (biased variance) through `workspace`
  * partial sums, mean_rstd[C][2] written for the backward, running = {mean[C], var[C]} updated like torch or NULL;
  * train = 0: the running statistics (BatchNorm1d.eval()).  Two launches (partial sums, fold + apply), deterministic. */
+#define W2V2_BN_ACT_NONE 0
+#define W2V2_BN_ACT_RELU 1
+#define W2V2_BN_ACT_LEAKY 2
 int w2v2_bn_workspace_floats(int M, int C);
 int w2v2_bn_fwd(const void* a, int64_t lda, float* workspace, float* mean_rstd, float* running, const float* gamma,
-                const float* beta, void* y, int64_t ldy, int M, int C, float eps, float momentum, int relu, int train,
+                const float* beta, void* y, int64_t ldy, int M, int C, float eps, float momentum, int act, int train,
                 int dtype, void* stream);
-/* dy -> da (through BatchNorm and the optional relu); writes dgamma[C], dbeta[C].  colsum_partial (may be NULL):
+/* dy -> da (through BatchNorm and the activation); writes dgamma[C], dbeta[C].  colsum_partial (may be NULL):
  * [w2v2_bn_colsum_rows(M, C)][C] f32, WRITTEN with the column sums of da over each row block -- the bias gradient of the
  * convolution in front of the BatchNorm (TDNNBlock = conv -> ReLU -> BatchNorm) is their sum: a w2v2_colsum over
  * M / 256 rows (M / 64 for the narrow Res2Net slices, whose row blocks are shorter so that they fill the chip) instead of
  * a second pass over the M rows of da. */
 int w2v2_bn_colsum_rows(int M, int C);
 int w2v2_bn_bwd(const void* dy, int64_t lddy, const void* a, int64_t lda, const float* mean_rstd, const float* gamma,
-                float* workspace, float* dgamma, float* dbeta, void* da, int64_t ldda, int M, int C, int relu,
+                float* workspace, float* dgamma, float* dbeta, void* da, int64_t ldda, int M, int C, int act,
                 float* colsum_partial, int dtype, void* stream);
 /* The same with the output gradient given as dy + dy2 (same shape, own row strides; both kernels add them as they read):
  * a Res2Net chunk's output feeds the next chunk and the block's concatenation, so its gradient has two sources. */
 int w2v2_bn_bwd_sum(const void* dy, int64_t lddy, const void* dy2, int64_t lddy2, const void* a, int64_t lda,
                     const float* mean_rstd, const float* gamma, float* workspace, float* dgamma, float* dbeta, void* da,
-                    int64_t ldda, int M, int C, int relu, float* colsum_partial, int dtype, void* stream);
+                    int64_t ldda, int M, int C, int act, float* colsum_partial, int dtype, void* stream);
 /* Conv1d(padding="same", padding_mode="reflect", dilation d, odd k) as im2col + GEMM:
  * col[(b,t)][j*Cin + c] = x[b][reflect(t + (j - (k-1)/2) d)][c]; col2im is its exact adjoint (gather, deterministic) */
 int w2v2_im2col_reflect(const void* x, int64_t ldx, void* col, int B, int T, int Cin, int k, int dilation, int dtype,
@@ -553,6 +557,20 @@ int w2v2_se_bwd_x(const void* dout, const float* g, const float* ds, void* dx, i
 /* f32 vectors; mode 0 relu, 1 sigmoid; the backward takes the forward output */
 int w2v2_act_fwd(const float* x, float* y, int64_t n, int mode, void* stream);
 int w2v2_act_bwd(const float* dy, const float* y, float* dx, int64_t n, int mode, void* stream);
+
+/* speechbrain StatisticsPooling of the x-vector over time: x f32 [B][T] rows of C channels (C % 4 == 0, row stride ldx,
+ * T >= 2) -> out f32 [B][2C] = cat(mean, std_unbiased + eps), mean FIRST (w2v2_pool_fwd mode 0 has the std first and no
+ * eps).  Two passes (mean, then centred squares), fixed-order reductions, no atomics.  stats [B][2C] (may be NULL)
+ * receives (mean, std) for the backward.  _len: over the first lens[b] frames (device int32 [B], 2 <= lens[b] <= T) of
+ * each utterance, bit-identical to the plain form on the [1, lens[b], C] slice.
+ * bwd: dx[b][t][c] = dmean / T + dstd (x - mean) / ((T - 1) std), dout = cat(dmean, dstd); in a constant column
+ * (std = 0) the second term is taken as 0, as torch's std backward does. */
+int w2v2_stat_pool_fwd(const float* x, int64_t ldx, float* out, float* stats, int B, int T, int C, float eps,
+                       void* stream);
+int w2v2_stat_pool_fwd_len(const float* x, int64_t ldx, float* out, float* stats, const int* lens, int B, int T, int C,
+                           float eps, void* stream);
+int w2v2_stat_pool_bwd(const float* x, int64_t ldx, const float* stats, const float* dout, float* dx, int64_t lddx, int B,
+                       int T, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------- log-mel filterbank front-end
  * The ECAPA input features from waveforms (the device twin of data/fbank.py + InputNormalizer2D(True), data/pipeline.py;

@@ -6,6 +6,9 @@
 //   conv       = im2col_reflect (taps gathered with reflection, channels-last) + GEMM (gemm.hip) [k = 1: GEMM only]
 //   SE block   = mean_t -> Linear -> ReLU -> Linear -> sigmoid -> per-(utterance, channel) gate
 //   Res2Net    = channel slices of one [B*T, C] tensor (row-strided views) with cumulative adds
+// and of the x-vector path (xvector.py; ref: src/lightning_modules/speaker/xvector.py -> speechbrain 0.5.x Xvector, as
+// recollected): its TDNN block is Conv1d -> LeakyReLU(0.01) -> BatchNorm1d (the `act` mode of the BatchNorm kernels), its
+// pooling the plain statistics pooling below (w2v2_stat_pool_*).
 //
 // Everything here is HBM-bound elementwise / reduction work over channels-last [B*T, C] activations; reductions
 // over rows are two-stage with a fixed order (deterministic, no atomics).  Row-strided operands (ld*) let the
@@ -25,6 +28,14 @@ constexpr int BN_UN = 4;          // rows in flight per thread (memory-level par
 // block order -- the same numbers in every workgroup, so the result does not depend on the grid), then walks its
 // rows.  The workgroups of row-block 0 publish mean / rstd (the backward reads them), update the running
 // statistics, and in the backward write dgamma / dbeta.  No finalize launch, no atomics, no grid-wide fence.
+// The activation in front of the statistics (`act`, W2V2_BN_ACT_*): 0 none, 1 ReLU (ECAPA's TDNNBlock), 2 LeakyReLU with
+// slope 0.01 (the x-vector blocks: conv -> LeakyReLU -> BatchNorm).  The backward multiplies by 1 where the saved
+// pre-activation is > 0 and by 0 / the slope elsewhere (torch's convention at a == 0).
+constexpr int BN_ACT_RELU = 1, BN_ACT_LEAKY = 2;
+constexpr float BN_LEAKY_SLOPE = 0.01f;
+__device__ __forceinline__ float bn_act(float v, int act) {
+  return act == BN_ACT_RELU ? fmaxf(v, 0.f) : (act == BN_ACT_LEAKY && !(v > 0.f)) ? BN_LEAKY_SLOPE * v : v;
+}
 constexpr int BN_PROWS = 256;     // rows per partial-sum block
 __device__ __forceinline__ int bn_rows(int) { return BN_PROWS; }
 static int bn_rows_host(int) { return BN_PROWS; }
@@ -74,7 +85,7 @@ __device__ __forceinline__ void bn_store_partial(float (*red)[BN_CW][2], const f
 }
 template <typename T>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const T* __restrict__ a, int64_t lda,
-                                                         float* __restrict__ partial, int M, int C, int relu) {
+                                                         float* __restrict__ partial, int M, int C, int act) {
   __shared__ float red[BN_RL_MAX][BN_CW][2];
   using G = BnGeom<T>;
   constexpr int EPT = G::EPT, RL = G::RL, UN = G::UN;
@@ -92,7 +103,7 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const T* __restrict__ a
         if (m + u * RL < m1) {
 #pragma unroll
           for (int e = 0; e < EPT; ++e) {
-            const float r = relu ? fmaxf(v[u].v[e], 0.f) : v[u].v[e];
+            const float r = bn_act(v[u].v[e], act);
             s1[e] += r;
             s2[e] = fmaf(r, r, s2[e]);
           }
@@ -140,7 +151,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ a, 
                                                        const float* __restrict__ partial, int nblk,
                                                        float* __restrict__ mean_rstd, float* __restrict__ running,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       T* __restrict__ y, int64_t ldy, int M, int C, int relu,
+                                                       T* __restrict__ y, int64_t ldy, int M, int C, int act,
                                                        float eps, float momentum, int mode, int arows) {
   __shared__ double fold[4][BN_CW][2];
   __shared__ float cf[4][BN_CW];                 // mean, rstd, gamma, beta of the strip
@@ -192,7 +203,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ a, 
       if (m + u * RL < m1) {
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
-          const float r = relu ? fmaxf(v[u].v[e], 0.f) : v[u].v[e];
+          const float r = bn_act(v[u].v[e], act);
           v[u].v[e] = (r - mus[e]) * rs[e] * ga[e] + be[e];
         }
         v[u].store(y + (int64_t)(m + u * RL) * ldy + cg);
@@ -204,7 +215,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict
                                                              const T* __restrict__ dy2, int64_t lddy2,
                                                              const T* __restrict__ a, int64_t lda,
                                                              const float* __restrict__ mean_rstd,
-                                                             float* __restrict__ partial, int M, int C, int relu) {
+                                                             float* __restrict__ partial, int M, int C, int act) {
   __shared__ float red[BN_RL_MAX][BN_CW][2];
   using G = BnGeom<T>;
   constexpr int EPT = G::EPT, RL = G::RL, UN = G::UN;
@@ -238,7 +249,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict
         if (m + u * RL < m1) {
 #pragma unroll
           for (int e = 0; e < EPT; ++e) {
-            const float r = relu ? fmaxf(v[u].v[e], 0.f) : v[u].v[e];
+            const float r = bn_act(v[u].v[e], act);
             s1[e] += d[u].v[e];
             s2[e] = fmaf(d[u].v[e], (r - mu[e]) * rs[e], s2[e]);
           }
@@ -255,7 +266,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
                                                            const float* __restrict__ gamma,
                                                            const float* __restrict__ partial, int nblk,
                                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                           T* __restrict__ da, int64_t ldda, int M, int C, int relu,
+                                                           T* __restrict__ da, int64_t ldda, int M, int C, int act,
                                                            float invM, float* __restrict__ cs_partial, int arows) {
   __shared__ double fold[4][BN_CW][2];
   __shared__ float csred[BN_RL_MAX][BN_CW];          // column sums of da over this workgroup's rows (cs_partial != NULL)
@@ -310,10 +321,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
           const float av = v[u].v[e];
-          const float r = relu ? fmaxf(av, 0.f) : av;
+          const float r = bn_act(av, act);
           const float rh = (r - mu[e]) * rs[e];
           const float dr = gr[e] * (d[u].v[e] - m1s[e] - rh * m2s[e]);
-          d[u].v[e] = (relu && !(av > 0.f)) ? 0.f : dr;
+          d[u].v[e] = (act && !(av > 0.f)) ? (act == BN_ACT_LEAKY ? BN_LEAKY_SLOPE * dr : 0.f) : dr;
           cs[e] += d[u].v[e];
         }
         d[u].store(da + (int64_t)(m + u * RL) * ldda + cg);
@@ -528,6 +539,116 @@ __global__ void se_bwd_x_kernel(const T* __restrict__ dout, const float* __restr
   }
 }
 
+// ------------------------------------------------------------------------------------------ statistics pooling (x-vector)
+// speechbrain StatisticsPooling over time on an f32 channels-last [B][T][C] tensor with a row stride:
+//   out[b] = cat(mean_t x, std_t x + eps)   (mean FIRST, unbiased std, eps added to the std -- the wav2vec2 pool of
+//   pool.hip returns the std first and has no eps)
+// Two passes in the torch.std_mean order: the mean, then the centred squares.  One workgroup per (128-channel strip,
+// utterance): 32 channel lanes x 4 channels, 8 time lanes that walk the frames SP_UN at a time; the time lanes are folded
+// through LDS in lane order -- a fixed order, no atomics, and the same order for an utterance of n frames whether it
+// stands alone or in a padded batch (LEN: the first lens[b] frames of utterance b).  stats (may be NULL) keeps
+// (mean, std) without the eps for the backward.
+constexpr int SP_UN = 4;
+template <bool LEN>
+__global__ __launch_bounds__(256) void stat_pool_fwd_kernel(const float* __restrict__ x, int64_t ldx,
+                                                            float* __restrict__ out, float* __restrict__ stats,
+                                                            const int* __restrict__ lens, int Tn, int C, float eps) {
+  __shared__ float red[8][BN_CW];
+  __shared__ float mean_s[BN_CW];
+  using G = BnGeom<float>;
+  constexpr int EPT = G::EPT, RL = G::RL;
+  static_assert(RL == 8 && EPT == 4, "stat_pool: 32 channel lanes x 8 time lanes");
+  const int b = blockIdx.y;
+  const int tid = threadIdx.y * G::XL + threadIdx.x;
+  const int cl = threadIdx.x * EPT, cg = blockIdx.x * BN_CW + cl;
+  const int n = LEN ? lens[b] : Tn;
+  const float* xb = x + (int64_t)b * Tn * ldx;
+  const bool on = cg < C;
+  float s[EPT] = {};
+  if (on)
+    for (int t = threadIdx.y; t < n; t += SP_UN * RL) {
+      Vec4f v[SP_UN];
+#pragma unroll
+      for (int u = 0; u < SP_UN; ++u) v[u].load(xb + (int64_t)min(t + u * RL, n - 1) * ldx + cg);
+#pragma unroll
+      for (int u = 0; u < SP_UN; ++u)
+        if (t + u * RL < n) {
+#pragma unroll
+          for (int e = 0; e < EPT; ++e) s[e] += v[u].v[e];
+        }
+    }
+#pragma unroll
+  for (int e = 0; e < EPT; ++e) red[threadIdx.y][cl + e] = s[e];
+  __syncthreads();
+  if (tid < BN_CW) {
+    float m = 0.f;
+#pragma unroll
+    for (int y = 0; y < RL; ++y) m += red[y][tid];
+    mean_s[tid] = m / (float)n;
+  }
+  __syncthreads();
+  float mu[EPT], q[EPT] = {};
+#pragma unroll
+  for (int e = 0; e < EPT; ++e) mu[e] = mean_s[cl + e];
+  if (on)
+    for (int t = threadIdx.y; t < n; t += SP_UN * RL) {
+      Vec4f v[SP_UN];
+#pragma unroll
+      for (int u = 0; u < SP_UN; ++u) v[u].load(xb + (int64_t)min(t + u * RL, n - 1) * ldx + cg);
+#pragma unroll
+      for (int u = 0; u < SP_UN; ++u)
+        if (t + u * RL < n) {
+#pragma unroll
+          for (int e = 0; e < EPT; ++e) {
+            const float d = v[u].v[e] - mu[e];
+            q[e] = fmaf(d, d, q[e]);
+          }
+        }
+    }
+#pragma unroll
+  for (int e = 0; e < EPT; ++e) red[threadIdx.y][cl + e] = q[e];
+  __syncthreads();
+  const int cc = blockIdx.x * BN_CW + tid;
+  if (tid < BN_CW && cc < C) {
+    float v = 0.f;
+#pragma unroll
+    for (int y = 0; y < RL; ++y) v += red[y][tid];
+    const float sd = sqrtf(v / (float)(n - 1));
+    const int64_t o = (int64_t)b * 2 * C;
+    out[o + cc] = mean_s[tid];
+    out[o + C + cc] = sd + eps;
+    if (stats != nullptr) {
+      stats[o + cc] = mean_s[tid];
+      stats[o + C + cc] = sd;
+    }
+  }
+}
+// dx[b][t][c] = dmean[b][c] / T + dstd[b][c] (x - mean) / ((T - 1) std): one 16-byte vector per thread.  A constant
+// column has std = 0, where the second term is 0 / 0: it is taken as 0, which is what torch's std backward returns there
+// (it masks the division where the result is 0), so no NaN reaches the weights through the Linear's data gradient.
+__global__ void stat_pool_bwd_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ stats,
+                                     const float* __restrict__ dout, float* __restrict__ dx, int64_t lddx, int B, int Tn,
+                                     int C) {
+  const int cv = C >> 2;
+  const int64_t total = (int64_t)B * Tn * cv;
+  const float invT = 1.0f / (float)Tn, tm1 = (float)(Tn - 1);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = i / cv;
+    const int c = (int)(i - row * cv) * 4;
+    const int64_t o = (row / Tn) * 2 * C + c;
+    Vec4f xv, mu, sd, dm, ds;
+    xv.load(x + row * ldx + c);
+    mu.load(stats + o);
+    sd.load(stats + o + C);
+    dm.load(dout + o);
+    ds.load(dout + o + C);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      xv.v[e] = dm.v[e] * invT + (sd.v[e] > 0.f ? ds.v[e] * (xv.v[e] - mu.v[e]) / (tm1 * sd.v[e]) : 0.f);
+    xv.store(dx + row * lddx + c);
+  }
+}
+
 // ------------------------------------------------------------------------------------------ small f32 activations
 // mode 0: relu, 1: sigmoid.  bwd takes the forward OUTPUT y.
 __global__ void act_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n, int mode) {
@@ -555,11 +676,17 @@ extern "C" int w2v2_bn_workspace_floats(int M, int C) { return (int)cdiv(M, 128)
 static int bn_arows(int M, int C) { return cdiv(C, BN_CW) * cdiv(M, BN_AROWS) >= 256 ? BN_AROWS : 64; }
 extern "C" int w2v2_bn_colsum_rows(int M, int C) { return (int)cdiv(M, bn_arows(M, C)); }
 
+// One thread owns one 16-byte vector of a row (BnGeom): 8 channels of a 16-bit tensor, 4 of an f32 one, and every guard of
+// the strip kernels is per vector -- so C and the row strides are multiples of 8, or of 4 for f32 (the x-vector's last
+// TDNN layer has 1500 channels: 1500 % 8 = 4).  The partial-sum fold reads channel PAIRS, which any such C keeps whole.
+static int bn_align(int dtype) { return dtype == W2V2_F32 ? 4 : 8; }
 extern "C" int w2v2_bn_fwd(const void* a, int64_t lda, float* workspace, float* mean_rstd, float* running,
                            const float* gamma, const float* beta, void* y, int64_t ldy, int M, int C, float eps,
-                           float momentum, int relu, int train, int dtype, void* stream) {
-  W2V2_REQUIRE(a && mean_rstd && gamma && beta && y && M > 0 && C > 0 && C % 8 == 0 && lda >= C && lda % 8 == 0 &&
-                   ldy % 8 == 0, "bn_fwd: bad arguments (C, lda, ldy multiples of 8)");
+                           float momentum, int act, int train, int dtype, void* stream) {
+  const int al = bn_align(dtype);
+  W2V2_REQUIRE(a && mean_rstd && gamma && beta && y && M > 0 && C > 0 && C % al == 0 && lda >= C && lda % al == 0 &&
+                   ldy % al == 0 && act >= 0 && act <= BN_ACT_LEAKY,
+               "bn_fwd: bad arguments (C, lda, ldy multiples of 8, of 4 for f32; act 0, 1 or 2)");
   W2V2_REQUIRE(train ? workspace != nullptr : running != nullptr,
                "bn_fwd: training needs the workspace, evaluation the running statistics");
   const int nblk = (int)cdiv(M, bn_rows_host(C));
@@ -568,9 +695,9 @@ extern "C" int w2v2_bn_fwd(const void* a, int64_t lda, float* workspace, float* 
   hipStream_t st = as_stream(stream);
 #define TD_BNF(T_)                                                                                                   \
   if (train)                                                                                                         \
-    hipLaunchKernelGGL(bn_partial_kernel<T_>, gp, dim3(BnGeom<T_>::XL, BnGeom<T_>::RL), 0, st, (const T_*)a, lda, workspace, M, C, relu);             \
+    hipLaunchKernelGGL(bn_partial_kernel<T_>, gp, dim3(BnGeom<T_>::XL, BnGeom<T_>::RL), 0, st, (const T_*)a, lda, workspace, M, C, act);             \
   hipLaunchKernelGGL(bn_apply_kernel<T_>, ga, dim3(BnGeom<T_>::XL, BnGeom<T_>::RL), 0, st, (const T_*)a, lda, workspace, nblk, mean_rstd, running,    \
-                     gamma, beta, (T_*)y, ldy, M, C, relu, eps, momentum, train, arows)
+                     gamma, beta, (T_*)y, ldy, M, C, act, eps, momentum, train, arows)
   W2V2_DISPATCH_ACT(dtype, "bn_fwd", TD_BNF(AT););
 #undef TD_BNF
   W2V2_CHECK_LAUNCH("bn_fwd");
@@ -579,19 +706,21 @@ extern "C" int w2v2_bn_fwd(const void* a, int64_t lda, float* workspace, float* 
 
 static int bn_bwd_impl(const void* dy, int64_t lddy, const void* dy2, int64_t lddy2, const void* a, int64_t lda,
                        const float* mean_rstd, const float* gamma, float* workspace, float* dgamma, float* dbeta, void* da,
-                       int64_t ldda, int M, int C, int relu, float* colsum_partial, int dtype, void* stream) {
-  W2V2_REQUIRE(dy && a && mean_rstd && gamma && workspace && dgamma && dbeta && da && M > 0 && C > 0 && C % 8 == 0 &&
-                   lda % 8 == 0 && lddy % 8 == 0 && ldda % 8 == 0 && (dy2 == nullptr || lddy2 % 8 == 0),
-               "bn_bwd: bad arguments (C and strides multiples of 8)");
+                       int64_t ldda, int M, int C, int act, float* colsum_partial, int dtype, void* stream) {
+  const int al = bn_align(dtype);
+  W2V2_REQUIRE(dy && a && mean_rstd && gamma && workspace && dgamma && dbeta && da && M > 0 && C > 0 && C % al == 0 &&
+                   lda % al == 0 && lddy % al == 0 && ldda % al == 0 && (dy2 == nullptr || lddy2 % al == 0) && act >= 0 &&
+                   act <= BN_ACT_LEAKY,
+               "bn_bwd: bad arguments (C and strides multiples of 8, of 4 for f32; act 0, 1 or 2)");
   const int nblk = (int)cdiv(M, bn_rows_host(C));
   const int arows = bn_arows(M, C);
   const dim3 gp((unsigned)cdiv(C, BN_CW), nblk), ga((unsigned)cdiv(C, BN_CW), (unsigned)cdiv(M, arows));
   hipStream_t st = as_stream(stream);
 #define TD_BNB(T_)                                                                                                  \
   hipLaunchKernelGGL(bn_bwd_partial_kernel<T_>, gp, dim3(BnGeom<T_>::XL, BnGeom<T_>::RL), 0, st, (const T_*)dy, lddy, (const T_*)dy2, lddy2,         \
-                     (const T_*)a, lda, mean_rstd, workspace, M, C, relu);                                          \
+                     (const T_*)a, lda, mean_rstd, workspace, M, C, act);                                          \
   hipLaunchKernelGGL(bn_bwd_apply_kernel<T_>, ga, dim3(BnGeom<T_>::XL, BnGeom<T_>::RL), 0, st, (const T_*)dy, lddy, (const T_*)dy2, lddy2,           \
-                     (const T_*)a, lda, mean_rstd, gamma, workspace, nblk, dgamma, dbeta, (T_*)da, ldda, M, C, relu, \
+                     (const T_*)a, lda, mean_rstd, gamma, workspace, nblk, dgamma, dbeta, (T_*)da, ldda, M, C, act, \
                      1.0f / (float)M, colsum_partial, arows)
   W2V2_DISPATCH_ACT(dtype, "bn_bwd", TD_BNB(AT););
 #undef TD_BNB
@@ -600,18 +729,18 @@ static int bn_bwd_impl(const void* dy, int64_t lddy, const void* dy2, int64_t ld
 }
 extern "C" int w2v2_bn_bwd(const void* dy, int64_t lddy, const void* a, int64_t lda, const float* mean_rstd,
                            const float* gamma, float* workspace, float* dgamma, float* dbeta, void* da, int64_t ldda,
-                           int M, int C, int relu, float* colsum_partial, int dtype, void* stream) {
-  return bn_bwd_impl(dy, lddy, nullptr, 0, a, lda, mean_rstd, gamma, workspace, dgamma, dbeta, da, ldda, M, C, relu,
+                           int M, int C, int act, float* colsum_partial, int dtype, void* stream) {
+  return bn_bwd_impl(dy, lddy, nullptr, 0, a, lda, mean_rstd, gamma, workspace, dgamma, dbeta, da, ldda, M, C, act,
                      colsum_partial, dtype, stream);
 }
 // the same with the output gradient given as dy + dy2 (two row-strided operands of one shape; both kernels add them as
 // they read): the Res2Net chunk whose output feeds the next chunk AND the block's concatenation
 extern "C" int w2v2_bn_bwd_sum(const void* dy, int64_t lddy, const void* dy2, int64_t lddy2, const void* a, int64_t lda,
                                const float* mean_rstd, const float* gamma, float* workspace, float* dgamma, float* dbeta,
-                               void* da, int64_t ldda, int M, int C, int relu, float* colsum_partial, int dtype,
+                               void* da, int64_t ldda, int M, int C, int act, float* colsum_partial, int dtype,
                                void* stream) {
   W2V2_REQUIRE(dy2 != nullptr, "bn_bwd_sum: null second operand");
-  return bn_bwd_impl(dy, lddy, dy2, lddy2, a, lda, mean_rstd, gamma, workspace, dgamma, dbeta, da, ldda, M, C, relu,
+  return bn_bwd_impl(dy, lddy, dy2, lddy2, a, lda, mean_rstd, gamma, workspace, dgamma, dbeta, da, ldda, M, C, act,
                      colsum_partial, dtype, stream);
 }
 
@@ -724,5 +853,38 @@ extern "C" int w2v2_act_bwd(const float* dy, const float* y, float* dx, int64_t 
   W2V2_REQUIRE(dy && y && dx && n > 0 && (mode == 0 || mode == 1), "act_bwd: bad arguments");
   hipLaunchKernelGGL(act_bwd_kernel, dim3(td_blocks(n)), dim3(256), 0, as_stream(stream), dy, y, dx, n, mode);
   W2V2_CHECK_LAUNCH("act_bwd");
+  return 0;
+}
+
+// x f32 [B][T] rows of C channels with row stride ldx; out / stats / dout f32 [B][2C]; lens (the _len form): device int32 [B],
+// 2 <= lens[b] <= T (checked by the caller on the host)
+static int stat_pool_fwd_impl(const char* name, const float* x, int64_t ldx, float* out, float* stats, const int* lens,
+                              int B, int T, int C, float eps, void* stream) {
+  W2V2_REQUIRE(x && out && B > 0 && T >= 2 && C > 0 && C % 4 == 0 && ldx >= C && ldx % 4 == 0 &&
+                   (reinterpret_cast<uintptr_t>(x) & 15) == 0,
+               "%s: bad arguments (T >= 2, C and ldx multiples of 4, 16-byte aligned x)", name);
+  const dim3 grid((unsigned)cdiv(C, BN_CW), (unsigned)B), block(BnGeom<float>::XL, BnGeom<float>::RL);
+  hipStream_t st = as_stream(stream);
+  W2V2_DISPATCH_LEN(lens, hipLaunchKernelGGL(stat_pool_fwd_kernel<LEN>, grid, block, 0, st, x, ldx, out, stats, lens, T, C, eps));
+  W2V2_CHECK_LAUNCH(name);
+  return 0;
+}
+extern "C" int w2v2_stat_pool_fwd(const float* x, int64_t ldx, float* out, float* stats, int B, int T, int C, float eps,
+                                  void* stream) {
+  return stat_pool_fwd_impl("stat_pool_fwd", x, ldx, out, stats, nullptr, B, T, C, eps, stream);
+}
+extern "C" int w2v2_stat_pool_fwd_len(const float* x, int64_t ldx, float* out, float* stats, const int* lens, int B, int T,
+                                      int C, float eps, void* stream) {
+  W2V2_REQUIRE(lens != nullptr, "stat_pool_fwd_len: bad arguments (null lens)");
+  return stat_pool_fwd_impl("stat_pool_fwd_len", x, ldx, out, stats, lens, B, T, C, eps, stream);
+}
+extern "C" int w2v2_stat_pool_bwd(const float* x, int64_t ldx, const float* stats, const float* dout, float* dx,
+                                  int64_t lddx, int B, int T, int C, void* stream) {
+  W2V2_REQUIRE(x && stats && dout && dx && B > 0 && T >= 2 && C > 0 && C % 4 == 0 && ldx >= C && ldx % 4 == 0 &&
+                   lddx >= C && lddx % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0,
+               "stat_pool_bwd: bad arguments (T >= 2, C and strides multiples of 4, 16-byte aligned x and dx)");
+  hipLaunchKernelGGL(stat_pool_bwd_kernel, dim3(td_blocks((int64_t)B * T * (C >> 2))), dim3(256), 0, as_stream(stream), x,
+                     ldx, stats, dout, dx, lddx, B, T, C);
+  W2V2_CHECK_LAUNCH("stat_pool_bwd");
   return 0;
 }

@@ -142,21 +142,17 @@ def ecapa_param_shapes(cfg: EcapaConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     return s
 
 
-class EcapaStore(FlatArena):
-    """Flat parameter arena (f32 master, gradient, Adam moments, bf16 operand copy) of the ECAPA model + AAM head: the
-    whole arena trains, and there is no loss-scale record."""
+class BnArena(FlatArena):
+    """Flat parameter arena (f32 master, gradient, Adam moments, bf16 operand copy) of a model whose BatchNorm1d buffers
+    live beside it: the whole arena trains, and there is no loss-scale record.  Base of EcapaStore and
+    xvector.XVectorStore."""
     PREFIX = FE
     BATCHES_TRACKED = "bn_batches_tracked"
 
-    def __init__(self, cfg: EcapaConfig, device, act_dtype: torch.dtype = torch.bfloat16, num_speakers: int = 5994):
-        assert act_dtype in (torch.bfloat16, torch.float32), "ECAPA: bf16 or f32 (the reference runs it in fp32; no loss scaler here)"
-        self.cfg, self.act_dtype, self.num_speakers = cfg, act_dtype, num_speakers
-        self.embed_dim = cfg.lin_neurons
-        shapes: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
-        shapes["loss_fn.fc_weights"] = (num_speakers, cfg.lin_neurons)
-        shapes.update(ecapa_param_shapes(cfg))
+    def __init__(self, shapes: "OrderedDict[str, Tuple[int, ...]]", device, act_dtype: torch.dtype):
         super().__init__(shapes, device)
         dev = self.device
+        self.act_dtype = act_dtype
         self.flat_lp = torch.zeros(self.n_total, dtype=act_dtype, device=dev) if ops.is16(act_dtype) else None
         # BatchNorm1d buffers of EVERY norm layer live in the store (shared by the training and the evaluation plans,
         # saved / loaded under the speechbrain names ``...norm.running_mean`` / ``running_var``): one f32 record
@@ -165,7 +161,6 @@ class EcapaStore(FlatArena):
         for n, shp in shapes.items():
             if n.endswith("norm.weight"):
                 self.bn_running[n] = torch.cat([torch.zeros(shp[0]), torch.ones(shp[0])]).to(dev)
-        self.asp_running = self.bn_running[FE + "asp.tdnn.norm.norm.weight"]
         self.bn_batches_tracked = 0
 
     def running(self, weight_name: str) -> torch.Tensor:
@@ -193,6 +188,37 @@ class EcapaStore(FlatArena):
         else:
             self.grad.zero_()
 
+    def optimizer_step(self, lr: float, momentum_or_beta1: float = 0.9, cfg: Optional[OptimConfig] = None,
+                       grad_scale: float = 1.0, gradient_clip_val: float = 0.0, head_only: bool = False,
+                       grad: Optional[torch.Tensor] = None) -> None:
+        """Same contract as ParamStore.optimizer_step (one range: the whole arena trains; no loss-scale record)."""
+        g = self.grad if grad is None else grad
+        assert not head_only, "no frozen-encoder step: the whole arena trains"
+        cfg = cfg if cfg is not None else fused.DEFAULT
+        fused.ensure_state(self, cfg, momentum_or_beta1)
+        self.step_count += 1
+        norm = None
+        if gradient_clip_val > 0 or self.track_grad_norm:
+            fused.norm_pass(self, self.n_total, grad_scale, None, gradient_clip_val, g)
+            norm = self.grad_norm if gradient_clip_val > 0 else None
+        fused.launch(cfg, self.flat, g, self.exp_avg, self.exp_avg_sq, self.flat_lp, self.n_total, lr,
+                     momentum_or_beta1, self.step_count, grad_scale, None, 0, norm)
+        self.version += 1
+
+
+class EcapaStore(BnArena):
+    """Parameter arena of the ECAPA model + AAM head."""
+
+    def __init__(self, cfg: EcapaConfig, device, act_dtype: torch.dtype = torch.bfloat16, num_speakers: int = 5994):
+        assert act_dtype in (torch.bfloat16, torch.float32), "ECAPA: bf16 or f32 (the reference runs it in fp32; no loss scaler here)"
+        self.cfg, self.num_speakers = cfg, num_speakers
+        self.embed_dim = cfg.lin_neurons
+        shapes: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+        shapes["loss_fn.fc_weights"] = (num_speakers, cfg.lin_neurons)
+        shapes.update(ecapa_param_shapes(cfg))
+        super().__init__(shapes, device, act_dtype)
+        self.asp_running = self.bn_running[FE + "asp.tdnn.norm.norm.weight"]
+
     def init_weights(self, seed: int = 20211) -> None:
         g = torch.Generator(device="cpu").manual_seed(seed)
         for n, s in self.shapes.items():
@@ -206,23 +232,6 @@ class EcapaStore(FlatArena):
                 t = (torch.rand(s, generator=g) * 2 - 1) / math.sqrt(s[1] * s[2])
             self.p(n).copy_(t.to(self.device))
         self.sync_lowp()
-
-    def optimizer_step(self, lr: float, momentum_or_beta1: float = 0.9, cfg: Optional[OptimConfig] = None,
-                       grad_scale: float = 1.0, gradient_clip_val: float = 0.0, head_only: bool = False,
-                       grad: Optional[torch.Tensor] = None) -> None:
-        """Same contract as ParamStore.optimizer_step (one range: the whole arena trains; no loss-scale record)."""
-        g = self.grad if grad is None else grad
-        assert not head_only, "ECAPA has no frozen-encoder step"
-        cfg = cfg if cfg is not None else fused.DEFAULT
-        fused.ensure_state(self, cfg, momentum_or_beta1)
-        self.step_count += 1
-        norm = None
-        if gradient_clip_val > 0 or self.track_grad_norm:
-            fused.norm_pass(self, self.n_total, grad_scale, None, gradient_clip_val, g)
-            norm = self.grad_norm if gradient_clip_val > 0 else None
-        fused.launch(cfg, self.flat, g, self.exp_avg, self.exp_avg_sq, self.flat_lp, self.n_total, lr,
-                     momentum_or_beta1, self.step_count, grad_scale, None, 0, norm)
-        self.version += 1
 
 
 def _cols(v: torch.Tensor, c0: int, c1: Optional[int] = None) -> torch.Tensor:
@@ -257,18 +266,25 @@ def f32_dw_split(n_out: int, n_in: int, tokens: int, slots: int = 512) -> int:
 
 
 class _Tdnn:
-    """TDNNBlock = Conv1d("same", reflect, dilation) -> ReLU -> BatchNorm1d over one [M, Cin] view -> [M, Cout] view."""
+    """TDNNBlock = Conv1d("same", reflect, dilation) -> activation -> BatchNorm1d over one [M, Cin] view -> [M, Cout] view.
+    The activation is ReLU in ECAPA and LeakyReLU(0.01) in the x-vector (xvector.py), whose blocks also name their two
+    modules differently."""
 
     def __init__(self, plan: "EcapaPlan", prefix: str, x: torch.Tensor, ldx: int, cin: int, cout: int, k: int, dil: int,
                  y: torch.Tensor, ldy: int, x2: Optional[torch.Tensor] = None, ldx2: int = 0,
-                 shared: Optional[dict] = None):
-        """x2 (k > 1 only): the block convolves x + x2 -- the im2col pass sums the two while it gathers the taps.
+                 shared: Optional[dict] = None, act: int = ops.BN_ACT_RELU, conv: str = "conv.conv.",
+                 norm: str = "norm.norm."):
+        """act: the BN_ACT_* mode in front of the BatchNorm.  conv / norm: the state-dict names of the Conv1d and the
+        BatchNorm1d under ``prefix``.
+        x2 (k > 1 only): the block convolves x + x2 -- the im2col pass sums the two while it gathers the taps.
         shared (exact-f32 training, Res2Net chunks): {"col", "da", "dwp"} views into the owner's [chunks, ...] arrays -- the
         owner then computes the weight gradients of all its chunks in ONE batched product (_SERes2Net.backward)."""
         st, B, T, dev, adt, f32 = plan.store, plan.B, plan.T, plan.dev, plan.adt, torch.float32
         assert x2 is None or k > 1, "a second input operand needs the im2col pass (k > 1)"
         self.plan, self.pre, self.x, self.ldx, self.y, self.ldy = plan, FE + prefix, x, ldx, y, ldy
-        self.x2, self.ldx2 = x2, ldx2
+        self.x2, self.ldx2, self.act = x2, ldx2, act
+        self.n_w, self.n_b = self.pre + conv + "weight", self.pre + conv + "bias"
+        self.n_gamma, self.n_beta = self.pre + norm + "weight", self.pre + norm + "bias"
         self.cin, self.cout, self.k, self.dil = cin, cout, k, dil
         M, K = B * T, k * cin
         self.M, self.K = M, K
@@ -277,21 +293,21 @@ class _Tdnn:
         self.col = (shared["col"] if shared else plan.buf(M, K)) if k > 1 else None
         self.a = torch.empty(M, cout, dtype=adt, device=dev)                   # pre-activation (saved)
         self.mean_rstd = torch.empty(cout, 2, dtype=f32, device=dev)
-        self.running = st.running(self.pre + "norm.norm.weight")            # shared BatchNorm1d buffers (store)
+        self.running = st.running(self.n_gamma)            # shared BatchNorm1d buffers (store)
         self.work = ops.bn_workspace(M, cout, dev)
         A, lda = (self.col, K) if k > 1 else (x, ldx)
         self.g_fwd = Gemm(M, cout, K, A, self.wp, self.a, lda=lda, ldb=K, ldc=cout, epilogue=EPI_BIAS,
-                          bias=st.p(self.pre + "conv.conv.bias"))
+                          bias=st.p(self.n_b))
         if plan.train:
             self.da = shared["da"] if shared else plan.buf(M, cout)
             self.cs_part = torch.empty(ops.bn_colsum_rows(M, cout), cout, dtype=f32, device=dev)   # bias-gradient partials
             self.dwp = (shared["dwp"] if shared else torch.zeros(cout, K, dtype=f32, device=dev)) if k > 1 else None
-            dW = self.dwp if k > 1 else st.g(self.pre + "conv.conv.weight").view(cout, cin)
+            dW = self.dwp if k > 1 else st.g(self.n_w).view(cout, cin)
             # bf16: weight + bias gradient through the grouped, atomic-free wgrad kernels (K-major operands: da and the
             # conv input / im2col buffer, both zero-padded to a multiple of 64 rows), launched per group by the owner
             self.grouped = ops.is16(adt) and hasattr(A, "_full")
             if self.grouped:
-                self.wg_problem = (self.da._full, A._full, dW, st.g(self.pre + "conv.conv.bias"))
+                self.wg_problem = (self.da._full, A._full, dW, st.g(self.n_b))
             # exact-f32 mode (no grouped launch): K of this product = the B * T tokens, its output only
             # cout x K / 128^2 tiles (3 for a Res2Net chunk) -- split the token dimension over ~2 workgroups per CU
             # (f32 atomics into a zeroed target), like the wav2vec2 engine's f32 weight gradients
@@ -308,7 +324,7 @@ class _Tdnn:
             self._dx_gemm = {}
 
     def refresh(self) -> None:
-        ops.pack_conv_weight(self.plan.store.p(self.pre + "conv.conv.weight"), self.wp)
+        ops.pack_conv_weight(self.plan.store.p(self.n_w), self.wp)
 
     def forward(self) -> None:
         st, pl = self.plan.store, self.plan
@@ -318,8 +334,8 @@ class _Tdnn:
         elif self.k > 1:
             ops.im2col_reflect(self.x, self.ldx, self.col, pl.B, pl.T, self.cin, self.k, self.dil, self.x2, self.ldx2)
         self.g_fwd()
-        ops.bn_fwd(self.a, self.cout, self.work, self.mean_rstd, self.running, st.p(self.pre + "norm.norm.weight"),
-                   st.p(self.pre + "norm.norm.bias"), self.y, self.ldy, self.M, self.cout, BN_EPS, BN_MOMENTUM, True,
+        ops.bn_fwd(self.a, self.cout, self.work, self.mean_rstd, self.running, st.p(self.n_gamma),
+                   st.p(self.n_beta), self.y, self.ldy, self.M, self.cout, BN_EPS, BN_MOMENTUM, self.act,
                    pl.train)
 
     def weight_grad_single(self) -> None:
@@ -331,7 +347,7 @@ class _Tdnn:
             self._wg()
         else:
             # (the BatchNorm backward left the column sums of da per row block: 78 rows to fold instead of 19800)
-            ops.colsum(self.cs_part, st.g(self.pre + "conv.conv.bias"), self.cs_part.shape[0], self.cout)
+            ops.colsum(self.cs_part, st.g(self.n_b), self.cs_part.shape[0], self.cout)
             if self._dwp_ztab is not None:
                 ops.zero_ranges(self.dwp.view(-1), self._dwp_ztab, blocks_per_range=64)
             self.g_dw()
@@ -340,7 +356,7 @@ class _Tdnn:
     def finish_weight_grad(self) -> None:
         if self.k > 1:       # packed [cout][tap][cin] gradient -> torch layout [cout][cin][tap] (added into the arena)
             ops.unpack_conv_grad(self.dwp.view(self.cout, self.k, self.cin),
-                                 self.plan.store.g(self.pre + "conv.conv.weight"))
+                                 self.plan.store.g(self.n_w))
 
     def backward(self, dy: torch.Tensor, lddy: int, dx: Optional[torch.Tensor], lddx: int, accumulate: bool,
                  defer_dw: bool = False, dy2: Optional[torch.Tensor] = None, lddy2: int = 0) -> None:
@@ -348,9 +364,9 @@ class _Tdnn:
         ``accumulate``, is incremented by the input gradient.  Parameter gradients go to the arena; with ``defer_dw``
         (bf16) the owner launches the weight gradients of several blocks in one grouped call afterwards."""
         st, pl = self.plan.store, self.plan
-        ops.bn_bwd(dy, lddy, self.a, self.cout, self.mean_rstd, st.p(self.pre + "norm.norm.weight"), self.work,
-                   st.g(self.pre + "norm.norm.weight"), st.g(self.pre + "norm.norm.bias"), self.da, self.cout, self.M,
-                   self.cout, True, colsum_partial=None if self.grouped else self.cs_part, dy2=dy2, lddy2=lddy2)
+        ops.bn_bwd(dy, lddy, self.a, self.cout, self.mean_rstd, st.p(self.n_gamma), self.work,
+                   st.g(self.n_gamma), st.g(self.n_beta), self.da, self.cout, self.M,
+                   self.cout, self.act, colsum_partial=None if self.grouped else self.cs_part, dy2=dy2, lddy2=lddy2)
         if not ((self.grouped or self.shared) and defer_dw):
             self.weight_grad_single()
         if dx is None:
@@ -497,7 +513,7 @@ class _SERes2Net:
             ops.zero_ranges(self._dwp_all.view(-1), self._dw_ztab, blocks_per_range=64)
             self._g_dw_all()
             for c in self.chunks[1:]:
-                ops.colsum(c.cs_part, st.g(c.pre + "conv.conv.bias"), c.cs_part.shape[0], c.cout)
+                ops.colsum(c.cs_part, st.g(c.n_b), c.cs_part.shape[0], c.cout)
                 c.finish_weight_grad()
         ops.copy_strided(self.d_r2, C, self.d_t1, C, M, w)
         self.tdnn1.backward(self.d_t1, C, dx, lddx, accumulate, defer_dw=True)
@@ -507,18 +523,17 @@ class _SERes2Net:
         # mode leaves them to ONE grouped launch at the end of the plan's backward (EcapaPlan.backward)
 
 
-class EcapaPlan:
-    """Static plan of one ECAPA-TDNN forward (+ backward) for a fixed [B, T, n_mels] input."""
+class TdnnPlan:
+    """What the static plans of the two TDNN models (EcapaPlan, xvector.XVectorPlan) share: the packed-weight arenas of
+    their _Tdnn blocks, the zero-padded activation buffers, the input plumbing of embed() / embed_waveform() with its
+    variable-length form, and the device filterbank front-end.  A plan supplies ``_tdnns()`` (its blocks) and
+    ``_embed_features()`` (the forward from ``self.feat`` on)."""
 
-    def __init__(self, store: EcapaStore, batch: int, frames: int, *, train: bool, aam_margin: float = 0.2,
-                 aam_scale: float = 30.0):
+    def __init__(self, store, batch: int, frames: int, train: bool):
         cfg = store.cfg
         self.store, self.cfg, self.B, self.T, self.train = store, cfg, batch, frames, train
         self.dev, self.adt = store.device, store.act_dtype
-        B, T, M, dev, adt, f32 = batch, frames, batch * frames, self.dev, self.adt, torch.float32
-        C = cfg.channels
-        nb = len(C) - 2                                                       # SE-Res2Net blocks
-        assert all(c == C[1] for c in C[1:-1]) and C[-1] == nb * C[1], "MFA concatenates the SE-Res2Net outputs"
+        dev, adt = self.dev, self.adt
         # packed conv weights of all TDNN blocks in one arena (+ a second one with their transposes for the 16-bit
         # data-gradient products): the transposes are refreshed by one w2v2_transpose_many launch per optimiser step
         self._wp_pool = torch.empty(store.n_total, dtype=adt, device=dev)
@@ -527,44 +542,8 @@ class EcapaPlan:
         # variable-length evaluation (embed(..., lengths=)): device int32 [B] table of frame counts, uploaded per forward
         self._len_dev, self._len = None, None
         self.frame_lengths: Optional[List[int]] = None
-        F_ = cfg.input_mel_coefficients
-        self.feat = self.buf(M, F_)
-        self.x0 = self.buf(M, C[0])
-        self.cat = self.buf(M, C[-1])                                         # MFA input: block outputs side by side
-        self.block0 = _Tdnn(self, "blocks.0.", self.feat, F_, F_, C[0], cfg.kernel_sizes[0], cfg.dilations[0],
-                            self.x0, C[0])
-        self.blocks: List[_SERes2Net] = []
-        for i in range(1, nb + 1):
-            x, ldx = (self.x0, C[0]) if i == 1 else (_cols(self.cat, (i - 2) * C[1], (i - 1) * C[1]), C[-1])
-            self.blocks.append(_SERes2Net(self, i, x, ldx, self.cat[:, (i - 1) * C[1]:], C[-1]))
-        rows = (M + 63) // 64 * 64
-        self.mfa_out = self.buf(M, C[-1])
-        self.mfa_out._w2v2_padded = self.mfa_out._full
-        self.mfa = _Tdnn(self, "mfa.", self.cat, C[-1], C[-1], C[-1], cfg.kernel_sizes[-1], cfg.dilations[-1],
-                         self.mfa_out, C[-1])
-        self.pooled = torch.empty(B, 2 * C[-1], dtype=f32, device=dev)
-        self.d_mfa = torch.zeros(rows, C[-1], dtype=adt, device=dev)[:M] if train else None
-        self.asp = AttentivePool(store, self.mfa_out, self.pooled, self.d_mfa, B, T, train, prefix=FE + "asp.")
-        E2, L = 2 * C[-1], cfg.lin_neurons
-        self.bn_mr = torch.empty(E2, 2, dtype=f32, device=dev)
-        self.bn_running = store.running(FE + "asp_bn.norm.weight")
-        self.bn_work = ops.bn_workspace(B, E2, dev)
-        self.e2 = torch.empty(B, E2, dtype=f32, device=dev)
-        self.emb = torch.empty(B, L, dtype=f32, device=dev)
-        p, g = store.p, store.g
-        Wfc = p(FE + "fc.conv.weight").view(L, E2)
-        self.Wfc = Wfc
-        self.head = ClassifierHead("aam", B, L, store.num_speakers, w_master=p("loss_fn.fc_weights"),
-                                   w_operand=store.w("loss_fn.fc_weights"),
-                                   w_grad=g("loss_fn.fc_weights") if train else None, emb=self.emb, act_dtype=adt,
-                                   train=train, margin=aam_margin, scale=aam_scale)
-        if train:
-            self.de2 = torch.empty(B, E2, dtype=f32, device=dev)
-            self.dpooled = torch.empty(B, E2, dtype=f32, device=dev)
-            self.d_cat = torch.empty(M, C[-1], dtype=adt, device=dev)
-            self.d_x0 = torch.empty(M, C[0], dtype=adt, device=dev)
+        self.feat = self.buf(batch * frames, cfg.input_mel_coefficients)
         self._version = -1
-        self._wgs = None
 
     def weight_pair(self, cout: int, K: int):
         """([cout, K] packed-weight view, [K, cout] transposed view or None) out of the plan's two weight arenas."""
@@ -585,12 +564,6 @@ class EcapaPlan:
         v = full[:rows]
         v._full = full
         return v
-
-    def _tdnns(self) -> List[_Tdnn]:
-        out = [self.block0]
-        for b in self.blocks:
-            out += b.blocks()
-        return out + [self.mfa]
 
     def _refresh(self) -> None:
         if self._version != self.store.version:
@@ -673,6 +646,61 @@ class EcapaPlan:
         ops.fbank_db(wav.contiguous(), slen, window, fbank, db, pmax)
         ops.fbank_normalize(db, pmax, slen, self.feat, self.feat.stride(0))
         return self._embed_features()
+
+
+class EcapaPlan(TdnnPlan):
+    """Static plan of one ECAPA-TDNN forward (+ backward) for a fixed [B, T, n_mels] input."""
+
+    def __init__(self, store: EcapaStore, batch: int, frames: int, *, train: bool, aam_margin: float = 0.2,
+                 aam_scale: float = 30.0):
+        super().__init__(store, batch, frames, train)
+        cfg = store.cfg
+        B, T, M, dev, adt, f32 = batch, frames, batch * frames, self.dev, self.adt, torch.float32
+        C = cfg.channels
+        nb = len(C) - 2                                                       # SE-Res2Net blocks
+        assert all(c == C[1] for c in C[1:-1]) and C[-1] == nb * C[1], "MFA concatenates the SE-Res2Net outputs"
+        F_ = cfg.input_mel_coefficients
+        self.x0 = self.buf(M, C[0])
+        self.cat = self.buf(M, C[-1])                                         # MFA input: block outputs side by side
+        self.block0 = _Tdnn(self, "blocks.0.", self.feat, F_, F_, C[0], cfg.kernel_sizes[0], cfg.dilations[0],
+                            self.x0, C[0])
+        self.blocks: List[_SERes2Net] = []
+        for i in range(1, nb + 1):
+            x, ldx = (self.x0, C[0]) if i == 1 else (_cols(self.cat, (i - 2) * C[1], (i - 1) * C[1]), C[-1])
+            self.blocks.append(_SERes2Net(self, i, x, ldx, self.cat[:, (i - 1) * C[1]:], C[-1]))
+        rows = (M + 63) // 64 * 64
+        self.mfa_out = self.buf(M, C[-1])
+        self.mfa_out._w2v2_padded = self.mfa_out._full
+        self.mfa = _Tdnn(self, "mfa.", self.cat, C[-1], C[-1], C[-1], cfg.kernel_sizes[-1], cfg.dilations[-1],
+                         self.mfa_out, C[-1])
+        self.pooled = torch.empty(B, 2 * C[-1], dtype=f32, device=dev)
+        self.d_mfa = torch.zeros(rows, C[-1], dtype=adt, device=dev)[:M] if train else None
+        self.asp = AttentivePool(store, self.mfa_out, self.pooled, self.d_mfa, B, T, train, prefix=FE + "asp.")
+        E2, L = 2 * C[-1], cfg.lin_neurons
+        self.bn_mr = torch.empty(E2, 2, dtype=f32, device=dev)
+        self.bn_running = store.running(FE + "asp_bn.norm.weight")
+        self.bn_work = ops.bn_workspace(B, E2, dev)
+        self.e2 = torch.empty(B, E2, dtype=f32, device=dev)
+        self.emb = torch.empty(B, L, dtype=f32, device=dev)
+        p, g = store.p, store.g
+        Wfc = p(FE + "fc.conv.weight").view(L, E2)
+        self.Wfc = Wfc
+        self.head = ClassifierHead("aam", B, L, store.num_speakers, w_master=p("loss_fn.fc_weights"),
+                                   w_operand=store.w("loss_fn.fc_weights"),
+                                   w_grad=g("loss_fn.fc_weights") if train else None, emb=self.emb, act_dtype=adt,
+                                   train=train, margin=aam_margin, scale=aam_scale)
+        if train:
+            self.de2 = torch.empty(B, E2, dtype=f32, device=dev)
+            self.dpooled = torch.empty(B, E2, dtype=f32, device=dev)
+            self.d_cat = torch.empty(M, C[-1], dtype=adt, device=dev)
+            self.d_x0 = torch.empty(M, C[0], dtype=adt, device=dev)
+        self._wgs = None
+
+    def _tdnns(self) -> List[_Tdnn]:
+        out = [self.block0]
+        for b in self.blocks:
+            out += b.blocks()
+        return out + [self.mfa]
 
     def _embed_features(self) -> torch.Tensor:
         """The forward from the plan's feature buffer on (shared by embed and embed_waveform)."""

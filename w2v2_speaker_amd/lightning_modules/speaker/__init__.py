@@ -1,0 +1,1 @@
+from .xvector import XVectorModule, XVectorModuleConfig  # noqa: F401

@@ -35,53 +35,21 @@ class EcapaTDNNModuleConfig:
     explicit_num_speakers: Optional[int] = None
 
 
-class EcapaTdnnModule(OptimizerSurface, EmbeddingEvaluation):
-    def __init__(self, hyperparameters_to_save, cfg: EcapaTDNNModuleConfig, num_speakers: int,
-                 loss_fn_constructor: Callable[[], object], validation_pairs=None, test_pairs=None, evaluator=None, *,
-                 device="cuda", act_dtype: torch.dtype = torch.bfloat16, max_lr: float = 1e-3,
-                 max_steps: int = 100_000, init_seed: int = 20211, gradient_clip_val: float = 0.0,
-                 accumulate_grad_batches: int = 1, input_features: str = "fbank"):
-        """Positional arguments = ref: ecapa_tdnn.py:51-62 (what src/main.py:256-285 passes to every network class).
-        ``loss_fn_constructor`` is called once and read for its type and hyper-parameters: the engine runs the ECAPA
-        model under AAM-softmax (``skip_classifier`` of ref :93-95; the paper's configuration,
-        config/experiment/speaker_ecapa_tdnn.yaml) -- the cross-entropy + cosine ``Classifier`` variant is not on the
-        path.  ``act_dtype=torch.float32`` is the reference's own precision for this model (``precision: 32``).
-        ``input_features``: "fbank" -- inputs are [B, T, n_mels] filterbank tensors, the output of the reference's
-        ``filterbank`` + ``normalizer`` pipeline stages (data/fbank.py, InputNormalizer2D) -- or "waveform": inputs are
-        what the ``selector`` stage delivers ([B, 1, N], [B, N] or [N] audio) and the two stages run on the device
-        (EcapaPlan.embed_waveform)."""
-        if input_features not in ("fbank", "waveform"):
-            raise ValueError(f"input_features: 'fbank' or 'waveform', got {input_features!r}")
-        self.input_features = input_features
+class FilterbankSpeakerModule(OptimizerSurface, EmbeddingEvaluation):
+    """What the modules of the two filterbank models (EcapaTdnnModule, xvector.XVectorModule) share: the input forms, the
+    plan caches, the batched variable-length evaluation and ``training_step``.  A module sets ``cfg``, ``model_cfg`` (with
+    ``input_mel_coefficients``, ``kernel_sizes``, ``dilations``), ``store``, and supplies ``_new_plan(batch, frames,
+    train)`` and ``_new_trainer(plan)``."""
+
+    def _init_runtime(self, device, input_features: str, validation_pairs, test_pairs, evaluator, max_lr: float,
+                      max_steps: int, gradient_clip_val: float, accumulate_grad_batches: int) -> None:
         from ...evaluation.speaker.cosine_distance import CosineDistanceEvaluator
-        from ...optim.loss import AngularAdditiveMarginSoftMaxLoss
-        loss_fn = loss_fn_constructor()
-        if not isinstance(loss_fn, AngularAdditiveMarginSoftMaxLoss):
-            raise NotImplementedError(f"loss {type(loss_fn).__name__}: the ECAPA path runs under "
-                                      "AngularAdditiveMarginSoftMaxLoss (speechbrain's Classifier + CE is outside it)")
-        aam_margin, aam_scale = float(loss_fn.margin), float(loss_fn.scale)
-        del loss_fn
-        self.hyperparameters_to_save = hyperparameters_to_save
+        self.input_features = input_features
         self.validation_pairs, self.test_pairs = validation_pairs or [], test_pairs or []
         self.evaluator = evaluator or CosineDistanceEvaluator(False, False, 0)
-        if not cfg.global_context:
-            raise NotImplementedError("global_context=False (the reference config sets True)")
-        self.cfg = cfg
-        self.embedding_size = cfg.lin_neurons
-        self.num_speakers = cfg.explicit_num_speakers or num_speakers
-        self.model_cfg = EcapaConfig(cfg.input_mel_coefficients, cfg.lin_neurons, tuple(cfg.channels),
-                                     tuple(cfg.kernel_sizes), tuple(cfg.dilations), cfg.attention_channels,
-                                     cfg.res2net_scale, cfg.se_channels)
-        self.store = EcapaStore(self.model_cfg, device, act_dtype, num_speakers=self.num_speakers)
-        self.store.init_weights(init_seed)
-        if cfg.pretrained_weights_path is not None:       # ref :88-91: a bare ECAPA_TDNN state dict
-            sd = torch.load(cfg.pretrained_weights_path, map_location="cpu", weights_only=True)
-            self.store.load_state_dict(dict(sd), strict=False)    # incl. every BatchNorm running_mean / running_var
-        self.margin, self.scale = aam_margin, aam_scale
         self.schedule = OneCycle(max_lr=max_lr, total_steps=max_steps)
         self.gradient_clip_val = float(gradient_clip_val)      # PL ``trainer.gradient_clip_val`` (global norm, 0 = off)
         self._set_accumulate_grad_batches(accumulate_grad_batches)     # PL ``trainer.accumulate_grad_batches``
-        self.skip_classifier = True                        # AAM owns the classifier weight (ref :93-95, :129-131)
         self.device = torch.device(device)
         self._plans = PlanCache()                          # one per (batch, frames, train) shape, all kept
         self._trainers: Dict[Tuple, EcapaTrainer] = {}
@@ -89,25 +57,18 @@ class EcapaTdnnModule(OptimizerSurface, EmbeddingEvaluation):
         self.steps = 0              # backward passes (micro-batches)
         self.schedule_step = 0      # optimiser steps = position in the learning-rate schedule
 
-    @classmethod
-    def from_config(cls, cfg: EcapaTDNNModuleConfig, num_speakers: int, aam_margin: float = 0.2,
-                    aam_scale: float = 30.0, **kw) -> "EcapaTdnnModule":
-        """Short form for scripts and tests: the AAM loss by its two hyper-parameters instead of a constructor."""
-        from ...optim.loss import AngularAdditiveMarginSoftMaxLoss
-        dev = kw.get("device", "cuda")
-        ctor = lambda: AngularAdditiveMarginSoftMaxLoss(2, 2, margin=aam_margin, scale=aam_scale, device=dev,
-                                                        act_dtype=torch.float32)
-        return cls(None, cfg, num_speakers, ctor, kw.pop("validation_pairs", None), kw.pop("test_pairs", None),
-                   kw.pop("evaluator", None), **kw)
+    @staticmethod
+    def _check_input_features(input_features: str) -> None:
+        if input_features not in ("fbank", "waveform"):
+            raise ValueError(f"input_features: 'fbank' or 'waveform', got {input_features!r}")
 
-    def _plan(self, batch: int, frames: int, train: bool) -> EcapaPlan:
-        return self._plans.lookup((batch, frames, train), lambda: EcapaPlan(
-            self.store, batch, frames, train=train, aam_margin=self.margin, aam_scale=self.scale))
+    def _plan(self, batch: int, frames: int, train: bool):
+        return self._plans.lookup((batch, frames, train), lambda: self._new_plan(batch, frames, train))
 
     def generate_example_input(self, include_batch_dimension: bool, batch_size: Optional[int] = None):
         # ref :97-108: [BATCH_SIZE, NUMBER_OF_WINDOWS, NUMBER_OF_MEL_COEFFICIENTS]
-        shape = [batch_size, 100, self.cfg.input_mel_coefficients] if include_batch_dimension else \
-            [100, self.cfg.input_mel_coefficients]
+        shape = [batch_size, 100, self.model_cfg.input_mel_coefficients] if include_batch_dimension else \
+            [100, self.model_cfg.input_mel_coefficients]
         return torch.rand(size=shape)
 
     def compute_speaker_embedding(self, input_tensor: torch.Tensor) -> torch.Tensor:
@@ -126,9 +87,8 @@ class EcapaTdnnModule(OptimizerSurface, EmbeddingEvaluation):
             raise ValueError(f"expected [B, 1, N], [B, N] or [N] audio, got {tuple(input_tensor.shape)}")
         return x.to(self.device, torch.float32).contiguous()
 
-    def _bucket_plan(self, batch: int, frames: int) -> EcapaPlan:
-        return self._bucket_plans.lookup((batch, frames), lambda: EcapaPlan(
-            self.store, batch, frames, train=False, aam_margin=self.margin, aam_scale=self.scale))
+    def _bucket_plan(self, batch: int, frames: int):
+        return self._bucket_plans.lookup((batch, frames), lambda: self._new_plan(batch, frames, False))
 
     def compute_speaker_embeddings(self, feats, *, quantum: int = DEFAULT_FRAME_QUANTUM,
                                    max_batch_frames: int = DEFAULT_MAX_BATCH_FRAMES,
@@ -142,7 +102,7 @@ class EcapaTdnnModule(OptimizerSurface, EmbeddingEvaluation):
         EcapaPlan.embed_waveform(..., lengths=)."""
         if self.input_features == "waveform":
             return self._waveform_embeddings(feats, quantum, max_batch_frames, max_batch)
-        F_ = self.cfg.input_mel_coefficients
+        F_ = self.model_cfg.input_mel_coefficients
         xs = []
         for f in feats:
             x = f[0] if (f.dim() == 3 and f.shape[0] == 1) else f
@@ -174,9 +134,6 @@ class EcapaTdnnModule(OptimizerSurface, EmbeddingEvaluation):
                 out[i] = emb[j:j + 1].clone()
         return out
 
-    def compute_speaker_prediction(self, embedding_tensor: torch.Tensor) -> torch.Tensor:
-        return embedding_tensor.squeeze()                  # ref :120-122 under AAM
-
     def forward(self, input_tensor: torch.Tensor):
         embedding = self.compute_speaker_embedding(input_tensor)
         return embedding, self.compute_speaker_prediction(embedding)
@@ -193,8 +150,7 @@ class EcapaTdnnModule(OptimizerSurface, EmbeddingEvaluation):
             key = (x.shape[0], x.shape[1])
         label = batch.ground_truth.to(self.device)
         loss, pred = self._trainer_step(
-            key, lambda: EcapaTrainer(self.store, self._plan(key[0], key[1], True), self.schedule,
-                                      **self._trainer_options()),
+            key, lambda: self._new_trainer(self._plan(key[0], key[1], True)),
             lambda tr: tr.train_step(x, label))
         self.steps += 1
         return {"loss": loss, "prediction": pred}
@@ -204,3 +160,66 @@ class EcapaTdnnModule(OptimizerSurface, EmbeddingEvaluation):
 
     def load_state_dict(self, sd, strict: bool = True):
         self.store.load_state_dict(sd, strict=strict)
+
+
+class EcapaTdnnModule(FilterbankSpeakerModule):
+    def __init__(self, hyperparameters_to_save, cfg: EcapaTDNNModuleConfig, num_speakers: int,
+                 loss_fn_constructor: Callable[[], object], validation_pairs=None, test_pairs=None, evaluator=None, *,
+                 device="cuda", act_dtype: torch.dtype = torch.bfloat16, max_lr: float = 1e-3,
+                 max_steps: int = 100_000, init_seed: int = 20211, gradient_clip_val: float = 0.0,
+                 accumulate_grad_batches: int = 1, input_features: str = "fbank"):
+        """Positional arguments = ref: ecapa_tdnn.py:51-62 (what src/main.py:256-285 passes to every network class).
+        ``loss_fn_constructor`` is called once and read for its type and hyper-parameters: the engine runs the ECAPA
+        model under AAM-softmax (``skip_classifier`` of ref :93-95; the paper's configuration,
+        config/experiment/speaker_ecapa_tdnn.yaml) -- the cross-entropy + cosine ``Classifier`` variant is not on the
+        path.  ``act_dtype=torch.float32`` is the reference's own precision for this model (``precision: 32``).
+        ``input_features``: "fbank" -- inputs are [B, T, n_mels] filterbank tensors, the output of the reference's
+        ``filterbank`` + ``normalizer`` pipeline stages (data/fbank.py, InputNormalizer2D) -- or "waveform": inputs are
+        what the ``selector`` stage delivers ([B, 1, N], [B, N] or [N] audio) and the two stages run on the device
+        (EcapaPlan.embed_waveform)."""
+        self._check_input_features(input_features)
+        from ...optim.loss import AngularAdditiveMarginSoftMaxLoss
+        loss_fn = loss_fn_constructor()
+        if not isinstance(loss_fn, AngularAdditiveMarginSoftMaxLoss):
+            raise NotImplementedError(f"loss {type(loss_fn).__name__}: the ECAPA path runs under "
+                                      "AngularAdditiveMarginSoftMaxLoss (speechbrain's Classifier + CE is outside it)")
+        aam_margin, aam_scale = float(loss_fn.margin), float(loss_fn.scale)
+        del loss_fn
+        self.hyperparameters_to_save = hyperparameters_to_save
+        if not cfg.global_context:
+            raise NotImplementedError("global_context=False (the reference config sets True)")
+        self.cfg = cfg
+        self.embedding_size = cfg.lin_neurons
+        self.num_speakers = cfg.explicit_num_speakers or num_speakers
+        self.model_cfg = EcapaConfig(cfg.input_mel_coefficients, cfg.lin_neurons, tuple(cfg.channels),
+                                     tuple(cfg.kernel_sizes), tuple(cfg.dilations), cfg.attention_channels,
+                                     cfg.res2net_scale, cfg.se_channels)
+        self.store = EcapaStore(self.model_cfg, device, act_dtype, num_speakers=self.num_speakers)
+        self.store.init_weights(init_seed)
+        if cfg.pretrained_weights_path is not None:       # ref :88-91: a bare ECAPA_TDNN state dict
+            sd = torch.load(cfg.pretrained_weights_path, map_location="cpu", weights_only=True)
+            self.store.load_state_dict(dict(sd), strict=False)    # incl. every BatchNorm running_mean / running_var
+        self.margin, self.scale = aam_margin, aam_scale
+        self.skip_classifier = True                        # AAM owns the classifier weight (ref :93-95, :129-131)
+        self._init_runtime(device, input_features, validation_pairs, test_pairs, evaluator, max_lr, max_steps,
+                           gradient_clip_val, accumulate_grad_batches)
+
+    @classmethod
+    def from_config(cls, cfg: EcapaTDNNModuleConfig, num_speakers: int, aam_margin: float = 0.2,
+                    aam_scale: float = 30.0, **kw) -> "EcapaTdnnModule":
+        """Short form for scripts and tests: the AAM loss by its two hyper-parameters instead of a constructor."""
+        from ...optim.loss import AngularAdditiveMarginSoftMaxLoss
+        dev = kw.get("device", "cuda")
+        ctor = lambda: AngularAdditiveMarginSoftMaxLoss(2, 2, margin=aam_margin, scale=aam_scale, device=dev,
+                                                        act_dtype=torch.float32)
+        return cls(None, cfg, num_speakers, ctor, kw.pop("validation_pairs", None), kw.pop("test_pairs", None),
+                   kw.pop("evaluator", None), **kw)
+
+    def _new_plan(self, batch: int, frames: int, train: bool) -> EcapaPlan:
+        return EcapaPlan(self.store, batch, frames, train=train, aam_margin=self.margin, aam_scale=self.scale)
+
+    def _new_trainer(self, plan: EcapaPlan) -> EcapaTrainer:
+        return EcapaTrainer(self.store, plan, self.schedule, **self._trainer_options())
+
+    def compute_speaker_prediction(self, embedding_tensor: torch.Tensor) -> torch.Tensor:
+        return embedding_tensor.squeeze()                  # ref :120-122 under AAM

@@ -877,9 +877,13 @@ def bn_workspace(M: int, C: int, device) -> torch.Tensor:
     return torch.empty(lib().w2v2_bn_workspace_floats(M, C), dtype=torch.float32, device=device)
 
 
+BN_ACT_NONE, BN_ACT_RELU, BN_ACT_LEAKY = 0, 1, 2     # W2V2_BN_ACT_* (include/w2v2_hip.h); False / True are the first two
+
+
 def bn_fwd(a, lda: int, work, mean_rstd, running, gamma, beta, y, ldy: int, M: int, C: int, eps: float,
-           momentum: float, relu: bool, train: bool) -> None:
-    """BatchNorm1d (optionally on relu(a)): batch statistics + running update (train) or the running statistics."""
+           momentum: float, relu, train: bool) -> None:
+    """BatchNorm1d on act(a) (``relu``: a BN_ACT_* mode, or a bool for none / ReLU): batch statistics + running update
+    (train) or the running statistics."""
     _dev(a, work, mean_rstd, running, gamma, beta, y)
     _lib.check(lib().w2v2_bn_fwd(a.data_ptr(), lda, _p(work), mean_rstd.data_ptr(), _p(running), gamma.data_ptr(),
                                  beta.data_ptr(), y.data_ptr(), ldy, M, C, eps, momentum, int(relu), int(train), dt(a),
@@ -891,7 +895,7 @@ def bn_colsum_rows(M: int, C: int) -> int:
 
 
 def bn_bwd(dy, lddy: int, a, lda: int, mean_rstd, gamma, work, dgamma, dbeta, da, ldda: int, M: int, C: int,
-           relu: bool, colsum_partial=None, dy2=None, lddy2: int = 0) -> None:
+           relu, colsum_partial=None, dy2=None, lddy2: int = 0) -> None:
     """colsum_partial [bn_colsum_rows(M, C), C] f32 (optional): written with the per-row-block column sums of da.
     dy2 (optional, same shape as dy, own row stride): the output gradient is dy + dy2."""
     _dev(dy, a, mean_rstd, gamma, work, dgamma, dbeta, da, colsum_partial, dy2)
@@ -904,6 +908,34 @@ def bn_bwd(dy, lddy: int, a, lda: int, mean_rstd, gamma, work, dgamma, dbeta, da
                                          mean_rstd.data_ptr(), gamma.data_ptr(), work.data_ptr(), dgamma.data_ptr(),
                                          dbeta.data_ptr(), da.data_ptr(), ldda, M, C, int(relu), _p(colsum_partial),
                                          dt(a), stream()), "bn_bwd_sum")
+
+
+STAT_POOL_EPS = 1e-5          # speechbrain StatisticsPooling: added to the std
+
+
+def stat_pool_fwd(x, ldx: int, out, stats, B: int, T: int, C: int, lens=None, eps: float = STAT_POOL_EPS) -> None:
+    """out [B, 2C] = cat(mean_t, std_t unbiased + eps) of the f32 rows x [B * T, C] (row stride ldx); stats [B, 2C] or None:
+    (mean, std) for stat_pool_bwd.  lens (device int32 [B], 2 <= lens[b] <= T): over each utterance's first lens[b] frames."""
+    _dev(x, out, stats, lens)
+    assert x.dtype == out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * 2 * C
+    assert stats is None or (stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == B * 2 * C)
+    if lens is None:
+        _lib.check(lib().w2v2_stat_pool_fwd(x.data_ptr(), ldx, out.data_ptr(), _p(stats), B, T, C, eps, stream()),
+                   "stat_pool_fwd")
+    else:
+        assert lens.dtype == torch.int32 and lens.numel() == B
+        _lib.check(lib().w2v2_stat_pool_fwd_len(x.data_ptr(), ldx, out.data_ptr(), _p(stats), lens.data_ptr(), B, T, C, eps,
+                                                stream()), "stat_pool_fwd_len")
+
+
+def stat_pool_bwd(x, ldx: int, stats, dout, dx, lddx: int, B: int, T: int, C: int) -> None:
+    """dx [B * T, C] (row stride lddx) = dmean / T + dstd (x - mean) / ((T - 1) std), dout [B, 2C] = cat(dmean, dstd); the
+    second term is 0 where std = 0, as in torch."""
+    _dev(x, stats, dout, dx)
+    assert x.dtype == dx.dtype == stats.dtype == dout.dtype == torch.float32
+    assert stats.is_contiguous() and dout.is_contiguous() and stats.numel() == dout.numel() == B * 2 * C
+    _lib.check(lib().w2v2_stat_pool_bwd(x.data_ptr(), ldx, stats.data_ptr(), dout.data_ptr(), dx.data_ptr(), lddx, B, T, C,
+                                        stream()), "stat_pool_bwd")
 
 
 def im2col_reflect(x, ldx: int, col, B: int, T: int, Cin: int, k: int, dilation: int, x2=None, ldx2: int = 0) -> None:
