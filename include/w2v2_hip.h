@@ -166,8 +166,9 @@ int w2v2_tune_wgrad_kernel(int family);
  * Layer 0 of HF:382-419: Conv1d(1->C,k,stride,no bias) + GroupNorm(C groups == per-(b,c) over time,
  * biased var, eps) + GELU(erf)  (HF:302-323).  wav [B,N] f32 -> y [B,L,C] act dtype, channels-last.
  * Two passes, conv recomputed in both so the [B,L,C] pre-norm tensor never touches HBM:
- *   stats: per-block partial {sum, sumsq} -> partial[B][nchunk][C][2] (f32 workspace of
- *          B * w2v2_conv0_workspace_floats() floats), folded in a fixed order (f64) into
+ *   stats: per 128-frame chunk {mean, sum (u - mean)^2} from f64 accumulators -> partial[B][nchunk][C][2] (f32
+ *          workspace of B * w2v2_conv0_workspace_floats() floats), combined in a fixed order (f64, pairwise-variance
+ *          update: no E[u^2] - mean^2, exact on a constant waveform) into
  *          mean_rstd[B][C][2] = {mean, 1/sqrt(var+eps)}: deterministic and batch-invariant.
  *   apply: normalise + GELU + store. */
 int w2v2_conv0_workspace_floats(int N, int C, int k, int stride);

@@ -1,11 +1,18 @@
 // conv0.hip -- layer 0 of the wav2vec2 feature encoder (HF:302-323, HF:382-419):
 // Conv1d(1 -> C, k=10, stride=5, no bias) + GroupNorm(C groups == per-(utterance, channel) statistics
 // over time, biased variance) + GELU(erf), fused so the [B, L, C] pre-norm tensor never exists in HBM:
-//   pass 1 (stats): conv, per-block partial sum / sum-of-squares per (b, chunk, c), then a tiny
-//                   finalize kernel folds the partials in a FIXED order (f64) -> {mean, rstd}:
-//                   bitwise deterministic and independent of the batch an utterance sits in.
-//                   (16-bit activations, k = 10: no convolution at all -- window moments of the waveform,
-//                   see conv0_gram_kernel below.)
+//   pass 1 (stats): conv, then per (b, 128-frame chunk, c) the chunk's MEAN and CENTRED second moment
+//                   sum (u - mean_chunk)^2, both accumulated in f64 and stored as f32; a tiny finalize kernel
+//                   combines the chunks in a FIXED order (f64, the pairwise-variance update: M2 = sum_j M2_j +
+//                   n_j (mean_j - mean)^2) -> {mean, rstd}: bitwise deterministic and independent of the batch
+//                   an utterance sits in.  No E[u^2] - mean^2 anywhere on this route: with f32 sums of u and u^2 the
+//                   f32 rounding of u^2 alone is 2^-24 u^2 against eps = 1e-5, and rstd came out 17 to 29 % off on a
+//                   constant waveform and 1 to 86 % off at one frame (var = 0 must give rstd = 1 / sqrt(eps)), the
+//                   apply pass 1e-4 off per frame on 1 + 0.1 N(0,1); now all within 1e-6 of float64
+//                   (profiles/conv0_parity.txt).
+//                   (16-bit activations, k = 10: no convolution at all -- window moments of the waveform in f64,
+//                   see conv0_gram_kernel below; k != 10: the split-bf16 convolution's moments about its first output per
+//                   workgroup, conv0_mfma_kernel, combined by the same finalize.)
 //   pass 2 (apply): conv again (10 MAC per output, cheaper than a 9.8 MB/utt round trip),
 //                   normalise, GELU, store channels-last in the activation dtype.
 // HBM-bound: algorithmic bytes/utt = 2 x 192 KB waveform reads + L*C*sizeof(T) output (9.83 MB bf16).
@@ -46,19 +53,24 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ wa
 #pragma unroll
     for (int j = 0; j < C0_MAXK; ++j) wr[j] = j < k ? w[c * k + j] : 0.f;
     if constexpr (!APPLY) {
-      float s1 = 0.f, s2 = 0.f;
+      // f64 moments of the chunk's f32 outputs (u * u is exact in f64), left as {mean, sum (u - mean)^2}: what reaches
+      // the f32 partials carries no cancellation, however large the chunk's mean is next to its spread
+      double s1 = 0.0, s2 = 0.0;
       for (int f = 0; f < nf; ++f) {
         const float* xp = xs + f * stride;
         float acc = 0.f;
 #pragma unroll
         for (int j = 0; j < C0_MAXK; ++j)
           if (j < k) acc = fmaf(wr[j], xp[j], acc);
-        s1 += acc;
-        s2 = fmaf(acc, acc, s2);
+        const double a = (double)acc;
+        s1 += a;
+        s2 = fma(a, a, s2);
       }
+      const double m = s1 / (double)nf;
+      const double m2 = s2 - s1 * m;
       float* pt = partial + (((int64_t)b * gridDim.x + blockIdx.x) * C + c) * 2;
-      pt[0] = s1;
-      pt[1] = s2;
+      pt[0] = (float)m;
+      pt[1] = (float)(m2 > 0.0 ? m2 : 0.0);
     } else {
       const float* st = mr + ((int64_t)b * C + c) * 2;
       const float ga = gamma[c] * st[1];
@@ -76,30 +88,33 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ wa
   }
 }
 
-// fold the per-chunk partials of one (b, c) in chunk order (f64) -> {mean, rstd}
-// LEN: the first cdiv(frames[b], C0_FRAMES) partials, divided by frames[b]: the same sums in the same order as on the
-// utterance alone
+// combine the per-partial {mean, centred second moment} of one (b, c) in order (f64) -> {mean, rstd}: partial j holds
+// n_j = min(fpp, L - j * fpp) frames (fpp = C0_FRAMES for the kernel above, C0_FRAMES * C0_CPB for the matrix-core
+// statistics below), mean = sum n_j mean_j / L, var = (sum M2_j + n_j (mean_j - mean)^2) / L
+// LEN: the first cdiv(frames[b], fpp) partials with L = frames[b]: the same sums in the same order as on the utterance
+// alone
 template <bool LEN>
 __global__ void conv0_finalize_kernel(const float* __restrict__ partial, float* __restrict__ mr, int B, int C,
-                                      int nchunk, int L, float eps, LensArg<LEN> frames) {
+                                      int npart, int fpp, int L, float eps, LensArg<LEN> frames) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * C) return;
   const int b = i / C, c = i - b * C;
-  int nc = nchunk;
+  int np = npart;
   if constexpr (LEN) {
     L = frames[b];
-    nc = (L + C0_FRAMES - 1) / C0_FRAMES;
+    np = (L + fpp - 1) / fpp;
   }
-  double s1 = 0.0, s2 = 0.0;
-  for (int j = 0; j < nc; ++j) {
-    const float* pt = partial + (((int64_t)b * nchunk + j) * C + c) * 2;
-    s1 += (double)pt[0];
-    s2 += (double)pt[1];
-  }
+  const float* pt = partial + ((int64_t)b * npart * C + c) * 2;
+  double s1 = 0.0;
+  for (int j = 0; j < np; ++j) s1 += (double)min(fpp, L - j * fpp) * (double)pt[(int64_t)j * C * 2];
   const double mu = s1 / (double)L;
-  const double var = s2 / (double)L - mu * mu;
+  double m2 = 0.0;
+  for (int j = 0; j < np; ++j) {
+    const double d = (double)pt[(int64_t)j * C * 2] - mu;
+    m2 += (double)pt[(int64_t)j * C * 2 + 1] + (double)min(fpp, L - j * fpp) * d * d;
+  }
   mr[(int64_t)i * 2] = (float)mu;
-  mr[(int64_t)i * 2 + 1] = (float)(1.0 / sqrt((var > 0.0 ? var : 0.0) + (double)eps));
+  mr[(int64_t)i * 2 + 1] = (float)(1.0 / sqrt(m2 / (double)L + (double)eps));
 }
 
 // ------------------------------------------------------------------------------ matrix-core variant (bf16 activations)
@@ -183,10 +198,13 @@ __global__ __launch_bounds__(CW == 64 ? 512 : 256, CW == 64 ? 4 : 2) void conv0_
         if ((q & 3) == 3) __builtin_amdgcn_sched_barrier(0);
       }
     }
-    float s1[NQ], s2[NQ];
+    // statistics: sums of u - pv and (u - pv)^2, pv = the channel's output at the workgroup's first frame.  Sums of u
+    // and u^2 themselves lose var = E[u^2] - mean^2 to the f32 rounding of u^2 as soon as |mean| >> the spread (one frame:
+    // var must be 0 and came out as 2^-24 u^2, 2 % of eps at |u| = 2); about a sample of the data nothing cancels
+    float s1[NQ], s2[NQ], pv[NQ];
     if constexpr (!APPLY) {
 #pragma unroll
-      for (int q = 0; q < NQ; ++q) { s1[q] = 0.f; s2[q] = 0.f; }
+      for (int q = 0; q < NQ; ++q) { s1[q] = 0.f; s2[q] = 0.f; pv[q] = 0.f; }
     }
 #pragma unroll 1
     for (int chunk = chunk0; chunk < chunk1; ++chunk) {
@@ -242,11 +260,15 @@ __global__ __launch_bounds__(CW == 64 ? 512 : 256, CW == 64 ? 4 : 2) void conv0_
             if (fa + 8 < nf) store16_wt(dst + (int64_t)8 * C + u * 64, db);
           }
         } else {
+          const bool first = chunk == chunk0 && f0 == 0;       // uniform: frame row 0 holds the workgroup's first frame
+          const bool valid = f0 + r < nf;                      // rows past the last frame hold u = 0, not a sample
 #pragma unroll
           for (int q = 0; q < NQ; ++q) {
             const float u = acc[q >> 2][q & 3];
-            s1[q] += u;
-            s2[q] = fmaf(u, u, s2[q]);
+            if (first) pv[q] = __shfl(u, lane & 48, 64);       // row 0 of this lane's channel quad
+            const float d = valid ? u - pv[q] : 0.f;
+            s1[q] += d;
+            s2[q] = fmaf(d, d, s2[q]);
           }
         }
       }
@@ -262,11 +284,14 @@ __global__ __launch_bounds__(CW == 64 ? 512 : 256, CW == 64 ? 4 : 2) void conv0_
         }
       }
       if (r == 0 && active) {
+        // the workgroup's {mean, centred second moment} over its n frames, as conv0_finalize_kernel combines them
+        const float n = (float)(min(L, chunk1 * C0_FRAMES) - chunk0 * C0_FRAMES);
         float* pt = partial + ((int64_t)b * gridDim.x + blockIdx.x) * C * 2;
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
-          pt[2 * chq(q)] = s1[q];
-          pt[2 * chq(q) + 1] = s2[q];
+          const float ms = s1[q] / n;
+          pt[2 * chq(q)] = pv[q] + ms;
+          pt[2 * chq(q) + 1] = fmaxf(fmaf(-s1[q], ms, s2[q]), 0.f);
         }
       }
     }
@@ -389,7 +414,7 @@ static int conv0_stats_launch(const char* name, const float* wav, const float* w
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, N, L, C, k,
                        stride, 0.f, frames);
     hipLaunchKernelGGL(conv0_finalize_kernel<LEN>, dim3((unsigned)cdiv((int64_t)B * C, 256)), dim3(256), 0,
-                       as_stream(stream), partial, mean_rstd, B, C, nchunk, L, eps, frames));
+                       as_stream(stream), partial, mean_rstd, B, C, nchunk, C0_FRAMES, L, eps, frames));
   W2V2_CHECK_LAUNCH(name);
   return 0;
 }
@@ -439,7 +464,7 @@ extern "C" int w2v2_conv0_stats_mfma(const float* wav, const float* w, float* pa
                      (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (bf16_t*)nullptr, N, L, C, k,
                      stride);
   hipLaunchKernelGGL(conv0_finalize_kernel<false>, dim3((unsigned)cdiv((int64_t)B * C, 256)), dim3(256), 0,
-                     as_stream(stream), partial, mean_rstd, B, C, nchunk, L, eps, (const int*)nullptr);
+                     as_stream(stream), partial, mean_rstd, B, C, nchunk, C0_FRAMES * C0_CPB, L, eps, (const int*)nullptr);
   W2V2_CHECK_LAUNCH("conv0_stats_mfma");
   return 0;
 }
