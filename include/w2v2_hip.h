@@ -573,6 +573,55 @@ int w2v2_stat_pool_fwd_len(const float* x, int64_t ldx, float* out, float* stats
 int w2v2_stat_pool_bwd(const float* x, int64_t ldx, const float* stats, const float* dout, float* dx, int64_t lddx, int B,
                        int T, int C, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ wav2spk pieces
+ * ref: src/lightning_modules/speaker/wav2spk.py:116-299, src/layers/temporal_gating.py.  f32 only, channels-last
+ * [B*T][C] activations with a row stride; C, Cin and the row strides are multiples of 4 (one 16-byte vector per thread,
+ * guards per vector).  No atomics, fixed-order reductions: bitwise reproducible.
+ * `lens` (device int32 [B], may be NULL = every utterance has all T frames): the variable-length form of evaluation.
+ * Every stage writes ZEROS into the rows at or past an utterance's own frame count, which is what lets the zero padding
+ * of the next layer's gather fall out by itself; statistics blocks are counted from each utterance's first frame and do
+ * not depend on T, so a row of a padded batch is bit-identical to the utterance run alone.
+ *
+ * Layer 0 (Cin = 1), straight from the waveform x [B] rows of N samples (row stride ldx):
+ *   z[b][t][c] = bias[c] + sum_j w[c][j] * x[b][t * stride + j - pad], zero outside [0, n_b); T = (N + 2 pad - k) / stride + 1.
+ *   lens here are SAMPLE counts n_b: utterance b has (n_b + 2 pad - k) / stride + 1 frames.
+ * _bwd: dw[c][j] += sum_{b,t} dz[b][t][c] * x[b][t * stride + j - pad] through per-workgroup partial rows in `workspace`
+ *   (w2v2_conv1d_first_bwd_workspace_floats of M = B * T rows) folded in block order in double.  No data gradient. */
+int w2v2_conv1d_first(const float* x, int64_t ldx, const float* w, const float* bias, float* z, int64_t ldz, const int* lens,
+                      int B, int N, int T, int C, int k, int stride, int pad, void* stream);
+int w2v2_conv1d_first_bwd_workspace_floats(int M, int C, int k);
+int w2v2_conv1d_first_bwd(const float* x, int64_t ldx, const float* dz, int64_t lddz, float* workspace, float* dw, int B,
+                          int N, int T, int C, int k, int stride, int pad, void* stream);
+/* Zero-padded strided gather: col[(b,t)][j * Cin + c] = x[b][t * stride + j - pad][c] or 0, Tout = (Tin + 2 pad - k) /
+ * stride + 1, col rows contiguous (k * Cin); the convolution is this + a GEMM against the packed [Cout][k][Cin] weight.
+ * col2im_zero is its exact adjoint written as a gather (dx WRITTEN, one writer per element, taps in ascending order). */
+int w2v2_im2col_zero(const float* x, int64_t ldx, float* col, int B, int Tin, int Tout, int Cin, int k, int stride, int pad,
+                     void* stream);
+int w2v2_col2im_zero(const float* dcol, float* dx, int64_t lddx, int B, int Tin, int Tout, int Cin, int k, int stride,
+                     int pad, void* stream);
+/* y = relu(InstanceNorm1d(z)): no affine, no running statistics, biased variance over the frames of each (utterance,
+ * channel).  Two launches per direction: per block of 128 frames the mean and the CENTRED second moment (sums in double:
+ * a large DC component costs the variance nothing and a constant channel gives rstd = eps^-1/2 and y = 0 exactly), then
+ * every workgroup combines the blocks of its utterance in double, in block order, and applies.  mean_rstd [B][C][2] is
+ * written for the backward.  workspace: w2v2_instnorm_workspace_floats f32, shared by both directions.
+ * _bwd: dz = rstd * (g - mean_t g - zhat * mean_t (g * zhat)), g = dy where y > 0 and 0 elsewhere, zhat = (z - mean) * rstd,
+ * from the saved z, y and mean_rstd (training: fixed length only). */
+int w2v2_instnorm_workspace_floats(int B, int T, int C);
+int w2v2_instnorm_relu_fwd(const float* z, int64_t ldz, float* workspace, float* mean_rstd, float* y, int64_t ldy,
+                           const int* lens, int B, int T, int C, float eps, void* stream);
+int w2v2_instnorm_relu_bwd(const float* dy, int64_t lddy, const float* z, int64_t ldz, const float* y, int64_t ldy,
+                           const float* mean_rstd, float* workspace, float* dz, int64_t lddz, int B, int T, int C,
+                           void* stream);
+/* Temporal gate over n contiguous elements (n % 4 == 0): y = sigmoid(p) * x with p = X W^T + b from a GEMM;
+ * backward: dp = dy * x * s (1 - s) and the direct part dx = dy * s in one pass (the caller adds dp W). */
+int w2v2_gate_fwd(const float* p, const float* x, float* y, int64_t n, void* stream);
+int w2v2_gate_bwd(const float* dy, const float* p, const float* x, float* dp, float* dx, int64_t n, void* stream);
+/* y[b][t][c] = act(bias[c] + ((p_0 + p_1) + ... + p_{S-1})[b][t][c]) over contiguous [B][T][C] rows, zeros for t >= lens[b]:
+ * p_s = parts + s * part_stride are the partial products of a convolution whose K range was cut into S chunks (one batched
+ * GEMM), folded in a fixed order; bias may be NULL, relu = 1 applies the aggregator's ReLU; y may be p_0. */
+int w2v2_sum_bias_act_rows(const float* parts, int S, int64_t part_stride, const float* bias, float* y, const int* lens, int B,
+                           int T, int C, int relu, void* stream);
+
 /* ---------------------------------------------------------------------------------------- log-mel filterbank front-end
  * The ECAPA input features from waveforms (the device twin of data/fbank.py + InputNormalizer2D(True), data/pipeline.py;
  * ref: src/data/preprocess/audio_features.py:62-78, input_normalisation.py:44-75).  An utterance of n samples has

@@ -144,6 +144,18 @@ _SIGS = {
     "w2v2_stat_pool_fwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp]),
     "w2v2_stat_pool_fwd_len": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp]),
     "w2v2_stat_pool_bwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp]),
+    "w2v2_conv1d_first": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp] + [c_i32] * 7 + [c_vp]),
+    "w2v2_conv1d_first_bwd_workspace_floats": (c_i32, [c_i32, c_i32, c_i32]),
+    "w2v2_conv1d_first_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp] + [c_i32] * 7 + [c_vp]),
+    "w2v2_im2col_zero": (c_i32, [c_vp, c_i64, c_vp] + [c_i32] * 7 + [c_vp]),
+    "w2v2_col2im_zero": (c_i32, [c_vp, c_vp, c_i64] + [c_i32] * 7 + [c_vp]),
+    "w2v2_instnorm_workspace_floats": (c_i32, [c_i32, c_i32, c_i32]),
+    "w2v2_instnorm_relu_fwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp]),
+    "w2v2_instnorm_relu_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32,
+                                       c_vp]),
+    "w2v2_gate_fwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "w2v2_gate_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "w2v2_sum_bias_act_rows": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "w2v2_fbank_db": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "w2v2_fbank_normalize": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "w2v2_asp_context": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),

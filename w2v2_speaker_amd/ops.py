@@ -1086,6 +1086,132 @@ def act_bwd(dy, y, dx, mode: int) -> None:
     _lib.check(lib().w2v2_act_bwd(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), dy.numel(), mode, stream()), "act_bwd")
 
 
+# ------------------------------------------------------------------------------------------------ wav2spk pieces
+def _f32(*ts) -> None:
+    for t in ts:
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("the wav2spk kernels are f32 only")
+
+
+def _lens(lens, B: int):
+    if lens is None:
+        return None
+    assert lens.dtype == torch.int32 and lens.numel() == B and lens.is_cuda
+    return lens.data_ptr()
+
+
+def conv_out_frames(n: int, k: int, stride: int, pad: int) -> int:
+    """Frames of a zero-padded strided Conv1d over n input frames (0 when the padded input is shorter than the kernel)."""
+    return (n + 2 * pad - k) // stride + 1 if n + 2 * pad >= k else 0
+
+
+def conv1d_first(wav, w, bias, z, ldz: int, k: int, stride: int, pad: int, lens=None) -> None:
+    """z [B * T, C] (row stride ldz) = the Cin = 1 convolution of wav [B, N] with w [C, 1, k] + bias, zero padding;
+    lens (device int32 [B]): SAMPLES per utterance -- samples past them count as zero, rows past the utterance's own
+    frame count are written as zeros."""
+    _dev(wav, w, bias, z, lens)
+    _f32(wav, w, bias, z)
+    B, N = wav.shape
+    assert wav.stride(1) == 1 and w.is_contiguous() and w.numel() == bias.numel() * k
+    _lib.check(lib().w2v2_conv1d_first(wav.data_ptr(), wav.stride(0), w.data_ptr(), bias.data_ptr(), z.data_ptr(), ldz,
+                                       _lens(lens, B), B, N, conv_out_frames(N, k, stride, pad), bias.numel(), k, stride,
+                                       pad, stream()), "conv1d_first")
+
+
+def conv1d_first_bwd_workspace(M: int, C: int, k: int, device) -> torch.Tensor:
+    return torch.empty(lib().w2v2_conv1d_first_bwd_workspace_floats(M, C, k), dtype=torch.float32, device=device)
+
+
+def conv1d_first_bwd(wav, dz, lddz: int, work, dw, k: int, stride: int, pad: int) -> None:
+    """dw [C, 1, k] += sum over the rows of dz [B * T, C] (row stride lddz) times the taps of wav [B, N]; fixed order."""
+    _dev(wav, dz, work, dw)
+    _f32(wav, dz, work, dw)
+    B, N = wav.shape
+    C = dw.shape[0]
+    T = conv_out_frames(N, k, stride, pad)
+    assert wav.stride(1) == 1 and dw.is_contiguous() and dw.numel() == C * k
+    assert work.numel() >= lib().w2v2_conv1d_first_bwd_workspace_floats(B * T, C, k)
+    _lib.check(lib().w2v2_conv1d_first_bwd(wav.data_ptr(), wav.stride(0), dz.data_ptr(), lddz, work.data_ptr(), dw.data_ptr(),
+                                           B, N, T, C, k, stride, pad, stream()), "conv1d_first_bwd")
+
+
+def im2col_zero(x, ldx: int, col, B: int, Tin: int, Cin: int, k: int, stride: int, pad: int) -> None:
+    """col [B * Tout, k * Cin] (tap-major) <- x [B * Tin, Cin] (row stride ldx), zero padding."""
+    _dev(x, col)
+    _f32(x, col)
+    Tout = conv_out_frames(Tin, k, stride, pad)
+    assert col.is_contiguous() and col.numel() >= B * Tout * k * Cin
+    _lib.check(lib().w2v2_im2col_zero(x.data_ptr(), ldx, col.data_ptr(), B, Tin, Tout, Cin, k, stride, pad, stream()),
+               "im2col_zero")
+
+
+def col2im_zero(dcol, dx, lddx: int, B: int, Tin: int, Cin: int, k: int, stride: int, pad: int) -> None:
+    """dx [B * Tin, Cin] (row stride lddx, written) = the adjoint of im2col_zero applied to dcol [B * Tout, k * Cin]."""
+    _dev(dcol, dx)
+    _f32(dcol, dx)
+    Tout = conv_out_frames(Tin, k, stride, pad)
+    assert dcol.is_contiguous() and dcol.numel() >= B * Tout * k * Cin
+    _lib.check(lib().w2v2_col2im_zero(dcol.data_ptr(), dx.data_ptr(), lddx, B, Tin, Tout, Cin, k, stride, pad, stream()),
+               "col2im_zero")
+
+
+INSTNORM_EPS = 1e-5           # torch.nn.InstanceNorm1d default
+
+
+def instnorm_workspace(B: int, T: int, C: int, device) -> torch.Tensor:
+    return torch.empty(lib().w2v2_instnorm_workspace_floats(B, T, C), dtype=torch.float32, device=device)
+
+
+def instnorm_relu_fwd(z, ldz: int, work, mean_rstd, y, ldy: int, B: int, T: int, C: int, lens=None,
+                      eps: float = INSTNORM_EPS) -> None:
+    """y = relu(InstanceNorm1d(z)) over [B * T, C] rows, statistics per (utterance, channel) over time (biased variance);
+    mean_rstd [B, C, 2] written.  lens (device int32 [B]): frames per utterance; rows past them are written as zeros."""
+    _dev(z, work, mean_rstd, y, lens)
+    _f32(z, work, mean_rstd, y)
+    assert mean_rstd.is_contiguous() and mean_rstd.numel() == B * C * 2
+    assert work.numel() >= lib().w2v2_instnorm_workspace_floats(B, T, C)
+    _lib.check(lib().w2v2_instnorm_relu_fwd(z.data_ptr(), ldz, work.data_ptr(), mean_rstd.data_ptr(), y.data_ptr(), ldy,
+                                            _lens(lens, B), B, T, C, eps, stream()), "instnorm_relu_fwd")
+
+
+def instnorm_relu_bwd(dy, lddy: int, z, ldz: int, y, ldy: int, mean_rstd, work, dz, lddz: int, B: int, T: int,
+                      C: int) -> None:
+    """dz = the gradient of instnorm_relu_fwd's input from dy, the saved z, y and mean_rstd."""
+    _dev(dy, z, y, mean_rstd, work, dz)
+    _f32(dy, z, y, mean_rstd, work, dz)
+    assert mean_rstd.is_contiguous() and mean_rstd.numel() == B * C * 2
+    assert work.numel() >= lib().w2v2_instnorm_workspace_floats(B, T, C)
+    _lib.check(lib().w2v2_instnorm_relu_bwd(dy.data_ptr(), lddy, z.data_ptr(), ldz, y.data_ptr(), ldy, mean_rstd.data_ptr(),
+                                            work.data_ptr(), dz.data_ptr(), lddz, B, T, C, stream()), "instnorm_relu_bwd")
+
+
+def gate_fwd(p, x, y) -> None:
+    """y = sigmoid(p) * x (contiguous f32 tensors of one shape)."""
+    _dev(p, x, y)
+    _f32(p, x, y)
+    assert p.is_contiguous() and x.is_contiguous() and y.is_contiguous() and p.numel() == x.numel() == y.numel()
+    _lib.check(lib().w2v2_gate_fwd(p.data_ptr(), x.data_ptr(), y.data_ptr(), x.numel(), stream()), "gate_fwd")
+
+
+def gate_bwd(dy, p, x, dp, dx) -> None:
+    """dp = dy * x * s (1 - s), dx = dy * s with s = sigmoid(p)."""
+    _dev(dy, p, x, dp, dx)
+    _f32(dy, p, x, dp, dx)
+    assert all(t.is_contiguous() and t.numel() == x.numel() for t in (dy, p, x, dp, dx))
+    _lib.check(lib().w2v2_gate_bwd(dy.data_ptr(), p.data_ptr(), x.data_ptr(), dp.data_ptr(), dx.data_ptr(), x.numel(),
+                                   stream()), "gate_bwd")
+
+
+def sum_bias_act_rows(parts, bias, y, B: int, T: int, C: int, relu: bool, lens=None) -> None:
+    """y [B * T, C] = act(bias + the sum of parts [S, B * T, C] over S, in order); lens (device int32 [B]): zeros in the rows
+    past each utterance's frames.  bias None: none; y may be parts[0]."""
+    _dev(parts, bias, y, lens)
+    _f32(parts, bias, y)
+    assert parts.is_contiguous() and y.is_contiguous() and parts.dim() == 3 and y.numel() == parts[0].numel() == B * T * C
+    _lib.check(lib().w2v2_sum_bias_act_rows(parts.data_ptr(), parts.shape[0], B * T * C, _p(bias), y.data_ptr(), _lens(lens, B),
+                                            B, T, C, int(relu), stream()), "sum_bias_act_rows")
+
+
 def bce_head_fwd_bwd(emb, w, b, label, prob, loss_rows, dlogit, demb, dw, db, B: int, H: int, loss_scale=None) -> None:
     _dev(emb, w, b, label, prob, loss_rows, dlogit, demb, dw, db, loss_scale)
     _lib.check(lib().w2v2_bce_head_fwd_bwd(emb.data_ptr(), w.data_ptr(), b.data_ptr(), label.data_ptr(), prob.data_ptr(),

@@ -6,8 +6,9 @@ wired at src/main.py:323-335): cosine anneal, two phases, pct_start 0.3, div_fac
 from __future__ import annotations
 
 import math
+from collections import Counter
 from dataclasses import dataclass
-from typing import Callable, Tuple
+from typing import Callable, Sequence, Tuple
 
 
 @dataclass
@@ -103,9 +104,29 @@ class LambdaSchedule:
         return self.base_lr * self.fn(step), self.momentum
 
 
+@dataclass
+class MultiStep:
+    """torch ``MultiStepLR`` (ref: config/optim/schedule/schedule_wav2spk.yaml): the lr is multiplied by ``gamma`` at every
+    milestone (a milestone listed n times: by gamma ** n), one factor after the other as torch's chained form does, so the
+    values agree with the torch scheduler to the last bit; the second value (Adam's beta1 / SGD's momentum) is not cycled."""
+    base_lr: float
+    milestones: Sequence[int]
+    gamma: float = 0.1
+    momentum: float = 0.9
+
+    def at(self, step: int) -> Tuple[float, float]:
+        """(lr, beta1) used by optimiser step number ``step`` (0-based)."""
+        lr = self.base_lr
+        count = Counter(int(m) for m in self.milestones)
+        for m in sorted(count):
+            if m <= step:
+                lr = lr * self.gamma ** count[m]
+        return lr, self.momentum
+
+
 def from_torch_scheduler(sched):
-    """A ``torch.optim.lr_scheduler.OneCycleLR`` -> ``OneCycle``, a ``LambdaLR`` -> ``LambdaSchedule`` (what the
-    reference's config/optim/schedule/{one_cycle,tri_stage}.yaml instantiate).  ``.at(step)`` of the result is the lr
+    """A ``torch.optim.lr_scheduler.OneCycleLR`` -> ``OneCycle``, a ``LambdaLR`` -> ``LambdaSchedule``, a ``MultiStepLR`` ->
+    ``MultiStep`` (what the reference's config/optim/schedule/{one_cycle,tri_stage,schedule_wav2spk}.yaml instantiate).  ``.at(step)`` of the result is the lr
     and beta1 / momentum the torch scheduler leaves in the param group after ``step`` calls of ``scheduler.step()``.
     Read from the scheduler's attributes and its optimiser's first param group; anything else raises."""
     from torch.optim import lr_scheduler as L
@@ -127,4 +148,6 @@ def from_torch_scheduler(sched):
                         base_momentum=base, max_momentum=top)
     if isinstance(sched, L.LambdaLR):
         return LambdaSchedule(sched.base_lrs[0], sched.lr_lambdas[0], own)
-    raise NotImplementedError(f"scheduler class {type(sched).__name__}: only OneCycleLR and LambdaLR are mapped")
+    if isinstance(sched, L.MultiStepLR):
+        return MultiStep(sched.base_lrs[0], sorted(sched.milestones.elements()), sched.gamma, own)
+    raise NotImplementedError(f"scheduler class {type(sched).__name__}: only OneCycleLR, LambdaLR and MultiStepLR are mapped")
