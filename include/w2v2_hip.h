@@ -496,6 +496,30 @@ int w2v2_ctc_fwd_bwd(const float* logits, int64_t ldc, const int64_t* targets, i
                      void* dlogits, const float* loss_scale, float* workspace, int64_t workspace_floats, int B, int T, int C,
                      int dtype, void* stream);
 
+/* The same loss for transcripts (ref: src/lightning_modules/speech/speech_recognition_module.py:100-116): the contract
+ * of w2v2_ctc_fwd_bwd word for word, with 0 <= target_width <= 1023.  The lattice of one utterance is one workgroup of
+ * 64 ... 1024 threads (the smallest with target_width + 1 threads), thread j owning the blank state 2j and the label
+ * state 2j + 1.  The workspace is laid out differently and is smaller per state (the posterior takes alpha's place, there
+ * is no beta): at least w2v2_ctc_long_workspace_floats(B, T, target_width) elements (-1: bad arguments), 16-byte
+ * aligned.  A bad row's part of the workspace is left as it was, apart from its status.  Three launches (two when
+ * forward only).  w2v2_ctc_long_stage_frames: the number of frames whose emissions the lattice stages in LDS at a time
+ * at this width (-1: bad width); the tests put utterance lengths around it. */
+int64_t w2v2_ctc_long_workspace_floats(int B, int T, int target_width);
+int w2v2_ctc_long_stage_frames(int target_width);
+int w2v2_ctc_long_fwd_bwd(const float* logits, int64_t ldc, const int64_t* targets, int64_t target_stride, int target_width,
+                          int target_offset, const int* input_lengths, const int* target_lengths, int blank,
+                          float* loss_rows, void* dlogits, const float* loss_scale, float* workspace,
+                          int64_t workspace_floats, int B, int T, int C, int dtype, void* stream);
+
+/* Greedy CTC decoding (ref: speech_recognition_module.py:233-248, one argmax and one host synchronisation per utterance
+ * there).  logits [B*T][ldc] f32 as above; per utterance b the argmax over c < C of every frame t < input_lengths[b] (the
+ * lowest index wins a tie), runs of equal indices collapsed, THEN the blank dropped (`a a _ a` decodes to `a a`).
+ * tokens_out int32 [B][T]: the first counts_out[b] entries of row b are the result in frame order, the rest is not
+ * written; counts_out int32 [B] (-1 for an input length outside [0, T], of which nothing is read).  One launch, no
+ * atomics; the caller copies tokens and counts to the host once per batch. */
+int w2v2_ctc_greedy_decode(const float* logits, int64_t ldc, const int* input_lengths, int blank, int B, int T, int C,
+                           int* tokens_out, int* counts_out, void* stream);
+
 /* ------------------------------------------------------------------------------ ECAPA-TDNN pieces
  * ref: src/lightning_modules/speaker/ecapa_tdnn.py:75-85 -> speechbrain 0.5.x ECAPA_TDNN (not part of the reference
  * tree; restated in oracle/ecapa_oracle.py).  Channels-last [B*T][C] activations; `ld*` = row stride in elements so

@@ -118,6 +118,11 @@ _SIGS = {
     "w2v2_ctc_workspace_floats": (c_i64, [c_i32, c_i32, c_i32]),
     "w2v2_ctc_fwd_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,
                                  c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "w2v2_ctc_long_workspace_floats": (c_i64, [c_i32, c_i32, c_i32]),
+    "w2v2_ctc_long_stage_frames": (c_i32, [c_i32]),
+    "w2v2_ctc_long_fwd_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                      c_i64, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "w2v2_ctc_greedy_decode": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "w2v2_bn_workspace_floats": (c_i32, [c_i32, c_i32]),
     "w2v2_bn_fwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_f32, c_i32,
                             c_i32, c_i32, c_vp]),

@@ -8,9 +8,10 @@ from .loader import DeviceFeeder, ShardDataset
 from .fbank import Fbank, FilterBank
 from .paired import (EvaluationPair, PairedBatchProcessor, PairedSpeakerClassificationDataSample,
                      paired_default_collate_fn, read_test_pairs_file)
+from .speech import SpeechRecognitionDataBatch, SpeechRecognitionDataSample, speech_collate_fn
 
 __all__ = ["AudioChunkSelector", "BatchProcessor", "InputNormalizer2D", "SpeakerClassificationDataSample",
            "default_collate_fn", "find_shards", "iter_shard", "read_meta", "write_shards", "DeviceFeeder",
            "ShardDataset", "Fbank", "FilterBank", "EvaluationPair", "PairedBatchProcessor",
            "PairedSpeakerClassificationDataSample", "paired_default_collate_fn", "read_test_pairs_file",
-           "TripletSpeakerBatchProcessor"]
+           "TripletSpeakerBatchProcessor", "SpeechRecognitionDataBatch", "SpeechRecognitionDataSample", "speech_collate_fn"]

@@ -23,7 +23,7 @@ from .ops import (EPI_ADD, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_GRAD, EPI_GELU
                   WgradGroup)
 from .params import W2V_PREFIX, ParamStore
 
-_SITE = {"featproj": 1, "prologue": 2, "attn": 3, "post_attn": 4, "ffn": 5, "act": 6}
+_SITE = {"featproj": 1, "prologue": 2, "attn": 3, "post_attn": 4, "ffn": 5, "act": 6, "final": 7}
 
 
 def _splitk(m_tiles: int, n_tiles: int, k: int, batch: int = 1) -> int:
@@ -178,8 +178,11 @@ class Plan:
                  aam_margin: float = 0.2, aam_scale: float = 30.0, fused_attention: Optional[bool] = None,
                  seed: int = 7, keep_hidden_states: bool = False, paired: bool = False,
                  sep_token_constant: float = -1.0, encoder_frames: Optional[int] = None,
-                 triplet_margin: float = 1.0, triplet_coef: float = 1.0):
+                 triplet_margin: float = 1.0, triplet_coef: float = 1.0, final_dropout: float = 0.0,
+                 max_target: int = ops.CTC_LONG_MAX_TARGET):
         cfg = store.cfg
+        # the letter head (store.head "letter"): dropout in front of its Linear, the longest transcript it holds
+        self.final_dropout, self.max_target = float(final_dropout), int(max_target)
         self.triplet_margin, self.triplet_coef = float(triplet_margin), float(triplet_coef)
         self.store, self.cfg, self.B, self.N, self.train = store, cfg, batch, n_samples, train
         # paired input (ref: wav2vec2_paired_input.py:163-207): the conv stack and projection run on 2B waveforms (first
@@ -200,6 +203,9 @@ class Plan:
             raise ValueError(f"a training plan of a \"ctc\" store needs pooling=\"none\" (got {pooling!r}): the CTC loss acts "
                              "on the logits of every frame (ref: config/experiment/speaker_wav2vec2_ctc.yaml "
                              "stat_pooling_type: none)")
+        if store.head == "letter" and not self.no_pool:
+            raise ValueError(f"a plan of a \"letter\" store needs pooling=\"none\" (got {pooling!r}): the letter head "
+                             "predicts the vocabulary on every frame (ref: config/experiment/speech_wav2vec2_ctc.yaml)")
         self._rand_idx = 0
         self.cls, self.cls_c = insert_cls_token, cls_token_constant
         self.margin, self.scale = aam_margin, aam_scale
@@ -414,6 +420,16 @@ class Plan:
                                 bias_grad=st.g(f"fc_list.{nh}.0.bias") if self.train else None,
                                 emb=self.fc.x[-1] if self.fc is not None else self.emb, act_dtype=self.adt,
                                 train=self.train, loss_scale=st.scaler)
+        elif st.head == "letter":
+            # ref: config/experiment/speech_wav2vec2_ctc.yaml + wav2vec2_fc_letter.py:65-86: dropout + lm_head on every
+            # frame, the CTC loss against the transcript
+            from .heads import LetterHead
+            W, Bn = "speech_recognition_head.lm_head.weight", "speech_recognition_head.lm_head.bias"
+            self.head = LetterHead(B, T, st.head_in_dim, st.vocab_size, max_target=self.max_target,
+                                   final_dropout=self.final_dropout, w_master=st.p(W), w_operand=st.w(W),
+                                   w_grad=st.g(W) if self.train else None, bias=st.p(Bn),
+                                   bias_grad=st.g(Bn) if self.train else None, emb=self.emb, act_dtype=self.adt,
+                                   train=self.train, loss_scale=st.scaler)
         elif st.head is not None and st.head != "triplet":
             from .heads import ClassifierHead, FcStack
             aam = st.head == "aam"
@@ -1041,14 +1057,29 @@ class Plan:
         return self._asp_cur
 
     # ------------------------------------------------------------------------------------------ head
-    def head_forward_backward(self, label: torch.Tensor, triplets=None):
+    def frames_of(self, sample_counts) -> List[int]:
+        """Encoder frames of utterances of the given sample counts (ref: wav2vec2_fc_letter.py:146
+        ``floor((n - 80) / 320)``, which is the conv stack's output length), on the host."""
+        return [int(math.floor((int(n) - 80) / 320)) for n in sample_counts]
+
+    def head_forward_backward(self, label: torch.Tensor, triplets=None, transcript=None):
         """Loss head on self.emb (hidden FC layers, then heads.ClassifierHead): returns (loss scalar tensor,
         softmax [B,C]); a training plan also leaves d(loss)/d(pooled embedding) in self.demb and the head gradients
         in the flat buffer.  Triplet heads: ``triplets`` = (pos, neg) row indices of every anchor row (None: heads.TripletHead
         draws them from ``label.tolist()``, a host synchronisation); "triplet" returns (loss, None), "triplet_ce" returns
-        (CE + triplet_coef * triplet, softmax) with the sum taken on the device."""
+        (CE + triplet_coef * triplet, softmax) with the sum taken on the device.  The "letter" head: ``transcript`` =
+        (targets [B, width], target lengths [B], sample counts [B]) still on the host (heads.LetterHead uploads them without
+        waiting; ``label`` is not used) -> (loss, None)."""
         if triplets is not None and self.triplet is None:
             raise ValueError(f"triplets were given, but the head is {self.store.head!r}")
+        if (transcript is not None) != (self.store.head == "letter"):
+            raise ValueError(f"a transcript is what the \"letter\" head takes, and all it takes; the head is "
+                             f"{self.store.head!r}")
+        if transcript is not None:
+            # (targets [B, width], target lengths [B], sample counts [B]) on the host: one upload, no wait
+            targets, target_lengths, sample_counts = transcript
+            self.head.set_batch(targets, target_lengths, self.frames_of(sample_counts))
+            return self.head.forward_backward(seed=self._sd("final", 0, self._step))
         if self.store.head == "triplet":
             return self.triplet.forward_backward(label, triplets)
         if self.no_pool and self.store.head != "ctc":    # one prediction per frame: the utterance label for each of its

@@ -167,6 +167,128 @@ class CtcHead(ClassifierHead):
         return loss, None
 
 
+class LetterHead(ClassifierHead):
+    """ref: src/lightning_modules/speech/wav2vec2_fc_letter.py:65-86 (SpeechRecognitionHead: dropout + ``lm_head``) +
+    speech_recognition_module.py:100-116 (the CTC loss against the transcript): CtcHead's sibling over the ``batch *
+    frames`` rows of the no-pooling embedding, with ``classes`` = the vocabulary size, class 0 the blank and the labels
+    taken as they are (``target_offset`` 0).  Transcripts of up to ``max_target`` <= 1023 letters: the kernels of
+    csrc/ctc_long.hip where the step's transcript tensor is wider than 31, the short ones below (the rule of
+    ``CtcLoss(long_targets=True)``).
+
+    A step's transcript [batch, width] int64, its target lengths and the input lengths IN FRAMES travel in one upload
+    through two pinned staging buffers used in turn, the way TripletHead uploads its indices: the host never waits for
+    the step it enqueues.  ``final_dropout`` > 0 in training: the library's dropout kernel in front of the Linear, the
+    same keep-mask (same seed) on d(emb) behind it; 0 launches nothing.  ``decode()`` runs the greedy decoder on the logits
+    the step just produced.  Returns (loss, None)."""
+
+    def __init__(self, batch: int, frames: int, embed_dim: int, classes: int, *, blank: int = 0,
+                 max_target: int = ops.CTC_LONG_MAX_TARGET, final_dropout: float = 0.0, **kw):
+        if not 1 <= max_target <= ops.CTC_LONG_MAX_TARGET:
+            raise ValueError(f"letter head: max_target {max_target} outside [1, {ops.CTC_LONG_MAX_TARGET}]")
+        self.emb_in = kw["emb"]
+        self.p_drop = float(final_dropout) if kw["train"] else 0.0
+        if self.p_drop > 0:
+            kw["emb"] = torch.empty_like(self.emb_in)           # dropout(emb): what the Linear and its weight gradient read
+        super().__init__("ctc", batch * frames, embed_dim, classes, **kw)
+        dev = self.emb.device
+        self.U, self.T, self.blank, self.Wmax, self.width = batch, frames, int(blank), int(max_target), 0
+        self.loss_rows = torch.empty(batch, dtype=torch.float32, device=dev)
+        self.correct = None
+        floats = max(ops.ctc_long_workspace_floats(batch, frames, self.Wmax),
+                     ops.ctc_workspace_floats(batch, frames, min(self.Wmax, ops.CTC_MAX_TARGET)))
+        self.workspace = torch.empty(floats, dtype=torch.float32, device=dev)
+        # one byte image {transcript int64 [U, Wmax] | input lengths int32 [U] | target lengths int32 [U]} on the device
+        # and in two pinned staging buffers: one copy per step
+        nb = batch * self.Wmax * 8
+        self._raw = torch.zeros(nb + 8 * batch, dtype=torch.uint8, device=dev)
+        self.targets, self.in_len, self.tgt_len = self._views(self._raw)
+        self._stage = [torch.zeros(nb + 8 * batch, dtype=torch.uint8, pin_memory=dev.type == "cuda") for _ in range(2)]
+        self._copied = [None, None]
+        self._turn = 0
+        # decoder output {tokens int32 [U, T] | counts int32 [U]}: one buffer, one copy to the host per batch
+        self._dec = torch.zeros(batch * frames + batch, dtype=torch.int32, device=dev)
+        self.tokens, self.counts = self._dec[:batch * frames].view(batch, frames), self._dec[batch * frames:]
+
+    def _views(self, raw: torch.Tensor):
+        U, nb = self.U, self.U * self.Wmax * 8
+        return (raw[:nb].view(torch.int64).view(U, self.Wmax), raw[nb:nb + 4 * U].view(torch.int32),
+                raw[nb + 4 * U:].view(torch.int32))
+
+    def set_batch(self, transcript: torch.Tensor, target_lengths, input_frames) -> None:
+        """transcript [U, width] integer host tensor (right-padded), target_lengths [U] and input_frames [U] (frames of
+        each utterance, at most ``frames``) host sequences or tensors.  Validated here, on the host."""
+        U = self.U
+        transcript = torch.as_tensor(transcript).to("cpu", torch.int64)
+        if transcript.dim() == 1:
+            transcript = transcript[None]
+        tl = [int(v) for v in (target_lengths.tolist() if hasattr(target_lengths, "tolist") else target_lengths)]
+        fl = [int(v) for v in (input_frames.tolist() if hasattr(input_frames, "tolist") else input_frames)]
+        if transcript.dim() != 2 or transcript.shape[0] != U or len(tl) != U or len(fl) != U:
+            raise ValueError(f"letter head: a transcript [{U}, width] with {U} target and {U} input lengths is needed, got "
+                             f"{tuple(transcript.shape)}, {len(tl)} and {len(fl)}")
+        width = int(transcript.shape[1])
+        if max(tl) > self.Wmax:
+            raise ValueError(f"letter head: a transcript of {max(tl)} labels; at most {self.Wmax} per utterance are built")
+        width = min(width, self.Wmax)                      # (columns past the longest transcript are padding)
+        if min(tl) < 0 or max(tl) > width:
+            raise ValueError(f"letter head: target lengths must lie in [0, {width}]")
+        if min(fl) < 0 or max(fl) > self.T:
+            raise ValueError(f"letter head: input lengths must lie in [0, {self.T}] frames")
+        t = self._turn
+        self._turn = 1 - t
+        if self._copied[t] is not None:
+            self._copied[t].synchronize()     # the upload of two steps ago has left this staging buffer
+        tg, il, tgl = self._views(self._stage[t])
+        tg[:, :width] = transcript[:, :width]
+        il.copy_(torch.tensor(fl, dtype=torch.int32))
+        tgl.copy_(torch.tensor(tl, dtype=torch.int32))
+        self._raw.copy_(self._stage[t], non_blocking=True)
+        if self._stage[t].is_pinned():
+            self._copied[t] = torch.cuda.Event()
+            self._copied[t].record()
+        self.width = width
+
+    def forward_backward(self, label: Optional[torch.Tensor] = None, seed: int = 0):
+        """On what ``set_batch`` uploaded (``label`` is not used) -> (loss, None).  ``seed``: the dropout stream key."""
+        tr = self.train
+        if self.p_drop > 0:
+            ops.dropout(self.emb_in, self.emb, self.p_drop, seed)
+        self._forward_logits()
+        long = self.width > ops.CTC_MAX_TARGET
+        (ops.ctc_long_fwd_bwd if long else ops.ctc_fwd_bwd)(
+            self.logits, self.targets if self.width else None, self.in_len, self.tgt_len, self.loss_rows,
+            self.dcos_w if tr else None, self.workspace, self.U, self.T, self.C, self.ldc, target_width=self.width,
+            target_stride=self.Wmax, target_offset=0, blank=self.blank, loss_scale=self.loss_scale if tr else None)
+        loss = torch.empty((), dtype=torch.float32, device=self.loss_rows.device)
+        ops.mean(self.loss_rows, loss)
+        if tr:
+            self._backward_from_dlogits()
+            if self.p_drop > 0:
+                ops.dropout_(self.demb, self.p_drop, seed)
+        return loss, None
+
+    def forward_only(self, input_frames) -> None:
+        """The logits of the current embedding without a loss (test_step): uploads the input lengths for ``decode()``."""
+        self.set_batch(torch.zeros(self.U, 0, dtype=torch.int64), [0] * self.U, input_frames)
+        if self.p_drop > 0:
+            raise RuntimeError("letter head: forward_only is the evaluation path; a training head with final_dropout "
+                               "draws its mask in forward_backward")
+        self._forward_logits()
+
+    def decode(self):
+        """Greedy decoding of the current logits over each utterance's input length -> (tokens int32 [U, T], counts int32
+        [U]) on the device: views of ONE buffer, ``decoded()`` copies it to the host once."""
+        ops.ctc_greedy_decode(self.logits, self.in_len, self.tokens, self.counts, self.U, self.T, self.C, self.ldc,
+                              blank=self.blank)
+        return self.tokens, self.counts
+
+    def decoded(self):
+        """decode() and the one device-to-host copy of the batch -> (tokens [U, T], counts [U]) host tensors."""
+        self.decode()
+        host = self._dec.cpu()
+        return host[:self.U * self.T].view(self.U, self.T), host[self.U * self.T:]
+
+
 class BceHead:
     """ref: wav2vec2_paired_input.py:200-206 + binary_cross_entropy.py:24-40: Linear(H -> 1) on the CLS token,
     BCE-with-logits (mean over pairs), prediction = sigmoid(logit).  Same interface as ClassifierHead."""

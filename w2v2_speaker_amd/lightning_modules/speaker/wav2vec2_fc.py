@@ -54,6 +54,40 @@ def _load_checkpoint_file(path: str, trust_pickle: bool):
         return torch.load(path, map_location="cpu", weights_only=False)
 
 
+def restore_from_checkpoint(cls, checkpoint_path: str, strict: bool, kwargs: dict):
+    """``load_from_checkpoint`` of the modules over a ParamStore (Wav2vec2FCModule, Wav2vec2FcLetterRecognizer): construct
+    from the reference's kwargs, load ``checkpoint["state_dict"]``, resume counters, loss scale and optimiser state."""
+    kwargs_trusted = bool(kwargs.pop("trust_checkpoint_pickle", False))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")              # weights come from the checkpoint, not from "pretrained"
+        module = cls(**kwargs)
+    ckpt = _load_checkpoint_file(checkpoint_path, kwargs_trusted)
+    sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
+    if not strict:
+        shapes = module.store.shapes
+        canon = lambda k: next((k[: -len(o)] + n for o, n in _WN_LEGACY.items() if k.endswith(o)), k)
+        sd = {k: v for k, v in sd.items() if canon(k) not in shapes or tuple(v.shape) == tuple(shapes[canon(k)])}
+    module.load_state_dict(sd, strict=strict)
+    if isinstance(ckpt, dict):
+        module.schedule_step = int(ckpt.get("global_step", 0))
+        fs = ckpt.get("w2v2_amd") or ckpt.get("freeze_schedule") or {}
+        module.steps = int(fs.get("steps", module.schedule_step))
+        module._is_wav2vec_frozen = bool(fs.get("is_wav2vec_frozen", False))
+        if module.store.scaler is not None and fs.get("loss_scaler") is not None:
+            rec = torch.as_tensor(fs["loss_scaler"]).to(module.store.device, torch.float32).reshape(-1)
+            module.store.scaler[:min(rec.numel(), module.store.scaler.numel())] = rec[:module.store.scaler.numel()]
+        for ost in ckpt.get("optimizer_states") or []:
+            try:
+                if "param_groups" in ost:             # torch Adam / SGD state_dict() (reference parameter order)
+                    module.store.load_torch_optimizer_state(ost)
+                else:                                 # round-2 files: flat moment arenas
+                    module.store.load_optimizer_state(ost)
+            except (ValueError, IndexError):
+                if strict:
+                    raise
+    return module
+
+
 MAX_PLANS = 8      # static plans kept per module (LRU): evaluation over variable-length utterances builds one per length
 MAX_BUCKET_PLANS = 12     # plans of compute_speaker_embeddings' length buckets (their own LRU, one per bucket shape)
 
@@ -560,32 +594,4 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
         missing ones keep their fresh initialisation.  Optimiser moments, the loss scale and the schedule position
         resume when the checkpoint has them and the arena still has the same size."""
         kwargs.setdefault("hyperparameters_to_save", None)
-        kwargs_trusted = bool(kwargs.pop("trust_checkpoint_pickle", False))
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")              # weights come from the checkpoint, not from "pretrained"
-            module = cls(**kwargs)
-        ckpt = _load_checkpoint_file(checkpoint_path, kwargs_trusted)
-        sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
-        if not strict:
-            shapes = module.store.shapes
-            canon = lambda k: next((k[: -len(o)] + n for o, n in _WN_LEGACY.items() if k.endswith(o)), k)
-            sd = {k: v for k, v in sd.items() if canon(k) not in shapes or tuple(v.shape) == tuple(shapes[canon(k)])}
-        module.load_state_dict(sd, strict=strict)
-        if isinstance(ckpt, dict):
-            module.schedule_step = int(ckpt.get("global_step", 0))
-            fs = ckpt.get("w2v2_amd") or ckpt.get("freeze_schedule") or {}
-            module.steps = int(fs.get("steps", module.schedule_step))
-            module._is_wav2vec_frozen = bool(fs.get("is_wav2vec_frozen", False))
-            if module.store.scaler is not None and fs.get("loss_scaler") is not None:
-                rec = torch.as_tensor(fs["loss_scaler"]).to(module.store.device, torch.float32).reshape(-1)
-                module.store.scaler[:min(rec.numel(), module.store.scaler.numel())] = rec[:module.store.scaler.numel()]
-            for ost in ckpt.get("optimizer_states") or []:
-                try:
-                    if "param_groups" in ost:             # torch Adam / SGD state_dict() (reference parameter order)
-                        module.store.load_torch_optimizer_state(ost)
-                    else:                                 # round-2 files: flat moment arenas
-                        module.store.load_optimizer_state(ost)
-                except (ValueError, IndexError):
-                    if strict:
-                        raise
-        return module
+        return restore_from_checkpoint(cls, checkpoint_path, strict, kwargs)

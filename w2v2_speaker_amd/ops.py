@@ -432,6 +432,13 @@ def dropout_(x: torch.Tensor, p: float, seed: int) -> None:
     _lib.check(lib().w2v2_dropout(x.data_ptr(), x.data_ptr(), x.numel(), p, seed, dt(x), stream()), "dropout")
 
 
+def dropout(x: torch.Tensor, y: torch.Tensor, p: float, seed: int) -> None:
+    """y = dropout(x): the kernel and keep-mask of ``dropout_``, written to another tensor of the same type and size."""
+    _dev(x, y)
+    assert x.dtype == y.dtype and x.numel() == y.numel() and x.is_contiguous() and y.is_contiguous()
+    _lib.check(lib().w2v2_dropout(x.data_ptr(), y.data_ptr(), x.numel(), p, seed, dt(x), stream()), "dropout")
+
+
 def gelu_bwd(dy, pre, dx) -> None:
     _dev(dy, pre, dx)
     _lib.check(lib().w2v2_gelu_bwd(dy.data_ptr(), pre.data_ptr(), dx.data_ptr(), dy.numel(), dt(dy), stream()),
@@ -1273,3 +1280,63 @@ def ctc_fwd_bwd(logits, targets, input_lengths, target_lengths, loss_rows, dlogi
                                       input_lengths.data_ptr(), target_lengths.data_ptr(), blank, loss_rows.data_ptr(),
                                       _p(dlogits), _p(loss_scale), workspace.data_ptr(), workspace.numel(), B, T, C,
                                       dt(dlogits) if dlogits is not None else F32, stream()), "ctc")
+
+
+CTC_LONG_MAX_TARGET = 1023      # labels per utterance of the long form: L + 1 <= 1024 threads of one workgroup (csrc/ctc_long.hip)
+
+
+def ctc_long_workspace_floats(B: int, T: int, target_width: int) -> int:
+    n = lib().w2v2_ctc_long_workspace_floats(B, T, target_width)
+    if n < 0:
+        raise ValueError(f"ctc_long: no workspace for B = {B}, T = {T}, target width {target_width} "
+                         f"(at most {CTC_LONG_MAX_TARGET} labels per utterance)")
+    return int(n)
+
+
+def ctc_long_stage_frames(target_width: int) -> int:
+    """Frames whose emissions the long lattice kernel stages in LDS at a time at this target width."""
+    n = lib().w2v2_ctc_long_stage_frames(target_width)
+    if n < 0:
+        raise ValueError(f"ctc_long: target width {target_width} (at most {CTC_LONG_MAX_TARGET} labels per utterance)")
+    return int(n)
+
+
+def ctc_long_fwd_bwd(logits, targets, input_lengths, target_lengths, loss_rows, dlogits, workspace, B: int, T: int, C: int,
+                     ldc: int, *, target_width: int, target_stride: Optional[int] = None, target_offset: int = 0,
+                     blank: int = 0, loss_scale=None) -> None:
+    """``ctc_fwd_bwd`` for transcripts (w2v2_ctc_long_fwd_bwd): the same arguments and results with up to 1023 labels per
+    utterance; workspace: f32, ``ctc_long_workspace_floats(B, T, target_width)`` elements."""
+    _dev(logits, targets, input_lengths, target_lengths, loss_rows, dlogits, workspace, loss_scale)
+    if not 0 <= target_width <= CTC_LONG_MAX_TARGET:
+        raise ValueError(f"ctc_long: targets of width {target_width}; at most {CTC_LONG_MAX_TARGET} labels per utterance "
+                         "are built")
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() >= B * T * ldc and ldc >= C
+    assert targets is None or (targets.dtype == torch.int64 and targets.stride(-1) == 1)
+    assert input_lengths.dtype == torch.int32 and target_lengths.dtype == torch.int32
+    assert input_lengths.numel() == B and target_lengths.numel() == B and loss_rows.numel() >= B
+    assert input_lengths.is_contiguous() and target_lengths.is_contiguous() and loss_rows.dtype == torch.float32
+    assert workspace.dtype == torch.float32 and workspace.is_contiguous()
+    assert dlogits is None or (dlogits.is_contiguous() and dlogits.numel() >= B * T * ldc)
+    if target_stride is None:
+        target_stride = target_width if targets is None or targets.dim() < 2 else targets.stride(0)
+    assert targets is None or target_width == 0 or targets.numel() >= (B - 1) * target_stride + target_width
+    _lib.check(lib().w2v2_ctc_long_fwd_bwd(logits.data_ptr(), ldc, _p(targets), target_stride, target_width, target_offset,
+                                           input_lengths.data_ptr(), target_lengths.data_ptr(), blank,
+                                           loss_rows.data_ptr(), _p(dlogits), _p(loss_scale), workspace.data_ptr(),
+                                           workspace.numel(), B, T, C, dt(dlogits) if dlogits is not None else F32,
+                                           stream()), "ctc_long")
+
+
+def ctc_greedy_decode(logits, input_lengths, tokens, counts, B: int, T: int, C: int, ldc: int, *, blank: int = 0) -> None:
+    """Greedy CTC decoding (w2v2_ctc_greedy_decode; ref: speech_recognition_module.py:233-248): logits [B*T, ldc] f32,
+    input_lengths int32 [B] -> tokens int32 [B, T] (the first counts[b] of row b: argmax per frame, runs collapsed, then the
+    blank dropped; the rest is not written) and counts int32 [B].  Everything on the device; one launch."""
+    _dev(logits, input_lengths, tokens, counts)
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() >= B * T * ldc and ldc >= C
+    assert input_lengths.dtype == torch.int32 and input_lengths.is_contiguous() and input_lengths.numel() == B
+    assert tokens.dtype == torch.int32 and tokens.is_contiguous() and tokens.numel() >= B * T
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() >= B
+    if not 0 <= blank < C:
+        raise ValueError(f"ctc_greedy_decode: blank {blank} outside [0, {C})")
+    _lib.check(lib().w2v2_ctc_greedy_decode(logits.data_ptr(), ldc, input_lengths.data_ptr(), blank, B, T, C,
+                                            tokens.data_ptr(), counts.data_ptr(), stream()), "ctc_greedy_decode")

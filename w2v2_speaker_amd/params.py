@@ -205,13 +205,17 @@ class ParamStore(FlatArena):
     def __init__(self, cfg: W2V2Config, device, act_dtype: torch.dtype = torch.bfloat16,
                  head: Optional[str] = "aam", num_speakers: int = 5994, embed_dim: Optional[int] = None,
                  freeze_cnn: bool = True, attentive_pool: bool = False, attention_channels: int = 128,
-                 init_loss_scale: float = 16384.0, two_term_weights: bool = True, hidden_fc: Tuple[int, ...] = ()):
+                 init_loss_scale: float = 16384.0, two_term_weights: bool = True, hidden_fc: Tuple[int, ...] = (),
+                 vocab_size: Optional[int] = None):
         """embed_dim: size of the pooled embedding (statistics-pooling output).  hidden_fc: output sizes of the hidden
         Linear+ReLU layers between pooling and the loss head (ref: wav2vec2_fc.py:185-228 ``hidden_fc_layers_out``);
         the CE head's Linear is fc_list.{len(hidden_fc)}.0, the AAM weight keeps input size embed_dim like the
         reference (wav2vec2_fc.py:212-224)."""
         assert act_dtype in (torch.bfloat16, torch.float16, torch.float32)
-        assert head in (None, "aam", "ce", "bce", "triplet", "triplet_ce", "ctc")
+        assert head in (None, "aam", "ce", "bce", "triplet", "triplet_ce", "ctc", "letter")
+        if (head == "letter") != (vocab_size is not None):
+            raise ValueError("vocab_size is what the \"letter\" head needs, and only that head")
+        self.vocab_size = None if vocab_size is None else int(vocab_size)
         self.cfg, self.act_dtype = cfg, act_dtype
         self.head, self.num_speakers, self.freeze_cnn = head, num_speakers, freeze_cnn
         self.embed_dim = embed_dim if embed_dim is not None else 2 * cfg.hidden_size
@@ -231,6 +235,18 @@ class ParamStore(FlatArena):
             rows = num_speakers + 1 if head == "ctc" else num_speakers
             shapes[f"fc_list.{n}.0.weight"] = (rows, dims[-1])
             shapes[f"fc_list.{n}.0.bias"] = (rows,)
+        if head == "letter":
+            # ref: wav2vec2_fc_letter.py:65-86 -- HF's ``lm_head`` (Linear hidden_size -> vocabulary) on every frame; the CE
+            # head's tensors with ``vocab_size`` rows, without the speaker path's extra row and [100, 0, ...] bias (the
+            # vocabulary holds its own blank, ``<pad>`` = 0)
+            if self.hidden_fc:
+                raise NotImplementedError("letter head: the reference's speech head is dropout + one Linear")
+            if self.vocab_size < 2:
+                raise ValueError(f"letter head: a vocabulary of {self.vocab_size} entries")
+            if embed_dim is None:
+                self.embed_dim = self.head_in_dim = cfg.hidden_size
+            shapes["speech_recognition_head.lm_head.weight"] = (self.vocab_size, self.embed_dim)
+            shapes["speech_recognition_head.lm_head.bias"] = (self.vocab_size,)
         if head == "triplet" and self.hidden_fc:
             raise NotImplementedError("triplet head: the loss acts on the pooled embedding; hidden FC layers would never "
                                       "receive a gradient")
@@ -443,6 +459,7 @@ class ParamStore(FlatArena):
         names += [n for n in self.shapes if n.startswith("stat_pooling.")]
         fc = sorted({int(n.split(".")[1]) for n in self.shapes if n.startswith("fc_list.")})
         names += [f"fc_list.{i}.0.{w}" for i in fc for w in ("weight", "bias")]
+        names += [n for n in self.shapes if n.startswith("speech_recognition_head.")]      # (registered after wav2vec)
         assert sorted(names) == sorted(self.shapes), "reference_parameter_order does not cover the arena"
         return names
 
@@ -584,7 +601,7 @@ class ParamStore(FlatArena):
                 t = torch.zeros(s)
             elif n == "loss_fn.fc_weights":
                 t = torch.randn(s, generator=g) * math.sqrt(2.0 / (s[0] + s[1]))
-            elif n.startswith("fc_list.") and leaf == "weight":       # nn.Linear default: U(-1/sqrt(in), 1/sqrt(in))
+            elif n.startswith(("fc_list.", "speech_recognition_head.")) and leaf == "weight":   # nn.Linear default: U(-1/sqrt(in), 1/sqrt(in))
                 t = (torch.rand(s, generator=g) * 2 - 1) / math.sqrt(s[1])
             elif n.endswith("original1"):
                 t = torch.randn(s, generator=g) * (2.0 * math.sqrt(1.0 / (s[2] * s[1] * self.cfg.num_conv_pos_embedding_groups)))

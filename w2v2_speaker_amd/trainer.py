@@ -189,15 +189,16 @@ class SpeakerTrainer(fused.WindowedTrainer):
                                  getattr(plan.cfg, "mask_feature_min_masks", 0), rng=self._mask_rng)
         return torch.from_numpy(m.astype(np.uint8)).to(plan.dev, non_blocking=True)
 
-    def train_step_frozen_encoder(self, frozen_plan: Plan, wav: torch.Tensor, label: torch.Tensor, triplets=None):
+    def train_step_frozen_encoder(self, frozen_plan: Plan, wav: torch.Tensor, label: torch.Tensor, triplets=None,
+                                  transcript=None):
         """``triplets``: see train_step.  Step while the whole wav2vec2 network is frozen (ref: wav2vec2_fc.py:339-347 + PL ``freeze()`` =
         requires_grad False AND eval mode): eval-mode forward, head forward/backward, Adam on the head only."""
         store = self.store
         if self.accumulate_grad_batches > 1:
-            return self._micro_batch_frozen_encoder(frozen_plan, wav, label, triplets=triplets)
+            return self._micro_batch_frozen_encoder(frozen_plan, wav, label, triplets=triplets, transcript=transcript)
         store.zero_grad()
         frozen_plan.embed(wav, None, (), self.step)
-        loss, softmax = self._head(frozen_plan, label, triplets)
+        loss, softmax = self._head(frozen_plan, label, triplets, transcript)
         self.reducer.bucket_ready("head")
         self.reducer.wait()
         self._optimizer_step(head_only=True)
@@ -206,8 +207,10 @@ class SpeakerTrainer(fused.WindowedTrainer):
 
     def train_step(self, wav: torch.Tensor, label: torch.Tensor, mask: Optional[torch.Tensor] = None,
                    skip_layers: Optional[Sequence[int]] = None, feature_mask: Optional[torch.Tensor] = None,
-                   triplets=None):
+                   triplets=None, transcript=None):
         """ref: speaker_recognition_module.py:207-220 (_train_step_ce_loss) + PL backward/optimizer step.
+        The "letter" head (ref: speech_recognition_module.py:100-116): ``label`` None and ``transcript`` = (targets
+        [B, width], target lengths [B], sample counts [B]) on the host, see Plan.head_forward_backward; returns (loss, None).
         Returns (loss, softmax) as device tensors; no host sync.  Triplet heads (store.head "triplet" / "triplet_ce",
         ref: :269-294): ``triplets`` = (pos, neg), the positive and negative batch row of every row
         (heads.sample_triplets); None lets the head draw them from ``label.tolist()`` (heads.TripletHead, the one place
@@ -222,10 +225,10 @@ class SpeakerTrainer(fused.WindowedTrainer):
         if feature_mask is None:
             feature_mask = self.sample_feature_mask()
         if self.accumulate_grad_batches > 1:
-            return self._micro_batch(wav, label, mask, skip_layers, feature_mask, triplets=triplets)
+            return self._micro_batch(wav, label, mask, skip_layers, feature_mask, triplets=triplets, transcript=transcript)
         store.zero_grad(tuple(skip_layers) if plan.grouped else None)
         plan.embed(wav, mask, skip_layers, self.step, feature_mask)
-        loss, softmax = self._head(plan, label, triplets)
+        loss, softmax = self._head(plan, label, triplets, transcript)
         plan.backward(on_bucket_ready=self.reducer.bucket_ready)
         self.reducer.wait()
         self._optimizer_step()
@@ -239,14 +242,16 @@ class SpeakerTrainer(fused.WindowedTrainer):
     # coefficient, so the clip sees the averaged gradient as torch's clip_grad_norm_ does.  The loss-scale record is only
     # touched by optimizer_step, i.e. constant over a window like torch's GradScaler between update() calls.
     @staticmethod
-    def _head(plan: Plan, label: torch.Tensor, triplets):
+    def _head(plan: Plan, label: torch.Tensor, triplets, transcript=None):
         """The head of every step function.  Without triplets the call is ``head_forward_backward(label)``, the form it
         has always had (callers replace that method with one-argument functions of their own)."""
+        if transcript is not None:
+            return plan.head_forward_backward(label, triplets=triplets, transcript=transcript)
         if triplets is None:
             return plan.head_forward_backward(label)
         return plan.head_forward_backward(label, triplets=triplets)
 
-    def _micro_batch(self, wav, label, mask, skip_layers, feature_mask, triplets=None):
+    def _micro_batch(self, wav, label, mask, skip_layers, feature_mask, triplets=None, transcript=None):
         plan, store, N = self.plan, self.store, self.accumulate_grad_batches
         if store.accum_count > 0 and store.accum_head_only:
             raise RuntimeError("this accumulation window was opened by a frozen-encoder micro-batch; a window cannot mix "
@@ -254,7 +259,7 @@ class SpeakerTrainer(fused.WindowedTrainer):
         last = store.accum_count == N - 1
         store.zero_grad(tuple(skip_layers) if plan.grouped else None)
         plan.embed(wav, mask, skip_layers, self.step * N + store.accum_count, feature_mask)    # a dropout seed per micro-batch
-        loss, softmax = self._head(plan, label, triplets)
+        loss, softmax = self._head(plan, label, triplets, transcript)
         if last and self.world > 1:
             plan.backward(on_bucket_ready=self._accumulate_and_reduce)     # the all-reduce of grad_acc overlaps backward
         else:
@@ -275,7 +280,7 @@ class SpeakerTrainer(fused.WindowedTrainer):
             self.reducer.buffer = self.store.grad_acc
         self.reducer.bucket_ready(name)
 
-    def _micro_batch_frozen_encoder(self, frozen_plan: Plan, wav, label, triplets=None):
+    def _micro_batch_frozen_encoder(self, frozen_plan: Plan, wav, label, triplets=None, transcript=None):
         store, N = self.store, self.accumulate_grad_batches
         if store.accum_count > 0 and not store.accum_head_only:
             raise RuntimeError("this accumulation window was opened by an unfrozen micro-batch; a window cannot mix frozen "
@@ -283,7 +288,7 @@ class SpeakerTrainer(fused.WindowedTrainer):
         last = store.accum_count == N - 1
         store.zero_grad()
         frozen_plan.embed(wav, None, (), self.step * N + store.accum_count)
-        loss, softmax = self._head(frozen_plan, label, triplets)
+        loss, softmax = self._head(frozen_plan, label, triplets, transcript)
         fused.accumulate(store, 0, store.head_size())
         store.accum_count += 1
         store.accum_head_only = True
