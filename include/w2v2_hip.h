@@ -716,6 +716,41 @@ int w2v2_normalize_bwd(const float* g, const void* x, int64_t ldx, const float* 
 int w2v2_aam_dw(const void* dcos_x, int64_t ldc, const void* emb, const float* colprod, const float* W,
                 const float* inv_w, float* dW, int B, int C, int E, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------- trial scoring
+ * The last stage of the speaker path on device buffers: f32 banks with D % 4 == 0 and row stride ld >= D (elements,
+ * ld % 4 == 0, 16-byte aligned base); every row * ld is formed in 64 bits.  No atomics, fixed-order folds: equal inputs
+ * give equal bits.  Nothing is allocated; all work goes on `stream`.
+ *
+ * Per-dimension mean and UNBIASED std over the N rows of bank [N][ld] -> mean_out / std_out [D] (ref:
+ * speaker_recognition_evaluator.py:154-159 compute_mean_std_batch, called by CosineDistanceEvaluator.fit_parameters at
+ * cosine_distance.py:84-97).  Per chunk of 128 rows the mean and the CENTRED second moment, summed in double; the chunks
+ * are combined in double in chunk order (E[x^2] - mean^2 is never formed: a constant dimension gives std exactly 0).
+ * workspace: caller-owned, 2 * ceil(N / 128) * D doubles, 8-byte aligned.  Two launches.  N < 2 is an argument error. */
+int w2v2_embed_stats(const float* bank, int64_t ld, int N, int D, float* mean_out, float* std_out, void* workspace,
+                     void* stream);
+/* Cosine score of P trials over bank [N][ld]; pairs [P][2] int32 (device) names the two rows of each trial (ref:
+ * cosine_distance.py:105-132 _compute_prediction_scores + :235-241 compute_cosine_scores, which stack a left and a right
+ * [P][D] tensor on the host).  One trial per wavefront, one pass over the two rows.  With mean / std [D] (both NULL or both
+ * set) every element is first u = (x - mean) / (std + 1e-12) in f32 (center_batch, speaker_recognition_evaluator.py:162-167);
+ * with length_norm != 0 the rows are rescaled by 1 / max(||u||, 1e-12) (F.normalize; the three sums rescale, no second
+ * pass); then cos = a.b / (max(||a||, 1e-8) * max(||b||, 1e-8)), each norm clamped on its own as torch's
+ * cosine_similarity does.  cos_out [P] = cos, score_out [P] = clamp((cos + 1) / 2, 0, 1) (speaker_recognition_evaluator.py:81).
+ * An index outside [0, N) is not dereferenced: both outputs of that trial are NaN. */
+int w2v2_score_pairs(const float* bank, int64_t ld, int N, int D, const int32_t* pairs /*int32 [P][2]*/, int P,
+                     const float* mean, const float* std /*both null or both set*/, int length_norm, float* cos_out /*[P]*/,
+                     float* score_out /*[P]*/, void* stream);
+/* The non-pooled score (ref: cosine_distance.py:187-232 compute_non_pooled_cosine_scores: per trial two [<= 50][D] frame
+ * tensors, 2500 cosines and their mean, in a Python loop).  frames [rows][ld] is a ragged frame bank; sel [P][2][W] int32
+ * holds ABSOLUTE row numbers, counts [P][2] int32 how many of the W slots of each side are used (1 <= W <= 256).  Uses
+ *   mean_{i,j} cos(l_i, r_j) = < mean_i l_i / max(||l_i||, 1e-8) , mean_j r_j / max(||r_j||, 1e-8) >,
+ * exact because the two norms are clamped separately: count_l + count_r row reads (each row twice) and one D-length dot
+ * per trial.  One workgroup per trial; every wave folds its rows in ascending position, the waves are folded in wave
+ * order; sums in double.  A count outside [1, W] or a selected row outside [0, rows) gives NaN outputs without a frame
+ * read.  No centring and no length norm, as in the reference. */
+int w2v2_score_frame_sets(const float* frames, int64_t ld, int64_t rows, int D,
+                          const int32_t* sel /*int32 [P][2][W]: absolute row numbers*/, const int32_t* counts /*int32 [P][2]*/,
+                          int W, int P, float* cos_out, float* score_out, void* stream);
+
 /* ------------------------------------------------------------------------------------ optimiser
  * torch.optim.Adam (ref: config/optim/algo/adam.yaml, src/main.py:323-335) over one flat f32
  * parameter arena; also refreshes the 16-bit copy (pb_dtype = W2V2_BF16 / W2V2_F16) the GEMMs read

@@ -169,3 +169,45 @@ class CosineDistanceEvaluator:
             print(f"mdc calculation had {e}")
             mdc, mdc_threshold = 1, 1337
         return {"eer": eer, "eer_threshold": eer_threshold, "mdc": mdc, "mdc_threshold": mdc_threshold}
+
+    # ------------------------------------------------------------------ the same evaluation over a bank on the device
+    def fit_parameters_bank(self, bank: torch.Tensor):
+        """``fit_parameters`` for embeddings that are rows of a device ``[N, D]`` bank: mean / std by w2v2_embed_stats,
+        kept on the device."""
+        if not self._using_parameters():
+            return
+        if bank.shape[0] <= 2:
+            raise ValueError("mean/std calculation requires more than 2 samples")
+        from ... import ops
+        self.mean, self.std = ops.embed_stats(bank)
+
+    def evaluate_bank(self, pairs: List[EvaluationPair], keys: List[str], bank, frame_offsets=None):
+        """``evaluate`` without the embeddings leaving the device: ``bank`` is an ``[N, D]`` device tensor whose row r is
+        the embedding of ``keys[r]``, a list of such tensors (an ensemble), or -- with ``frame_offsets`` [N + 1] -- a ragged
+        ``[sum T, D]`` frame bank (the non-pooled form; no centring / length norm there, as in the reference).  Scores are
+        computed by the kernels of csrc/score.hip and one array of P (ensemble of n: n * P) floats is copied to the host;
+        EER / minDCF as in ``evaluate``.  ``last_bank_scoring`` keeps the scores and the copy's size."""
+        from .device_scoring import TrialIndex, score_trials_device
+        index = TrialIndex(pairs, keys)
+        if index.missing is not None:
+            warn(f"{index.missing[0]} or {index.missing[1]} not in sample_map")
+            return {"eer": -1, "eer_threshold": -1, "mdc": -1, "mdc_threshold": -1}
+        centre = self.center_before_scoring and frame_offsets is None
+        if centre and (self.mean is None or self.std is None):
+            raise TypeError("center_before_scoring=True but fit_parameters() has not been called "
+                            "(mean / std are None)")
+        self.last_bank_scoring = score_trials_device(
+            bank, index, mean=self.mean if centre else None, std=self.std if centre else None,
+            length_norm=self.length_norm_before_scoring and frame_offsets is None, frame_offsets=frame_offsets)
+        gt, scores = index.ground_truth, self.last_bank_scoring.scores.tolist()
+        try:
+            eer, eer_threshold = calculate_eer(gt, scores, pos_label=1)
+        except (ValueError, ZeroDivisionError) as e:
+            print(f"EER calculation had {e}")
+            eer, eer_threshold = 1, 1337
+        try:
+            mdc, mdc_threshold = calculate_mdc(gt, scores)
+        except (ValueError, ZeroDivisionError) as e:
+            print(f"mdc calculation had {e}")
+            mdc, mdc_threshold = 1, 1337
+        return {"eer": eer, "eer_threshold": eer_threshold, "mdc": mdc, "mdc_threshold": mdc_threshold}

@@ -1,0 +1,175 @@
+"""Trial scoring on the device (csrc/score.hip): what ``CosineDistanceEvaluator.evaluate_bank`` runs.
+
+The host evaluator (cosine_distance.py, a mirror of the reference) gathers a left and a right ``[P, D]`` tensor on the
+host from one ``EmbeddingSample`` object per utterance.  Here the embeddings stay where the forward left them -- one
+``[N, D]`` bank on the device -- the trial list becomes one ``[P, 2]`` int32 table of bank rows, built and checked once on
+the host, and ``P`` scores come back in one copy.  ROC / EER / minDCF stay on the host (eval_metrics.py)."""
+from __future__ import annotations
+
+import random
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from ... import ops
+
+FRAME_CAP = 50      # frames per side of a non-pooled trial (ref: cosine_distance.py:203-232)
+
+
+def _upload(a: np.ndarray, device) -> torch.Tensor:
+    """Host array -> device tensor through pinned memory (one asynchronous copy on the current stream)."""
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    if torch.device(device).type == "cuda":
+        t = t.pin_memory()
+    return t.to(device, non_blocking=True)
+
+
+class TrialIndex:
+    """A trial list as bank rows.  ``keys[r]`` is the sample id of bank row ``r``; ``pairs`` are the evaluator's
+    ``EvaluationPair``s.  ``table`` is the int32 ``[P, 2]`` array of (row of sample1, row of sample2), ``ground_truth`` the
+    0 / 1 list of ``evaluate``.  A pair that names a key the bank does not hold leaves ``table`` None and ``missing`` set to
+    the two ids (``evaluate`` answers that with a warning and a dict of -1).  Duplicate keys raise, as in ``evaluate``."""
+
+    def __init__(self, pairs, keys: Sequence[str]):
+        self.row_of = {}
+        for r, k in enumerate(keys):
+            if k in self.row_of:
+                raise ValueError(f"duplicate key {k}")
+            self.row_of[k] = r
+        self.num_rows = len(self.row_of)
+        self.missing: Optional[Tuple[str, str]] = None
+        self.ground_truth: List[int] = []
+        rows = []
+        for pair in pairs:
+            if pair.sample1_id not in self.row_of or pair.sample2_id not in self.row_of:
+                self.missing = (pair.sample1_id, pair.sample2_id)
+                break
+            self.ground_truth.append(1 if pair.same_speaker else 0)
+            rows.append((self.row_of[pair.sample1_id], self.row_of[pair.sample2_id]))
+        self.table = None if self.missing else self._checked(rows, self.num_rows)
+        self._device_table = None
+
+    @classmethod
+    def from_rows(cls, rows, ground_truth: Sequence[int], num_rows: int) -> "TrialIndex":
+        """From row numbers directly (a caller that has no string keys); an index outside [0, num_rows) raises."""
+        self = cls.__new__(cls)
+        self.row_of, self.num_rows, self.missing = {}, int(num_rows), None
+        self.ground_truth = [int(g) for g in ground_truth]
+        self.table = cls._checked(rows, self.num_rows)
+        if len(self.ground_truth) != len(self.table):
+            raise ValueError("one ground-truth label per trial")
+        self._device_table = None
+        return self
+
+    @staticmethod
+    def _checked(rows, num_rows: int) -> np.ndarray:
+        t = np.asarray(rows, dtype=np.int64).reshape(-1, 2)
+        if t.shape[0] == 0:
+            raise ValueError("empty trial list")
+        if num_rows > np.iinfo(np.int32).max:
+            raise ValueError(f"{num_rows} bank rows do not fit the int32 trial table")
+        if t.min() < 0 or t.max() >= num_rows:
+            bad = int(np.argmax((t < 0).any(1) | (t >= num_rows).any(1)))
+            raise ValueError(f"trial {bad} names row {tuple(int(v) for v in t[bad])} outside [0, {num_rows})")
+        return t.astype(np.int32)
+
+    def __len__(self) -> int:
+        return 0 if self.table is None else self.table.shape[0]
+
+    def device_table(self, device) -> torch.Tensor:
+        """The table on ``device``, uploaded once."""
+        if self.table is None:
+            raise ValueError(f"{self.missing[0]} or {self.missing[1]} not in the bank")
+        if self._device_table is None or self._device_table.device != torch.device(device):
+            self._device_table = _upload(self.table, device)
+        return self._device_table
+
+
+def draw_frame_sets(frame_counts: Sequence[int], trial_index: TrialIndex, cap: int = FRAME_CAP):
+    """The frame draws of the non-pooled score, as the host evaluator makes them (compute_non_pooled_cosine_scores): per
+    trial, left side then right side, ``random.sample(range(p), min(cap, p))`` on the GLOBAL ``random`` -- a caller who
+    seeds it gets the reference's draws.  ``frame_counts[r]`` = frames of utterance ``r``, whose frames are rows
+    ``offset[r] .. offset[r] + p`` of the ragged frame bank.  -> (sel int32 [P, 2, cap] absolute row numbers, unused slots
+    0; counts int32 [P, 2])."""
+    if not 1 <= cap <= ops.FRAME_SET_MAX_W:
+        raise ValueError(f"cap = {cap} outside [1, {ops.FRAME_SET_MAX_W}]")
+    counts_in = np.asarray(frame_counts, dtype=np.int64)
+    if counts_in.shape != (trial_index.num_rows,) or (counts_in < 1).any():
+        raise ValueError("one positive frame count per bank utterance")
+    offsets = np.concatenate([[0], np.cumsum(counts_in)])
+    if offsets[-1] > np.iinfo(np.int32).max:
+        raise ValueError(f"{int(offsets[-1])} frame rows do not fit the int32 selection table")
+    if trial_index.table is None:
+        raise ValueError(f"{trial_index.missing[0]} or {trial_index.missing[1]} not in the bank")
+    P = len(trial_index)
+    sel = np.zeros((P, 2, cap), dtype=np.int32)
+    counts = np.zeros((P, 2), dtype=np.int32)
+    for t, (l, r) in enumerate(trial_index.table.tolist()):
+        for side, u in ((0, l), (1, r)):
+            p = int(counts_in[u])
+            drawn = random.sample(range(p), min(cap, p))
+            counts[t, side] = len(drawn)
+            sel[t, side, :len(drawn)] = offsets[u] + np.asarray(drawn, dtype=np.int64)
+    return sel, counts
+
+
+@dataclass
+class DeviceScores:
+    """What score_trials_device hands back: ``scores`` float64 [P] in [0, 1] (what ``evaluate`` feeds the metrics),
+    ``host_copy_floats`` the number of floats that crossed to the host (P, or n * P for an ensemble of n),
+    ``bank_floats`` the elements of the bank(s) that stayed on the device."""
+    scores: np.ndarray
+    host_copy_floats: int
+    bank_floats: int
+
+
+def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial_index: TrialIndex, *, mean=None, std=None,
+                        length_norm: bool = False, frame_offsets=None, cap: int = FRAME_CAP) -> DeviceScores:
+    """Score ``trial_index`` over ``bank`` on the device.  bank: an ``[N, D]`` device tensor; a list of those (an
+    ensemble: every member scored into one ``[n, P]`` buffer, combined on the host in the reference's order
+    ``score += s_i * (1 / n)`` as Python floats, ref: cosine_distance.py:172-181); or, with ``frame_offsets`` ([N + 1],
+    utterance r = rows frame_offsets[r] .. frame_offsets[r + 1]), a ragged ``[sum T, D]`` frame bank scored as the
+    non-pooled form (frames drawn by draw_frame_sets from the global ``random``; no centring, no length norm, as in the
+    reference).  One device -> host copy."""
+    members = list(bank) if isinstance(bank, (list, tuple)) else [bank]
+    if not members or not all(isinstance(b, torch.Tensor) for b in members):
+        raise ValueError("bank is a device tensor or a non-empty list of them")
+    dev = members[0].device
+    P = len(trial_index)
+    if frame_offsets is not None:
+        if len(members) != 1:
+            raise ValueError("a frame bank is one tensor")
+        off = np.asarray(torch.as_tensor(frame_offsets).cpu() if isinstance(frame_offsets, torch.Tensor) else frame_offsets,
+                         dtype=np.int64)
+        if off.shape != (trial_index.num_rows + 1,) or off[0] != 0 or off[-1] != members[0].shape[0]:
+            raise ValueError(f"frame_offsets is [N + 1] = [{trial_index.num_rows + 1}], from 0 to the rows of the frame bank")
+        sel, counts = draw_frame_sets(np.diff(off), trial_index, cap)
+        _, score = ops.score_frame_sets(members[0], _upload(sel, dev), _upload(counts, dev))
+        host = score.cpu().numpy()
+        return DeviceScores(host.astype(np.float64), host.size, members[0].numel())
+    table = trial_index.device_table(dev)
+    for b in members:
+        if b.dim() != 2 or b.shape[0] != trial_index.num_rows:
+            raise ValueError(f"bank of shape {tuple(b.shape)}: expected [{trial_index.num_rows}, D]")
+    mean = None if mean is None else mean.to(dev, torch.float32).contiguous()
+    std = None if std is None else std.to(dev, torch.float32).contiguous()
+    n = len(members)
+    cos = torch.empty(n, P, dtype=torch.float32, device=dev)
+    score = torch.empty(n, P, dtype=torch.float32, device=dev)
+    for i, b in enumerate(members):
+        ops.score_pairs(b, table, mean, std, length_norm, cos[i], score[i])
+    bank_floats = sum(b.numel() for b in members)
+    if n == 1:
+        host = score[0].cpu().numpy()
+        return DeviceScores(host.astype(np.float64), host.size, bank_floats)
+    host = cos.cpu().numpy()
+    member_scores = host.tolist()
+    combined = []
+    for idx in range(P):
+        s = 0
+        for i in range(n):                           # same accumulation order as the reference
+            s += member_scores[i][idx] * (1 / n)
+        combined.append(s)
+    return DeviceScores(np.clip((np.array(combined) + 1) / 2, 0, 1), host.size, bank_floats)

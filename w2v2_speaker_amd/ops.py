@@ -1340,3 +1340,99 @@ def ctc_greedy_decode(logits, input_lengths, tokens, counts, B: int, T: int, C: 
         raise ValueError(f"ctc_greedy_decode: blank {blank} outside [0, {C})")
     _lib.check(lib().w2v2_ctc_greedy_decode(logits.data_ptr(), ldc, input_lengths.data_ptr(), blank, B, T, C,
                                             tokens.data_ptr(), counts.data_ptr(), stream()), "ctc_greedy_decode")
+
+
+# ---------------------------------------------------------------------------------------------- trial scoring (score.hip)
+STATS_CHUNK_ROWS = 128      # rows per partial of w2v2_embed_stats (csrc/score.hip ST_ROWS)
+FRAME_SET_MAX_W = 256       # slots per side of w2v2_score_frame_sets (csrc/score.hip FS_MAX_W)
+
+
+def _bank(bank, what: str) -> Tuple[int, int, int]:
+    """(rows, D, ld) of an f32 bank [rows, D] whose rows are ``ld`` elements apart; shape errors first (they need no
+    device), then the device check every op makes."""
+    if not isinstance(bank, torch.Tensor) or bank.dim() != 2 or bank.dtype != torch.float32:
+        raise ValueError(f"{what}: the bank is a 2-D float32 tensor")
+    rows, D = bank.shape
+    ld = bank.stride(0) if rows > 1 else max(bank.stride(0), D)
+    if rows < 1 or D < 4 or D % 4 != 0:
+        raise ValueError(f"{what}: D = {D} must be a positive multiple of 4 (and the bank non-empty)")
+    if bank.stride(1) != 1 or ld < D or ld % 4 != 0 or bank.data_ptr() % 16 != 0:
+        raise ValueError(f"{what}: row stride ld = {ld} must be >= D = {D} and a multiple of 4, features contiguous, "
+                         "base 16-byte aligned")
+    return rows, D, ld
+
+
+def _score_out(t, P: int, device, what: str) -> torch.Tensor:
+    if t is None:
+        return torch.empty(P, dtype=torch.float32, device=device)
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < P:
+        raise ValueError(f"{what}: outputs are contiguous float32 tensors of at least P = {P} elements")
+    return t
+
+
+def embed_stats_workspace(N: int, D: int, device) -> torch.Tensor:
+    return torch.empty(2 * ((N + STATS_CHUNK_ROWS - 1) // STATS_CHUNK_ROWS) * D, dtype=torch.float64, device=device)
+
+
+def embed_stats(bank, mean_out=None, std_out=None, workspace=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-dimension mean and unbiased std of bank [N, D] (w2v2_embed_stats = torch.std_mean(bank, dim=0), the evaluator's
+    compute_mean_std_batch) -> (mean [D], std [D]) on the device.  Two launches, sums in double."""
+    N, D, ld = _bank(bank, "embed_stats")
+    if N < 2:
+        raise ValueError(f"embed_stats: the unbiased std needs N >= 2 rows (got {N})")
+    _dev(bank, mean_out, std_out, workspace)
+    mean_out = _score_out(mean_out, D, bank.device, "embed_stats")
+    std_out = _score_out(std_out, D, bank.device, "embed_stats")
+    if workspace is None:
+        workspace = embed_stats_workspace(N, D, bank.device)
+    need = embed_stats_workspace(N, D, "meta").numel()
+    if workspace.dtype != torch.float64 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"embed_stats: workspace holds {need} float64 (embed_stats_workspace)")
+    _lib.check(lib().w2v2_embed_stats(bank.data_ptr(), ld, N, D, mean_out.data_ptr(), std_out.data_ptr(),
+                                      workspace.data_ptr(), stream()), "embed_stats")
+    return mean_out, std_out
+
+
+def score_pairs(bank, pairs, mean=None, std=None, length_norm: bool = False, cos_out=None,
+                score_out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Cosine score of the trials pairs [P, 2] (device int32 rows of bank [N, D]) -> (cos [P], score [P]) with
+    score = clamp((cos + 1) / 2, 0, 1); mean / std [D] (both or neither): z-score first; length_norm: F.normalize first
+    (w2v2_score_pairs).  The indices are NOT checked here (they are on the device: a trial with an index outside [0, N)
+    comes back NaN); TrialIndex checks a list before it is uploaded."""
+    N, D, ld = _bank(bank, "score_pairs")
+    if (mean is None) != (std is None):
+        raise ValueError("score_pairs: mean and std are given together or not at all")
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 \
+            or pairs.shape[0] < 1 or not pairs.is_contiguous():
+        raise ValueError("score_pairs: pairs is a contiguous int32 [P, 2] tensor, P >= 1")
+    for v in (mean, std):
+        if v is not None and (v.dtype != torch.float32 or v.shape != (D,) or not v.is_contiguous()):
+            raise ValueError(f"score_pairs: mean / std are contiguous float32 [{D}]")
+    _dev(bank, pairs, mean, std, cos_out, score_out)
+    P = pairs.shape[0]
+    cos_out = _score_out(cos_out, P, bank.device, "score_pairs")
+    score_out = _score_out(score_out, P, bank.device, "score_pairs")
+    _lib.check(lib().w2v2_score_pairs(bank.data_ptr(), ld, N, D, pairs.data_ptr(), P, _p(mean), _p(std),
+                                      int(bool(length_norm)), cos_out.data_ptr(), score_out.data_ptr(), stream()),
+               "score_pairs")
+    return cos_out, score_out
+
+
+def score_frame_sets(frames, sel, counts, cos_out=None, score_out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The non-pooled score (w2v2_score_frame_sets): frames [rows, D] a ragged frame bank, sel [P, 2, W] device int32
+    absolute row numbers (left side, right side), counts [P, 2] device int32 the slots used -> (cos [P], score [P]), cos =
+    the mean of all pairwise frame cosines.  A count outside [1, W] or a row outside [0, rows) gives NaN for that trial."""
+    rows, D, ld = _bank(frames, "score_frame_sets")
+    if not isinstance(sel, torch.Tensor) or sel.dtype != torch.int32 or sel.dim() != 3 or sel.shape[1] != 2 \
+            or sel.shape[0] < 1 or not 1 <= sel.shape[2] <= FRAME_SET_MAX_W or not sel.is_contiguous():
+        raise ValueError(f"score_frame_sets: sel is a contiguous int32 [P, 2, W] tensor, 1 <= W <= {FRAME_SET_MAX_W}")
+    P, _, W = sel.shape
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.shape != (P, 2) \
+            or not counts.is_contiguous():
+        raise ValueError(f"score_frame_sets: counts is a contiguous int32 [{P}, 2] tensor")
+    _dev(frames, sel, counts, cos_out, score_out)
+    cos_out = _score_out(cos_out, P, frames.device, "score_frame_sets")
+    score_out = _score_out(score_out, P, frames.device, "score_frame_sets")
+    _lib.check(lib().w2v2_score_frame_sets(frames.data_ptr(), ld, rows, D, sel.data_ptr(), counts.data_ptr(), W, P,
+                                           cos_out.data_ptr(), score_out.data_ptr(), stream()), "score_frame_sets")
+    return cos_out, score_out
