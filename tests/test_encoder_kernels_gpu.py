@@ -290,6 +290,34 @@ def test_layernorm_bwd_vs_float64(dtype, H):
     assert all(x.ok for x in w.values())
 
 
+@pytest.mark.parametrize("entries", (1, 3))
+@pytest.mark.parametrize("dtype,H,M", ((torch.float16, 768, 132), (torch.float32, 40, 5)), ids=("f16-768x132", "f32-40x5"))
+def test_layernorm_bwd_fold_routes_give_the_same_bits(dtype, H, M, entries):
+    """dgamma / dbeta of an immediate layernorm_bwd and of a deferred one folded through LnFoldGroup -- alone, or as one of
+    three entries of one fold launch -- are bitwise equal: one fold kernel serves both routes, with the same lane walk over
+    the partial rows (M = 132: 33 of them, one block lane takes two) and the same lane-order LDS fold."""
+    o = ops()
+    cases = [K.ln_bwd_case(cls, M, H, dtype) for cls in K.LN_CLASSES[:entries]]
+    grp = o.LnFoldGroup(H, DEV)
+    deferred = []
+    for c in cases:
+        dg, db = (t.clone().to(DEV) for t in K.ln_prefill(H))
+        ds = torch.empty(M, H, dtype=dtype, device=DEV)
+        o.layernorm_bwd(c.dy.to(dtype).to(DEV), c.s.to(dtype).to(DEV), c.mean.to(DEV), c.rstd.to(DEV), c.gamma.to(DEV), ds,
+                        None, dg, db, 0.0, K.LN_SEED, defer_to=grp)
+        deferred.append(SimpleRun(ds=ds, dg=dg, db=db))
+    grp.fold()
+    differ = []
+    for cls, c, d in zip(K.LN_CLASSES, cases, deferred):
+        first = _ln_bwd(c, dtype, "immediate", 0.0, False)
+        assert first.intact
+        if not first.same_bits(d, ("ds", "dg", "db")):
+            differ.append(cls)
+    say(f"layernorm bwd fold routes {NAME[dtype]} H={H} M={M}, {entries} deferred: entries that differ from the immediate "
+        f"fold {differ}")
+    assert not differ
+
+
 @pytest.mark.parametrize("cls", K.LN_CHAIN_CLASSES)
 @pytest.mark.parametrize("dtype", K.LP, ids=NAME.get)
 def test_layernorm_chained_fwd_bwd(dtype, cls):

@@ -76,7 +76,6 @@ __device__ __forceinline__ void attn_drop4_rows(uint32_t k, uint32_t thr, IDX co
   ms[2] = ((r2 >> sh) & 0xffffu) >= thr ? inv_keep : 0.f;
   ms[3] = ((r3 >> sh) & 0xffffu) >= thr ? inv_keep : 0.f;
 }
-__device__ __forceinline__ int aswz(int row) { return ((row ^ (row >> 1)) & 3) | (row & 4); }   // measured map, see gemm.hip swz()
 
 __device__ __forceinline__ frag8_t as_frag(uint4 v) {
   union { uint4 u; frag8_t f; } c;
@@ -113,7 +112,7 @@ __device__ __forceinline__ float frag_dot(frag8_t a, frag8_t b) {
 // MFMA fragment (16 rows x 32 k) from the swizzled row-major image
 __device__ __forceinline__ frag8_t lds_frag(const bf16_t* lds, int row0, int kk, int lane) {
   const int fr = lane & 15;                         // row0 is a multiple of 16: swizzle depends on fr only
-  const int lane_off = fr * 64 + (((kk * 4 + (lane >> 4)) ^ aswz(fr)) << 3);
+  const int lane_off = fr * 64 + (((kk * 4 + (lane >> 4)) ^ swz(fr)) << 3);
   return as_frag(*reinterpret_cast<const uint4*>(lds + lane_off + row0 * 64));
 }
 // the wave's own 16 rows straight from global into registers (2 k-steps)
@@ -180,7 +179,7 @@ struct TrOff { int o[4]; };
 __device__ __forceinline__ TrOff tr_offsets(int lane) {
   const int i = lane & 15, g = lane >> 4;
   const int r = g * 4 + (i >> 2);                    // row within the 32-row block (first read; second = +16)
-  const int sw = aswz(r);
+  const int sw = swz(r);
   TrOff t;
 #pragma unroll
   for (int df = 0; df < 4; ++df) t.o[df] = r * 64 + (((2 * df + ((i & 3) >> 1)) ^ sw) << 3) + ((i & 1) << 2);
@@ -233,13 +232,13 @@ __device__ __forceinline__ void tile_store(const TileRegs& r, bf16_t* lds) {
   for (int i = 0; i < 2; ++i) {
     const int c = threadIdx.x + NT * i;
     const int row = c >> 3, ch = c & 7;
-    *reinterpret_cast<uint4*>(lds + row * 64 + ((ch ^ aswz(row)) << 3)) = r.v[i];
+    *reinterpret_cast<uint4*>(lds + row * 64 + ((ch ^ swz(row)) << 3)) = r.v[i];
   }
 }
 
 // The same tile straight from global memory into LDS (global_load_lds_dwordx4: no staging registers).  A wave-instruction
 // moves 64 x 16 B = 8 rows of the image; lane l lands at chunk (l & 7) of row 8 p + (l >> 3), so the XOR swizzle is
-// applied on the SOURCE side (the lane fetches chunk (l & 7) ^ aswz(row)).  The DMA cannot write zeros: rows past
+// applied on the SOURCE side (the lane fetches chunk (l & 7) ^ swz(row)).  The DMA cannot write zeros: rows past
 // n_valid are CLAMPED onto the last valid row (finite data) and the caller makes their contribution vanish
 // (dK / dV kernel: lse = +inf for those query rows -> p = 0).  KT / (8 NW) instructions per wave and operand.
 template <int NW, int KT>
@@ -249,7 +248,7 @@ __device__ __forceinline__ void tile_dma(const bf16_t* g, int64_t gs, int row0, 
     const int piece = wave * (KT / (8 * NW)) + i;
     const int row = piece * 8 + (lane >> 3);
     const int src_row = min(row0 + row, n_valid - 1);
-    const int ch = (lane & 7) ^ aswz(row);
+    const int ch = (lane & 7) ^ swz(row);
     __builtin_amdgcn_global_load_lds((gvoid_t*)(g + (int64_t)src_row * gs + ch * 8), (lvoid_t*)(lds + piece * 8 * 64), 16, 0, 0);
   }
 }

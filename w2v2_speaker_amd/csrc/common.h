@@ -236,6 +236,21 @@ template <> struct Vec8<f16_t> {
   }
 };
 
+// 16-byte f32 access (4 values): the load as a float4, the store written through like Vec8's; p must be 16-byte aligned.
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float a, float b, float c, float d) {
+  store16_wt(p, make_uint4(__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d)));
+}
+// ... as an array, with Vec8's interface (what StripGeom<float> of strip_common.h hands its kernels)
+struct Vec4f {
+  float v[4];
+  __device__ __forceinline__ void load(const float* p) {
+    const float4 a = ld4(p);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  }
+  __device__ __forceinline__ void store(float* p) const { st4(p, v[0], v[1], v[2], v[3]); }
+};
+
 // ---------------------------------------------------------------- matrix cores: one 16x16x32 step on raw 16-bit fragments
 // Fragments travel as 8 x 16 raw bits (LDS images and registers do not care about the number format); the
 // instruction is picked by the activation type: v_mfma_f32_16x16x32_bf16 / v_mfma_f32_16x16x32_f16 (same rate).
@@ -304,6 +319,16 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
 }
+
+// The row -> 16-byte-chunk XOR map of every LDS operand image with 128-byte rows (GEMMs, attention, positional convolution).
+// depends on (row & 15) only: every 16-row MFMA fragment of a tile shares one per-lane swizzle, so the
+// fragment addresses of a wave differ by compile-time constants (ds_read offset immediates)
+// Measured on gfx950 (tools/probes/lds_bank_probe.hip times all 4096 GF(2)-linear row->chunk maps): with this
+// map the fragment ds_read_b128 pattern (16 rows x 4 k-chunks, 128-B rows) issues at the conflict-free
+// 4 clk/instruction AND the transposing ds_read_b64_tr_b16 pattern of the attention backward at 2.4 clk (best
+// found 2.3).  The textbook (row & 7) XOR costs 7 clk resp. 4 clk: the 64 x 4-B banks serve 16-byte accesses
+// in lane groups that are not 16 consecutive lanes, so "8 rows -> 8 chunks" is not enough.
+__device__ __forceinline__ int swz(int row) { return ((row ^ (row >> 1)) & 3) | (row & 4); }
 
 // `s_waitcnt vmcnt(N)` in front of a barrier: all but the N most recent vector-memory operations of this wave (its
 // LDS-DMA pieces) have landed

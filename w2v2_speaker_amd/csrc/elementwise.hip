@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, in
       for (; m + 7 * step < M; m += 8 * step) {
         float4 v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(x + (int64_t)(m + u * step) * ld + col);
+        for (int u = 0; u < 8; ++u) v[u] = ld4(x + (int64_t)(m + u * step) * ld + col);
 #pragma unroll
         for (int u = 0; u < 8; ++u) { acc[0] += v[u].x; acc[1] += v[u].y; acc[2] += v[u].z; acc[3] += v[u].w; }
       }
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, in
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] += v.v[e];
       } else if constexpr (VEC == 4) {
-        const float4 v = *reinterpret_cast<const float4*>(x + (int64_t)m * ld + col);
+        const float4 v = ld4(x + (int64_t)m * ld + col);
         acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w;
       } else {
         acc[0] += to_f32<T>(x[(int64_t)m * ld + col]);

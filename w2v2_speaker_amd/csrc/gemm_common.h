@@ -57,14 +57,7 @@ __device__ __forceinline__ int64_t outer_off(const OpDev& o, int64_t idx) {
   return idx * o.ld;
 }
 
-// depends on (row & 15) only: every 16-row MFMA fragment of a tile shares one per-lane swizzle, so the
-// fragment addresses of a wave differ by compile-time constants (ds_read offset immediates)
-// Measured on gfx950 (tools/probes/lds_bank_probe.hip times all 4096 GF(2)-linear row->chunk maps): with this
-// map the fragment ds_read_b128 pattern (16 rows x 4 k-chunks, 128-B rows) issues at the conflict-free
-// 4 clk/instruction AND the transposing ds_read_b64_tr_b16 pattern of the attention backward at 2.4 clk (best
-// found 2.3).  The textbook (row & 7) XOR costs 7 clk resp. 4 clk: the 64 x 4-B banks serve 16-byte accesses
-// in lane groups that are not 16 consecutive lanes, so "8 rows -> 8 chunks" is not enough.
-__device__ __forceinline__ int swz(int row) { return ((row ^ (row >> 1)) & 3) | (row & 4); }
+// (swz(), the row swizzle of the operand images, is in common.h: attention and the positional convolution use it too)
 // B image of the 256x128 ring kernel: its fragments take tile rows (rho >> 2) * 16 + j * 4 + (rho & 3), so the map
 // is applied to the fragment-local row index rho = ((row >> 4) & 3) * 4 + (row & 3) (same lane pattern as above)
 __device__ __forceinline__ int swz_b(int row) { return swz((((row >> 4) & 3) << 2) | (row & 3)); }

@@ -43,16 +43,6 @@ extern "C" int w2v2_row_invnorm(const void* x, int64_t ld, float* inv, int rows,
   return 0;
 }
 
-__device__ __forceinline__ float block_reduce(float v, float* sh, bool is_max) {
-  v = is_max ? wave_max(v) : wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  const float a = sh[0], b = sh[1], c = sh[2], d = sh[3];
-  return is_max ? fmaxf(fmaxf(a, b), fmaxf(c, d)) : (a + b + c + d);
-}
-
 // (block_reduce_n / block_reduce_sum2, which the row kernels below fold with, are in common.h: ctc.hip uses them too)
 
 // One workgroup per utterance row.  z_c = s*cos_c (c != y), z_y = s*phi(cos_y); loss = lse(z) - z_y.

@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256, 4) void ln_bwd_kernel(const T* __restrict__ dy
       const int col = (ln + 64 * ci) * 8 + e;
       if (col < H) {
         const float v = red[0][i] + red[1][i] + red[2][i] + red[3][i];
-        if (partial != nullptr) partial[((int64_t)blockIdx.x * 2 + pass) * H + col] = v;   // folded by ln_bwd_finalize
+        if (partial != nullptr) partial[((int64_t)blockIdx.x * 2 + pass) * H + col] = v;   // folded by colpart_fold
         else unsafeAtomicAdd((pass == 0 ? dgamma : dbeta) + col, v);
       }
     }
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256, 3) void ln_bwd16_kernel(const T* __restrict__ 
       const int col = (ln + 64 * ci) * 8 + e;
       if (col < H) {
         const float v = red[0][i] + red[1][i] + red[2][i] + red[3][i];
-        if (partial != nullptr) partial[((int64_t)blockIdx.x * 2 + pass) * H + col] = v;   // folded by ln_bwd_finalize
+        if (partial != nullptr) partial[((int64_t)blockIdx.x * 2 + pass) * H + col] = v;   // folded by colpart_fold
         else unsafeAtomicAdd((pass == 0 ? dgamma : dbeta) + col, v);
       }
     }
@@ -418,63 +418,56 @@ __global__ __launch_bounds__(256, 4) void ln_bwd16q_kernel(const T* __restrict__
   }
 }
 
-// fold the per-block column partials in a fixed order (deterministic) and add them to dgamma / dbeta:
+// Fold per-block column partials in a fixed order (deterministic, no atomics) and ADD them to their targets: THE fold of
+// every backward here.  partial [nblk][nslot * C] f32: slot s < kdw is tap s of a convolution weight gradient dw[c][kdw]
+// (w2v2_conv0_layernorm_gelu_bwd), the three slots after them go to d0 / d1 / d2 [C] (NULL: skipped) -- LayerNorm:
+// nslot = 2, kdw = 0, d0 = dgamma, d1 = dbeta.
 // 32 columns x 32 block lanes per workgroup (round 5: 1024 threads; with 8 lanes a thread walked 96 partial rows and a
 // four-LayerNorm fold took 11.6 us), each lane sums every 32nd block (independent loads, unrolled), then a fixed-order
-// LDS fold over the 32 lanes
-constexpr int LN_FOLD_LANES = 32;
-__global__ __launch_bounds__(1024) void ln_bwd_finalize_kernel(const float* __restrict__ partial,
-                                                               float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                               int nblk, int H) {
+// LDS fold over the 32 lanes.  Up to COLFOLD_MAX folds of one shape in one launch (blockIdx.y selects the entry): the
+// engine defers the folds of a gradient bucket (two transformer blocks = four LayerNorms) to a single launch instead of
+// four 6-us ones.
+constexpr int LN_FOLD_LANES = 32, COLFOLD_MAX = 8;
+struct ColFold {
+  const float* partial;
+  float *dw, *d0, *d1, *d2;
+};
+struct ColFoldArgs { ColFold e[COLFOLD_MAX]; };
+__global__ __launch_bounds__(1024) void colpart_fold_kernel(const ColFoldArgs a, int nblk, int nslot, int C, int kdw) {
   __shared__ float red[LN_FOLD_LANES][32];
+  const ColFold& f = a.e[blockIdx.y];
+  const float* __restrict__ partial = f.partial;
   const int cl = threadIdx.x & 31, bl = threadIdx.x >> 5;
-  const int i = blockIdx.x * 32 + cl;                 // index into [2][H]
+  const int i = blockIdx.x * 32 + cl;                 // index into [nslot][C]
+  const int n = nslot * C;
   float s = 0.f;
-  if (i < 2 * H) {
-    const int pass = i / H, col = i - pass * H;
+  if (i < n) {
 #pragma unroll 8
-    for (int b = bl; b < nblk; b += LN_FOLD_LANES) s += partial[((int64_t)b * 2 + pass) * H + col];
+    for (int b = bl; b < nblk; b += LN_FOLD_LANES) s += partial[(int64_t)b * n + i];
   }
   red[bl][cl] = s;
   __syncthreads();
-  if (bl == 0 && i < 2 * H) {
+  if (bl == 0 && i < n) {
     float t = 0.f;
 #pragma unroll
     for (int k = 0; k < LN_FOLD_LANES; ++k) t += red[k][cl];
-    const int pass = i / H, col = i - pass * H;
-    float* dst = (pass == 0 ? dgamma : dbeta) + col;
+    const int slot = i / C, c = i - slot * C;
+    float* dst = slot < kdw ? f.dw + (int64_t)c * kdw + slot
+                            : (slot == kdw ? f.d0 : slot == kdw + 1 ? f.d1 : f.d2);
+    if (slot >= kdw) { if (dst == nullptr) return; dst += c; }
     *dst += t;
   }
 }
-
-// the same fold for up to 8 LayerNorms in one launch (blockIdx.y selects the entry): the engine defers the folds of a
-// gradient bucket (two transformer blocks = four LayerNorms) to a single launch instead of four 6-us ones
-struct LnFoldArgs {
-  const float* partial[8];
-  float* dgamma[8];
-  float* dbeta[8];
-};
-__global__ __launch_bounds__(1024) void ln_bwd_finalize_many_kernel(const LnFoldArgs a, int nblk, int H) {
-  __shared__ float red[LN_FOLD_LANES][32];
-  const float* __restrict__ partial = a.partial[blockIdx.y];
-  const int cl = threadIdx.x & 31, bl = threadIdx.x >> 5;
-  const int i = blockIdx.x * 32 + cl;                 // index into [2][H]
-  float s = 0.f;
-  if (i < 2 * H) {
-    const int pass = i / H, col = i - pass * H;
-#pragma unroll 8
-    for (int b = bl; b < nblk; b += LN_FOLD_LANES) s += partial[((int64_t)b * 2 + pass) * H + col];
-  }
-  red[bl][cl] = s;
-  __syncthreads();
-  if (bl == 0 && i < 2 * H) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < LN_FOLD_LANES; ++k) t += red[k][cl];
-    const int pass = i / H, col = i - pass * H;
-    float* dst = (pass == 0 ? a.dgamma[blockIdx.y] : a.dbeta[blockIdx.y]) + col;
-    *dst += t;
-  }
+static void colpart_fold_launch(const ColFoldArgs& a, int nfold, int nblk, int nslot, int C, int kdw, void* stream) {
+  hipLaunchKernelGGL(colpart_fold_kernel, dim3((unsigned)cdiv((int64_t)nslot * C, 32), nfold), dim3(32 * LN_FOLD_LANES), 0,
+                     as_stream(stream), a, nblk, nslot, C, kdw);
+}
+int colpart_fold(const float* partial, int nblk, int nslot, int C, int kdw, float* dw, float* d0, float* d1, float* d2,
+                 void* stream) {
+  ColFoldArgs a = {};
+  a.e[0] = ColFold{partial, dw, d0, d1, d2};
+  colpart_fold_launch(a, 1, nblk, nslot, C, kdw, stream);
+  return 0;
 }
 
 // workgroups of the backward (= partial blocks the fold walks): a function of (M, H) only, so that w2v2_layernorm_bwd_fold
@@ -486,16 +479,14 @@ static int ln_bwd_nblocks(int M, int H) {
 }
 
 extern "C" int w2v2_layernorm_bwd_fold(const w2v2_ln_fold* e, int n, int M, int H, void* stream) {
-  W2V2_REQUIRE(e && n >= 0 && n <= 8 && H > 0, "layernorm_bwd_fold: bad arguments (at most 8 entries)");
+  W2V2_REQUIRE(e && n >= 0 && n <= COLFOLD_MAX && H > 0, "layernorm_bwd_fold: bad arguments (at most 8 entries)");
   if (n == 0 || M <= 0) return 0;
-  LnFoldArgs a;
+  ColFoldArgs a = {};
   for (int i = 0; i < n; ++i) {
     W2V2_REQUIRE(e[i].partial && e[i].dgamma && e[i].dbeta, "layernorm_bwd_fold: null pointer in entry %d", i);
-    a.partial[i] = e[i].partial; a.dgamma[i] = e[i].dgamma; a.dbeta[i] = e[i].dbeta;
+    a.e[i] = ColFold{e[i].partial, nullptr, e[i].dgamma, e[i].dbeta, nullptr};
   }
-  const int nb = ln_bwd_nblocks(M, H);
-  hipLaunchKernelGGL(ln_bwd_finalize_many_kernel, dim3((unsigned)cdiv(2 * H, 32), n), dim3(32 * LN_FOLD_LANES), 0, as_stream(stream),
-                     a, nb, H);
+  colpart_fold_launch(a, n, ln_bwd_nblocks(M, H), 2, H, 0, stream);
   W2V2_CHECK_LAUNCH("layernorm_bwd_fold");
   return 0;
 }
@@ -564,9 +555,7 @@ extern "C" int w2v2_layernorm_bwd(const void* dy, const void* s, const float* me
                          (const AT*)s, mean, rstd, gamma, (AT*)ds, (AT*)d_r, dgamma, dbeta, partial, M, H,
                          drop_p, seed););
   }
-  if (partial != nullptr && dgamma != nullptr)
-    hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((unsigned)cdiv(2 * H, 32)), dim3(32 * LN_FOLD_LANES), 0, as_stream(stream),
-                       partial, dgamma, dbeta, nb, H);
+  if (partial != nullptr && dgamma != nullptr) colpart_fold(partial, nb, 2, H, 0, nullptr, dgamma, dbeta, nullptr, stream);
   W2V2_CHECK_LAUNCH("layernorm_bwd");
   return 0;
 }
@@ -672,42 +661,6 @@ __global__ __launch_bounds__(256) void ln_gelu_bwd_kernel(const T* dy, const T* 
     for (int col = threadIdx.x; col < H; col += 256)
       partial[((int64_t)blockIdx.x * 3 + pass) * H + col] = red[0][col] + red[1][col] + red[2][col] + red[3][col];
   }
-}
-
-// partial [nblk][nslot * C] -> targets, ADDED in a fixed order (the scheme of ln_bwd_finalize_kernel): slot s < kdw is tap s
-// of a convolution weight gradient dw[c][kdw] (w2v2_conv0_layernorm_gelu_bwd), the three slots after them go to
-// d0 / d1 / d2 [C] (NULL: skipped).
-__global__ __launch_bounds__(1024) void colpart_fold_kernel(const float* __restrict__ partial, int nblk, int nslot, int C,
-                                                            int kdw, float* __restrict__ dw, float* __restrict__ d0,
-                                                            float* __restrict__ d1, float* __restrict__ d2) {
-  __shared__ float red[LN_FOLD_LANES][32];
-  const int cl = threadIdx.x & 31, bl = threadIdx.x >> 5;
-  const int i = blockIdx.x * 32 + cl;                 // index into [nslot][C]
-  const int n = nslot * C;
-  float s = 0.f;
-  if (i < n) {
-#pragma unroll 8
-    for (int b = bl; b < nblk; b += LN_FOLD_LANES) s += partial[(int64_t)b * n + i];
-  }
-  red[bl][cl] = s;
-  __syncthreads();
-  if (bl == 0 && i < n) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < LN_FOLD_LANES; ++k) t += red[k][cl];
-    const int slot = i / C, c = i - slot * C;
-    float* dst = slot < kdw ? dw + (int64_t)c * kdw + slot
-                            : (slot == kdw ? d0 : slot == kdw + 1 ? d1 : d2);
-    if (slot >= kdw) { if (dst == nullptr) return; dst += c; }
-    *dst += t;
-  }
-}
-
-int colpart_fold(const float* partial, int nblk, int nslot, int C, int kdw, float* dw, float* d0, float* d1, float* d2,
-                 void* stream) {
-  hipLaunchKernelGGL(colpart_fold_kernel, dim3((unsigned)cdiv((int64_t)nslot * C, 32)), dim3(32 * LN_FOLD_LANES), 0,
-                     as_stream(stream), partial, nblk, nslot, C, kdw, dw, d0, d1, d2);
-  return 0;
 }
 
 extern "C" int w2v2_layernorm_gelu_bwd_workspace_floats(int M, int H) { return M > 0 ? lng_bwd_nblocks(M) * 3 * H : 0; }

@@ -32,8 +32,6 @@ template <int CG> struct PdGeom {
   static constexpr int NJ = CG / 16;                                         // channel fragments
 };
 
-__device__ __forceinline__ int pd_swz(int row) { return ((row ^ (row >> 1)) & 3) | (row & 4); }   // gemm_common.h swz()
-
 template <typename TE, int MODE, int CG>   // MODE 0: bias + GELU (aux = pre-activation, may be NULL); 1: + aux
 __global__ __launch_bounds__(256) void posconv_direct_kernel(const bf16_t* __restrict__ xg, const bf16_t* __restrict__ w,
                                                              bf16_t* __restrict__ out, bf16_t* __restrict__ aux,
@@ -59,7 +57,7 @@ __global__ __launch_bounds__(256) void posconv_direct_kernel(const bf16_t* __res
       int64_t off;
       if constexpr (CG == 64) {                   // 8 rows x 8 chunks per piece; the lane lands at chunk (lane & 7) of its row
         const int row = p * 8 + (lane >> 3);
-        off = base + (int64_t)row * 64 + (((lane & 7) ^ pd_swz(row)) << 3);
+        off = base + (int64_t)row * 64 + (((lane & 7) ^ swz(row)) << 3);
       } else {
         off = base + p * 512 + lane * 8;
       }
@@ -75,7 +73,7 @@ __global__ __launch_bounds__(256) void posconv_direct_kernel(const bf16_t* __res
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int row = (wave * 2 + j) * 8 + r8;
-    boff[j] = (row < PD_CG ? row : PD_CG - 1) * (K * PD_CG) + ((c8 ^ pd_swz(row)) << 3);
+    boff[j] = (row < PD_CG ? row : PD_CG - 1) * (K * PD_CG) + ((c8 ^ swz(row)) << 3);
   }
   const bool loader = wave * 16 < PD_CG;         // waves 0..2 (48 channels) / 0..3 (64) issue two 8-row pieces per stage
   auto issue = [&](int kt) {
@@ -93,7 +91,7 @@ __global__ __launch_bounds__(256) void posconv_direct_kernel(const bf16_t* __res
   const int nmf = (wave < 2) ? 3 : 2;            // frame fragments of this wave: w, w + 4, (w + 8)
   // A: byte offset of (frame 16 i + fr, k chunk kg) in the image; B: fragment j, row 16 j + fr
   const int aoff = fr * ROWB + kg * 16;
-  const int sw = pd_swz(fr);
+  const int sw = swz(fr);
   f32x4 acc[3][NJ];
 #pragma unroll
   for (int i = 0; i < 3; ++i)
@@ -123,7 +121,7 @@ __global__ __launch_bounds__(256) void posconv_direct_kernel(const bf16_t* __res
         if (i < nmf) {
           if constexpr (CG == 64)       // row (frame + kt) of the image, logical chunk kk * 4 + kg, swizzled by that row
             af[i] = *reinterpret_cast<const frag8_t*>(smem + ((wave + 4 * i) * 16 + fr + kt) * 128 +
-                                                      (((kk * 4 + kg) ^ pd_swz(fr + kt)) << 4));
+                                                      (((kk * 4 + kg) ^ swz(fr + kt)) << 4));
           else
             af[i] = *reinterpret_cast<const frag8_t*>(smem + (wave + 4 * i) * (16 * 96) + aoff + kt * 128 + kk * 64);
         }

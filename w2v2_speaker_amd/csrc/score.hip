@@ -5,11 +5,10 @@
 // Conventions of the f32 strip kernels: a thread reads one 16-byte vector of 4 features per step, every guard is per
 // vector (D % 4 == 0, ld % 4 == 0), every row * ld is formed in 64 bits, no atomics and fixed-order folds (bitwise
 // reproducible), nothing allocated here, everything on the caller's stream.
-#include "common.h"
+#include "strip_common.h"
 
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float qnan() { return __uint_as_float(0x7fc00000u); }
 // (cos + 1) / 2 clipped to [0, 1] (ref: speaker_recognition_evaluator.py:81); NaN stays NaN
 __device__ __forceinline__ float score_of(double c) {
@@ -20,66 +19,28 @@ __device__ __forceinline__ float score_of(double c) {
 // ------------------------------------------------------------------------------------------ embed_stats
 // The scheme of conv0.hip / wav2spk.hip.  (1) partial: a workgroup takes ST_ROWS rows and a 128-dimension strip, holds its
 // rows in registers, and writes per dimension the chunk mean and the CENTRED second moment sum (x - mean_chunk)^2, both
-// summed in double and stored as doubles (E[x^2] - mean^2 is never formed: a dimension with mean 1e3 and std 1e-2 would
-// lose ten digits, and a constant dimension would not come out with std exactly 0).  (2) one thread per dimension
-// combines the chunks in double, in chunk order (Chan et al.: M2 += M2_j + delta^2 n n_j / (n + n_j)).
-constexpr int ST_ROWS = 128, ST_XL = 32, ST_RL = 8, ST_CW = ST_XL * 4, ST_RPT = ST_ROWS / ST_RL;
+// summed in double and stored as doubles (strip_centred_moments: E[x^2] - mean^2 is never formed: a dimension with mean 1e3
+// and std 1e-2 would lose ten digits, and a constant dimension would not come out with std exactly 0).  (2) one thread
+// per dimension combines the chunks in double, in chunk order (Chan et al.: M2 += M2_j + delta^2 n n_j / (n + n_j)).
+using StGeom = StripGeom<float>;
+constexpr int ST_ROWS = 128, ST_RPT = ST_ROWS / StGeom::RL;
 
 __global__ __launch_bounds__(256) void stats_partial_kernel(const float* __restrict__ bank, int64_t ld, int N, int D,
                                                             double* __restrict__ partial) {
-  __shared__ double red[ST_RL][ST_CW];
-  __shared__ float mu_s[ST_CW];
+  __shared__ double red[StGeom::RL][STRIP_CW];
+  __shared__ float mu_s[STRIP_CW];
   const int blk = blockIdx.y;
   const int r0 = blk * ST_ROWS;
   const int n = min(ST_ROWS, N - r0);                       // >= 1: the grid has cdiv(N, ST_ROWS) chunks
-  const int cl = threadIdx.x * 4, cg = blockIdx.x * ST_CW + cl;
-  const bool on = cg < D;
-  const int tid = threadIdx.y * ST_XL + threadIdx.x;
-  float4 v[ST_RPT];
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int r = 0; r < ST_RPT; ++r) {
-    const int t = threadIdx.y + r * ST_RL;
-    v[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (on && t < n) v[r] = ld4(bank + (int64_t)(r0 + t) * ld + cg);
-  }
-#pragma unroll
-  for (int r = 0; r < ST_RPT; ++r) {
-    s[0] += (double)v[r].x; s[1] += (double)v[r].y; s[2] += (double)v[r].z; s[3] += (double)v[r].w;
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) red[threadIdx.y][cl + e] = s[e];
-  __syncthreads();
-  double mean_d = 0.0;                                      // (threads tid < ST_CW: the chunk mean of dimension tid)
-  if (tid < ST_CW) {
-    double a = 0.0;
-#pragma unroll
-    for (int y = 0; y < ST_RL; ++y) a += red[y][tid];
-    mean_d = a / n;
-    mu_s[tid] = (float)mean_d;                              // the centre of the squares: the mean to f32
-  }
-  __syncthreads();
-  const float mu[4] = {mu_s[cl], mu_s[cl + 1], mu_s[cl + 2], mu_s[cl + 3]};
-  double q[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int r = 0; r < ST_RPT; ++r)
-    if (threadIdx.y + r * ST_RL < n) {
-      const float d0 = v[r].x - mu[0], d1 = v[r].y - mu[1], d2 = v[r].z - mu[2], d3 = v[r].w - mu[3];
-      q[0] += (double)d0 * d0; q[1] += (double)d1 * d1; q[2] += (double)d2 * d2; q[3] += (double)d3 * d3;
-    }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) red[threadIdx.y][cl + e] = q[e];      // (the sums were read out of red before the barrier above)
-  __syncthreads();
-  const int cc = blockIdx.x * ST_CW + tid;
-  if (tid < ST_CW && cc < D) {
-    double a = 0.0;
-#pragma unroll
-    for (int y = 0; y < ST_RL; ++y) a += red[y][tid];
-    // the squares re-centred from the f32 centre c to the chunk mean m: sum (x - m)^2 = sum (x - c)^2 - n (m - c)^2
-    const double off = mean_d - (double)mu_s[tid];
+  const int cg = blockIdx.x * STRIP_CW + threadIdx.x * 4;
+  const int tid = threadIdx.y * StGeom::XL + threadIdx.x;
+  double mean_d, m2;
+  strip_centred_moments<ST_RPT>(bank + (int64_t)r0 * ld + cg, ld, n, cg < D, red, mu_s, mean_d, m2);
+  const int cc = blockIdx.x * STRIP_CW + tid;
+  if (tid < STRIP_CW && cc < D) {
     double* dst = partial + ((int64_t)blk * D + cc) * 2;
     dst[0] = mean_d;
-    dst[1] = fmax(a - (double)n * off * off, 0.0);
+    dst[1] = m2;
   }
 }
 
@@ -270,7 +231,7 @@ extern "C" int w2v2_embed_stats(const float* bank, int64_t ld, int N, int D, flo
   W2V2_REQUIRE(N >= 2, "embed_stats: the unbiased std needs N >= 2 rows (got %d)", N);
   const int nchunk = (int)cdiv(N, ST_ROWS);
   W2V2_REQUIRE(nchunk <= 65535, "embed_stats: N = %d is more than 65535 chunks of %d rows", N, ST_ROWS);
-  hipLaunchKernelGGL(stats_partial_kernel, dim3((unsigned)cdiv(D, ST_CW), (unsigned)nchunk), dim3(ST_XL, ST_RL), 0,
+  hipLaunchKernelGGL(stats_partial_kernel, dim3((unsigned)cdiv(D, STRIP_CW), (unsigned)nchunk), dim3(StGeom::XL, StGeom::RL), 0,
                      as_stream(stream), bank, ld, N, D, (double*)workspace);
   W2V2_CHECK_LAUNCH("embed_stats(partial)");
   hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)cdiv(D, SF_DIMS)), dim3(SF_SEG * SF_DIMS), 0, as_stream(stream),

@@ -10,7 +10,7 @@
 // out, so one SE block is 2 + 4 launches instead of 4 + 9.  All sums are f32 in a fixed order (deterministic).
 //
 //   act: 0 none, 1 relu, 2 sigmoid.  Backward kernels take the forward OUTPUT y and form dy' = dy * act'(y).
-#include "common.h"
+#include "strip_common.h"
 
 constexpr int SK_BT = 16;   // batch rows per workgroup of the forward kernel
 constexpr int SK_NT = 4;    // weight rows per workgroup of the forward kernel
@@ -19,10 +19,10 @@ constexpr int SK_NC = 1024; // dy' columns staged per LDS chunk of the dx kernel
 constexpr int SK_XW = 8;    // waves (n slices) of the dx kernel
 
 __device__ __forceinline__ float sk_act(float v, int act) {
-  return act == 1 ? fmaxf(v, 0.f) : act == 2 ? 1.0f / (1.0f + __expf(-v)) : v;
+  return act == 1 ? fmaxf(v, 0.f) : act == 2 ? sigmoid_f(v) : v;
 }
 __device__ __forceinline__ float sk_dact(float dy, float y, int act) {
-  return act == 1 ? (y > 0.f ? dy : 0.f) : act == 2 ? dy * y * (1.0f - y) : dy;
+  return act == 1 ? (y > 0.f ? dy : 0.f) : act == 2 ? sigmoid_bwd_f(dy, y) : dy;
 }
 
 // Sum 64 per-lane accumulators over the 64 lanes of a wave with 63 exchanges instead of 64 x 6: at every step a lane
@@ -59,10 +59,10 @@ __global__ __launch_bounds__(256) void skinny_fwd_kernel(const float* __restrict
     float4 wv[SK_NT];
 #pragma unroll
     for (int j = 0; j < SK_NT; ++j)
-      wv[j] = *reinterpret_cast<const float4*>(W + (int64_t)min(n0 + j, N - 1) * K + k);   // clamped rows: dropped
+      wv[j] = ld4(W + (int64_t)min(n0 + j, N - 1) * K + k);   // clamped rows: dropped
 #pragma unroll
     for (int i = 0; i < SK_BT; ++i) {
-      const float4 xv = *reinterpret_cast<const float4*>(x + (int64_t)min(b0 + i, B - 1) * K + k);
+      const float4 xv = ld4(x + (int64_t)min(b0 + i, B - 1) * K + k);
 #pragma unroll
       for (int j = 0; j < SK_NT; ++j)
         acc[j * SK_BT + i] =
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void skinny_bwd_w_kernel(const float* __restri
     for (; i + 8 <= nb; i += 8) {
       float4 xv[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) xv[u] = *reinterpret_cast<const float4*>(xp + (int64_t)(i + u) * K);
+      for (int u = 0; u < 8; ++u) xv[u] = ld4(xp + (int64_t)(i + u) * K);
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dl), i + u));
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void skinny_bwd_w_kernel(const float* __restri
       }
     }
     for (; i < nb; ++i) {
-      const float4 xv = *reinterpret_cast<const float4*>(xp + (int64_t)i * K);
+      const float4 xv = ld4(xp + (int64_t)i * K);
       const float d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dl), i));
       acc.x = fmaf(d, xv.x, acc.x);
       acc.y = fmaf(d, xv.y, acc.y);

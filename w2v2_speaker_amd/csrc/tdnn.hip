@@ -13,13 +13,9 @@
 // Everything here is HBM-bound elementwise / reduction work over channels-last [B*T, C] activations; reductions
 // over rows are two-stage with a fixed order (deterministic, no atomics).  Row-strided operands (ld*) let the
 // Res2Net slices and the MFA concatenation live inside their parent tensors without copies.
-#include "common.h"
-#include <type_traits>
+#include "strip_common.h"
 
-constexpr int BN_CW = 128;        // channels per workgroup of the BatchNorm kernels: 16 lanes x 8 channels (16 B)
-constexpr int BN_RL = 16;         // row lanes of the 16-bit BatchNorm / SE workgroups (BnGeom below: 8 for f32)
 constexpr int BN_AROWS = 256;     // rows one workgroup of the apply kernels walks (64 where that leaves CUs idle: bn_arows)
-constexpr int BN_UN = 4;          // rows in flight per thread (memory-level parallelism of the row walks)
 
 // ------------------------------------------------------------------------------------------ BatchNorm (+ReLU)
 // Two launches per direction.  (1) partial: every workgroup reduces `rows` rows of a 128-channel strip to one
@@ -37,64 +33,18 @@ __device__ __forceinline__ float bn_act(float v, int act) {
   return act == BN_ACT_RELU ? fmaxf(v, 0.f) : (act == BN_ACT_LEAKY && !(v > 0.f)) ? BN_LEAKY_SLOPE * v : v;
 }
 constexpr int BN_PROWS = 256;     // rows per partial-sum block
-__device__ __forceinline__ int bn_rows(int) { return BN_PROWS; }
-static int bn_rows_host(int) { return BN_PROWS; }
 
-// Thread geometry of the strip kernels.  A thread owns ONE 16-byte vector of a row: 8 channels of a 16-bit tensor, 4 of an
-// f32 one -- round 6: with 8 f32 channels per thread (two 16-byte loads whose lanes sit 32 bytes apart) every load / store
-// instruction used half of each 64-byte request and the f32 apply passes streamed 2.6 TB/s where a device copy of the
-// same bytes streams 4.5 (profiles/r06_bn_rows_path.txt).  128 channels x RL row lanes = 256 threads either way.
-struct Vec4f {
-  float v[4];
-  __device__ __forceinline__ void load(const float* p) {
-    const float4 a = *reinterpret_cast<const float4*>(p);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-  }
-  __device__ __forceinline__ void store(float* p) const {
-    store16_wt(p, make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])));
-  }
-};
-template <typename T> struct BnGeom {
-  static constexpr int EPT = sizeof(T) == 4 ? 4 : 8;     // channels per thread
-  static constexpr int XL = BN_CW / EPT;                 // channel lanes (blockDim.x)
-  static constexpr int RL = 256 / XL;                    // row lanes (blockDim.y)
-  static constexpr int UN = sizeof(T) == 4 ? 8 : 4;      // rows in flight per thread: 128 bytes either way
-  using Vec = typename std::conditional<sizeof(T) == 4, Vec4f, Vec8<T>>::type;
-  using FVec = typename std::conditional<sizeof(T) == 4, Vec4f, Vec8<float>>::type;   // f32 side operand, same channels
-};
-constexpr int BN_RL_MAX = 16;
-
-// red[row lane][channel][2] -> partial[blockIdx.y][channel][2]
-template <int EPT>
-__device__ __forceinline__ void bn_store_partial(float (*red)[BN_CW][2], const float* s1, const float* s2,
-                                                 float* __restrict__ partial, int C) {
-  constexpr int XL = BN_CW / EPT, RL = 256 / XL;
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) {
-    red[threadIdx.y][threadIdx.x * EPT + e][0] = s1[e];
-    red[threadIdx.y][threadIdx.x * EPT + e][1] = s2[e];
-  }
-  __syncthreads();
-  const int tid = threadIdx.y * XL + threadIdx.x;
-  const int c = tid & (BN_CW - 1), w = tid >> 7;
-  float s = 0.f;
-#pragma unroll
-  for (int y = 0; y < RL; ++y) s += red[y][c][w];
-  const int cc = blockIdx.x * BN_CW + c;
-  if (cc < C) partial[((int64_t)blockIdx.y * C + cc) * 2 + w] = s;
-}
 template <typename T>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const T* __restrict__ a, int64_t lda,
                                                          float* __restrict__ partial, int M, int C, int act) {
-  __shared__ float red[BN_RL_MAX][BN_CW][2];
-  using G = BnGeom<T>;
+  __shared__ float red[STRIP_RL_MAX][STRIP_CW][2];
+  using G = StripGeom<T>;
   constexpr int EPT = G::EPT, RL = G::RL, UN = G::UN;
-  const int cg = blockIdx.x * BN_CW + threadIdx.x * EPT;
-  const int rows = bn_rows(C);
-  const int m0 = blockIdx.y * rows, m1 = min(M, m0 + rows);
+  const int cg = blockIdx.x * STRIP_CW + threadIdx.x * EPT;
+  const int m0 = blockIdx.y * BN_PROWS, m1 = min(M, m0 + BN_PROWS);
   float s1[EPT] = {}, s2[EPT] = {};
   if (cg < C)
-    for (int m = m0 + threadIdx.y; m < m1; m += UN * RL) {      // BN_UN independent 16-byte loads in flight
+    for (int m = m0 + threadIdx.y; m < m1; m += UN * RL) {      // UN independent 16-byte loads in flight
       typename G::Vec v[UN];
 #pragma unroll
       for (int u = 0; u < UN; ++u) v[u].load(a + (int64_t)min(m + u * RL, m1 - 1) * lda + cg);
@@ -109,15 +59,15 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const T* __restrict__ a
           }
         }
     }
-  bn_store_partial<EPT>(red, s1, s2, partial, C);
+  strip_store_partial2<EPT>(red, s1, s2, partial, (int64_t)blockIdx.y, C);
 }
 // the two column sums of channel blockIdx.x*128 + (tid & 127), folded over the partial blocks in a fixed order: wave g
 // takes blocks g, g+4, ... (one 16-byte load = 2 channels x 2 sums per lane, four loads in flight), then the four
 // wave results are added in wave order
-__device__ __forceinline__ void bn_fold(const float* __restrict__ partial, int nblk, int C, double (*fold)[BN_CW][2],
+__device__ __forceinline__ void bn_fold(const float* __restrict__ partial, int nblk, int C, double (*fold)[STRIP_CW][2],
                                         double& s1, double& s2, int tid) {
   const int q = tid & 63, grp = tid >> 6;
-  const int cq = blockIdx.x * BN_CW + 2 * q;
+  const int cq = blockIdx.x * STRIP_CW + 2 * q;
   double p[4] = {0.0, 0.0, 0.0, 0.0};
   if (cq < C) {
     const float* src = partial + (int64_t)cq * 2;
@@ -141,7 +91,7 @@ __device__ __forceinline__ void bn_fold(const float* __restrict__ partial, int n
   fold[grp][2 * q + 1][0] = p[2];
   fold[grp][2 * q + 1][1] = p[3];
   __syncthreads();
-  const int c = tid & (BN_CW - 1);
+  const int c = tid & (STRIP_CW - 1);
   s1 = ((fold[0][c][0] + fold[1][c][0]) + fold[2][c][0]) + fold[3][c][0];
   s2 = ((fold[0][c][1] + fold[1][c][1]) + fold[2][c][1]) + fold[3][c][1];
 }
@@ -153,12 +103,12 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ a, 
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        T* __restrict__ y, int64_t ldy, int M, int C, int act,
                                                        float eps, float momentum, int mode, int arows) {
-  __shared__ double fold[4][BN_CW][2];
-  __shared__ float cf[4][BN_CW];                 // mean, rstd, gamma, beta of the strip
-  using G = BnGeom<T>;
+  __shared__ double fold[4][STRIP_CW][2];
+  __shared__ float cf[4][STRIP_CW];                 // mean, rstd, gamma, beta of the strip
+  using G = StripGeom<T>;
   constexpr int EPT = G::EPT, RL = G::RL, UN = G::UN;
   const int tid = threadIdx.y * G::XL + threadIdx.x;
-  const int c = tid & (BN_CW - 1), cc = blockIdx.x * BN_CW + c;
+  const int c = tid & (STRIP_CW - 1), cc = blockIdx.x * STRIP_CW + c;
   float mu = 0.f, rstd = 0.f;
   if (mode) {
     double s1, s2;
@@ -168,7 +118,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ a, 
     var = var > 0.0 ? var : 0.0;
     mu = (float)mud;
     rstd = (float)(1.0 / sqrt(var + (double)eps));
-    if (blockIdx.y == 0 && tid < BN_CW && cc < C && running != nullptr) {   // torch BatchNorm1d buffers: momentum
+    if (blockIdx.y == 0 && tid < STRIP_CW && cc < C && running != nullptr) {   // torch BatchNorm1d buffers: momentum
       const double unb = M > 1 ? var * M / (M - 1) : var;                  // update with the unbiased variance
       running[cc] = (1.f - momentum) * running[cc] + momentum * mu;
       running[C + cc] = (1.f - momentum) * running[C + cc] + momentum * (float)unb;
@@ -177,7 +127,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ a, 
     mu = running[cc];
     rstd = 1.0f / sqrtf(running[C + cc] + eps);
   }
-  if (tid < BN_CW && cc < C) {
+  if (tid < STRIP_CW && cc < C) {
     cf[0][c] = mu;
     cf[1][c] = rstd;
     cf[2][c] = gamma[cc];
@@ -188,7 +138,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ a, 
     }
   }
   __syncthreads();
-  const int cl = threadIdx.x * EPT, cg = blockIdx.x * BN_CW + cl;
+  const int cl = threadIdx.x * EPT, cg = blockIdx.x * STRIP_CW + cl;
   if (cg >= C) return;
   const int m0 = blockIdx.y * arows, m1 = min(M, m0 + arows);
   float mus[EPT], rs[EPT], ga[EPT], be[EPT];
@@ -216,12 +166,11 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict
                                                              const T* __restrict__ a, int64_t lda,
                                                              const float* __restrict__ mean_rstd,
                                                              float* __restrict__ partial, int M, int C, int act) {
-  __shared__ float red[BN_RL_MAX][BN_CW][2];
-  using G = BnGeom<T>;
+  __shared__ float red[STRIP_RL_MAX][STRIP_CW][2];
+  using G = StripGeom<T>;
   constexpr int EPT = G::EPT, RL = G::RL, UN = G::UN;
-  const int cg = blockIdx.x * BN_CW + threadIdx.x * EPT;
-  const int rows = bn_rows(C);
-  const int m0 = blockIdx.y * rows, m1 = min(M, m0 + rows);
+  const int cg = blockIdx.x * STRIP_CW + threadIdx.x * EPT;
+  const int m0 = blockIdx.y * BN_PROWS, m1 = min(M, m0 + BN_PROWS);
   float s1[EPT] = {}, s2[EPT] = {};
   if (cg < C) {
     float mu[EPT], rs[EPT];
@@ -256,7 +205,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T* __restrict
         }
     }
   }
-  bn_store_partial<EPT>(red, s1, s2, partial, C);
+  strip_store_partial2<EPT>(red, s1, s2, partial, (int64_t)blockIdx.y, C);
 }
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ dy, int64_t lddy,
@@ -268,16 +217,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
                                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                            T* __restrict__ da, int64_t ldda, int M, int C, int act,
                                                            float invM, float* __restrict__ cs_partial, int arows) {
-  __shared__ double fold[4][BN_CW][2];
-  __shared__ float csred[BN_RL_MAX][BN_CW];          // column sums of da over this workgroup's rows (cs_partial != NULL)
-  __shared__ float cf[5][BN_CW];                 // mean, rstd, gamma*rstd, sum dy / M, sum dy xhat / M
-  using G = BnGeom<T>;
+  __shared__ double fold[4][STRIP_CW][2];
+  __shared__ float csred[STRIP_RL_MAX][STRIP_CW];          // column sums of da over this workgroup's rows (cs_partial != NULL)
+  __shared__ float cf[5][STRIP_CW];                 // mean, rstd, gamma*rstd, sum dy / M, sum dy xhat / M
+  using G = StripGeom<T>;
   constexpr int EPT = G::EPT, RL = G::RL, UN = G::UN;
   const int tid = threadIdx.y * G::XL + threadIdx.x;
-  const int c = tid & (BN_CW - 1), cc = blockIdx.x * BN_CW + c;
+  const int c = tid & (STRIP_CW - 1), cc = blockIdx.x * STRIP_CW + c;
   double s1, s2;
   bn_fold(partial, nblk, C, fold, s1, s2, tid);
-  if (tid < BN_CW && cc < C) {
+  if (tid < STRIP_CW && cc < C) {
     const float f1 = (float)s1, f2 = (float)s2, rstd = mean_rstd[2 * cc + 1];
     cf[0][c] = mean_rstd[2 * cc];
     cf[1][c] = rstd;
@@ -290,7 +239,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     }
   }
   __syncthreads();
-  const int cl = threadIdx.x * EPT, cg = blockIdx.x * BN_CW + cl;
+  const int cl = threadIdx.x * EPT, cg = blockIdx.x * STRIP_CW + cl;
   if (cg >= C && cs_partial == nullptr) return;
   const int m0 = blockIdx.y * arows, m1 = (cg < C) ? min(M, m0 + arows) : m0;
   float mu[EPT], rs[EPT], gr[EPT], m1s[EPT], m2s[EPT], cs[EPT] = {};
@@ -332,11 +281,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
   }
   // column sums of da (= the bias gradient of the convolution in front of this BatchNorm) while the values are in
   // registers: per row-block partials, folded by the caller (w2v2_colsum over nblk rows instead of M)
+  // (the lane-order fold of strip_common.h spelled out: its shared forms flip the branch around this tail)
   if (cs_partial != nullptr) {
 #pragma unroll
     for (int e = 0; e < EPT; ++e) csred[threadIdx.y][cl + e] = cs[e];
     __syncthreads();
-    if (tid < BN_CW && cc < C) {
+    if (tid < STRIP_CW && cc < C) {
       float t = 0.f;
 #pragma unroll
       for (int y = 0; y < RL; ++y) t += csred[y][c];
@@ -361,11 +311,11 @@ __device__ __forceinline__ int reflect(int p, int Tn) {
 template <typename T, bool LEN>
 __global__ void im2col_reflect_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ x2, int64_t ldx2,
                                       T* __restrict__ col, int B, int Tn, int Cin, int k, int dil, LensArg<LEN> lens) {
-  constexpr int EPT = BnGeom<T>::EPT;              // one 16-byte vector per thread (BnGeom)
+  constexpr int EPT = StripGeom<T>::EPT;              // one 16-byte vector per thread (StripGeom)
   const int nch = Cin / EPT;
   const int64_t total = (int64_t)B * Tn * k * nch;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    typename BnGeom<T>::Vec zero;                    // (LEN only)
+    typename StripGeom<T>::Vec zero;                    // (LEN only)
     if constexpr (LEN) {
 #pragma unroll
       for (int e = 0; e < EPT; ++e) zero.v[e] = 0.f;
@@ -393,10 +343,10 @@ __global__ void im2col_reflect_kernel(const T* __restrict__ x, int64_t ldx, cons
     int src = reflect(t + (j - (k - 1) / 2) * dil, L);
     // (the host guarantees padding < lens[b]; the clamp keeps a bad table inside the utterance's rows)
     if constexpr (LEN) src = min(max(src, 0), L - 1);
-    typename BnGeom<T>::Vec v;
+    typename StripGeom<T>::Vec v;
     v.load(x + ((int64_t)b * Tn + src) * ldx + ch * EPT);
     if (x2 != nullptr) {                   // taps of x + x2 (Res2Net: chunk input + previous chunk's output), summed here
-      typename BnGeom<T>::Vec w;
+      typename StripGeom<T>::Vec w;
       w.load(x2 + ((int64_t)b * Tn + src) * ldx2 + ch * EPT);
 #pragma unroll
       for (int e = 0; e < EPT; ++e) v.v[e] += w.v[e];
@@ -408,7 +358,7 @@ __global__ void im2col_reflect_kernel(const T* __restrict__ x, int64_t ldx, cons
 template <typename T>
 __global__ void col2im_reflect_kernel(const T* __restrict__ dcol, T* __restrict__ dx, int64_t lddx, int B, int Tn,
                                       int Cin, int k, int dil, int accumulate) {
-  constexpr int EPT = BnGeom<T>::EPT;              // one 16-byte vector per thread (BnGeom)
+  constexpr int EPT = StripGeom<T>::EPT;              // one 16-byte vector per thread (StripGeom)
   const int nch = Cin / EPT;
   const int64_t total = (int64_t)B * Tn * nch;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -427,14 +377,14 @@ __global__ void col2im_reflect_kernel(const T* __restrict__ dcol, T* __restrict_
         const int p = t + off;
         const bool hit = q == 0 ? (p >= 0 && p < Tn) : q == 1 ? (p < 0) : (p >= Tn);
         if (!hit || reflect(p, Tn) != s) continue;
-        typename BnGeom<T>::Vec v;
+        typename StripGeom<T>::Vec v;
         v.load(dcol + ((int64_t)b * Tn + t) * ((int64_t)k * Cin) + (int64_t)j * Cin + ch * EPT);
 #pragma unroll
         for (int e = 0; e < EPT; ++e) acc[e] += v.v[e];
       }
     }
     T* dst = dx + row * lddx + ch * EPT;
-    typename BnGeom<T>::Vec o;
+    typename StripGeom<T>::Vec o;
     if (accumulate) {
       o.load(dst);
 #pragma unroll
@@ -451,13 +401,13 @@ __global__ void col2im_reflect_kernel(const T* __restrict__ dcol, T* __restrict_
 template <typename T>
 __global__ void add_strided_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b, int64_t ldb,
                                    T* __restrict__ y, int64_t ldy, int M, int C) {
-  constexpr int EPT = BnGeom<T>::EPT;
+  constexpr int EPT = StripGeom<T>::EPT;
   const int nch = C / EPT;
   const int64_t total = (int64_t)M * nch;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int ch = (int)(i % nch);
     const int64_t m = i / nch;
-    typename BnGeom<T>::Vec va, vb;
+    typename StripGeom<T>::Vec va, vb;
     va.load(a + m * lda + ch * EPT);
     if (b != nullptr) {                    // b == NULL: a strided copy (Res2Net pass-through chunk, SE input slice)
       vb.load(b + m * ldb + ch * EPT);
@@ -469,19 +419,19 @@ __global__ void add_strided_kernel(const T* __restrict__ a, int64_t lda, const T
 }
 
 // ------------------------------------------------------------------------------------------ squeeze-excitation gate
-// one 16-byte vector per thread (BnGeom: 8 channels of a 16-bit tensor, 4 of an f32 one); C % 8 == 0.
+// one 16-byte vector per thread (StripGeom: 8 channels of a 16-bit tensor, 4 of an f32 one); C % 8 == 0.
 // y[b,t,c] = x[b,t,c] * g[b,c]
 template <typename T>
 __global__ void se_scale_kernel(const T* __restrict__ x, const float* __restrict__ g, T* __restrict__ y, int B, int Tn,
                                 int C) {
-  constexpr int EPT = BnGeom<T>::EPT;
+  constexpr int EPT = StripGeom<T>::EPT;
   const int nch = C / EPT;
   const int total = B * Tn * nch;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int row = i / nch, ch = i - row * nch;
     const int b = row / Tn;
-    typename BnGeom<T>::Vec v;
-    typename BnGeom<T>::FVec gv;
+    typename StripGeom<T>::Vec v;
+    typename StripGeom<T>::FVec gv;
     v.load(x + (int64_t)row * C + ch * EPT);
     gv.load(g + (int64_t)b * C + ch * EPT);
 #pragma unroll
@@ -489,47 +439,48 @@ __global__ void se_scale_kernel(const T* __restrict__ x, const float* __restrict
     v.store(y + (int64_t)row * C + ch * EPT);
   }
 }
-// dg[b,c] = sum_t dout[b,t,c] * x[b,t,c]        blockDim = (BnGeom<T>::XL channel lanes, BnGeom<T>::RL time lanes)
+// dg[b,c] = sum_t dout[b,t,c] * x[b,t,c]        blockDim = (StripGeom<T>::XL channel lanes, StripGeom<T>::RL time lanes)
 template <typename T>
 __global__ __launch_bounds__(256) void se_bwd_gate_kernel(const T* __restrict__ dout, const T* __restrict__ x,
                                                           float* __restrict__ dg, int Tn, int C) {
-  __shared__ float red[BN_RL_MAX][BN_CW];
-  constexpr int EPT = BnGeom<T>::EPT, XL = BnGeom<T>::XL, RL = BnGeom<T>::RL;
-  const int b = blockIdx.y, cg = blockIdx.x * BN_CW + threadIdx.x * EPT;
+  __shared__ float red[STRIP_RL_MAX][STRIP_CW];
+  constexpr int EPT = StripGeom<T>::EPT, XL = StripGeom<T>::XL, RL = StripGeom<T>::RL;
+  const int b = blockIdx.y, cg = blockIdx.x * STRIP_CW + threadIdx.x * EPT;
   float s[EPT] = {};
   if (cg < C)
     for (int t = threadIdx.y; t < Tn; t += RL) {
       const int64_t i = ((int64_t)b * Tn + t) * C + cg;
-      typename BnGeom<T>::Vec d, v;
+      typename StripGeom<T>::Vec d, v;
       d.load(dout + i);
       v.load(x + i);
 #pragma unroll
       for (int e = 0; e < EPT; ++e) s[e] = fmaf(d.v[e], v.v[e], s[e]);
     }
+  // (strip_put / strip_lane_sum spelled out: every shared form re-schedules this tail, profiles/strip_pieces_device_code.txt)
 #pragma unroll
   for (int e = 0; e < EPT; ++e) red[threadIdx.y][threadIdx.x * EPT + e] = s[e];
   __syncthreads();
   const int tid = threadIdx.y * XL + threadIdx.x;
-  if (tid < BN_CW && blockIdx.x * BN_CW + tid < C) {
+  if (tid < STRIP_CW && blockIdx.x * STRIP_CW + tid < C) {
     float acc = 0.f;
 #pragma unroll
     for (int yy = 0; yy < RL; ++yy) acc += red[yy][tid];
-    dg[(int64_t)b * C + blockIdx.x * BN_CW + tid] = acc;
+    dg[(int64_t)b * C + blockIdx.x * STRIP_CW + tid] = acc;
   }
 }
 // dx[b,t,c] = dout[b,t,c] * g[b,c] + ds[b,c] / T      (ds = gradient wrt the time mean that feeds the gate)
 template <typename T>
 __global__ void se_bwd_x_kernel(const T* __restrict__ dout, const float* __restrict__ g, const float* __restrict__ ds,
                                 T* __restrict__ dx, int B, int Tn, int C) {
-  constexpr int EPT = BnGeom<T>::EPT;
+  constexpr int EPT = StripGeom<T>::EPT;
   const int nch = C / EPT;
   const int total = B * Tn * nch;
   const float invT = 1.0f / (float)Tn;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int row = i / nch, ch = i - row * nch;
     const int b = row / Tn;
-    typename BnGeom<T>::Vec v;
-    typename BnGeom<T>::FVec gv, sv;
+    typename StripGeom<T>::Vec v;
+    typename StripGeom<T>::FVec gv, sv;
     v.load(dout + (int64_t)row * C + ch * EPT);
     gv.load(g + (int64_t)b * C + ch * EPT);
     sv.load(ds + (int64_t)b * C + ch * EPT);
@@ -553,14 +504,14 @@ template <bool LEN>
 __global__ __launch_bounds__(256) void stat_pool_fwd_kernel(const float* __restrict__ x, int64_t ldx,
                                                             float* __restrict__ out, float* __restrict__ stats,
                                                             const int* __restrict__ lens, int Tn, int C, float eps) {
-  __shared__ float red[8][BN_CW];
-  __shared__ float mean_s[BN_CW];
-  using G = BnGeom<float>;
+  __shared__ float red[8][STRIP_CW];
+  __shared__ float mean_s[STRIP_CW];
+  using G = StripGeom<float>;
   constexpr int EPT = G::EPT, RL = G::RL;
   static_assert(RL == 8 && EPT == 4, "stat_pool: 32 channel lanes x 8 time lanes");
   const int b = blockIdx.y;
   const int tid = threadIdx.y * G::XL + threadIdx.x;
-  const int cl = threadIdx.x * EPT, cg = blockIdx.x * BN_CW + cl;
+  const int cl = threadIdx.x * EPT, cg = blockIdx.x * STRIP_CW + cl;
   const int n = LEN ? lens[b] : Tn;
   const float* xb = x + (int64_t)b * Tn * ldx;
   const bool on = cg < C;
@@ -577,15 +528,8 @@ __global__ __launch_bounds__(256) void stat_pool_fwd_kernel(const float* __restr
           for (int e = 0; e < EPT; ++e) s[e] += v[u].v[e];
         }
     }
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) red[threadIdx.y][cl + e] = s[e];
-  __syncthreads();
-  if (tid < BN_CW) {
-    float m = 0.f;
-#pragma unroll
-    for (int y = 0; y < RL; ++y) m += red[y][tid];
-    mean_s[tid] = m / (float)n;
-  }
+  strip_put<EPT>(red, s);
+  if (tid < STRIP_CW) mean_s[tid] = strip_lane_sum<RL>(red, tid) / (float)n;
   __syncthreads();
   float mu[EPT], q[EPT] = {};
 #pragma unroll
@@ -605,15 +549,10 @@ __global__ __launch_bounds__(256) void stat_pool_fwd_kernel(const float* __restr
           }
         }
     }
-#pragma unroll
-  for (int e = 0; e < EPT; ++e) red[threadIdx.y][cl + e] = q[e];
-  __syncthreads();
-  const int cc = blockIdx.x * BN_CW + tid;
-  if (tid < BN_CW && cc < C) {
-    float v = 0.f;
-#pragma unroll
-    for (int y = 0; y < RL; ++y) v += red[y][tid];
-    const float sd = sqrtf(v / (float)(n - 1));
+  strip_put<EPT>(red, q);
+  const int cc = blockIdx.x * STRIP_CW + tid;
+  if (tid < STRIP_CW && cc < C) {
+    const float sd = sqrtf(strip_lane_sum<RL>(red, tid) / (float)(n - 1));
     const int64_t o = (int64_t)b * 2 * C;
     out[o + cc] = mean_s[tid];
     out[o + C + cc] = sd + eps;
@@ -654,29 +593,26 @@ __global__ void stat_pool_bwd_kernel(const float* __restrict__ x, int64_t ldx, c
 __global__ void act_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n, int mode) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float v = x[i];
-    y[i] = mode == 0 ? fmaxf(v, 0.f) : 1.0f / (1.0f + __expf(-v));
+    y[i] = mode == 0 ? fmaxf(v, 0.f) : sigmoid_f(v);
   }
 }
 __global__ void act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, float* __restrict__ dx,
                                int64_t n, int mode) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float yv = y[i];
-    dx[i] = mode == 0 ? (yv > 0.f ? dy[i] : 0.f) : dy[i] * yv * (1.0f - yv);
+    dx[i] = mode == 0 ? (yv > 0.f ? dy[i] : 0.f) : sigmoid_bwd_f(dy[i], yv);
   }
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
-// (no cap on the grid: 8192 blocks made every thread of the 60 M-element passes walk 7 strides -- the Adam kernel lost 20 % to the same cap)
-static int td_blocks(int64_t n) { return (int)(cdiv(n, 256) > (1 << 20) ? (1 << 20) : (cdiv(n, 256) < 1 ? 1 : cdiv(n, 256))); }
-
 extern "C" int w2v2_bn_workspace_floats(int M, int C) { return (int)cdiv(M, 128) * C * 2; }
 // Rows per workgroup of the apply kernels: 256, or 64 where 256 would leave most CUs without a workgroup -- the 128-channel
 // Res2Net slices of the ECAPA path are ONE strip wide: 78 workgroups of 256 rows at M = 19800 ran a 10 MB pass in 17-19 us
 // (four dependent load rounds behind the statistics fold on 78 of 256 CUs), 310 workgroups of 64 rows do one round each.
-static int bn_arows(int M, int C) { return cdiv(C, BN_CW) * cdiv(M, BN_AROWS) >= 256 ? BN_AROWS : 64; }
+static int bn_arows(int M, int C) { return cdiv(C, STRIP_CW) * cdiv(M, BN_AROWS) >= 256 ? BN_AROWS : 64; }
 extern "C" int w2v2_bn_colsum_rows(int M, int C) { return (int)cdiv(M, bn_arows(M, C)); }
 
-// One thread owns one 16-byte vector of a row (BnGeom): 8 channels of a 16-bit tensor, 4 of an f32 one, and every guard of
+// One thread owns one 16-byte vector of a row (StripGeom): 8 channels of a 16-bit tensor, 4 of an f32 one, and every guard of
 // the strip kernels is per vector -- so C and the row strides are multiples of 8, or of 4 for f32 (the x-vector's last
 // TDNN layer has 1500 channels: 1500 % 8 = 4).  The partial-sum fold reads channel PAIRS, which any such C keeps whole.
 static int bn_align(int dtype) { return dtype == W2V2_F32 ? 4 : 8; }
@@ -689,14 +625,14 @@ extern "C" int w2v2_bn_fwd(const void* a, int64_t lda, float* workspace, float* 
                "bn_fwd: bad arguments (C, lda, ldy multiples of 8, of 4 for f32; act 0, 1 or 2)");
   W2V2_REQUIRE(train ? workspace != nullptr : running != nullptr,
                "bn_fwd: training needs the workspace, evaluation the running statistics");
-  const int nblk = (int)cdiv(M, bn_rows_host(C));
+  const int nblk = (int)cdiv(M, BN_PROWS);
   const int arows = bn_arows(M, C);
-  const dim3 gp((unsigned)cdiv(C, BN_CW), nblk), ga((unsigned)cdiv(C, BN_CW), (unsigned)cdiv(M, arows));
+  const dim3 gp((unsigned)cdiv(C, STRIP_CW), nblk), ga((unsigned)cdiv(C, STRIP_CW), (unsigned)cdiv(M, arows));
   hipStream_t st = as_stream(stream);
 #define TD_BNF(T_)                                                                                                   \
   if (train)                                                                                                         \
-    hipLaunchKernelGGL(bn_partial_kernel<T_>, gp, dim3(BnGeom<T_>::XL, BnGeom<T_>::RL), 0, st, (const T_*)a, lda, workspace, M, C, act);             \
-  hipLaunchKernelGGL(bn_apply_kernel<T_>, ga, dim3(BnGeom<T_>::XL, BnGeom<T_>::RL), 0, st, (const T_*)a, lda, workspace, nblk, mean_rstd, running,    \
+    hipLaunchKernelGGL(bn_partial_kernel<T_>, gp, dim3(StripGeom<T_>::XL, StripGeom<T_>::RL), 0, st, (const T_*)a, lda, workspace, M, C, act);             \
+  hipLaunchKernelGGL(bn_apply_kernel<T_>, ga, dim3(StripGeom<T_>::XL, StripGeom<T_>::RL), 0, st, (const T_*)a, lda, workspace, nblk, mean_rstd, running,    \
                      gamma, beta, (T_*)y, ldy, M, C, act, eps, momentum, train, arows)
   W2V2_DISPATCH_ACT(dtype, "bn_fwd", TD_BNF(AT););
 #undef TD_BNF
@@ -712,14 +648,14 @@ static int bn_bwd_impl(const void* dy, int64_t lddy, const void* dy2, int64_t ld
                    lda % al == 0 && lddy % al == 0 && ldda % al == 0 && (dy2 == nullptr || lddy2 % al == 0) && act >= 0 &&
                    act <= BN_ACT_LEAKY,
                "bn_bwd: bad arguments (C and strides multiples of 8, of 4 for f32; act 0, 1 or 2)");
-  const int nblk = (int)cdiv(M, bn_rows_host(C));
+  const int nblk = (int)cdiv(M, BN_PROWS);
   const int arows = bn_arows(M, C);
-  const dim3 gp((unsigned)cdiv(C, BN_CW), nblk), ga((unsigned)cdiv(C, BN_CW), (unsigned)cdiv(M, arows));
+  const dim3 gp((unsigned)cdiv(C, STRIP_CW), nblk), ga((unsigned)cdiv(C, STRIP_CW), (unsigned)cdiv(M, arows));
   hipStream_t st = as_stream(stream);
 #define TD_BNB(T_)                                                                                                  \
-  hipLaunchKernelGGL(bn_bwd_partial_kernel<T_>, gp, dim3(BnGeom<T_>::XL, BnGeom<T_>::RL), 0, st, (const T_*)dy, lddy, (const T_*)dy2, lddy2,         \
+  hipLaunchKernelGGL(bn_bwd_partial_kernel<T_>, gp, dim3(StripGeom<T_>::XL, StripGeom<T_>::RL), 0, st, (const T_*)dy, lddy, (const T_*)dy2, lddy2,         \
                      (const T_*)a, lda, mean_rstd, workspace, M, C, act);                                          \
-  hipLaunchKernelGGL(bn_bwd_apply_kernel<T_>, ga, dim3(BnGeom<T_>::XL, BnGeom<T_>::RL), 0, st, (const T_*)dy, lddy, (const T_*)dy2, lddy2,           \
+  hipLaunchKernelGGL(bn_bwd_apply_kernel<T_>, ga, dim3(StripGeom<T_>::XL, StripGeom<T_>::RL), 0, st, (const T_*)dy, lddy, (const T_*)dy2, lddy2,           \
                      (const T_*)a, lda, mean_rstd, gamma, workspace, nblk, dgamma, dbeta, (T_*)da, ldda, M, C, act, \
                      1.0f / (float)M, colsum_partial, arows)
   W2V2_DISPATCH_ACT(dtype, "bn_bwd", TD_BNB(AT););
@@ -751,7 +687,7 @@ static int im2col_reflect_impl(const char* name, const void* x, int64_t ldx, con
   W2V2_REQUIRE(x && col && B > 0 && T > 0 && Cin % 8 == 0 && k % 2 == 1 && dilation >= 1 && ldx % 8 == 0 &&
                    (x2 == nullptr || ldx2 % 8 == 0) && dilation * (k - 1) / 2 < T,
                "%s: bad arguments (odd k, Cin %% 8 == 0, padding < T)", name);
-  const int nb = td_blocks((int64_t)B * T * k * (Cin >> (dtype == W2V2_F32 ? 2 : 3)));   // one 16-byte vector per thread
+  const int nb = blocks256((int64_t)B * T * k * (Cin / bn_align(dtype)));   // one 16-byte vector per thread
   hipStream_t st = as_stream(stream);
   W2V2_DISPATCH_LEN(lens, W2V2_DISPATCH_ACT(dtype, name,
     hipLaunchKernelGGL((im2col_reflect_kernel<AT, LEN>), dim3(nb), dim3(256), 0, st, (const AT*)x, ldx, (const AT*)x2,
@@ -787,7 +723,7 @@ extern "C" int w2v2_col2im_reflect(const void* dcol, void* dx, int64_t lddx, int
   W2V2_REQUIRE(dcol && dx && B > 0 && T > 0 && Cin % 8 == 0 && k % 2 == 1 && dilation >= 1 && lddx % 8 == 0 &&
                    dilation * (k - 1) / 2 < T,
                "col2im_reflect: bad arguments");
-  const int nb = td_blocks((int64_t)B * T * (Cin >> (dtype == W2V2_F32 ? 2 : 3)));
+  const int nb = blocks256((int64_t)B * T * (Cin / bn_align(dtype)));
   hipStream_t st = as_stream(stream);
   W2V2_DISPATCH_ACT(dtype, "col2im_reflect",
     hipLaunchKernelGGL(col2im_reflect_kernel<AT>, dim3(nb), dim3(256), 0, st, (const AT*)dcol, (AT*)dx,
@@ -800,7 +736,7 @@ extern "C" int w2v2_add_strided(const void* a, int64_t lda, const void* b, int64
                                 int C, int dtype, void* stream) {
   W2V2_REQUIRE(a && y && M > 0 && C % 8 == 0 && lda % 8 == 0 && (b == nullptr || ldb % 8 == 0) && ldy % 8 == 0,
                "add_strided: bad arguments");
-  const int nb = td_blocks((int64_t)M * (C >> (dtype == W2V2_F32 ? 2 : 3)));
+  const int nb = blocks256((int64_t)M * (C / bn_align(dtype)));
   hipStream_t st = as_stream(stream);
   W2V2_DISPATCH_ACT(dtype, "add_strided",
     hipLaunchKernelGGL(add_strided_kernel<AT>, dim3(nb), dim3(256), 0, st, (const AT*)a, lda,
@@ -811,7 +747,7 @@ extern "C" int w2v2_add_strided(const void* a, int64_t lda, const void* b, int64
 
 extern "C" int w2v2_se_scale(const void* x, const float* g, void* y, int B, int T, int C, int dtype, void* stream) {
   W2V2_REQUIRE(x && g && y && B > 0 && T > 0 && C > 0 && C % 8 == 0, "se_scale: bad arguments (C %% 8 == 0)");
-  const int nb = td_blocks((int64_t)B * T * (C >> (dtype == W2V2_F32 ? 2 : 3)));
+  const int nb = blocks256((int64_t)B * T * (C / bn_align(dtype)));
   hipStream_t st = as_stream(stream);
   W2V2_DISPATCH_ACT(dtype, "se_scale",
     hipLaunchKernelGGL(se_scale_kernel<AT>, dim3(nb), dim3(256), 0, st, (const AT*)x, g, (AT*)y, B, T, C););
@@ -822,10 +758,10 @@ extern "C" int w2v2_se_scale(const void* x, const float* g, void* y, int B, int 
 extern "C" int w2v2_se_bwd_gate(const void* dout, const void* x, float* dg, int B, int T, int C, int dtype,
                                 void* stream) {
   W2V2_REQUIRE(dout && x && dg && B > 0 && T > 0 && C > 0 && C % 8 == 0, "se_bwd_gate: bad arguments (C %% 8 == 0)");
-  dim3 grid((unsigned)cdiv(C, BN_CW), B);
+  dim3 grid((unsigned)cdiv(C, STRIP_CW), B);
   hipStream_t st = as_stream(stream);
   W2V2_DISPATCH_ACT(dtype, "se_bwd_gate",
-    hipLaunchKernelGGL(se_bwd_gate_kernel<AT>, grid, dim3(BnGeom<AT>::XL, BnGeom<AT>::RL), 0, st, (const AT*)dout, (const AT*)x, dg, T, C););
+    hipLaunchKernelGGL(se_bwd_gate_kernel<AT>, grid, dim3(StripGeom<AT>::XL, StripGeom<AT>::RL), 0, st, (const AT*)dout, (const AT*)x, dg, T, C););
   W2V2_CHECK_LAUNCH("se_bwd_gate");
   return 0;
 }
@@ -833,7 +769,7 @@ extern "C" int w2v2_se_bwd_gate(const void* dout, const void* x, float* dg, int 
 extern "C" int w2v2_se_bwd_x(const void* dout, const float* g, const float* ds, void* dx, int B, int T, int C, int dtype,
                              void* stream) {
   W2V2_REQUIRE(dout && g && ds && dx && B > 0 && T > 0 && C > 0 && C % 8 == 0, "se_bwd_x: bad arguments (C %% 8 == 0)");
-  const int nb = td_blocks((int64_t)B * T * (C >> (dtype == W2V2_F32 ? 2 : 3)));
+  const int nb = blocks256((int64_t)B * T * (C / bn_align(dtype)));
   hipStream_t st = as_stream(stream);
   W2V2_DISPATCH_ACT(dtype, "se_bwd_x",
     hipLaunchKernelGGL(se_bwd_x_kernel<AT>, dim3(nb), dim3(256), 0, st, (const AT*)dout, g, ds, (AT*)dx,
@@ -844,14 +780,14 @@ extern "C" int w2v2_se_bwd_x(const void* dout, const float* g, const float* ds, 
 
 extern "C" int w2v2_act_fwd(const float* x, float* y, int64_t n, int mode, void* stream) {
   W2V2_REQUIRE(x && y && n > 0 && (mode == 0 || mode == 1), "act_fwd: bad arguments");
-  hipLaunchKernelGGL(act_fwd_kernel, dim3(td_blocks(n)), dim3(256), 0, as_stream(stream), x, y, n, mode);
+  hipLaunchKernelGGL(act_fwd_kernel, dim3(blocks256(n)), dim3(256), 0, as_stream(stream), x, y, n, mode);
   W2V2_CHECK_LAUNCH("act_fwd");
   return 0;
 }
 
 extern "C" int w2v2_act_bwd(const float* dy, const float* y, float* dx, int64_t n, int mode, void* stream) {
   W2V2_REQUIRE(dy && y && dx && n > 0 && (mode == 0 || mode == 1), "act_bwd: bad arguments");
-  hipLaunchKernelGGL(act_bwd_kernel, dim3(td_blocks(n)), dim3(256), 0, as_stream(stream), dy, y, dx, n, mode);
+  hipLaunchKernelGGL(act_bwd_kernel, dim3(blocks256(n)), dim3(256), 0, as_stream(stream), dy, y, dx, n, mode);
   W2V2_CHECK_LAUNCH("act_bwd");
   return 0;
 }
@@ -863,7 +799,7 @@ static int stat_pool_fwd_impl(const char* name, const float* x, int64_t ldx, flo
   W2V2_REQUIRE(x && out && B > 0 && T >= 2 && C > 0 && C % 4 == 0 && ldx >= C && ldx % 4 == 0 &&
                    (reinterpret_cast<uintptr_t>(x) & 15) == 0,
                "%s: bad arguments (T >= 2, C and ldx multiples of 4, 16-byte aligned x)", name);
-  const dim3 grid((unsigned)cdiv(C, BN_CW), (unsigned)B), block(BnGeom<float>::XL, BnGeom<float>::RL);
+  const dim3 grid((unsigned)cdiv(C, STRIP_CW), (unsigned)B), block(StripGeom<float>::XL, StripGeom<float>::RL);
   hipStream_t st = as_stream(stream);
   W2V2_DISPATCH_LEN(lens, hipLaunchKernelGGL(stat_pool_fwd_kernel<LEN>, grid, block, 0, st, x, ldx, out, stats, lens, T, C, eps));
   W2V2_CHECK_LAUNCH(name);
@@ -883,7 +819,7 @@ extern "C" int w2v2_stat_pool_bwd(const float* x, int64_t ldx, const float* stat
   W2V2_REQUIRE(x && stats && dout && dx && B > 0 && T >= 2 && C > 0 && C % 4 == 0 && ldx >= C && ldx % 4 == 0 &&
                    lddx >= C && lddx % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0,
                "stat_pool_bwd: bad arguments (T >= 2, C and strides multiples of 4, 16-byte aligned x and dx)");
-  hipLaunchKernelGGL(stat_pool_bwd_kernel, dim3(td_blocks((int64_t)B * T * (C >> 2))), dim3(256), 0, as_stream(stream), x,
+  hipLaunchKernelGGL(stat_pool_bwd_kernel, dim3(blocks256((int64_t)B * T * (C >> 2))), dim3(256), 0, as_stream(stream), x,
                      ldx, stats, dout, dx, lddx, B, T, C);
   W2V2_CHECK_LAUNCH("stat_pool_bwd");
   return 0;

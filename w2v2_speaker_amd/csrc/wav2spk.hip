@@ -17,20 +17,12 @@
 // from its first frame -- never a function of T -- so a row of a padded batch (lens) equals the utterance run alone.
 // Variable-length forms (lens: device int32 [B]): every stage writes ZEROS into the rows past an utterance's own frame
 // count; those zeros are the zero padding of the next layer's gather, which therefore needs no lengths itself.
-#include "common.h"
+#include "strip_common.h"
 
-constexpr int IN_CW = 128;             // channels per workgroup of the InstanceNorm kernels: 32 lanes x 4 channels
-constexpr int IN_XL = IN_CW / 4;       // channel lanes (blockDim.x)
-constexpr int IN_RL = 256 / IN_XL;     // row lanes (blockDim.y)
+using InGeom = StripGeom<float>;       // the InstanceNorm workgroups: 32 channel lanes x 4 channels, 8 row lanes
 constexpr int IN_FB = 128;             // frames per statistics block
-constexpr int IN_RPT = IN_FB / IN_RL;  // rows per thread: all 16 in flight (64 registers)
+constexpr int IN_RPT = IN_FB / InGeom::RL;  // rows per thread: all 16 in flight (64 registers)
 constexpr int C1_ROWS = 256;           // rows per partial block of the layer-0 weight gradient
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float a, float b, float c, float d) {
-  store16_wt(p, make_uint4(__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d)));
-}
-static int ws_blocks(int64_t n) { const int64_t b = cdiv(n, 256); return (int)(b > (1 << 20) ? (1 << 20) : (b < 1 ? 1 : b)); }
 
 // ------------------------------------------------------------------------------------------ layer 0: Cin = 1
 // z[b][t][c] = bias[c] + sum_j w[c][j] * x[b][t * stride + j - pad], x = 0 outside [0, n_b).  lens = SAMPLES per utterance:
@@ -149,63 +141,24 @@ template <bool LEN>
 __global__ __launch_bounds__(256) void in_partial_kernel(const float* __restrict__ z, int64_t ldz,
                                                          float* __restrict__ partial, int T, int C, int nblk,
                                                          LensArg<LEN> lens) {
-  __shared__ double red[IN_RL][IN_CW];
-  __shared__ float mu_s[IN_CW];
+  __shared__ double red[InGeom::RL][STRIP_CW];
+  __shared__ float mu_s[STRIP_CW];
   const int b = blockIdx.z, blk = blockIdx.y;
   int Tb = T;
   if constexpr (LEN) Tb = min(lens[b], T);
   const int t0 = blk * IN_FB;
   if (t0 >= Tb) return;                                   // (the whole workgroup: no barrier is skipped by a part of it)
   const int n = min(IN_FB, Tb - t0);
-  const int cl = threadIdx.x * 4, cg = blockIdx.x * IN_CW + cl;
-  const bool on = cg < C;
-  const int tid = threadIdx.y * IN_XL + threadIdx.x;
-  float4 v[IN_RPT];
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int r = 0; r < IN_RPT; ++r) {
-    const int t = threadIdx.y + r * IN_RL;
-    v[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (on && t < n) v[r] = ld4(z + ((int64_t)b * T + t0 + t) * ldz + cg);
-  }
-#pragma unroll
-  for (int r = 0; r < IN_RPT; ++r) {
-    s[0] += (double)v[r].x; s[1] += (double)v[r].y; s[2] += (double)v[r].z; s[3] += (double)v[r].w;
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) red[threadIdx.y][cl + e] = s[e];
-  __syncthreads();
-  double mean_d = 0.0;                                    // (threads tid < IN_CW: the block mean of channel tid)
-  if (tid < IN_CW) {
-    double a = 0.0;
-#pragma unroll
-    for (int y = 0; y < IN_RL; ++y) a += red[y][tid];
-    mean_d = a / n;
-    mu_s[tid] = (float)mean_d;                            // the centre of the squares: the mean to f32
-  }
-  __syncthreads();
-  const float mu[4] = {mu_s[cl], mu_s[cl + 1], mu_s[cl + 2], mu_s[cl + 3]};
-  double q[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int r = 0; r < IN_RPT; ++r)
-    if (threadIdx.y + r * IN_RL < n) {
-      const float d0 = v[r].x - mu[0], d1 = v[r].y - mu[1], d2 = v[r].z - mu[2], d3 = v[r].w - mu[3];
-      q[0] += (double)d0 * d0; q[1] += (double)d1 * d1; q[2] += (double)d2 * d2; q[3] += (double)d3 * d3;
-    }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) red[threadIdx.y][cl + e] = q[e];      // (the sums were read out of red before the barrier above)
-  __syncthreads();
-  const int cc = blockIdx.x * IN_CW + tid;
-  if (tid < IN_CW && cc < C) {
-    double a = 0.0;
-#pragma unroll
-    for (int y = 0; y < IN_RL; ++y) a += red[y][tid];
-    // the block mean as an f32 pair, and the squares re-centred from the f32 centre to it: sum (z - m)^2 = sum (z - c)^2 - n (m - c)^2
-    const double off = mean_d - (double)mu_s[tid];
+  const int cg = blockIdx.x * STRIP_CW + threadIdx.x * 4;
+  const int tid = threadIdx.y * InGeom::XL + threadIdx.x;
+  double mean_d, m2;
+  strip_centred_moments<IN_RPT>(z + ((int64_t)b * T + t0) * ldz + cg, ldz, n, cg < C, red, mu_s, mean_d, m2);
+  const int cc = blockIdx.x * STRIP_CW + tid;
+  if (tid < STRIP_CW && cc < C) {                         // the block mean as an f32 pair (centre + remainder)
     float* dst = partial + (((int64_t)b * nblk + blk) * C + cc) * 4;
     dst[0] = mu_s[tid];
-    dst[1] = (float)off;
-    dst[2] = (float)fmax(a - (double)n * off * off, 0.0);
+    dst[1] = (float)(mean_d - (double)mu_s[tid]);
+    dst[2] = (float)m2;
     dst[3] = 0.f;
   }
 }
@@ -233,16 +186,16 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const float* __restrict__
                                                        const float* __restrict__ partial, int nblk,
                                                        float* __restrict__ mean_rstd, float* __restrict__ y, int64_t ldy,
                                                        int T, int C, float eps, LensArg<LEN> lens) {
-  __shared__ float cf[3][IN_CW];                          // mean, rstd, the mean's low part
+  __shared__ float cf[3][STRIP_CW];                          // mean, rstd, the mean's low part
   const int b = blockIdx.z, blk = blockIdx.y;
   int Tb = T;
   if constexpr (LEN) Tb = min(lens[b], T);
   const int t0 = blk * IN_FB, t1 = min(T, t0 + IN_FB);
-  const int cl = threadIdx.x * 4, cg = blockIdx.x * IN_CW + cl;
-  const int tid = threadIdx.y * IN_XL + threadIdx.x;
-  const int cc = blockIdx.x * IN_CW + tid;
+  const int cl = threadIdx.x * 4, cg = blockIdx.x * STRIP_CW + cl;
+  const int tid = threadIdx.y * InGeom::XL + threadIdx.x;
+  const int cc = blockIdx.x * STRIP_CW + tid;
   if (t0 < Tb) {
-    if (tid < IN_CW && cc < C) {
+    if (tid < STRIP_CW && cc < C) {
       float mu, mu_lo, rstd;
       in_combine(partial, b, nblk, C, cc, Tb, eps, mu, mu_lo, rstd);
       cf[0][tid] = mu;
@@ -256,7 +209,7 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const float* __restrict__
     __syncthreads();                                      // (t0 < Tb is uniform over the workgroup)
   }
   if (cg >= C) return;
-  for (int t = t0 + threadIdx.y; t < t1; t += IN_RL) {
+  for (int t = t0 + threadIdx.y; t < t1; t += InGeom::RL) {
     float* dst = y + ((int64_t)b * T + t) * ldy + cg;
     if (t >= Tb) {
       st4(dst, 0.f, 0.f, 0.f, 0.f);
@@ -277,11 +230,10 @@ __global__ __launch_bounds__(256) void in_bwd_partial_kernel(const float* __rest
                                                              const float* __restrict__ y, int64_t ldy,
                                                              const float* __restrict__ mean_rstd,
                                                              float* __restrict__ partial, int T, int C, int nblk) {
-  __shared__ float red[IN_RL][IN_CW][2];
+  __shared__ float red[InGeom::RL][STRIP_CW][2];
   const int b = blockIdx.z, blk = blockIdx.y;
   const int t0 = blk * IN_FB, t1 = min(T, t0 + IN_FB);
-  const int cl = threadIdx.x * 4, cg = blockIdx.x * IN_CW + cl;
-  const int tid = threadIdx.y * IN_XL + threadIdx.x;
+  const int cg = blockIdx.x * STRIP_CW + threadIdx.x * 4;
   float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
   if (cg < C) {
     float mu[4], rs[4];
@@ -290,7 +242,7 @@ __global__ __launch_bounds__(256) void in_bwd_partial_kernel(const float* __rest
       mu[e] = mean_rstd[((int64_t)b * C + cg + e) * 2];
       rs[e] = mean_rstd[((int64_t)b * C + cg + e) * 2 + 1];
     }
-    for (int t = t0 + threadIdx.y; t < t1; t += IN_RL) {
+    for (int t = t0 + threadIdx.y; t < t1; t += InGeom::RL) {
       const int64_t row = (int64_t)b * T + t;
       const float4 gv = ld4(dy + row * lddy + cg), zv = ld4(z + row * ldz + cg), yv = ld4(y + row * ldy + cg);
       const float g[4] = {yv.x > 0.f ? gv.x : 0.f, yv.y > 0.f ? gv.y : 0.f, yv.z > 0.f ? gv.z : 0.f, yv.w > 0.f ? gv.w : 0.f};
@@ -302,18 +254,7 @@ __global__ __launch_bounds__(256) void in_bwd_partial_kernel(const float* __rest
       }
     }
   }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    red[threadIdx.y][cl + e][0] = s1[e];
-    red[threadIdx.y][cl + e][1] = s2[e];
-  }
-  __syncthreads();
-  const int c = tid & (IN_CW - 1), w = tid >> 7;
-  const int cc = blockIdx.x * IN_CW + c;
-  float s = 0.f;
-#pragma unroll
-  for (int yy = 0; yy < IN_RL; ++yy) s += red[yy][c][w];
-  if (cc < C) partial[(((int64_t)b * nblk + blk) * C + cc) * 2 + w] = s;
+  strip_store_partial2<4>(red, s1, s2, partial, (int64_t)b * nblk + blk, C);
 }
 __global__ __launch_bounds__(256) void in_bwd_apply_kernel(const float* __restrict__ dy, int64_t lddy,
                                                            const float* __restrict__ z, int64_t ldz,
@@ -321,13 +262,13 @@ __global__ __launch_bounds__(256) void in_bwd_apply_kernel(const float* __restri
                                                            const float* __restrict__ mean_rstd,
                                                            const float* __restrict__ partial, int nblk,
                                                            float* __restrict__ dz, int64_t lddz, int T, int C) {
-  __shared__ float cf[4][IN_CW];                          // mean, rstd, mean_t g, mean_t (g zhat)
+  __shared__ float cf[4][STRIP_CW];                          // mean, rstd, mean_t g, mean_t (g zhat)
   const int b = blockIdx.z, blk = blockIdx.y;
   const int t0 = blk * IN_FB, t1 = min(T, t0 + IN_FB);
-  const int cl = threadIdx.x * 4, cg = blockIdx.x * IN_CW + cl;
-  const int tid = threadIdx.y * IN_XL + threadIdx.x;
-  const int cc = blockIdx.x * IN_CW + tid;
-  if (tid < IN_CW && cc < C) {
+  const int cl = threadIdx.x * 4, cg = blockIdx.x * STRIP_CW + cl;
+  const int tid = threadIdx.y * InGeom::XL + threadIdx.x;
+  const int cc = blockIdx.x * STRIP_CW + tid;
+  if (tid < STRIP_CW && cc < C) {
     double a1 = 0.0, a2 = 0.0;
     for (int j = 0; j < nblk; ++j) {
       const float* src = partial + (((int64_t)b * nblk + j) * C + cc) * 2;
@@ -341,7 +282,7 @@ __global__ __launch_bounds__(256) void in_bwd_apply_kernel(const float* __restri
   }
   __syncthreads();
   if (cg >= C) return;
-  for (int t = t0 + threadIdx.y; t < t1; t += IN_RL) {
+  for (int t = t0 + threadIdx.y; t < t1; t += InGeom::RL) {
     const int64_t row = (int64_t)b * T + t;
     const float4 gv = ld4(dy + row * lddy + cg), zv = ld4(z + row * ldz + cg), yv = ld4(y + row * ldy + cg);
     const float g[4] = {yv.x > 0.f ? gv.x : 0.f, yv.y > 0.f ? gv.y : 0.f, yv.z > 0.f ? gv.z : 0.f, yv.w > 0.f ? gv.w : 0.f};
@@ -357,7 +298,6 @@ __global__ __launch_bounds__(256) void in_bwd_apply_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------ temporal gate, row ReLU
-__device__ __forceinline__ float sigmoid_f(float v) { return 1.0f / (1.0f + __expf(-v)); }
 // y = sigmoid(p) * x over n / 4 vectors
 __global__ void gate_fwd_kernel(const float* __restrict__ p, const float* __restrict__ x, float* __restrict__ y, int64_t n4) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
@@ -429,7 +369,7 @@ extern "C" int w2v2_conv1d_first(const float* x, int64_t ldx, const float* w, co
   W2V2_REQUIRE(x && w && bias && z && B > 0 && C > 0 && C % 4 == 0 && ldz >= C && ldz % 4 == 0 && ldx >= N &&
                    conv_geom_ok(N, T, k, stride, pad),
                "conv1d_first: bad arguments (C, ldz multiples of 4; T = (N + 2 pad - k) / stride + 1)");
-  const int nb = ws_blocks((int64_t)B * T * (C >> 2));
+  const int nb = blocks256((int64_t)B * T * (C >> 2));
   hipStream_t st = as_stream(stream);
   W2V2_DISPATCH_LEN(lens, hipLaunchKernelGGL(conv1d_first_kernel<LEN>, dim3(nb), dim3(256), 0, st, x, ldx, w, bias, z, ldz,
                                              B, N, T, C, k, stride, pad, lens));
@@ -456,7 +396,7 @@ extern "C" int w2v2_im2col_zero(const float* x, int64_t ldx, float* col, int B, 
   W2V2_REQUIRE(x && col && B > 0 && Cin > 0 && Cin % 4 == 0 && ldx >= Cin && ldx % 4 == 0 &&
                    conv_geom_ok(Tin, Tout, k, stride, pad),
                "im2col_zero: bad arguments (Cin, ldx multiples of 4; Tout = (Tin + 2 pad - k) / stride + 1)");
-  const int nb = ws_blocks((int64_t)B * Tout * k * (Cin >> 2));
+  const int nb = blocks256((int64_t)B * Tout * k * (Cin >> 2));
   hipLaunchKernelGGL(im2col_zero_kernel, dim3(nb), dim3(256), 0, as_stream(stream), x, ldx, col, B, Tin, Tout, Cin, k,
                      stride, pad);
   W2V2_CHECK_LAUNCH("im2col_zero");
@@ -467,7 +407,7 @@ extern "C" int w2v2_col2im_zero(const float* dcol, float* dx, int64_t lddx, int 
   W2V2_REQUIRE(dcol && dx && B > 0 && Cin > 0 && Cin % 4 == 0 && lddx >= Cin && lddx % 4 == 0 &&
                    conv_geom_ok(Tin, Tout, k, stride, pad),
                "col2im_zero: bad arguments (Cin, lddx multiples of 4; Tout = (Tin + 2 pad - k) / stride + 1)");
-  const int nb = ws_blocks((int64_t)B * Tin * (Cin >> 2));
+  const int nb = blocks256((int64_t)B * Tin * (Cin >> 2));
   hipLaunchKernelGGL(col2im_zero_kernel, dim3(nb), dim3(256), 0, as_stream(stream), dcol, dx, lddx, B, Tin, Tout, Cin, k,
                      stride, pad);
   W2V2_CHECK_LAUNCH("col2im_zero");
@@ -482,7 +422,7 @@ extern "C" int w2v2_instnorm_relu_fwd(const float* z, int64_t ldz, float* worksp
                    ldz % 4 == 0 && ldy >= C && ldy % 4 == 0,
                "instnorm_relu_fwd: bad arguments (C and the row strides multiples of 4, B <= 65535)");
   const int nblk = (int)cdiv(T, IN_FB);
-  const dim3 grid((unsigned)cdiv(C, IN_CW), nblk, B), block(IN_XL, IN_RL);
+  const dim3 grid((unsigned)cdiv(C, STRIP_CW), nblk, B), block(InGeom::XL, InGeom::RL);
   hipStream_t st = as_stream(stream);
   W2V2_DISPATCH_LEN(lens,
     hipLaunchKernelGGL(in_partial_kernel<LEN>, grid, block, 0, st, z, ldz, workspace, T, C, nblk, lens);
@@ -498,7 +438,7 @@ extern "C" int w2v2_instnorm_relu_bwd(const float* dy, int64_t lddy, const float
                    lddz % 4 == 0,
                "instnorm_relu_bwd: bad arguments (C and the row strides multiples of 4, B <= 65535)");
   const int nblk = (int)cdiv(T, IN_FB);
-  const dim3 grid((unsigned)cdiv(C, IN_CW), nblk, B), block(IN_XL, IN_RL);
+  const dim3 grid((unsigned)cdiv(C, STRIP_CW), nblk, B), block(InGeom::XL, InGeom::RL);
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(in_bwd_partial_kernel, grid, block, 0, st, dy, lddy, z, ldz, y, ldy, mean_rstd, workspace, T, C, nblk);
   hipLaunchKernelGGL(in_bwd_apply_kernel, grid, block, 0, st, dy, lddy, z, ldz, y, ldy, mean_rstd, workspace, nblk, dz, lddz,
@@ -509,13 +449,13 @@ extern "C" int w2v2_instnorm_relu_bwd(const float* dy, int64_t lddy, const float
 
 extern "C" int w2v2_gate_fwd(const float* p, const float* x, float* y, int64_t n, void* stream) {
   W2V2_REQUIRE(p && x && y && n > 0 && n % 4 == 0, "gate_fwd: bad arguments (n a multiple of 4)");
-  hipLaunchKernelGGL(gate_fwd_kernel, dim3(ws_blocks(n >> 2)), dim3(256), 0, as_stream(stream), p, x, y, n >> 2);
+  hipLaunchKernelGGL(gate_fwd_kernel, dim3(blocks256(n >> 2)), dim3(256), 0, as_stream(stream), p, x, y, n >> 2);
   W2V2_CHECK_LAUNCH("gate_fwd");
   return 0;
 }
 extern "C" int w2v2_gate_bwd(const float* dy, const float* p, const float* x, float* dp, float* dx, int64_t n, void* stream) {
   W2V2_REQUIRE(dy && p && x && dp && dx && n > 0 && n % 4 == 0, "gate_bwd: bad arguments (n a multiple of 4)");
-  hipLaunchKernelGGL(gate_bwd_kernel, dim3(ws_blocks(n >> 2)), dim3(256), 0, as_stream(stream), dy, p, x, dp, dx, n >> 2);
+  hipLaunchKernelGGL(gate_bwd_kernel, dim3(blocks256(n >> 2)), dim3(256), 0, as_stream(stream), dy, p, x, dp, dx, n >> 2);
   W2V2_CHECK_LAUNCH("gate_bwd");
   return 0;
 }
@@ -524,7 +464,7 @@ extern "C" int w2v2_sum_bias_act_rows(const float* parts, int S, int64_t part_st
   W2V2_REQUIRE(parts && y && S >= 1 && B > 0 && T > 0 && C > 0 && C % 4 == 0 && (S == 1 || part_stride >= (int64_t)B * T * C) &&
                    part_stride % 4 == 0,
                "sum_bias_act_rows: bad arguments (C and part_stride multiples of 4, part_stride >= B * T * C)");
-  const int nb = ws_blocks((int64_t)B * T * (C >> 2));
+  const int nb = blocks256((int64_t)B * T * (C >> 2));
   hipStream_t st = as_stream(stream);
   W2V2_DISPATCH_LEN(lens, hipLaunchKernelGGL(sum_bias_act_rows_kernel<LEN>, dim3(nb), dim3(256), 0, st, parts, S, part_stride,
                                              bias, y, B, T, C, relu, lens));
