@@ -751,6 +751,42 @@ int w2v2_score_frame_sets(const float* frames, int64_t ld, int64_t rows, int D,
                           const int32_t* sel /*int32 [P][2][W]: absolute row numbers*/, const int32_t* counts /*int32 [P][2]*/,
                           int W, int P, float* cos_out, float* score_out, void* stream);
 
+/* ---------------------------------------------------------------------------------- trial metrics (metrics.hip)
+ * What follows the scores: ROC / EER / minDCF of a trial list without the P scores leaving the device.  No kernel waits
+ * on another workgroup (no look-back, no flag, no cooperative launch): every order between workgroups is a launch
+ * boundary.  No atomics on global memory, integer counters only in LDS; results are bitwise reproducible.  Nothing is
+ * allocated; all work goes on `stream`; workspaces are caller-owned and 16-byte aligned.
+ *
+ * Stable ascending argsort of keys [P] f32, 1 <= P < 2^31: order_out [P] int32 = np.argsort(keys, kind="stable") exactly
+ * (-0.0 and +0.0 are equal and tie by index; every NaN, of either sign bit, sorts behind +inf, NaNs in index order);
+ * keys_out [P] (may be NULL) = keys[order], the keys' own bits.  The order eval_metrics.py takes with two host argsorts
+ * (ref: src/eval_metrics.py:54-79 through sklearn's roc_curve, and :90-206).  An LSD radix sort of the order-preserving
+ * u32 image of the keys, 8 bits a pass: per pass a histogram per tile of w2v2_sort_tile() keys, a scan of the digit x tile
+ * table and a stable scatter (rank in a tile by wave ballots and a fixed wave-order prefix).  workspace: at least
+ * w2v2_sort_f32_index_workspace_bytes(P) bytes (-1: P out of range). */
+int w2v2_sort_tile(void);
+int64_t w2v2_sort_f32_index_workspace_bytes(int64_t P);
+int w2v2_sort_f32_index(const float* keys, int64_t P, int32_t* order_out, float* keys_out, void* workspace, void* stream);
+/* EER and minDCF of scores [P] f32 (as w2v2_score_pairs / w2v2_score_frame_sets leave them) with labels [P] uint8 (0 / 1),
+ * both on the device (ref: src/eval_metrics.py:54-79 calculate_eer, :90-206 calculate_mdc and _compute_error_rates) ->
+ * out [8] f64 on the device: eer, eer_threshold, mdc, mdc_threshold, n_pos, n_neg, n_nan, n_thresholds.
+ *   The stable sort above, then integer-exact steps: cumulative positives over the order, group ends (a position whose
+ * key differs from the next one's), the ROC points = the group ends in DESCENDING score order behind the origin
+ * (0, 0, +inf), kept as sklearn's drop_intermediate keeps them (origin, first and last point; between them where the
+ * second difference of fp or tp is non-zero; n_thresholds counts them).  EER: `1 - fp/N - tp/Pn <= 0` is tested as
+ * fp*Pn + tp*N >= N*Pn in int64; hi = first kept point that passes, lo = last kept point that does not (two index
+ * reductions); fp_lo == fp_hi: eer = fp_hi/N, threshold = thr_hi; otherwise the crossing of the segment with y = 1 - x and
+ * the threshold interpolated along it; lo = origin: threshold +inf.  minDCF: c_det = c_miss*fnr*p_target +
+ * c_fa*fpr*(1 - p_target) at EVERY position of the stable order (the minimum may fall inside a tie group), lowest index
+ * among equal minima, evaluated in f64 without contraction so that it rounds as numpy does; mdc = min / min(c_miss*p_target,
+ * c_fa*(1 - p_target)), mdc_threshold = the score there.
+ *   n_nan = NaN scores; when it is non-zero, or when one class is absent, the other outputs are unspecified (never a
+ * fault).  c_miss < 1, c_fa < 1 or p_target outside [0, 1] is an argument error, as in calculate_mdc.  workspace: at least
+ * w2v2_trial_metrics_workspace_bytes(P) bytes (-1: P out of range). */
+int64_t w2v2_trial_metrics_workspace_bytes(int64_t P);
+int w2v2_trial_metrics(const float* scores, const uint8_t* labels, int64_t P, double c_miss, double c_fa, double p_target,
+                       double* out, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------ optimiser
  * torch.optim.Adam (ref: config/optim/algo/adam.yaml, src/main.py:323-335) over one flat f32
  * parameter arena; also refreshes the 16-bit copy (pb_dtype = W2V2_BF16 / W2V2_F16) the GEMMs read

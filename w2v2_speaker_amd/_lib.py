@@ -14,7 +14,7 @@ F32, BF16, F16 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_GELU, EPI_GELU_BWD, EPI_ADD, EPI_SCALE_RC, EPI_BIAS_GELU_GRAD, EPI_MUL = range(8)
 OPTIM_ADAM, OPTIM_SGD = 0, 1
 
-c_i32, c_i64, c_u64, c_f32, c_vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p
+c_i32, c_i64, c_u64, c_f32, c_f64, c_vp = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_void_p
 
 
 class Operand(C.Structure):
@@ -183,6 +183,11 @@ _SIGS = {
     "w2v2_embed_stats": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "w2v2_score_pairs": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "w2v2_score_frame_sets": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "w2v2_sort_tile": (c_i32, []),
+    "w2v2_sort_f32_index_workspace_bytes": (c_i64, [c_i64]),
+    "w2v2_sort_f32_index": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "w2v2_trial_metrics_workspace_bytes": (c_i64, [c_i64]),
+    "w2v2_trial_metrics": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_f64, c_f64, c_vp, c_vp, c_vp]),
     "w2v2_adam_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32,
                                c_f32, c_f32, c_vp, c_i32, c_i32, c_vp]),
     "w2v2_optim_step": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32,

@@ -186,8 +186,24 @@ class CosineDistanceEvaluator:
         the embedding of ``keys[r]``, a list of such tensors (an ensemble), or -- with ``frame_offsets`` [N + 1] -- a ragged
         ``[sum T, D]`` frame bank (the non-pooled form; no centring / length norm there, as in the reference).  Scores are
         computed by the kernels of csrc/score.hip and one array of P (ensemble of n: n * P) floats is copied to the host;
-        EER / minDCF as in ``evaluate``.  ``last_bank_scoring`` keeps the scores and the copy's size."""
-        from .device_scoring import TrialIndex, score_trials_device
+        EER / minDCF as in ``evaluate``.  ``last_bank_scoring`` keeps the scores and the copy's size.  (The form that can
+        leave the metrics on the device as well: ``evaluate_bank_metrics``.)"""
+        return self.evaluate_bank_metrics(pairs, keys, bank, frame_offsets, metrics="host")
+
+    def evaluate_bank_metrics(self, pairs: List[EvaluationPair], keys: List[str], bank, frame_offsets=None,
+                              metrics: str = "host"):
+        """``evaluate_bank`` with the choice of where ROC / EER / minDCF are computed.  ``metrics="host"``: exactly
+        ``evaluate_bank``.  ``metrics="device"`` (one bank or a frame bank): the scores stay on the device too, the metrics
+        are computed there (csrc/metrics.hip, device_scoring.metrics_device) and eight doubles cross;
+        ``last_bank_scoring`` then has ``scores`` None and ``host_copy_floats`` 0, and ``last_bank_metrics`` says which
+        path answered.  An ensemble's members are combined on the host, so ``metrics="device"`` raises
+        NotImplementedError for one; any other value of ``metrics`` raises ValueError."""
+        from .device_scoring import TrialIndex, host_metrics, metrics_device, score_trials_device
+        if metrics not in ("host", "device"):
+            raise ValueError(f"metrics={metrics!r}: 'host' or 'device'")
+        if metrics == "device" and isinstance(bank, (list, tuple)):
+            raise NotImplementedError("metrics='device' takes one bank: the members of an ensemble are combined on the host "
+                                      "in the reference's Python-float order")
         index = TrialIndex(pairs, keys)
         if index.missing is not None:
             warn(f"{index.missing[0]} or {index.missing[1]} not in sample_map")
@@ -198,16 +214,12 @@ class CosineDistanceEvaluator:
                             "(mean / std are None)")
         self.last_bank_scoring = score_trials_device(
             bank, index, mean=self.mean if centre else None, std=self.std if centre else None,
-            length_norm=self.length_norm_before_scoring and frame_offsets is None, frame_offsets=frame_offsets)
-        gt, scores = index.ground_truth, self.last_bank_scoring.scores.tolist()
-        try:
-            eer, eer_threshold = calculate_eer(gt, scores, pos_label=1)
-        except (ValueError, ZeroDivisionError) as e:
-            print(f"EER calculation had {e}")
-            eer, eer_threshold = 1, 1337
-        try:
-            mdc, mdc_threshold = calculate_mdc(gt, scores)
-        except (ValueError, ZeroDivisionError) as e:
-            print(f"mdc calculation had {e}")
-            mdc, mdc_threshold = 1, 1337
-        return {"eer": eer, "eer_threshold": eer_threshold, "mdc": mdc, "mdc_threshold": mdc_threshold}
+            length_norm=self.length_norm_before_scoring and frame_offsets is None, frame_offsets=frame_offsets,
+            keep_on_device=metrics == "device")
+        if metrics == "device":
+            record = []
+            res = metrics_device(self.last_bank_scoring.device_scores, index, record=record)
+            self.last_bank_metrics = record[0]
+            self.last_bank_scoring.host_copy_floats = record[0].host_copy_floats      # (the host path copied them after all)
+            return res
+        return host_metrics(index.ground_truth, self.last_bank_scoring.scores.tolist())

@@ -3,7 +3,8 @@
 The host evaluator (cosine_distance.py, a mirror of the reference) gathers a left and a right ``[P, D]`` tensor on the
 host from one ``EmbeddingSample`` object per utterance.  Here the embeddings stay where the forward left them -- one
 ``[N, D]`` bank on the device -- the trial list becomes one ``[P, 2]`` int32 table of bank rows, built and checked once on
-the host, and ``P`` scores come back in one copy.  ROC / EER / minDCF stay on the host (eval_metrics.py)."""
+the host, and ``P`` scores come back in one copy.  ROC / EER / minDCF run on the host (eval_metrics.py) by default;
+``metrics_device`` computes them where the scores are (csrc/metrics.hip) and copies eight doubles instead."""
 from __future__ import annotations
 
 import random
@@ -14,6 +15,7 @@ import numpy as np
 import torch
 
 from ... import ops
+from ...eval_metrics import calculate_eer, calculate_mdc
 
 FRAME_CAP = 50      # frames per side of a non-pooled trial (ref: cosine_distance.py:203-232)
 
@@ -50,6 +52,7 @@ class TrialIndex:
             rows.append((self.row_of[pair.sample1_id], self.row_of[pair.sample2_id]))
         self.table = None if self.missing else self._checked(rows, self.num_rows)
         self._device_table = None
+        self._device_labels = None
 
     @classmethod
     def from_rows(cls, rows, ground_truth: Sequence[int], num_rows: int) -> "TrialIndex":
@@ -61,6 +64,7 @@ class TrialIndex:
         if len(self.ground_truth) != len(self.table):
             raise ValueError("one ground-truth label per trial")
         self._device_table = None
+        self._device_labels = None
         return self
 
     @staticmethod
@@ -85,6 +89,14 @@ class TrialIndex:
         if self._device_table is None or self._device_table.device != torch.device(device):
             self._device_table = _upload(self.table, device)
         return self._device_table
+
+    def device_labels(self, device) -> torch.Tensor:
+        """``ground_truth`` as uint8 [P] on ``device``, uploaded once."""
+        if self.table is None:
+            raise ValueError(f"{self.missing[0]} or {self.missing[1]} not in the bank")
+        if self._device_labels is None or self._device_labels.device != torch.device(device):
+            self._device_labels = _upload(np.asarray(self.ground_truth, dtype=np.uint8), device)
+        return self._device_labels
 
 
 def draw_frame_sets(frame_counts: Sequence[int], trial_index: TrialIndex, cap: int = FRAME_CAP):
@@ -119,25 +131,32 @@ def draw_frame_sets(frame_counts: Sequence[int], trial_index: TrialIndex, cap: i
 class DeviceScores:
     """What score_trials_device hands back: ``scores`` float64 [P] in [0, 1] (what ``evaluate`` feeds the metrics),
     ``host_copy_floats`` the number of floats that crossed to the host (P, or n * P for an ensemble of n),
-    ``bank_floats`` the elements of the bank(s) that stayed on the device."""
-    scores: np.ndarray
+    ``bank_floats`` the elements of the bank(s) that stayed on the device.  With ``keep_on_device`` the scores did not
+    cross: ``scores`` is None, ``host_copy_floats`` 0 and ``device_scores`` the float32 [P] tensor the kernel wrote."""
+    scores: Optional[np.ndarray]
     host_copy_floats: int
     bank_floats: int
+    device_scores: Optional[torch.Tensor] = None
 
 
 def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial_index: TrialIndex, *, mean=None, std=None,
-                        length_norm: bool = False, frame_offsets=None, cap: int = FRAME_CAP) -> DeviceScores:
+                        length_norm: bool = False, frame_offsets=None, cap: int = FRAME_CAP,
+                        keep_on_device: bool = False) -> DeviceScores:
     """Score ``trial_index`` over ``bank`` on the device.  bank: an ``[N, D]`` device tensor; a list of those (an
     ensemble: every member scored into one ``[n, P]`` buffer, combined on the host in the reference's order
     ``score += s_i * (1 / n)`` as Python floats, ref: cosine_distance.py:172-181); or, with ``frame_offsets`` ([N + 1],
     utterance r = rows frame_offsets[r] .. frame_offsets[r + 1]), a ragged ``[sum T, D]`` frame bank scored as the
     non-pooled form (frames drawn by draw_frame_sets from the global ``random``; no centring, no length norm, as in the
-    reference).  One device -> host copy."""
+    reference).  One device -> host copy; none with ``keep_on_device`` (one bank or a frame bank: the scores stay
+    where ``metrics_device`` reads them; an ensemble is combined on the host and cannot stay)."""
     members = list(bank) if isinstance(bank, (list, tuple)) else [bank]
     if not members or not all(isinstance(b, torch.Tensor) for b in members):
         raise ValueError("bank is a device tensor or a non-empty list of them")
     dev = members[0].device
     P = len(trial_index)
+    if keep_on_device and len(members) != 1:
+        raise NotImplementedError("keep_on_device: the members of an ensemble are combined on the host in the reference's "
+                                  "Python-float order")
     if frame_offsets is not None:
         if len(members) != 1:
             raise ValueError("a frame bank is one tensor")
@@ -147,6 +166,8 @@ def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial
             raise ValueError(f"frame_offsets is [N + 1] = [{trial_index.num_rows + 1}], from 0 to the rows of the frame bank")
         sel, counts = draw_frame_sets(np.diff(off), trial_index, cap)
         _, score = ops.score_frame_sets(members[0], _upload(sel, dev), _upload(counts, dev))
+        if keep_on_device:
+            return DeviceScores(None, 0, members[0].numel(), score)
         host = score.cpu().numpy()
         return DeviceScores(host.astype(np.float64), host.size, members[0].numel())
     table = trial_index.device_table(dev)
@@ -161,6 +182,8 @@ def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial
     for i, b in enumerate(members):
         ops.score_pairs(b, table, mean, std, length_norm, cos[i], score[i])
     bank_floats = sum(b.numel() for b in members)
+    if n == 1 and keep_on_device:
+        return DeviceScores(None, 0, bank_floats, score[0])
     if n == 1:
         host = score[0].cpu().numpy()
         return DeviceScores(host.astype(np.float64), host.size, bank_floats)
@@ -173,3 +196,59 @@ def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial
             s += member_scores[i][idx] * (1 / n)
         combined.append(s)
     return DeviceScores(np.clip((np.array(combined) + 1) / 2, 0, 1), host.size, bank_floats)
+
+
+def host_metrics(ground_truth: Sequence[int], scores: Sequence[float]) -> dict:
+    """EER / minDCF as ``CosineDistanceEvaluator.evaluate`` computes them from Python lists, with its fallbacks."""
+    try:
+        eer, eer_threshold = calculate_eer(ground_truth, scores, pos_label=1)
+    except (ValueError, ZeroDivisionError) as e:       # reference falls back to a very bad score
+        print(f"EER calculation had {e}")
+        eer, eer_threshold = 1, 1337
+    try:
+        mdc, mdc_threshold = calculate_mdc(ground_truth, scores)
+    except (ValueError, ZeroDivisionError) as e:
+        print(f"mdc calculation had {e}")
+        mdc, mdc_threshold = 1, 1337
+    return {"eer": eer, "eer_threshold": eer_threshold, "mdc": mdc, "mdc_threshold": mdc_threshold}
+
+
+@dataclass
+class DeviceMetrics:
+    """What metrics_device did: ``path`` "device" or "host" (one class only, or NaN scores: the host's answer by
+    construction), ``host_copy_floats`` the scores that crossed (0 on the device path), ``host_copy_doubles`` the eight
+    doubles of w2v2_trial_metrics (0 when nothing was launched), ``fields`` those eight by name."""
+    path: str
+    host_copy_floats: int
+    host_copy_doubles: int
+    fields: Optional[dict] = None
+
+
+def _host_scores(score: torch.Tensor) -> List[float]:
+    """The device scores as the list ``evaluate_bank`` feeds the host metrics (float64 of the float32 scores)."""
+    return score.cpu().numpy().astype(np.float64).tolist()
+
+
+def metrics_device(score: torch.Tensor, trial_index: TrialIndex, *, workspace=None, record: Optional[list] = None) -> dict:
+    """EER / minDCF of the device scores ``score`` (float32 [P], as score_trials_device(keep_on_device=True) leaves
+    them) against ``trial_index.ground_truth`` -> the dict of ``evaluate``.  One device -> host copy of eight doubles.
+    Two cases take exactly the host path of ``evaluate_bank``, so their answers (the ``1, 1337`` fallbacks included) are
+    the host's: a list with one class only (known before any launch; nothing is launched) and NaN among the scores
+    (``n_nan > 0``: the scores are then copied).  ``record``: a list that receives one DeviceMetrics."""
+    gt = trial_index.ground_truth
+    if not isinstance(score, torch.Tensor) or score.dim() != 1 or score.numel() != len(trial_index):
+        raise ValueError(f"metrics_device: one score per trial ({len(trial_index)})")
+    n_pos = sum(gt)
+    if n_pos == 0 or n_pos == len(gt):
+        if record is not None:
+            record.append(DeviceMetrics("host", score.numel(), 0))
+        return host_metrics(gt, _host_scores(score))
+    out = ops.trial_metrics(score, trial_index.device_labels(score.device), workspace=workspace).cpu().tolist()
+    fields = dict(zip(ops.TRIAL_METRICS_FIELDS, out))
+    if fields["n_nan"] > 0:
+        if record is not None:
+            record.append(DeviceMetrics("host", score.numel(), 8, fields))
+        return host_metrics(gt, _host_scores(score))
+    if record is not None:
+        record.append(DeviceMetrics("device", 0, 8, fields))
+    return {k: fields[k] for k in ("eer", "eer_threshold", "mdc", "mdc_threshold")}

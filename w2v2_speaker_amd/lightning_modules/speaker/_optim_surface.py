@@ -143,21 +143,26 @@ class EmbeddingEvaluation:
     def test_epoch_end(self, outputs: List[dict]):
         return self._evaluate_embeddings(outputs, self.test_pairs)
 
-    def evaluate_trials(self, pairs, input_by_key, *, scoring: str = "host", **batching) -> dict:
+    def evaluate_trials(self, pairs, input_by_key, *, scoring: str = "host", metrics: str = "host", **batching) -> dict:
         """Score a trial list: every utterance the pairs name (key -> one input of compute_speaker_embeddings in
         ``input_by_key``) is embedded once with compute_speaker_embeddings (``batching``: its keyword arguments) and the
         module's evaluator scores the pairs -- the same dict as test_epoch_end over the batch-size-1 test loop.
         ``scoring="device"``: the embeddings stay on the device as one bank and the evaluator's ``evaluate_bank`` scores
-        it there (pooled embeddings only)."""
+        it there (pooled embeddings only).  ``metrics="device"`` (with ``scoring="device"`` only): EER / minDCF are
+        computed on the device as well (``evaluate_bank_metrics(metrics="device")``) and eight doubles come back."""
         if scoring not in ("host", "device"):
             raise ValueError(f"scoring={scoring!r}: 'host' or 'device'")
+        if metrics not in ("host", "device"):
+            raise ValueError(f"metrics={metrics!r}: 'host' or 'device'")
+        if metrics == "device" and scoring != "device":
+            raise ValueError("metrics='device' needs scoring='device': the host path has no scores on the device")
         keys = sorted({k for p in pairs for k in (p.sample1_id, p.sample2_id)})
         embs = self.compute_speaker_embeddings([input_by_key[k] for k in keys], **batching)
         if scoring == "device":
             if embs[0].dim() != 2:
                 raise NotImplementedError("scoring='device' takes pooled embeddings; score a no-pooling head's frames with "
                                           "evaluator.evaluate_bank(frame_offsets=)")
-            return self.evaluator.evaluate_bank(pairs, keys, torch.cat(embs).detach().float())
+            return self.evaluator.evaluate_bank_metrics(pairs, keys, torch.cat(embs).detach().float(), metrics=metrics)
         return self._evaluate_embeddings([{"embedding": torch.cat(embs).detach().to("cpu"), "sample_id": keys}], pairs)
 
     @property

@@ -1436,3 +1436,85 @@ def score_frame_sets(frames, sel, counts, cos_out=None, score_out=None) -> Tuple
     _lib.check(lib().w2v2_score_frame_sets(frames.data_ptr(), ld, rows, D, sel.data_ptr(), counts.data_ptr(), W, P,
                                            cos_out.data_ptr(), score_out.data_ptr(), stream()), "score_frame_sets")
     return cos_out, score_out
+
+
+# ---------------------------------------------------------------------------------------------- trial metrics (metrics.hip)
+SORT_TILE = 2048            # keys per workgroup per pass of w2v2_sort_f32_index (csrc/metrics.hip SORT_TILE)
+TRIAL_METRICS_FIELDS = ("eer", "eer_threshold", "mdc", "mdc_threshold", "n_pos", "n_neg", "n_nan", "n_thresholds")
+
+
+def _trial_count(t, dtype, what: str, name: str) -> int:
+    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != dtype or not t.is_contiguous() or t.numel() < 1:
+        raise ValueError(f"{what}: {name} is a contiguous 1-D {str(dtype).replace('torch.', '')} tensor of P >= 1 elements")
+    if t.numel() >= 2 ** 31:
+        raise ValueError(f"{what}: P = {t.numel()} must be below 2^31")
+    return t.numel()
+
+
+def _byte_workspace(workspace, need: int, device, what: str, sizer: str) -> torch.Tensor:
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need \
+            or workspace.data_ptr() % 16 != 0:
+        raise ValueError(f"{what}: workspace holds {need} bytes, uint8, 16-byte aligned ({sizer})")
+    return workspace
+
+
+def _workspace_bytes(entry: str, P: int) -> int:
+    if not 1 <= int(P) < 2 ** 31:
+        raise ValueError(f"{entry}: P = {P} outside [1, 2^31)")
+    return int(getattr(lib(), entry)(int(P)))
+
+
+def sort_f32_index_workspace(P: int, device) -> torch.Tensor:
+    return torch.empty(_workspace_bytes("w2v2_sort_f32_index_workspace_bytes", P), dtype=torch.uint8, device=device)
+
+
+def sort_f32_index(keys, order_out=None, keys_out=None, workspace=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Stable ascending argsort of keys [P] f32 on the device (w2v2_sort_f32_index) -> (order int32 [P], keys_out): order
+    equals np.argsort(keys, kind="stable") exactly (-0.0 ties with +0.0, NaNs behind +inf in index order); keys_out (when
+    given) receives keys[order].  The order the host metrics take with two argsorts (ref: src/eval_metrics.py:54-79 through
+    roc_curve, :90-206)."""
+    P = _trial_count(keys, torch.float32, "sort_f32_index", "keys")
+    if order_out is not None and (order_out.dtype != torch.int32 or not order_out.is_contiguous() or order_out.numel() < P):
+        raise ValueError(f"sort_f32_index: order_out is a contiguous int32 tensor of at least P = {P} elements")
+    if keys_out is not None and (keys_out.dtype != torch.float32 or not keys_out.is_contiguous() or keys_out.numel() < P):
+        raise ValueError(f"sort_f32_index: keys_out is a contiguous float32 tensor of at least P = {P} elements")
+    _dev(keys, order_out, keys_out, workspace)
+    if order_out is None:
+        order_out = torch.empty(P, dtype=torch.int32, device=keys.device)
+    workspace = _byte_workspace(workspace, _workspace_bytes("w2v2_sort_f32_index_workspace_bytes", P), keys.device,
+                                "sort_f32_index", "sort_f32_index_workspace")
+    _lib.check(lib().w2v2_sort_f32_index(keys.data_ptr(), P, order_out.data_ptr(), _p(keys_out), workspace.data_ptr(),
+                                         stream()), "sort_f32_index")
+    return order_out, keys_out
+
+
+def trial_metrics_workspace(P: int, device) -> torch.Tensor:
+    return torch.empty(_workspace_bytes("w2v2_trial_metrics_workspace_bytes", P), dtype=torch.uint8, device=device)
+
+
+def trial_metrics(scores, labels, c_miss=1, c_fa=1, p_target=0.05, out=None, workspace=None) -> torch.Tensor:
+    """EER / minDCF of scores [P] f32 and labels [P] uint8 (0 / 1), both on the device (w2v2_trial_metrics; ref:
+    src/eval_metrics.py:54-79 calculate_eer, :90-206 calculate_mdc) -> out [8] float64 on the device, in the order of
+    TRIAL_METRICS_FIELDS.  With NaN scores (n_nan > 0) or one class absent the
+    other fields are unspecified: evaluation.speaker.device_scoring.metrics_device answers those on the host."""
+    if c_miss < 1:                                      # calculate_mdc's own errors
+        raise ValueError(f"c_miss={c_miss} should be >= 1")
+    if c_fa < 1:
+        raise ValueError(f"c_fa={c_fa} should be >= 1")
+    if p_target < 0 or p_target > 1:
+        raise ValueError(f"p_target={p_target} should be between 0 and 1")
+    P = _trial_count(scores, torch.float32, "trial_metrics", "scores")
+    if _trial_count(labels, torch.uint8, "trial_metrics", "labels") != P:
+        raise ValueError(f"trial_metrics: one label per score (P = {P})")
+    if out is not None and (out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < 8):
+        raise ValueError("trial_metrics: out is a contiguous float64 tensor of at least 8 elements")
+    _dev(scores, labels, out, workspace)
+    if out is None:
+        out = torch.empty(8, dtype=torch.float64, device=scores.device)
+    workspace = _byte_workspace(workspace, _workspace_bytes("w2v2_trial_metrics_workspace_bytes", P), scores.device,
+                                "trial_metrics", "trial_metrics_workspace")
+    _lib.check(lib().w2v2_trial_metrics(scores.data_ptr(), labels.data_ptr(), P, float(c_miss), float(c_fa), float(p_target),
+                                        out.data_ptr(), workspace.data_ptr(), stream()), "trial_metrics")
+    return out
