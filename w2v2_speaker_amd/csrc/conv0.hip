@@ -19,7 +19,9 @@
 // The waveform chunk of a block is staged in LDS once and read by broadcast (every thread of the
 // block needs the same 10-sample window for a given frame); threads map to adjacent channels so the
 // channels-last stores are fully coalesced (512 B per frame per block).
-#include "common.h"
+// Also here: w2v2_col2im, the data gradient of the strided conv layers behind layer 0 (the unfrozen feature extractor) --
+// the adjoint of tap_gather.h with zero padding at pad = 0 -- and the unpacking of their weight gradients.
+#include "tap_gather.h"
 #include <stdlib.h>
 
 constexpr int C0_FRAMES = 128;   // frames per block
@@ -871,44 +873,11 @@ extern "C" int w2v2_conv0_bwd(const float* wav, const float* w, const float* mea
   return 0;
 }
 
-// col2im of a strided Conv1d data gradient: col [B*Lout][k*Cin] (rows = output frames, K index = tap*Cin+ci)
-// -> dx [B][Lin][Cin], dx[b][r][ci] = sum over (l, tap) with stride*l + tap == r.  Every dx element written.
-template <typename T>
-__global__ void col2im_kernel(const T* __restrict__ col, T* __restrict__ dx, int B, int Lin, int Lout, int Cin,
-                              int k, int stride) {
-  const int nch = Cin >> 3;
-  const int64_t total = (int64_t)B * Lin * nch;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int ch = (int)(i % nch);
-    const int64_t row = i / nch;
-    const int b = (int)(row / Lin), r = (int)(row - (int64_t)b * Lin);
-    float acc[8] = {};
-    for (int tap = 0; tap < k; ++tap) {
-      const int t = r - tap;
-      if (t < 0 || t % stride != 0) continue;
-      const int l = t / stride;
-      if (l >= Lout) continue;
-      Vec8<T> v;
-      v.load(col + ((int64_t)b * Lout + l) * ((int64_t)k * Cin) + (int64_t)tap * Cin + ch * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] += v.v[e];
-    }
-    Vec8<T> o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o.v[e] = acc[e];
-    o.store(dx + row * Cin + ch * 8);
-  }
-}
-
 extern "C" int w2v2_col2im(const void* col, void* dx, int B, int Lin, int Lout, int Cin, int k, int stride, int dtype,
                            void* stream) {
   W2V2_REQUIRE(col && dx && B > 0 && Lin > 0 && Lout > 0 && Cin % 8 == 0 && k > 0 && stride > 0, "col2im: bad arguments");
-  const int64_t total = (int64_t)B * Lin * (Cin >> 3);
-  int nb = (int)(cdiv(total, 256) > 16384 ? 16384 : cdiv(total, 256));
-  W2V2_DISPATCH_ACT(dtype, "col2im",
-    hipLaunchKernelGGL(col2im_kernel<AT>, dim3(nb), dim3(256), 0, as_stream(stream), (const AT*)col, (AT*)dx, B, Lin, Lout, Cin, k, stride););
-  W2V2_CHECK_LAUNCH("col2im");
-  return 0;
+  const TapGeom g{B, Lin, Lout, Cin, k, stride, 1, 0};
+  W2V2_DISPATCH_ACT(dtype, "col2im", return (tap_adjoint_launch<AT, PadZero, false>("col2im", (const AT*)col, (AT*)dx, Cin, g, 0, stream)););
 }
 
 // gradient of the packed conv weight [Cout][k][Cin] (f32, from the dW GEMM) -> HF layout [Cout][Cin][k], ADDED

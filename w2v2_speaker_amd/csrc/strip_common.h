@@ -1,5 +1,6 @@
-// strip_common.h -- what the memory-bound channels-last kernels share (tdnn.hip: BatchNorm, SE, statistics pooling, the
-// reflect gathers; wav2spk.hip: InstanceNorm, gate, the zero gathers; score.hip: embed_stats; skinny.hip: the activations).
+// strip_common.h -- what the memory-bound channels-last kernels share (tdnn.hip: BatchNorm, SE, statistics pooling;
+// wav2spk.hip: InstanceNorm, gate; score.hip: embed_stats; skinny.hip: the activations; tap_gather.h: the tap gather and
+// its adjoint of tdnn.hip, wav2spk.hip and conv0.hip).
 // A strip is 128 columns of a [rows][C] tensor; a workgroup of 256 threads walks rows of one strip with one 16-byte vector
 // per thread.  Each kernel keeps its row walk, its arithmetic and its stores; everything else is here or in common.h:
 //   STRIP_CW / StripGeom<T>   the thread geometry: channels per thread, channel lanes x row lanes, rows in flight, vector types

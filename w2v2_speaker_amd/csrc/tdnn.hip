@@ -3,7 +3,8 @@
 // oracle/ecapa_oracle.py -- speechbrain is not part of the reference tree: parity unpinned).
 //
 //   TDNNBlock  = Conv1d("same", reflect padding, dilation) -> ReLU -> BatchNorm1d (batch statistics)
-//   conv       = im2col_reflect (taps gathered with reflection, channels-last) + GEMM (gemm.hip) [k = 1: GEMM only]
+//   conv       = im2col_reflect (taps gathered with reflection, channels-last: tap_gather.h with PadReflect, stride 1) +
+//                GEMM (gemm.hip) [k = 1: GEMM only]; col2im_reflect is the adjoint of the gather (tap_gather.h)
 //   SE block   = mean_t -> Linear -> ReLU -> Linear -> sigmoid -> per-(utterance, channel) gate
 //   Res2Net    = channel slices of one [B*T, C] tensor (row-strided views) with cumulative adds
 // and of the x-vector path (xvector.py; ref: src/lightning_modules/speaker/xvector.py -> speechbrain 0.5.x Xvector, as
@@ -13,7 +14,7 @@
 // Everything here is HBM-bound elementwise / reduction work over channels-last [B*T, C] activations; reductions
 // over rows are two-stage with a fixed order (deterministic, no atomics).  Row-strided operands (ld*) let the
 // Res2Net slices and the MFA concatenation live inside their parent tensors without copies.
-#include "strip_common.h"
+#include "tap_gather.h"
 
 constexpr int BN_AROWS = 256;     // rows one workgroup of the apply kernels walks (64 where that leaves CUs idle: bn_arows)
 
@@ -292,108 +293,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
       for (int y = 0; y < RL; ++y) t += csred[y][c];
       cs_partial[(int64_t)blockIdx.y * C + cc] = t;
     }
-  }
-}
-
-// ------------------------------------------------------------------------------------------ reflect-padded im2col
-// position t + (j - (k-1)/2) d, reflected at both ends (torch / speechbrain "reflect": ... 2 1 | 0 1 2 ... )
-__device__ __forceinline__ int reflect(int p, int Tn) {
-  if (p < 0) p = -p;
-  if (p >= Tn) p = 2 * (Tn - 1) - p;
-  return p;
-}
-// col[(b,t)][j*Cin + c] = x[b][reflect(t + off_j)][c];   one 16-byte vector per thread (8 / 4 channels)
-// LEN: variable-length batch (evaluation), utterance b has lens[b] valid frames out of Tn.  Taps reflect about the
-// utterance's OWN last frame lens[b] - 1, so a valid row reads rows < lens[b] only and equals the row of the fixed-length
-// form on the [1, lens[b], Cin] slice; rows t >= lens[b] are written as zeros (the products behind them then see no
-// padding content).  A workgroup whose 256 vectors all lie in padded rows of one utterance stores its zeros without
-// decoding or loading.
-template <typename T, bool LEN>
-__global__ void im2col_reflect_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ x2, int64_t ldx2,
-                                      T* __restrict__ col, int B, int Tn, int Cin, int k, int dil, LensArg<LEN> lens) {
-  constexpr int EPT = StripGeom<T>::EPT;              // one 16-byte vector per thread (StripGeom)
-  const int nch = Cin / EPT;
-  const int64_t total = (int64_t)B * Tn * k * nch;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    typename StripGeom<T>::Vec zero;                    // (LEN only)
-    if constexpr (LEN) {
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) zero.v[e] = 0.f;
-      const int64_t per_row = (int64_t)k * nch, i0 = i - threadIdx.x;     // i0: first vector of this workgroup's pass
-      const int64_t r0 = i0 / per_row, r1 = (min(i0 + (int64_t)blockDim.x, total) - 1) / per_row;   // first / last row here
-      const int b0 = (int)(r0 / Tn);
-      if (b0 == (int)(r1 / Tn) && (int)(r0 % Tn) >= lens[b0]) {     // (workgroup-uniform) nothing but padding
-        zero.store(col + i * EPT);                                 // col is dense: vector i sits at element i * EPT
-        continue;
-      }
-    }
-    const int ch = (int)(i % nch);
-    int64_t r = i / nch;
-    const int j = (int)(r % k);
-    r /= k;
-    const int t = (int)(r % Tn), b = (int)(r / Tn);
-    int L = Tn;
-    if constexpr (LEN) {
-      L = min(lens[b], Tn);
-      if (t >= L) {
-        zero.store(col + ((int64_t)b * Tn + t) * ((int64_t)k * Cin) + (int64_t)j * Cin + ch * EPT);
-        continue;
-      }
-    }
-    int src = reflect(t + (j - (k - 1) / 2) * dil, L);
-    // (the host guarantees padding < lens[b]; the clamp keeps a bad table inside the utterance's rows)
-    if constexpr (LEN) src = min(max(src, 0), L - 1);
-    typename StripGeom<T>::Vec v;
-    v.load(x + ((int64_t)b * Tn + src) * ldx + ch * EPT);
-    if (x2 != nullptr) {                   // taps of x + x2 (Res2Net: chunk input + previous chunk's output), summed here
-      typename StripGeom<T>::Vec w;
-      w.load(x2 + ((int64_t)b * Tn + src) * ldx2 + ch * EPT);
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) v.v[e] += w.v[e];
-    }
-    v.store(col + ((int64_t)b * Tn + t) * ((int64_t)k * Cin) + (int64_t)j * Cin + ch * EPT);
-  }
-}
-// dx[b][s][c] (+)= sum over (t, j) with reflect(t + off_j) == s of dcol[(b,t)][j*Cin + c]   (gather: deterministic)
-template <typename T>
-__global__ void col2im_reflect_kernel(const T* __restrict__ dcol, T* __restrict__ dx, int64_t lddx, int B, int Tn,
-                                      int Cin, int k, int dil, int accumulate) {
-  constexpr int EPT = StripGeom<T>::EPT;              // one 16-byte vector per thread (StripGeom)
-  const int nch = Cin / EPT;
-  const int64_t total = (int64_t)B * Tn * nch;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int ch = (int)(i % nch);
-    const int64_t row = i / nch;
-    const int s = (int)(row % Tn), b = (int)(row / Tn);
-    float acc[EPT] = {};
-    for (int j = 0; j < k; ++j) {
-      const int off = (j - (k - 1) / 2) * dil;
-      // sources t with reflect(t + off) == s: the direct one and the two mirror images
-      const int cand[3] = {s - off, -s - off, 2 * (Tn - 1) - s - off};
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const int t = cand[q];
-        if (t < 0 || t >= Tn) continue;
-        const int p = t + off;
-        const bool hit = q == 0 ? (p >= 0 && p < Tn) : q == 1 ? (p < 0) : (p >= Tn);
-        if (!hit || reflect(p, Tn) != s) continue;
-        typename StripGeom<T>::Vec v;
-        v.load(dcol + ((int64_t)b * Tn + t) * ((int64_t)k * Cin) + (int64_t)j * Cin + ch * EPT);
-#pragma unroll
-        for (int e = 0; e < EPT; ++e) acc[e] += v.v[e];
-      }
-    }
-    T* dst = dx + row * lddx + ch * EPT;
-    typename StripGeom<T>::Vec o;
-    if (accumulate) {
-      o.load(dst);
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) o.v[e] += acc[e];
-    } else {
-#pragma unroll
-      for (int e = 0; e < EPT; ++e) o.v[e] = acc[e];
-    }
-    o.store(dst);
   }
 }
 
@@ -687,13 +586,9 @@ static int im2col_reflect_impl(const char* name, const void* x, int64_t ldx, con
   W2V2_REQUIRE(x && col && B > 0 && T > 0 && Cin % 8 == 0 && k % 2 == 1 && dilation >= 1 && ldx % 8 == 0 &&
                    (x2 == nullptr || ldx2 % 8 == 0) && dilation * (k - 1) / 2 < T,
                "%s: bad arguments (odd k, Cin %% 8 == 0, padding < T)", name);
-  const int nb = blocks256((int64_t)B * T * k * (Cin / bn_align(dtype)));   // one 16-byte vector per thread
-  hipStream_t st = as_stream(stream);
+  const TapGeom g{B, T, T, Cin, k, 1, dilation, (k - 1) / 2 * dilation};
   W2V2_DISPATCH_LEN(lens, W2V2_DISPATCH_ACT(dtype, name,
-    hipLaunchKernelGGL((im2col_reflect_kernel<AT, LEN>), dim3(nb), dim3(256), 0, st, (const AT*)x, ldx, (const AT*)x2,
-                       ldx2, (AT*)col, B, T, Cin, k, dilation, lens);));
-  W2V2_CHECK_LAUNCH(name);
-  return 0;
+    return (tap_gather_launch<AT, PadReflect, LEN>(name, (const AT*)x, ldx, (const AT*)x2, ldx2, (AT*)col, lens, g, stream));));
 }
 extern "C" int w2v2_im2col_reflect(const void* x, int64_t ldx, void* col, int B, int T, int Cin, int k, int dilation,
                                    int dtype, void* stream) {
@@ -723,13 +618,9 @@ extern "C" int w2v2_col2im_reflect(const void* dcol, void* dx, int64_t lddx, int
   W2V2_REQUIRE(dcol && dx && B > 0 && T > 0 && Cin % 8 == 0 && k % 2 == 1 && dilation >= 1 && lddx % 8 == 0 &&
                    dilation * (k - 1) / 2 < T,
                "col2im_reflect: bad arguments");
-  const int nb = blocks256((int64_t)B * T * (Cin / bn_align(dtype)));
-  hipStream_t st = as_stream(stream);
+  const TapGeom g{B, T, T, Cin, k, 1, dilation, (k - 1) / 2 * dilation};
   W2V2_DISPATCH_ACT(dtype, "col2im_reflect",
-    hipLaunchKernelGGL(col2im_reflect_kernel<AT>, dim3(nb), dim3(256), 0, st, (const AT*)dcol, (AT*)dx,
-                           lddx, B, T, Cin, k, dilation, accumulate););
-  W2V2_CHECK_LAUNCH("col2im_reflect");
-  return 0;
+    return (tap_adjoint_launch<AT, PadReflect, true>("col2im_reflect", (const AT*)dcol, (AT*)dx, lddx, g, accumulate, stream)););
 }
 
 extern "C" int w2v2_add_strided(const void* a, int64_t lda, const void* b, int64_t ldb, void* y, int64_t ldy, int M,

@@ -5,8 +5,9 @@
 //                    utterance and channel, eps 1e-5) -> ReLU
 //   layer 0        = w2v2_conv1d_first: Cin = 1, straight from the waveform (no im2col: k = 10 taps per output)
 //   layers 1-4,
-//   aggregator     = w2v2_im2col_zero (taps gathered with zero padding, channels-last) + the exact-f32 GEMM (gemm_f32*.hip);
-//                    w2v2_col2im_zero is the exact adjoint of the gather, itself a gather (one writer per element)
+//   aggregator     = w2v2_im2col_zero (taps gathered with zero padding, channels-last: tap_gather.h with PadZero,
+//                    dilation 1) + the exact-f32 GEMM (gemm_f32*.hip); w2v2_col2im_zero is the exact adjoint of the gather,
+//                    itself a gather (one writer per element; tap_gather.h)
 //   temporal gate  = y = sigmoid(P) * x, P = X W^T + b a plain GEMM
 //   bias, ReLU     = w2v2_sum_bias_act_rows: the K range of a long convolution is cut into chunks (one batched GEMM), whose
 //                    partial products this kernel adds in a fixed order with the bias (and the aggregator's ReLU)
@@ -17,7 +18,7 @@
 // from its first frame -- never a function of T -- so a row of a padded batch (lens) equals the utterance run alone.
 // Variable-length forms (lens: device int32 [B]): every stage writes ZEROS into the rows past an utterance's own frame
 // count; those zeros are the zero padding of the next layer's gather, which therefore needs no lengths itself.
-#include "strip_common.h"
+#include "tap_gather.h"
 
 using InGeom = StripGeom<float>;       // the InstanceNorm workgroups: 32 channel lanes x 4 channels, 8 row lanes
 constexpr int IN_FB = 128;             // frames per statistics block
@@ -86,46 +87,6 @@ __global__ void conv1d_first_bwd_fold_kernel(const float* __restrict__ partial, 
   for (int i = 0; i < nblk; ++i) s += (double)partial[(int64_t)i * C * k + e];
   const int j = e / C, c = e - j * C;
   dw[c * k + j] += (float)s;
-}
-
-// ------------------------------------------------------------------------------------------ zero-padded gather / adjoint
-// col[(b,t)][j * Cin + c] = x[b][t * stride + j - pad][c], 0 outside [0, Tin)
-__global__ void im2col_zero_kernel(const float* __restrict__ x, int64_t ldx, float* __restrict__ col, int B, int Tin,
-                                   int Tout, int Cin, int k, int stride, int pad) {
-  const int C4 = Cin >> 2;
-  const int64_t K = (int64_t)k * Cin, total = (int64_t)B * Tout * k * C4;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C4) * 4;
-    const int64_t q = i / C4;
-    const int j = (int)(q % k);
-    const int64_t row = q / k;
-    const int b = (int)(row / Tout), t = (int)(row % Tout);
-    const int ti = t * stride + j - pad;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ti >= 0 && ti < Tin) v = ld4(x + ((int64_t)b * Tin + ti) * ldx + c);
-    st4(col + row * K + (int64_t)j * Cin + c, v.x, v.y, v.z, v.w);
-  }
-}
-// dx[b][ti][c] = sum over the (t, j) with t * stride + j - pad == ti of dcol[(b,t)][j * Cin + c], taps in ascending order
-__global__ void col2im_zero_kernel(const float* __restrict__ dcol, float* __restrict__ dx, int64_t lddx, int B, int Tin,
-                                   int Tout, int Cin, int k, int stride, int pad) {
-  const int C4 = Cin >> 2;
-  const int64_t K = (int64_t)k * Cin, total = (int64_t)B * Tin * C4;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C4) * 4;
-    const int64_t row = i / C4;
-    const int b = (int)(row / Tin), ti = (int)(row % Tin);
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < k; ++j) {
-      const int u = ti + pad - j;
-      if (u < 0 || u % stride != 0) continue;
-      const int t = u / stride;
-      if (t >= Tout) continue;
-      const float4 v = ld4(dcol + ((int64_t)b * Tout + t) * K + (int64_t)j * Cin + c);
-      acc[0] += v.x; acc[1] += v.y; acc[2] += v.z; acc[3] += v.w;
-    }
-    st4(dx + row * lddx + c, acc[0], acc[1], acc[2], acc[3]);
-  }
 }
 
 // ------------------------------------------------------------------------------------------ InstanceNorm1d + ReLU
@@ -396,22 +357,17 @@ extern "C" int w2v2_im2col_zero(const float* x, int64_t ldx, float* col, int B, 
   W2V2_REQUIRE(x && col && B > 0 && Cin > 0 && Cin % 4 == 0 && ldx >= Cin && ldx % 4 == 0 &&
                    conv_geom_ok(Tin, Tout, k, stride, pad),
                "im2col_zero: bad arguments (Cin, ldx multiples of 4; Tout = (Tin + 2 pad - k) / stride + 1)");
-  const int nb = blocks256((int64_t)B * Tout * k * (Cin >> 2));
-  hipLaunchKernelGGL(im2col_zero_kernel, dim3(nb), dim3(256), 0, as_stream(stream), x, ldx, col, B, Tin, Tout, Cin, k,
-                     stride, pad);
-  W2V2_CHECK_LAUNCH("im2col_zero");
-  return 0;
+  return tap_gather_launch<float, PadZero, false>("im2col_zero", x, ldx, nullptr, 0, col, nullptr,
+                                                  TapGeom{B, Tin, Tout, Cin, k, stride, 1, pad}, stream);
 }
 extern "C" int w2v2_col2im_zero(const float* dcol, float* dx, int64_t lddx, int B, int Tin, int Tout, int Cin, int k,
                                 int stride, int pad, void* stream) {
   W2V2_REQUIRE(dcol && dx && B > 0 && Cin > 0 && Cin % 4 == 0 && lddx >= Cin && lddx % 4 == 0 &&
                    conv_geom_ok(Tin, Tout, k, stride, pad),
                "col2im_zero: bad arguments (Cin, lddx multiples of 4; Tout = (Tin + 2 pad - k) / stride + 1)");
-  const int nb = blocks256((int64_t)B * Tin * (Cin >> 2));
-  hipLaunchKernelGGL(col2im_zero_kernel, dim3(nb), dim3(256), 0, as_stream(stream), dcol, dx, lddx, B, Tin, Tout, Cin, k,
-                     stride, pad);
-  W2V2_CHECK_LAUNCH("col2im_zero");
-  return 0;
+  const TapGeom g{B, Tin, Tout, Cin, k, stride, 1, pad};
+  return stride == 1 ? tap_adjoint_launch<float, PadZero, true>("col2im_zero", dcol, dx, lddx, g, 0, stream)   // the aggregator
+                     : tap_adjoint_launch<float, PadZero, false>("col2im_zero", dcol, dx, lddx, g, 0, stream);
 }
 
 // forward: {mean, its low part, centred squares, 0} per (utterance, block, channel); backward: two sums

@@ -1326,26 +1326,31 @@ class Plan:
         self.g_layer[l]["dWqkv"]()
         ops.colsum(self._gsets[l % len(self._gsets)]["DQKV"], self.store.qkv(l, "g", "bias"), self.M, 3 * self.cfg.hidden_size)
 
+    def _conv_layer_grads(self, i: int) -> None:
+        """Conv layer i >= 1 of the feature extractor, from d(pre-activation) in place of its output gradient: the weight
+        gradient (dW GEMM into dwp, unpacked into the HF layout and added) and the data gradient (dX GEMM into col,
+        folded into dconv[i - 1] by the adjoint of the tap gather)."""
+        cfg = self.cfg
+        self.dwp.zero_()
+        self.g_conv_dw[i]()
+        ops.unpack_conv_grad(self.dwp, self.store.mg(f"feature_extractor.conv_layers.{i}.conv.weight"))
+        self.g_conv_dx[i]()
+        ops.col2im(self.col, self.dconv[i - 1], self.Bc, self.lens[i - 1], self.lens[i], cfg.conv_dim[i - 1],
+                   cfg.conv_kernel[i], cfg.conv_stride[i])
+
     def _backward_cnn(self) -> None:
         """Backward of the 7-layer conv feature extractor (HF:382-419) -- the reference's
         ``completely_freeze_feature_extractor: false`` ablation.  self.dn holds d(conv[6] output)."""
-        cfg, st, B = self.cfg, self.store, self.Bc
+        cfg, st = self.cfg, self.store
         C = cfg.conv_dim
-        cins = (1,) + tuple(C[:-1])
         mg = st.mg
         if self.ln_conv:
             self._backward_cnn_layer_norm()
             return
         for i in reversed(range(1, len(C))):
-            k, sd, ci, co = cfg.conv_kernel[i], cfg.conv_stride[i], cins[i], C[i]
-            gout = self.dn if i == len(C) - 1 else self.dconv[i]
-            gv = gout.view(-1, co)
-            ops.gelu_bwd(gv, self.conv_pre[i].view(-1, co), gv)            # d(pre-activation), in place
-            self.dwp.zero_()
-            self.g_conv_dw[i]()
-            ops.unpack_conv_grad(self.dwp, mg(f"feature_extractor.conv_layers.{i}.conv.weight"))
-            self.g_conv_dx[i]()
-            ops.col2im(self.col, self.dconv[i - 1], B, self.lens[i - 1], self.lens[i], ci, k, sd)
+            gv = (self.dn if i == len(C) - 1 else self.dconv[i]).view(-1, C[i])
+            ops.gelu_bwd(gv, self.conv_pre[i].view(-1, C[i]), gv)          # d(pre-activation), in place
+            self._conv_layer_grads(i)
         ops.conv0_bwd(self._wav, st.mp("feature_extractor.conv_layers.0.conv.weight"), self.stats0,
                       st.mp("feature_extractor.conv_layers.0.layer_norm.weight"),
                       st.mp("feature_extractor.conv_layers.0.layer_norm.bias"), self.dconv[0], self.sums0,
@@ -1359,24 +1364,17 @@ class Plan:
         over the channels -> GELU.  Layers 6 .. 1: LayerNorm-GELU backward from the saved pre-norm z (in place on the
         incoming gradient; it also yields the LayerNorm's and the conv bias's gradients), then the same weight- and
         data-gradient products as the group-norm family.  Layer 0 recomputes its convolution from the waveform."""
-        cfg, st, B = self.cfg, self.store, self.Bc
+        cfg, st = self.cfg, self.store
         C = cfg.conv_dim
-        cins = (1,) + tuple(C[:-1])
         mp, mg = st.mp, st.mg
         fe = "feature_extractor.conv_layers."
         for i in reversed(range(1, len(C))):
-            k, sd, ci, co = cfg.conv_kernel[i], cfg.conv_stride[i], cins[i], C[i]
-            gout = self.dn if i == len(C) - 1 else self.dconv[i]
-            gv = gout.view(-1, co)
-            ops.layernorm_gelu_bwd(gv, self.conv_pre[i].view(-1, co), mp(fe + f"{i}.layer_norm.weight"),
+            gv = (self.dn if i == len(C) - 1 else self.dconv[i]).view(-1, C[i])
+            ops.layernorm_gelu_bwd(gv, self.conv_pre[i].view(-1, C[i]), mp(fe + f"{i}.layer_norm.weight"),
                                    mp(fe + f"{i}.layer_norm.bias"), gv, mg(fe + f"{i}.layer_norm.weight"),
                                    mg(fe + f"{i}.layer_norm.bias"), mg(fe + f"{i}.conv.bias") if cfg.conv_bias else None,
                                    self.lng_ws)
-            self.dwp.zero_()
-            self.g_conv_dw[i]()
-            ops.unpack_conv_grad(self.dwp, mg(fe + f"{i}.conv.weight"))
-            self.g_conv_dx[i]()
-            ops.col2im(self.col, self.dconv[i - 1], B, self.lens[i - 1], self.lens[i], ci, k, sd)
+            self._conv_layer_grads(i)
         ops.conv0_layernorm_gelu_bwd(self._wav, mp(fe + "0.conv.weight"), mp(fe + "0.conv.bias") if cfg.conv_bias else None,
                                      mp(fe + "0.layer_norm.weight"), mp(fe + "0.layer_norm.bias"), self.dconv[0],
                                      mg(fe + "0.conv.weight"), mg(fe + "0.conv.bias") if cfg.conv_bias else None,
