@@ -751,6 +751,54 @@ int w2v2_score_frame_sets(const float* frames, int64_t ld, int64_t rows, int D,
                           const int32_t* sel /*int32 [P][2][W]: absolute row numbers*/, const int32_t* counts /*int32 [P][2]*/,
                           int W, int P, float* cos_out, float* score_out, void* stream);
 
+/* ---------------------------------------------------------------------------------- score normalisation (score_norm.hip)
+ * Adaptive score normalisation with a cohort (Z-, T- and S-norm; K = M gives the non-adaptive forms), between the scores
+ * above and the metrics below.  The project this one mirrors has none: THIS COMMENT IS THE DEFINITION, its oracle is
+ * float64 numpy.  Inputs: bank [N][D] f32 (the bank of w2v2_score_pairs), cohort [M][D] f32, pairs [P][2] int32 (column 0
+ * the enrolment side e, column 1 the test side t), the evaluator's mean / std and length_norm.
+ *   1. transform   u = (x - mean) / (std + 1e-12) when centring is on, then u / max(||u||, 1e-12) with length_norm: the
+ *                  transform of w2v2_score_pairs, for bank rows and cohort rows alike.
+ *   2. cosines     S[r][m] = u_r . c_m / (max(||u_r||, 1e-8) * max(||c_m||, 1e-8)): w2v2_gemm on f32 operands with
+ *                  W2V2_EPI_SCALE_RC, row_scale / col_scale = the inv_norm of w2v2_rows_transform.  S is never held
+ *                  whole: the host loops over blocks of bank rows and one caller-owned [rows_per_block][ldS] buffer.
+ *   3. statistics  mu[r] = mean of the K largest values of S[r][:], sd[r] = their unbiased std (ddof = 1), 2 <= K <= M.
+ *                  The top K is a multiset: with t the K-th largest value and g = #{v > t} the sum is
+ *                  sum_{v > t} v + (K - g) t, so ties at t do not matter.  -0.0 equals +0.0.  A NaN anywhere in the row
+ *                  gives mu = sd = NaN for that row only.
+ *   4. score       z_e = (c - mu[e]) / (sd[e] + 1e-12) with c the raw cosine of the trial, z_t likewise with t;
+ *                  mode 0 ("z") -> z_e, 1 ("t") -> z_t, 2 ("s") -> (z_e + z_t) / 2.  NOT mapped through (x + 1) / 2 and
+ *                  not clipped (it is unbounded, and clipping is not monotone).  An index outside [0, N) gives NaN for
+ *                  that trial only.
+ * Conventions of the trial scoring above: 16-byte vectors, D % 4 == 0, ld % 4 == 0, 64-bit row offsets, no atomics on
+ * global memory, no workgroup waits on another, fixed-order folds (equal inputs give equal bits), nothing allocated,
+ * all work on `stream`.
+ *
+ * Step 1 for `rows` rows of x [rows][ld]: out [rows][ld_out] = the transformed rows, inv_norm [rows] = 1 / max(||u||, 1e-8)
+ * of what was stored (the squares of a row are summed in double).  One pass over HBM (with length_norm a row is read a
+ * second time out of the cache).  mean / std: both NULL or both set, [D], 16-byte aligned.  out may be NULL only when
+ * neither centring nor length norm is asked for: only inv_norm is written and the product reads x itself.  out != x. */
+int w2v2_rows_transform(const float* x, int64_t ld, int rows, int D, const float* mean, const float* std, int length_norm,
+                        float* out, int64_t ld_out, float* inv_norm, void* stream);
+/* Step 3 for the R rows of S [R][ldS] (ldS >= M, ldS % 4 == 0, 16-byte aligned; the columns behind M are never read).
+ * One workgroup per row: an exact radix select of the K-th largest value over the order-preserving u32 image of the
+ * values (four 8-bit histogram passes in LDS, most significant byte first), then the tie-aware sum and the centred second
+ * moment about that mean, both in double, folded in a fixed order.  A row of at most w2v2_topk_stats_lds_keys() values is
+ * staged in LDS; a longer one is re-read (from L2) in every pass; both routes give the same bits.  2 <= K <= M < 2^24,
+ * anything else is an argument error. */
+int w2v2_topk_stats_lds_keys(void);
+int w2v2_topk_stats(const float* S, int64_t ldS, int R, int M, int K, float* mu, float* sd, void* stream);
+/* Step 4: cos [P] as w2v2_score_pairs leaves it, pairs [P][2], mu / sd [N] of step 3 -> score_out [P].  One trial per
+ * thread, in double, rounded once.  sd = 0 gives what the formula gives (a division by 1e-12), never a fault. */
+int w2v2_score_pairs_norm(const float* cos, const int32_t* pairs, int P, const float* mu, const float* sd, int N, int mode,
+                          float* score_out, void* stream);
+/* The cohort builder: out [S][ld_out] = the mean of the bank rows of each of S segments (speakers).  order [N] int32 lists
+ * the rows of bank [N][ld] grouped by segment, offsets [S + 1] int32 (offsets[0] = 0, offsets[S] = N) cuts it.  One
+ * workgroup per segment and 128-dimension strip; row lane y of eight folds rows order[begin + y], order[begin + y + 8], ...
+ * in that sequence in double, the lanes are folded in lane order.  An empty segment is the host's argument error; on the
+ * device an empty or out-of-range segment, or a row number outside [0, N), is not dereferenced: that mean is NaN. */
+int w2v2_segment_mean(const float* bank, int64_t ld, int N, int D, const int32_t* order, const int32_t* offsets, int S,
+                      float* out, int64_t ld_out, void* stream);
+
 /* ---------------------------------------------------------------------------------- trial metrics (metrics.hip)
  * What follows the scores: ROC / EER / minDCF of a trial list without the P scores leaving the device.  No kernel waits
  * on another workgroup (no look-back, no flag, no cooperative launch): every order between workgroups is a launch

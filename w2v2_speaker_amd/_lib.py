@@ -183,6 +183,11 @@ _SIGS = {
     "w2v2_embed_stats": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "w2v2_score_pairs": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "w2v2_score_frame_sets": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "w2v2_rows_transform": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp]),
+    "w2v2_topk_stats_lds_keys": (c_i32, []),
+    "w2v2_topk_stats": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "w2v2_score_pairs_norm": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "w2v2_segment_mean": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
     "w2v2_sort_tile": (c_i32, []),
     "w2v2_sort_f32_index_workspace_bytes": (c_i64, [c_i64]),
     "w2v2_sort_f32_index": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),

@@ -66,6 +66,28 @@ def compute_non_pooled_cosine_scores(left_tensor: torch.Tensor, right_tensor: to
     return torch.mean(score).detach().cpu().numpy().tolist()
 
 
+def cohort_stats_host(bank: torch.Tensor, cohort: torch.Tensor, top_k: int):
+    """The cohort statistics of score normalisation in plain torch on the tensors' own device (f32 on the CPU for the host
+    evaluator): every row of the already transformed ``bank`` [N, D] against every row of the transformed ``cohort``
+    [M, D] as torch's cosine_similarity forms it (each norm clamped at 1e-8 on its own), then the mean and the unbiased std
+    of the ``top_k`` largest cosines of each row -> (mu [N], sd [N]).  The definition: include/w2v2_hip.h, "score
+    normalisation"; the reference project has no such stage."""
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 2 <= top_k <= cohort.shape[0]:
+        raise ValueError(f"score_norm: top_k = {top_k!r} outside [2, M = {cohort.shape[0]}]")
+    un = bank / torch.linalg.vector_norm(bank, dim=1, keepdim=True).clamp_min(1e-8)
+    cn = cohort / torch.linalg.vector_norm(cohort, dim=1, keepdim=True).clamp_min(1e-8)
+    top = torch.topk(torch.matmul(un, cn.t()), top_k, dim=1).values
+    return top.mean(dim=1), top.std(dim=1)
+
+
+def normalise_scores(cos: torch.Tensor, mu_e, sd_e, mu_t, sd_t, mode: str) -> torch.Tensor:
+    """z_e = (c - mu_e) / (sd_e + 1e-12), z_t likewise; "z" -> z_e, "t" -> z_t, "s" -> (z_e + z_t) / 2."""
+    if mode not in ("z", "t", "s"):
+        raise ValueError(f"score_norm: mode={mode!r}: 'z', 't' or 's'")
+    ze, zt = (cos - mu_e) / (sd_e + 1e-12), (cos - mu_t) / (sd_t + 1e-12)
+    return ze if mode == "z" else (zt if mode == "t" else (ze + zt) / 2)
+
+
 class CosineDistanceEvaluator:
     """ref: cosine_distance.py:66-201.  Defaults = config/evaluator/cosine_distance.yaml (no centering, no length
     norm, max_num_training_samples 0); the non-default branches follow the reference as well: centering is
@@ -144,7 +166,42 @@ class CosineDistanceEvaluator:
             combined.append(score)
         return combined
 
-    def evaluate(self, pairs: List[EvaluationPair], samples: List[EmbeddingSample]):
+    def _compute_normalised_scores(self, pairs: List[Tuple[EmbeddingSample, EmbeddingSample]], score_norm) -> List[float]:
+        """The score-normalised form of ``_compute_prediction_scores`` in plain torch f32 on the CPU (matmul, topk, mean,
+        std): ``score_norm`` carries ``cohort`` [M, D], ``top_k`` and ``mode`` (device_scoring.ScoreNorm).  Pooled
+        embeddings only.  The cohort takes the evaluator's centring / length norm, as the embeddings do."""
+        first = pairs[0][0].embedding
+        if isinstance(first, list):
+            raise NotImplementedError("score_norm takes one embedding per sample: a normalised ensemble score is not defined")
+        if len(first.shape) == 2:
+            raise NotImplementedError("score_norm takes pooled embeddings: a frame set has no single cohort cosine")
+        rows, order = {}, []
+        for a, b in pairs:
+            for smp in (a, b):
+                if id(smp) not in rows:
+                    rows[id(smp)] = len(order)
+                    order.append(smp)
+        bank = torch.stack([torch.as_tensor(s.embedding) for s in order]).float()
+        cohort = torch.as_tensor(score_norm.cohort).detach().to("cpu", torch.float32)
+        if self.center_before_scoring:
+            if self.mean is None or self.std is None:
+                raise TypeError("center_before_scoring=True but fit_parameters() has not been called "
+                                "(mean / std are None)")
+            bank = center_batch(bank, self.mean, self.std)
+            cohort = center_batch(cohort, self.mean, self.std)
+        if self.length_norm_before_scoring:
+            bank = length_norm_batch(bank)
+            cohort = length_norm_batch(cohort)
+        mu, sd = cohort_stats_host(bank, cohort, score_norm.top_k)
+        e = torch.tensor([rows[id(a)] for a, _ in pairs])
+        t = torch.tensor([rows[id(b)] for _, b in pairs])
+        cos = torch.nn.functional.cosine_similarity(bank[e], bank[t], dim=1, eps=1e-8)
+        return normalise_scores(cos, mu[e], sd[e], mu[t], sd[t], score_norm.mode).detach().cpu().numpy().tolist()
+
+    def evaluate(self, pairs: List[EvaluationPair], samples: List[EmbeddingSample], score_norm=None):
+        """``score_norm`` (device_scoring.ScoreNorm, default None: the reference's evaluation, unchanged): the trial scores
+        are normalised with its cohort first; they are then unbounded and go to the metrics as they are, NOT through
+        ``(s+1)/2`` and the clip."""
         sample_map = {}
         for sample in samples:
             if sample.sample_id in sample_map:
@@ -157,7 +214,10 @@ class CosineDistanceEvaluator:
                 return {"eer": -1, "eer_threshold": -1, "mdc": -1, "mdc_threshold": -1}
             gt.append(1 if pair.same_speaker else 0)
             pp.append((sample_map[pair.sample1_id], sample_map[pair.sample2_id]))
-        scores = np.clip((np.array(self._compute_prediction_scores(pp)) + 1) / 2, 0, 1).tolist()
+        if score_norm is not None:
+            scores = self._compute_normalised_scores(pp, score_norm)
+        else:
+            scores = np.clip((np.array(self._compute_prediction_scores(pp)) + 1) / 2, 0, 1).tolist()
         try:
             eer, eer_threshold = calculate_eer(gt, scores, pos_label=1)
         except (ValueError, ZeroDivisionError) as e:       # reference falls back to a very bad score
@@ -187,17 +247,20 @@ class CosineDistanceEvaluator:
         ``[sum T, D]`` frame bank (the non-pooled form; no centring / length norm there, as in the reference).  Scores are
         computed by the kernels of csrc/score.hip and one array of P (ensemble of n: n * P) floats is copied to the host;
         EER / minDCF as in ``evaluate``.  ``last_bank_scoring`` keeps the scores and the copy's size.  (The form that can
-        leave the metrics on the device as well: ``evaluate_bank_metrics``.)"""
+        leave the metrics on the device as well, and that takes ``score_norm``: ``evaluate_bank_metrics``.)"""
         return self.evaluate_bank_metrics(pairs, keys, bank, frame_offsets, metrics="host")
 
     def evaluate_bank_metrics(self, pairs: List[EvaluationPair], keys: List[str], bank, frame_offsets=None,
-                              metrics: str = "host"):
+                              metrics: str = "host", score_norm=None):
         """``evaluate_bank`` with the choice of where ROC / EER / minDCF are computed.  ``metrics="host"``: exactly
         ``evaluate_bank``.  ``metrics="device"`` (one bank or a frame bank): the scores stay on the device too, the metrics
         are computed there (csrc/metrics.hip, device_scoring.metrics_device) and eight doubles cross;
         ``last_bank_scoring`` then has ``scores`` None and ``host_copy_floats`` 0, and ``last_bank_metrics`` says which
         path answered.  An ensemble's members are combined on the host, so ``metrics="device"`` raises
-        NotImplementedError for one; any other value of ``metrics`` raises ValueError."""
+        NotImplementedError for one; any other value of ``metrics`` raises ValueError.  ``score_norm``
+        (device_scoring.ScoreNorm; one pooled bank only, anything else raises NotImplementedError): the scores are
+        normalised on the device with its cohort (csrc/score_norm.hip) before they cross or reach the metrics; they are
+        unbounded, not mapped to [0, 1]."""
         from .device_scoring import TrialIndex, host_metrics, metrics_device, score_trials_device
         if metrics not in ("host", "device"):
             raise ValueError(f"metrics={metrics!r}: 'host' or 'device'")
@@ -215,7 +278,7 @@ class CosineDistanceEvaluator:
         self.last_bank_scoring = score_trials_device(
             bank, index, mean=self.mean if centre else None, std=self.std if centre else None,
             length_norm=self.length_norm_before_scoring and frame_offsets is None, frame_offsets=frame_offsets,
-            keep_on_device=metrics == "device")
+            keep_on_device=metrics == "device", **({} if score_norm is None else {"score_norm": score_norm}))
         if metrics == "device":
             record = []
             res = metrics_device(self.last_bank_scoring.device_scores, index, record=record)

@@ -127,9 +127,48 @@ def draw_frame_sets(frame_counts: Sequence[int], trial_index: TrialIndex, cap: i
     return sel, counts
 
 
+SCORE_NORM_MODES = ("z", "t", "s")
+
+
+class ScoreNorm:
+    """Adaptive score normalisation of a trial list with a cohort (include/w2v2_hip.h, "score normalisation"): ``cohort``
+    an ``[M, D]`` float32 tensor of impostor embeddings (speaker_mean_cohort builds one), ``top_k`` the K largest cohort
+    cosines of each side that give its mean and std (``top_k = M``: the non-adaptive norm), ``mode`` "z" (the enrolment
+    side), "t" (the test side) or "s" (the mean of both).  The normalised score is unbounded: it is NOT mapped through
+    ``(x + 1) / 2`` and not clipped.  The cohort goes through the evaluator's own centring / length norm, as the bank does."""
+
+    def __init__(self, cohort: torch.Tensor, top_k: int, mode: str = "s"):
+        if mode not in SCORE_NORM_MODES:
+            raise ValueError(f"ScoreNorm: mode={mode!r}: 'z', 't' or 's'")
+        if not isinstance(cohort, torch.Tensor) or cohort.dim() != 2 or cohort.shape[0] < 2:
+            raise ValueError("ScoreNorm: cohort is an [M, D] tensor, M >= 2")
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 2 <= top_k <= cohort.shape[0]:
+            raise ValueError(f"ScoreNorm: top_k = {top_k!r} outside [2, M = {cohort.shape[0]}]")
+        self.cohort, self.top_k, self.mode = cohort, top_k, mode
+
+
+def speaker_mean_cohort(bank: torch.Tensor, labels: Sequence) -> torch.Tensor:
+    """The usual cohort: one mean embedding per speaker of ``bank`` [N, D] (a device tensor of training embeddings;
+    ``labels[r]`` = the speaker of row r, any hashable) -> [S, D] on the device, speakers in sorted label order
+    (w2v2_segment_mean).  The grouping -- a stable order of the rows by speaker and the segment offsets -- is built on the
+    host from the labels; every speaker named has at least one row by construction."""
+    labels = list(labels)
+    if not isinstance(bank, torch.Tensor) or bank.dim() != 2 or len(labels) != bank.shape[0] or not labels:
+        raise ValueError("speaker_mean_cohort: one label per bank row")
+    if len(labels) > np.iinfo(np.int32).max:
+        raise ValueError(f"{len(labels)} bank rows do not fit the int32 order table")
+    speakers = sorted(set(labels))
+    index = {s: i for i, s in enumerate(speakers)}
+    ids = np.fromiter((index[l] for l in labels), dtype=np.int64, count=len(labels))
+    order = np.argsort(ids, kind="stable").astype(np.int32)
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(ids, minlength=len(speakers)))]).astype(np.int32)
+    return ops.segment_mean(bank, _upload(order, bank.device), _upload(offsets, bank.device))
+
+
 @dataclass
 class DeviceScores:
-    """What score_trials_device hands back: ``scores`` float64 [P] in [0, 1] (what ``evaluate`` feeds the metrics),
+    """What score_trials_device hands back: ``scores`` float64 [P] in [0, 1] (what ``evaluate`` feeds the metrics; with
+    ``score_norm`` the normalised scores, unbounded),
     ``host_copy_floats`` the number of floats that crossed to the host (P, or n * P for an ensemble of n),
     ``bank_floats`` the elements of the bank(s) that stayed on the device.  With ``keep_on_device`` the scores did not
     cross: ``scores`` is None, ``host_copy_floats`` 0 and ``device_scores`` the float32 [P] tensor the kernel wrote."""
@@ -141,17 +180,24 @@ class DeviceScores:
 
 def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial_index: TrialIndex, *, mean=None, std=None,
                         length_norm: bool = False, frame_offsets=None, cap: int = FRAME_CAP,
-                        keep_on_device: bool = False) -> DeviceScores:
+                        keep_on_device: bool = False, score_norm: Optional[ScoreNorm] = None) -> DeviceScores:
     """Score ``trial_index`` over ``bank`` on the device.  bank: an ``[N, D]`` device tensor; a list of those (an
     ensemble: every member scored into one ``[n, P]`` buffer, combined on the host in the reference's order
     ``score += s_i * (1 / n)`` as Python floats, ref: cosine_distance.py:172-181); or, with ``frame_offsets`` ([N + 1],
     utterance r = rows frame_offsets[r] .. frame_offsets[r + 1]), a ragged ``[sum T, D]`` frame bank scored as the
     non-pooled form (frames drawn by draw_frame_sets from the global ``random``; no centring, no length norm, as in the
     reference).  One device -> host copy; none with ``keep_on_device`` (one bank or a frame bank: the scores stay
-    where ``metrics_device`` reads them; an ensemble is combined on the host and cannot stay)."""
+    where ``metrics_device`` reads them; an ensemble is combined on the host and cannot stay).  ``score_norm`` (one pooled
+    bank only): the scores are the normalised ones (ops.cohort_stats + ops.score_pairs_norm), computed where the bank is."""
     members = list(bank) if isinstance(bank, (list, tuple)) else [bank]
     if not members or not all(isinstance(b, torch.Tensor) for b in members):
         raise ValueError("bank is a device tensor or a non-empty list of them")
+    if score_norm is not None and len(members) != 1:
+        raise NotImplementedError("score_norm takes one bank: the members of an ensemble are combined on the host, and a "
+                                  "normalised ensemble score is not defined")
+    if score_norm is not None and frame_offsets is not None:
+        raise NotImplementedError("score_norm takes pooled embeddings: a frame bank has no single cohort cosine per "
+                                  "utterance")
     dev = members[0].device
     P = len(trial_index)
     if keep_on_device and len(members) != 1:
@@ -182,6 +228,14 @@ def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial
     for i, b in enumerate(members):
         ops.score_pairs(b, table, mean, std, length_norm, cos[i], score[i])
     bank_floats = sum(b.numel() for b in members)
+    if score_norm is not None:
+        cohort = score_norm.cohort.to(dev, torch.float32).contiguous()
+        mu, sd = ops.cohort_stats(members[0], cohort, score_norm.top_k, mean, std, length_norm)
+        normed = ops.score_pairs_norm(cos[0], table, mu, sd, score_norm.mode)
+        if keep_on_device:
+            return DeviceScores(None, 0, bank_floats, normed)
+        host = normed.cpu().numpy()
+        return DeviceScores(host.astype(np.float64), host.size, bank_floats)
     if n == 1 and keep_on_device:
         return DeviceScores(None, 0, bank_floats, score[0])
     if n == 1:

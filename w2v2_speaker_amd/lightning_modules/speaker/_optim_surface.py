@@ -132,9 +132,11 @@ class EmbeddingEvaluation:
             raise ValueError("expecting a batch size of 1 for evaluating speaker embeddings")   # ref: :468-469
         return self.validation_step(batch, batch_idx)
 
-    def _evaluate_embeddings(self, outputs: List[dict], pairs):
+    def _evaluate_embeddings(self, outputs: List[dict], pairs, score_norm=None):
         samples = [EmbeddingSample(sample_id=k, embedding=o["embedding"][i]) for o in outputs
                    for i, k in enumerate(o["sample_id"])]
+        if score_norm is not None:
+            return self.evaluator.evaluate(pairs, samples, score_norm=score_norm)
         return self.evaluator.evaluate(pairs, samples)
 
     def validation_epoch_end(self, outputs: List[dict]):
@@ -143,13 +145,16 @@ class EmbeddingEvaluation:
     def test_epoch_end(self, outputs: List[dict]):
         return self._evaluate_embeddings(outputs, self.test_pairs)
 
-    def evaluate_trials(self, pairs, input_by_key, *, scoring: str = "host", metrics: str = "host", **batching) -> dict:
+    def evaluate_trials(self, pairs, input_by_key, *, scoring: str = "host", metrics: str = "host", score_norm=None,
+                        **batching) -> dict:
         """Score a trial list: every utterance the pairs name (key -> one input of compute_speaker_embeddings in
         ``input_by_key``) is embedded once with compute_speaker_embeddings (``batching``: its keyword arguments) and the
         module's evaluator scores the pairs -- the same dict as test_epoch_end over the batch-size-1 test loop.
         ``scoring="device"``: the embeddings stay on the device as one bank and the evaluator's ``evaluate_bank`` scores
         it there (pooled embeddings only).  ``metrics="device"`` (with ``scoring="device"`` only): EER / minDCF are
-        computed on the device as well (``evaluate_bank_metrics(metrics="device")``) and eight doubles come back."""
+        computed on the device as well (``evaluate_bank_metrics(metrics="device")``) and eight doubles come back.
+        ``score_norm`` (evaluation.speaker.device_scoring.ScoreNorm): the scores are normalised with its cohort, on the
+        device with ``scoring="device"`` and in plain torch on the CPU otherwise."""
         if scoring not in ("host", "device"):
             raise ValueError(f"scoring={scoring!r}: 'host' or 'device'")
         if metrics not in ("host", "device"):
@@ -162,8 +167,10 @@ class EmbeddingEvaluation:
             if embs[0].dim() != 2:
                 raise NotImplementedError("scoring='device' takes pooled embeddings; score a no-pooling head's frames with "
                                           "evaluator.evaluate_bank(frame_offsets=)")
-            return self.evaluator.evaluate_bank_metrics(pairs, keys, torch.cat(embs).detach().float(), metrics=metrics)
-        return self._evaluate_embeddings([{"embedding": torch.cat(embs).detach().to("cpu"), "sample_id": keys}], pairs)
+            extra = {} if score_norm is None else {"score_norm": score_norm}
+            return self.evaluator.evaluate_bank_metrics(pairs, keys, torch.cat(embs).detach().float(), metrics=metrics, **extra)
+        return self._evaluate_embeddings([{"embedding": torch.cat(embs).detach().to("cpu"), "sample_id": keys}], pairs,
+                                         score_norm)
 
     @property
     def bucket_plans_built(self) -> int:

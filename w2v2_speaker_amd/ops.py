@@ -1438,6 +1438,173 @@ def score_frame_sets(frames, sel, counts, cos_out=None, score_out=None) -> Tuple
     return cos_out, score_out
 
 
+# ---------------------------------------------------------------------------------------------- score normalisation (score_norm.hip)
+TOPK_LDS_KEYS = 8192                    # longest row w2v2_topk_stats stages in LDS (csrc/score_norm.hip TK_LDS_KEYS)
+TOPK_MAX_M = 2 ** 24                    # M of w2v2_topk_stats stays below this
+SCORE_NORM_MODES = {"z": 0, "t": 1, "s": 2}
+COHORT_WORKSPACE_BYTES = 256 << 20      # the default block of cohort_stats keeps its [rows_per_block, ldS] buffer at or below this
+
+
+def _centring(mean, std, D: int, what: str) -> None:
+    if (mean is None) != (std is None):
+        raise ValueError(f"{what}: mean and std are given together or not at all")
+    for v in (mean, std):
+        if v is not None and (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.shape != (D,)
+                              or not v.is_contiguous()):
+            raise ValueError(f"{what}: mean / std are contiguous float32 [{D}]")
+
+
+def _top_k(K, M: int, what: str) -> int:
+    if isinstance(K, bool) or not isinstance(K, int) or not 2 <= K <= M:
+        raise ValueError(f"{what}: K = {K!r} outside [2, M = {M}]")
+    return K
+
+
+def rows_transform(x, mean=None, std=None, length_norm: bool = False, out=None,
+                   inv_norm=None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    """The evaluator's transform of the rows of x [rows, D] (w2v2_rows_transform: z-score with mean / std, then
+    F.normalize with length_norm, as w2v2_score_pairs applies them) -> (u [rows, D], inv_norm [rows] = 1 / max(|u|, 1e-8)).
+    Without centring and length norm nothing is copied: u is None (the rows are their own transform) and only inv_norm is
+    written, unless ``out`` is given."""
+    rows, D, ld = _bank(x, "rows_transform")
+    _centring(mean, std, D, "rows_transform")
+    plain = mean is None and not length_norm
+    if out is not None:
+        orows, oD, old = _bank(out, "rows_transform (out)")
+        if oD != D or orows < rows:
+            raise ValueError(f"rows_transform: out is float32 [{rows}, {D}]")
+    _dev(x, mean, std, out, inv_norm)
+    if out is None and not plain:
+        out = torch.empty(rows, D, dtype=torch.float32, device=x.device)
+    inv_norm = _score_out(inv_norm, rows, x.device, "rows_transform")
+    _lib.check(lib().w2v2_rows_transform(x.data_ptr(), ld, rows, D, _p(mean), _p(std), int(bool(length_norm)), _p(out),
+                                         0 if out is None else (out.stride(0) if out.shape[0] > 1 else max(out.stride(0), D)),
+                                         inv_norm.data_ptr(), stream()), "rows_transform")
+    return (None if out is None else out[:rows]), inv_norm
+
+
+def topk_stats(S, K: int, M: Optional[int] = None, mu_out=None, sd_out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Mean and unbiased std of the K largest of the first M values of every row of S [R, ldS] f32 (w2v2_topk_stats; M
+    defaults to the row length) -> (mu [R], sd [R]).  Exact selection, ties counted as a multiset, -0.0 = +0.0; a row with
+    a NaN gives NaN for that row.  2 <= K <= M < 2^24."""
+    if not isinstance(S, torch.Tensor) or S.dim() != 2 or S.dtype != torch.float32 or S.shape[0] < 1:
+        raise ValueError("topk_stats: S is a 2-D float32 tensor")
+    R = S.shape[0]
+    M = S.shape[1] if M is None else int(M)
+    ldS = S.stride(0) if R > 1 else max(S.stride(0), S.shape[1])
+    if not 2 <= M <= S.shape[1] or M >= TOPK_MAX_M:
+        raise ValueError(f"topk_stats: M = {M} outside [2, min({S.shape[1]} columns, 2^24 - 1)]")
+    if S.stride(1) != 1 or ldS % 4 != 0 or S.data_ptr() % 16 != 0:
+        raise ValueError(f"topk_stats: row stride ldS = {ldS} must be a multiple of 4, values contiguous, base 16-byte aligned")
+    K = _top_k(K, M, "topk_stats")
+    _dev(S, mu_out, sd_out)
+    mu_out = _score_out(mu_out, R, S.device, "topk_stats")
+    sd_out = _score_out(sd_out, R, S.device, "topk_stats")
+    _lib.check(lib().w2v2_topk_stats(S.data_ptr(), ldS, R, M, K, mu_out.data_ptr(), sd_out.data_ptr(), stream()), "topk_stats")
+    return mu_out, sd_out
+
+
+def score_pairs_norm(cos, pairs, mu, sd, mode: str = "s", score_out=None) -> torch.Tensor:
+    """The normalised score of the trials pairs [P, 2] (device int32) with raw cosines cos [P] and the cohort statistics
+    mu / sd [N] (w2v2_score_pairs_norm): z_e = (c - mu[e]) / (sd[e] + 1e-12), z_t likewise; mode "z" -> z_e, "t" -> z_t,
+    "s" -> their mean.  Unbounded: not mapped to [0, 1].  An index outside [0, N) gives NaN for that trial."""
+    if mode not in SCORE_NORM_MODES:
+        raise ValueError(f"score_pairs_norm: mode={mode!r}: 'z', 't' or 's'")
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 \
+            or pairs.shape[0] < 1 or not pairs.is_contiguous():
+        raise ValueError("score_pairs_norm: pairs is a contiguous int32 [P, 2] tensor, P >= 1")
+    P = pairs.shape[0]
+    if not isinstance(cos, torch.Tensor) or cos.dtype != torch.float32 or cos.dim() != 1 or cos.numel() != P \
+            or not cos.is_contiguous():
+        raise ValueError(f"score_pairs_norm: cos is a contiguous float32 [{P}] tensor")
+    for v in (mu, sd):
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.dim() != 1 or v.numel() < 1 \
+                or not v.is_contiguous() or v.shape != mu.shape:
+            raise ValueError("score_pairs_norm: mu / sd are contiguous float32 [N] tensors")
+    _dev(cos, pairs, mu, sd, score_out)
+    score_out = _score_out(score_out, P, cos.device, "score_pairs_norm")
+    _lib.check(lib().w2v2_score_pairs_norm(cos.data_ptr(), pairs.data_ptr(), P, mu.data_ptr(), sd.data_ptr(), mu.numel(),
+                                           SCORE_NORM_MODES[mode], score_out.data_ptr(), stream()), "score_pairs_norm")
+    return score_out
+
+
+def segment_mean(bank, order, offsets, out=None) -> torch.Tensor:
+    """Mean of the bank rows of every segment (w2v2_segment_mean): bank [N, D] f32, order int32 [N] the rows grouped by
+    segment, offsets int32 [S + 1] -> out [S, D].  order and offsets are device tensors built on the host
+    (evaluation.speaker.device_scoring.speaker_mean_cohort checks them there: a permutation, no empty segment)."""
+    N, D, ld = _bank(bank, "segment_mean")
+    if not isinstance(order, torch.Tensor) or order.dtype != torch.int32 or order.shape != (N,) or not order.is_contiguous():
+        raise ValueError(f"segment_mean: order is a contiguous int32 [{N}] tensor")
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int32 or offsets.dim() != 1 \
+            or not 2 <= offsets.numel() <= N + 1 or not offsets.is_contiguous():
+        raise ValueError(f"segment_mean: offsets is a contiguous int32 [S + 1] tensor, 1 <= S <= N = {N}")
+    S = offsets.numel() - 1
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != (S, D)
+                            or not out.is_contiguous()):
+        raise ValueError(f"segment_mean: out is a contiguous float32 [{S}, {D}] tensor")
+    _dev(bank, order, offsets, out)
+    if out is None:
+        out = torch.empty(S, D, dtype=torch.float32, device=bank.device)
+    _lib.check(lib().w2v2_segment_mean(bank.data_ptr(), ld, N, D, order.data_ptr(), offsets.data_ptr(), S, out.data_ptr(), D,
+                                       stream()), "segment_mean")
+    return out
+
+
+def cohort_rows_per_block(N: int, M: int) -> int:
+    """Bank rows per block of cohort_stats by default: the [rows, ldS] f32 buffer stays at or below 256 MiB."""
+    return max(1, min(int(N), COHORT_WORKSPACE_BYTES // (4 * ((int(M) + 3) // 4 * 4))))
+
+
+def cohort_stats(bank, cohort, K: int, mean=None, std=None, length_norm: bool = False, rows_per_block: Optional[int] = None,
+                 workspace=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The cohort statistics of every bank row (steps 1-3 of include/w2v2_hip.h, "score normalisation"): bank [N, D] and
+    cohort [M, D] go through the evaluator's transform, every bank row is scored against every cohort row
+    (S = U C^T on the exact-f32 MFMA GEMM with the two inverse norms as row / column scales) and the K largest cosines
+    of each row give (mu [N], sd [N]) on the device.  S is never held whole: the bank goes in blocks of ``rows_per_block``
+    rows through one ``workspace`` of at least rows_per_block * ldS float32 (ldS = M rounded up to 4)."""
+    N, D, _ = _bank(bank, "cohort_stats")
+    M, Dc, _ = _bank(cohort, "cohort_stats (cohort)")
+    if Dc != D:
+        raise ValueError(f"cohort_stats: the cohort has D = {Dc}, the bank D = {D}")
+    if M >= TOPK_MAX_M:
+        raise ValueError(f"cohort_stats: M = {M} cohort rows, at most 2^24 - 1")
+    K = _top_k(K, M, "cohort_stats")
+    _centring(mean, std, D, "cohort_stats")
+    ldS = (M + 3) // 4 * 4
+    if rows_per_block is None:
+        rows_per_block = cohort_rows_per_block(N, M)
+    if isinstance(rows_per_block, bool) or not isinstance(rows_per_block, int) or rows_per_block < 1:
+        raise ValueError(f"cohort_stats: rows_per_block = {rows_per_block!r} must be a positive integer")
+    rpb = min(rows_per_block, N)
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32
+                                  or not workspace.is_contiguous() or workspace.numel() < rpb * ldS
+                                  or workspace.data_ptr() % 16 != 0):
+        raise ValueError(f"cohort_stats: workspace holds rows_per_block * ldS = {rpb} * {ldS} float32, contiguous, 16-byte "
+                         "aligned")
+    _dev(bank, cohort, mean, std, workspace)
+    dev = bank.device
+    if workspace is None:
+        workspace = torch.empty(rpb * ldS, dtype=torch.float32, device=dev)
+    S = workspace.view(-1)[:rpb * ldS].view(rpb, ldS)
+    plain = mean is None and not length_norm
+    c_u, c_inv = rows_transform(cohort, mean, std, length_norm)
+    c_u = cohort if c_u is None else c_u
+    u_buf = None if plain else torch.empty(rpb, D, dtype=torch.float32, device=dev)
+    inv_buf = torch.empty(rpb, dtype=torch.float32, device=dev)
+    mu = torch.empty(N, dtype=torch.float32, device=dev)
+    sd = torch.empty(N, dtype=torch.float32, device=dev)
+    for r0 in range(0, N, rpb):
+        rows = min(rpb, N - r0)
+        blk = bank[r0:r0 + rows]
+        u, inv = rows_transform(blk, mean, std, length_norm, out=u_buf, inv_norm=inv_buf)
+        u = blk if u is None else u
+        Gemm(rows, M, D, u, c_u, S, lda=u.stride(0) if rows > 1 else max(u.stride(0), D),
+             ldb=c_u.stride(0) if M > 1 else max(c_u.stride(0), D), ldc=ldS, epilogue=EPI_SCALE_RC, row_scale=inv,
+             col_scale=c_inv)()
+        topk_stats(S[:rows], K, M, mu[r0:r0 + rows], sd[r0:r0 + rows])
+    return mu, sd
+
+
 # ---------------------------------------------------------------------------------------------- trial metrics (metrics.hip)
 SORT_TILE = 2048            # keys per workgroup per pass of w2v2_sort_f32_index (csrc/metrics.hip SORT_TILE)
 TRIAL_METRICS_FIELDS = ("eer", "eer_threshold", "mdc", "mdc_threshold", "n_pos", "n_neg", "n_nan", "n_thresholds")
