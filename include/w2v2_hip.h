@@ -667,6 +667,67 @@ int w2v2_fbank_db(const float* wav, const int* lens, const float* window, const 
 int w2v2_fbank_normalize(const float* db, const float* partial_max, const int* lens, void* out, int64_t ldo, int dtype,
                          int B, int T, int n_mels, void* stream);
 
+/* ---------------------------------------------------------------------------------------- waveform augmentation (augment.hip)
+ * The `augmenter` stage of the reference's training pipelines (ref: src/data/preprocess/augment.py,
+ * config/data/pipeline/xvector_*augment*.yaml: selector -> augmenter -> filterbank -> normalizer) on [B][N] f32 waveforms
+ * that already live on the device, in front of w2v2_fbank_db.  The reference hands every chunk to WavAugment (libsox),
+ * which is not available to compare against: THIS COMMENT IS THE DEFINITION of the five operations, its oracle is float64
+ * numpy (tests/augment_cases.py); what was taken from memory of WavAugment is listed in DESIGN.md 7.  The random draws
+ * (how many spans, where, which band, which speed, which SNR) are made on the host, in the reference's order of np.random
+ * calls (data/augment.py); the kernels only take their results as small device tables.
+ *
+ * Shared conventions.  Everything is f32.  A buffer is [rows][ld] with N valid columns, ld >= N, every row * ld formed in
+ * 64 bits.  Every entry takes a device int32 row list of R entries and touches only the rows it names (a row named twice
+ * is the caller's error); every other row, and every column >= N, keeps its bits.  Per-row parameter tables are indexed by
+ * the POSITION r in the list.  lens: device int32 sample counts indexed by the ROW NUMBER of the buffer that is read (NULL:
+ * every row has N), clamped to [0, N]; samples at index >= lens[b] count as zero BY INDEX whatever the buffer holds, and
+ * columns [len, N) of a touched row are written as zeros.  A row's result is a function of that row's own samples and
+ * parameters alone, each output accumulated in one fixed order: it is bit-identical to the same call on the row alone
+ * (R = 1, any B, any N >= len).  No atomics, one writer per element, nothing allocated, all work on `stream`.
+ *
+ * time dropout (in place): spans [R][S][2] int32 = (start, length) per listed row; x[start .. start + length) = 0, clipped
+ * to [0, len).  length <= 0 is a no-op, spans may overlap, S = 0 only zeroes the columns behind len. */
+int w2v2_aug_time_dropout(float* x, int64_t ld, int N, const int32_t* lens, const int32_t* rows, int R,
+                          const int32_t* spans, int S, void* stream);
+/* additive noise (in place): y[i] = fma(c, x[i], (1 - c) u[i]) for i < len, c = coef[r] f32 (1 - c formed in f32).  With
+ * the SNR in dB, r = 10^(snr / 10) and c = r / (1 + r) on the host.
+ * mix_uniform: u[i] in [0, 1) = (h >> 8) 2^-24 with h = rng_pair(rng_key(((uint64) row << 32) | rng_key(seed)), i), the
+ * counter hash of csrc/common.h (dropout's), keyed by the seed, the ROW NUMBER and the sample index: the same seed gives
+ * the same stream again, two rows under one seed get different streams.  The uniform [0, 1) law of the reference's
+ * torch.zeros_like(x).uniform_() -- DC offset of 1/2 included -- but not its bit stream. */
+int w2v2_aug_mix_uniform(float* x, int64_t ld, int N, const int32_t* lens, const int32_t* rows, int R, const float* coef,
+                         int64_t seed, void* stream);
+/* mix_bank: u[i] = bank[bank_row[r]][i mod bank_lens[bank_row[r]]], bank [M][ld_bank] f32 on the device: the noise
+ * repeated until it covers the utterance, then cut (ref: augment.py:374-392).  A bank row outside [0, M) or a bank
+ * length outside [1, ld_bank] is not dereferenced: that row's samples come out NaN. */
+int w2v2_aug_mix_bank(float* x, int64_t ld, int N, const int32_t* lens, const int32_t* rows, int R, const float* coef,
+                      const float* bank, int64_t ld_bank, const int32_t* bank_lens, int M, const int32_t* bank_row,
+                      void* stream);
+/* FIR, zero-phase "same" alignment (src row src_rows[r] -> dst row dst_rows[r]; the two buffers must not overlap):
+ *   y[n] = sum_{j = 0}^{K - 1} h[j] x[n + (K - 1) / 2 - j],   0 <= n < min(len, N_out),   x zero outside [0, len)
+ * with h = taps[r][0 .. K), K = ntaps[r] odd, 1 <= K <= W2V2_AUG_MAX_TAPS <= ldt; rows of one launch may differ in K.
+ * len = clamp(lens[src_rows[r]], 0, N_in); columns [len, N_out) of the dst row are zeros, a row longer than N_out is
+ * cropped.  Each output is one chain of f32 fmas over j = K - 1 down to 0 (every tap, also those that meet a zero by
+ * index).  A bad tap count is not run: that dst row comes out NaN.  One workgroup per (row, tile of w2v2_aug_fir_tile()
+ * outputs): the tile plus its halo and the reversed taps are staged in LDS, a thread keeps 8 consecutive outputs in
+ * registers and slides a 12-sample window over the taps, 32 fmas per two 16-byte LDS reads. */
+#define W2V2_AUG_MAX_TAPS 2561
+int w2v2_aug_fir_tile(void);
+int w2v2_aug_fir(const float* src, int64_t ld_src, int N_in, const int32_t* lens, const int32_t* src_rows, float* dst,
+                 int64_t ld_dst, int N_out, const int32_t* dst_rows, int R, const float* taps, int64_t ldt,
+                 const int32_t* ntaps, void* stream);
+/* Rational resampling by U / D (speed 1 / (U / D) followed by a return to the sample rate), one launch per ratio over
+ * the rows of that ratio; h [2 half + 1] is the prototype low-pass at the U-times-oversampled rate (data/augment.py designs
+ * it: Kaiser-windowed sinc, cutoff 1 / max(U, D), half = 32 max(U, D)):
+ *   out_len = min(ceil(len U / D), N_out),   y[m] = U * sum_j x[j] h[m D - j U + half],   0 <= m < out_len
+ * over the j in [0, len) whose tap index lies in [0, 2 half], ascending j, one chain of f32 fmas, then one multiply by U.
+ * Columns [out_len, N_out) are zeros; out_lens[dst_rows[r]] = out_len (out_lens may be NULL).  U == D copies the row
+ * (bit-exact, h is not read).  1 <= U, D <= 4096, 0 <= half <= 2^20. */
+int w2v2_aug_resample_tile(void);
+int w2v2_aug_resample(const float* src, int64_t ld_src, int N_in, const int32_t* lens, const int32_t* src_rows, float* dst,
+                      int64_t ld_dst, int N_out, const int32_t* dst_rows, int32_t* out_lens, int R, int U, int D,
+                      const float* h, int half, void* stream);
+
 /* ---------------------------------------------------------------------------------------- skinny linear layers
  * Exact-f32 nn.Linear / Conv1d(k=1) over a handful of rows (one per utterance): the SE bottleneck and the embedding
  * layer of ECAPA (speechbrain SEBlock / ECAPA_TDNN.fc) and the hidden fc_list of the wav2vec2 head (ref:

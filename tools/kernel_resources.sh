@@ -1,10 +1,11 @@
 #!/bin/bash
 # Registers / spills / LDS of every kernel in one .hip file (device-only compile with the resource-usage remarks).
 #   bash tools/kernel_resources.sh w2v2_speaker_amd/csrc/gemm_f32_dma.hip
+#   bash tools/kernel_resources.sh w2v2_speaker_amd/csrc/augment.hip -fno-slp-vectorize    (a file's _build.EXTRA_FLAGS go behind it)
 src=$(realpath "$1")
 root=$(dirname "$(dirname "$(realpath "$0")")")
 cd /tmp && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I$root/include -I$root/w2v2_speaker_amd/csrc \
-  --cuda-device-only -c "$src" -o /tmp/kres.co -Rpass-analysis=kernel-resource-usage 2>&1 |
+  "${@:2}" --cuda-device-only -c "$src" -o /tmp/kres.co -Rpass-analysis=kernel-resource-usage 2>&1 |
   python3 -c '
 import re, sys
 name, d = None, {}

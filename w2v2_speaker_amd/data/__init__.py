@@ -9,9 +9,15 @@ from .fbank import Fbank, FilterBank
 from .paired import (EvaluationPair, PairedBatchProcessor, PairedSpeakerClassificationDataSample,
                      paired_default_collate_fn, read_test_pairs_file)
 from .speech import SpeechRecognitionDataBatch, SpeechRecognitionDataSample, speech_collate_fn
+from .augment import (Augmenter, AugmentedBatch, ChoiceNoiseAugment, ChoiceRandomNoiseAugment, ChoiceRirsNoiseAugment,
+                      ChoiceSpeedAugment, FrequencyDropoutAugment, ReverbAugment, SpecAugmentBand, TimeDropoutAugment,
+                      UniformSpeedAugment)
 
 __all__ = ["AudioChunkSelector", "BatchProcessor", "InputNormalizer2D", "SpeakerClassificationDataSample",
            "default_collate_fn", "find_shards", "iter_shard", "read_meta", "write_shards", "DeviceFeeder",
            "ShardDataset", "Fbank", "FilterBank", "EvaluationPair", "PairedBatchProcessor",
            "PairedSpeakerClassificationDataSample", "paired_default_collate_fn", "read_test_pairs_file",
-           "TripletSpeakerBatchProcessor", "SpeechRecognitionDataBatch", "SpeechRecognitionDataSample", "speech_collate_fn"]
+           "TripletSpeakerBatchProcessor", "SpeechRecognitionDataBatch", "SpeechRecognitionDataSample", "speech_collate_fn",
+           "Augmenter", "AugmentedBatch", "ChoiceNoiseAugment", "ChoiceRandomNoiseAugment", "ChoiceRirsNoiseAugment",
+           "ChoiceSpeedAugment", "FrequencyDropoutAugment", "ReverbAugment", "SpecAugmentBand", "TimeDropoutAugment",
+           "UniformSpeedAugment"]

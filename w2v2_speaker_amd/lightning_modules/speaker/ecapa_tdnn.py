@@ -42,9 +42,10 @@ class FilterbankSpeakerModule(OptimizerSurface, EmbeddingEvaluation):
     train)`` and ``_new_trainer(plan)``."""
 
     def _init_runtime(self, device, input_features: str, validation_pairs, test_pairs, evaluator, max_lr: float,
-                      max_steps: int, gradient_clip_val: float, accumulate_grad_batches: int) -> None:
+                      max_steps: int, gradient_clip_val: float, accumulate_grad_batches: int, augmenter=None) -> None:
         from ...evaluation.speaker.cosine_distance import CosineDistanceEvaluator
         self.input_features = input_features
+        self.augmenter = augmenter                         # data.augment.Augmenter or None: training_step's first stage
         self.validation_pairs, self.test_pairs = validation_pairs or [], test_pairs or []
         self.evaluator = evaluator or CosineDistanceEvaluator(False, False, 0)
         self.schedule = OneCycle(max_lr=max_lr, total_steps=max_steps)
@@ -61,6 +62,15 @@ class FilterbankSpeakerModule(OptimizerSurface, EmbeddingEvaluation):
     def _check_input_features(input_features: str) -> None:
         if input_features not in ("fbank", "waveform"):
             raise ValueError(f"input_features: 'fbank' or 'waveform', got {input_features!r}")
+
+    @staticmethod
+    def _check_augmenter(augmenter, input_features: str) -> None:
+        """The augmenter works on waveforms (the reference's pipeline order: selector -> augmenter -> filterbank)."""
+        if augmenter is not None and input_features != "waveform":
+            raise ValueError(f"augmenter= needs input_features='waveform' (the augmenter runs in front of the filterbank), "
+                             f"got input_features={input_features!r}")
+        if augmenter is not None and not hasattr(augmenter, "process_batch"):
+            raise ValueError("augmenter= is a data.augment.Augmenter (or None)")
 
     def _plan(self, batch: int, frames: int, train: bool):
         return self._plans.lookup((batch, frames, train), lambda: self._new_plan(batch, frames, train))
@@ -142,13 +152,16 @@ class FilterbankSpeakerModule(OptimizerSurface, EmbeddingEvaluation):
 
     def training_step(self, batch: SpeakerClassificationDataBatch, batch_idx: int = 0,
                       optimizer_idx: Optional[int] = None):
+        label = batch.ground_truth.to(self.device)
         if self.input_features == "waveform":
             x = self._prep_waveform(batch.network_input)
+            if self.augmenter is not None:                 # [B, N] -> [B', N'] on the device; the plan is built for B', N'
+                aug = self.augmenter.process_batch(x, label, keys=getattr(batch, "keys", None))
+                x, label = aug.network_input, aug.ground_truth
             key = (x.shape[0], fbank_frames(x.shape[1]))
         else:
             x = batch.network_input.to(self.device, torch.float32)
             key = (x.shape[0], x.shape[1])
-        label = batch.ground_truth.to(self.device)
         loss, pred = self._trainer_step(
             key, lambda: self._new_trainer(self._plan(key[0], key[1], True)),
             lambda tr: tr.train_step(x, label))
@@ -167,7 +180,7 @@ class EcapaTdnnModule(FilterbankSpeakerModule):
                  loss_fn_constructor: Callable[[], object], validation_pairs=None, test_pairs=None, evaluator=None, *,
                  device="cuda", act_dtype: torch.dtype = torch.bfloat16, max_lr: float = 1e-3,
                  max_steps: int = 100_000, init_seed: int = 20211, gradient_clip_val: float = 0.0,
-                 accumulate_grad_batches: int = 1, input_features: str = "fbank"):
+                 accumulate_grad_batches: int = 1, input_features: str = "fbank", augmenter=None):
         """Positional arguments = ref: ecapa_tdnn.py:51-62 (what src/main.py:256-285 passes to every network class).
         ``loss_fn_constructor`` is called once and read for its type and hyper-parameters: the engine runs the ECAPA
         model under AAM-softmax (``skip_classifier`` of ref :93-95; the paper's configuration,
@@ -176,8 +189,10 @@ class EcapaTdnnModule(FilterbankSpeakerModule):
         ``input_features``: "fbank" -- inputs are [B, T, n_mels] filterbank tensors, the output of the reference's
         ``filterbank`` + ``normalizer`` pipeline stages (data/fbank.py, InputNormalizer2D) -- or "waveform": inputs are
         what the ``selector`` stage delivers ([B, 1, N], [B, N] or [N] audio) and the two stages run on the device
-        (EcapaPlan.embed_waveform)."""
+        (EcapaPlan.embed_waveform).  ``augmenter``: a data.augment.Augmenter that ``training_step`` runs on the waveforms
+        in front of the filterbank (the reference's `augmenter` pipeline stage); "waveform" inputs only."""
         self._check_input_features(input_features)
+        self._check_augmenter(augmenter, input_features)
         from ...optim.loss import AngularAdditiveMarginSoftMaxLoss
         loss_fn = loss_fn_constructor()
         if not isinstance(loss_fn, AngularAdditiveMarginSoftMaxLoss):
@@ -202,7 +217,7 @@ class EcapaTdnnModule(FilterbankSpeakerModule):
         self.margin, self.scale = aam_margin, aam_scale
         self.skip_classifier = True                        # AAM owns the classifier weight (ref :93-95, :129-131)
         self._init_runtime(device, input_features, validation_pairs, test_pairs, evaluator, max_lr, max_steps,
-                           gradient_clip_val, accumulate_grad_batches)
+                           gradient_clip_val, accumulate_grad_batches, augmenter)
 
     @classmethod
     def from_config(cls, cfg: EcapaTDNNModuleConfig, num_speakers: int, aam_margin: float = 0.2,

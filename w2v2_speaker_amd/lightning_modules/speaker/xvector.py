@@ -30,14 +30,16 @@ class XVectorModule(FilterbankSpeakerModule):
                  loss_fn_constructor: Callable[[], object], validation_pairs=None, test_pairs=None, evaluator=None, *,
                  device="cuda", act_dtype: torch.dtype = torch.float32, max_lr: float = 1e-3,
                  max_steps: int = 100_000, init_seed: int = 20211, gradient_clip_val: float = 0.0,
-                 accumulate_grad_batches: int = 1, input_features: str = "fbank"):
+                 accumulate_grad_batches: int = 1, input_features: str = "fbank", augmenter=None):
         """Positional arguments = ref: xvector.py:48-57 (what src/main.py:256-285 passes to every network class).
         ``loss_fn_constructor`` is called once and read for its type: the experiment (config/experiment/
         speaker_xvector.yaml) trains under ``CrossEntropyLoss``; an AAM loss raises the reference's own ValueError (ref
         :84-85), anything else NotImplementedError.  ``act_dtype``: f32 only, the reference's ``precision: 32``.
         ``input_features``: as in EcapaTdnnModule -- "fbank" [B, T, n_mels] tensors or "waveform" audio through the device
-        front-end."""
+        front-end.  ``augmenter``: as in EcapaTdnnModule -- a data.augment.Augmenter in front of the filterbank, "waveform"
+        inputs only."""
         self._check_input_features(input_features)
+        self._check_augmenter(augmenter, input_features)
         from ...optim.loss import AngularAdditiveMarginSoftMaxLoss, CrossEntropyLoss
         loss_fn = loss_fn_constructor()
         if isinstance(loss_fn, AngularAdditiveMarginSoftMaxLoss):
@@ -60,7 +62,7 @@ class XVectorModule(FilterbankSpeakerModule):
         self.store.init_weights(init_seed)
         self._classifiers = PlanCache()                    # evaluation classifiers, one per batch size
         self._init_runtime(device, input_features, validation_pairs, test_pairs, evaluator, max_lr, max_steps,
-                           gradient_clip_val, accumulate_grad_batches)
+                           gradient_clip_val, accumulate_grad_batches, augmenter)
 
     @classmethod
     def from_config(cls, cfg: XVectorModuleConfig, num_speakers: int, **kw) -> "XVectorModule":

@@ -1685,3 +1685,137 @@ def trial_metrics(scores, labels, c_miss=1, c_fa=1, p_target=0.05, out=None, wor
     _lib.check(lib().w2v2_trial_metrics(scores.data_ptr(), labels.data_ptr(), P, float(c_miss), float(c_fa), float(p_target),
                                         out.data_ptr(), workspace.data_ptr(), stream()), "trial_metrics")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ waveform augmentation
+# (csrc/augment.hip; include/w2v2_hip.h "waveform augmentation" defines every operation.)  Row lists and parameter tables
+# are DEVICE tensors the caller built on the host (data/augment.py uploads them in one copy per step): the wrappers check
+# shapes and dtypes, which needs no device, and never read a table back.
+AUG_MAX_TAPS = 2561                     # W2V2_AUG_MAX_TAPS of include/w2v2_hip.h
+AUG_FIR_TILE = 2048                     # outputs per workgroup of w2v2_aug_fir (w2v2_aug_fir_tile())
+AUG_RESAMPLE_TILE = 256                 # outputs per workgroup of w2v2_aug_resample (w2v2_aug_resample_tile())
+
+
+def _aug_wave(x, what: str) -> Tuple[int, int, int]:
+    """(rows, N, ld) of a 2-D float32 waveform buffer whose samples are contiguous."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] < 1 or x.shape[1] < 1 \
+            or x.stride(1) != 1:
+        raise ValueError(f"{what}: a 2-D float32 [rows, N] tensor with contiguous samples")
+    B, N = x.shape
+    ld = x.stride(0) if B > 1 else max(x.stride(0), N)
+    if ld < N:
+        raise ValueError(f"{what}: row stride {ld} below N = {N}")
+    return B, N, ld
+
+
+def _aug_i32(t, n: Optional[int], what: str) -> int:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise ValueError(f"{what}: a contiguous int32 tensor" + (f" of {n} elements" if n is not None else ""))
+    return t.numel()
+
+
+def _aug_rows(rows, what: str) -> int:
+    R = _aug_i32(rows, None, f"{what}: rows")
+    if rows.dim() != 1 or not 1 <= R <= 65535:
+        raise ValueError(f"{what}: rows is an int32 [R] tensor, 1 <= R <= 65535")
+    return R
+
+
+def _aug_lens(lens, B: int, what: str) -> None:
+    if lens is not None:
+        _aug_i32(lens, B, f"{what}: lens")
+
+
+def _aug_coef(coef, R: int, what: str) -> None:
+    if not isinstance(coef, torch.Tensor) or coef.dtype != torch.float32 or not coef.is_contiguous() or coef.numel() != R:
+        raise ValueError(f"{what}: coef is a contiguous float32 [{R}] tensor")
+
+
+def aug_time_dropout(x, rows, spans, lens=None) -> None:
+    """In place: zero the spans[r, s] = (start, length) of row rows[r] of x [B, N], clipped to that row's [0, len)
+    (w2v2_aug_time_dropout).  spans: int32 [R, S, 2] on the device (S may be 0); lens: int32 [B] or None."""
+    B, N, ld = _aug_wave(x, "aug_time_dropout")
+    R = _aug_rows(rows, "aug_time_dropout")
+    if not isinstance(spans, torch.Tensor) or spans.dtype != torch.int32 or spans.dim() != 3 or spans.shape[0] != R \
+            or spans.shape[2] != 2 or not spans.is_contiguous():
+        raise ValueError(f"aug_time_dropout: spans is a contiguous int32 [{R}, S, 2] tensor")
+    _aug_lens(lens, B, "aug_time_dropout")
+    _dev(x, rows, spans, lens)
+    S = spans.shape[1]
+    _lib.check(lib().w2v2_aug_time_dropout(x.data_ptr(), ld, N, _p(lens), rows.data_ptr(), R, spans.data_ptr() if S else None, S,
+                                           stream()), "aug_time_dropout")
+
+
+def aug_mix_uniform(x, rows, coef, seed: int, lens=None) -> None:
+    """In place: x[row] = coef[r] x[row] + (1 - coef[r]) u, u in [0, 1) from the counter hash keyed by (seed, row number,
+    sample index) (w2v2_aug_mix_uniform).  coef: float32 [R] on the device; seed: any Python int, taken modulo 2^64."""
+    B, N, ld = _aug_wave(x, "aug_mix_uniform")
+    R = _aug_rows(rows, "aug_mix_uniform")
+    _aug_coef(coef, R, "aug_mix_uniform")
+    _aug_lens(lens, B, "aug_mix_uniform")
+    _dev(x, rows, coef, lens)
+    s = int(seed) & (2 ** 64 - 1)
+    _lib.check(lib().w2v2_aug_mix_uniform(x.data_ptr(), ld, N, _p(lens), rows.data_ptr(), R, coef.data_ptr(),
+                                          s - 2 ** 64 if s >= 2 ** 63 else s, stream()), "aug_mix_uniform")
+
+
+def aug_mix_bank(x, rows, coef, bank, bank_lens, bank_row, lens=None) -> None:
+    """In place: the mix of aug_mix_uniform with u = bank[bank_row[r]] repeated to the row's length (w2v2_aug_mix_bank).
+    bank: float32 [M, L] on the device, bank_lens: int32 [M], bank_row: int32 [R]."""
+    B, N, ld = _aug_wave(x, "aug_mix_bank")
+    R = _aug_rows(rows, "aug_mix_bank")
+    _aug_coef(coef, R, "aug_mix_bank")
+    M, _, ldb = _aug_wave(bank, "aug_mix_bank (bank)")
+    _aug_i32(bank_lens, M, "aug_mix_bank: bank_lens")
+    _aug_i32(bank_row, R, "aug_mix_bank: bank_row")
+    _aug_lens(lens, B, "aug_mix_bank")
+    _dev(x, rows, coef, bank, bank_lens, bank_row, lens)
+    _lib.check(lib().w2v2_aug_mix_bank(x.data_ptr(), ld, N, _p(lens), rows.data_ptr(), R, coef.data_ptr(), bank.data_ptr(),
+                                       ldb, bank_lens.data_ptr(), M, bank_row.data_ptr(), stream()), "aug_mix_bank")
+
+
+def _aug_src_dst(src, dst, src_rows, dst_rows, lens, what: str):
+    Bs, N_in, lds = _aug_wave(src, f"{what} (src)")
+    _, N_out, ldd = _aug_wave(dst, f"{what} (dst)")
+    R = _aug_rows(src_rows, what)
+    if _aug_rows(dst_rows, what) != R:
+        raise ValueError(f"{what}: src_rows and dst_rows name {R} rows each")
+    _aug_lens(lens, Bs, what)
+    if src.untyped_storage().data_ptr() == dst.untyped_storage().data_ptr():
+        raise ValueError(f"{what}: src and dst must not share memory")
+    return N_in, lds, N_out, ldd, R
+
+
+def aug_fir(src, dst, src_rows, dst_rows, taps, ntaps, lens=None) -> None:
+    """dst[dst_rows[r]] = the zero-phase FIR of src[src_rows[r]] under taps[r, :ntaps[r]] (w2v2_aug_fir): float32 taps
+    [R, ldt] and int32 ntaps [R] on the device, every count odd and at most AUG_MAX_TAPS.  lens: int32 per src row."""
+    N_in, lds, N_out, ldd, R = _aug_src_dst(src, dst, src_rows, dst_rows, lens, "aug_fir")
+    if not isinstance(taps, torch.Tensor) or taps.dtype != torch.float32 or taps.dim() != 2 or taps.shape[0] != R \
+            or taps.shape[1] < 1 or taps.stride(1) != 1:
+        raise ValueError(f"aug_fir: taps is a float32 [{R}, ldt] tensor")
+    _aug_i32(ntaps, R, "aug_fir: ntaps")
+    _dev(src, dst, src_rows, dst_rows, taps, ntaps, lens)
+    ldt = taps.stride(0) if R > 1 else max(taps.stride(0), taps.shape[1])
+    _lib.check(lib().w2v2_aug_fir(src.data_ptr(), lds, N_in, _p(lens), src_rows.data_ptr(), dst.data_ptr(), ldd, N_out,
+                                  dst_rows.data_ptr(), R, taps.data_ptr(), ldt, ntaps.data_ptr(), stream()), "aug_fir")
+
+
+def aug_resample(src, dst, src_rows, dst_rows, U: int, D: int, h=None, lens=None, out_lens=None) -> None:
+    """dst[dst_rows[r]] = src[src_rows[r]] resampled by U / D through the prototype h [2 half + 1] (w2v2_aug_resample);
+    U == D copies.  out_lens: int32 per dst row, written at the listed rows, or None."""
+    N_in, lds, N_out, ldd, R = _aug_src_dst(src, dst, src_rows, dst_rows, lens, "aug_resample")
+    if isinstance(U, bool) or isinstance(D, bool) or not isinstance(U, int) or not isinstance(D, int) \
+            or not (1 <= U <= 4096 and 1 <= D <= 4096):
+        raise ValueError(f"aug_resample: U = {U!r}, D = {D!r}: integers in [1, 4096]")
+    half = 0
+    if U != D:
+        if not isinstance(h, torch.Tensor) or h.dtype != torch.float32 or h.dim() != 1 or not h.is_contiguous() \
+                or h.numel() % 2 != 1:
+            raise ValueError("aug_resample: h is a contiguous float32 [2 half + 1] tensor")
+        half = h.numel() // 2
+    if out_lens is not None:
+        _aug_i32(out_lens, dst.shape[0], "aug_resample: out_lens")
+    _dev(src, dst, src_rows, dst_rows, h if U != D else None, lens, out_lens)
+    _lib.check(lib().w2v2_aug_resample(src.data_ptr(), lds, N_in, _p(lens), src_rows.data_ptr(), dst.data_ptr(), ldd, N_out,
+                                       dst_rows.data_ptr(), _p(out_lens), R, U, D, h.data_ptr() if U != D else None, half,
+                                       stream()), "aug_resample")
