@@ -667,11 +667,11 @@ int w2v2_fbank_db(const float* wav, const int* lens, const float* window, const 
 int w2v2_fbank_normalize(const float* db, const float* partial_max, const int* lens, void* out, int64_t ldo, int dtype,
                          int B, int T, int n_mels, void* stream);
 
-/* ---------------------------------------------------------------------------------------- waveform augmentation (augment.hip)
+/* ---------------------------------------------------------------------------------------- waveform augmentation (augment.hip, reverb.hip)
  * The `augmenter` stage of the reference's training pipelines (ref: src/data/preprocess/augment.py,
  * config/data/pipeline/xvector_*augment*.yaml: selector -> augmenter -> filterbank -> normalizer) on [B][N] f32 waveforms
  * that already live on the device, in front of w2v2_fbank_db.  The reference hands every chunk to WavAugment (libsox),
- * which is not available to compare against: THIS COMMENT IS THE DEFINITION of the five operations, its oracle is float64
+ * which is not available to compare against: THIS COMMENT IS THE DEFINITION of the six operations, its oracle is float64
  * numpy (tests/augment_cases.py); what was taken from memory of WavAugment is listed in DESIGN.md 7.  The random draws
  * (how many spans, where, which band, which speed, which SNR) are made on the host, in the reference's order of np.random
  * calls (data/augment.py); the kernels only take their results as small device tables.
@@ -727,6 +727,39 @@ int w2v2_aug_resample_tile(void);
 int w2v2_aug_resample(const float* src, int64_t ld_src, int N_in, const int32_t* lens, const int32_t* src_rows, float* dst,
                       int64_t ld_dst, int N_out, const int32_t* dst_rows, int32_t* out_lens, int R, int U, int D,
                       const float* h, int half, void* stream);
+/* Reverb (reverb.hip; src row src_rows[r] -> dst row dst_rows[r], the two buffers must not overlap): sox's `reverb
+ * <reverberance> <damping> <room scale>` followed by `channels 1`, the freeverb bank of 8 damped feedback combs and 4
+ * all-passes per output channel, restated from memory of sox's reverb.c.  The host (data/augment.py
+ * reverb_parameters) does this arithmetic in float64:
+ *   comb lengths at 44.1 kHz {1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617}, all-pass {225, 341, 441, 556}, stereo
+ *   adjust 12.  A mono input at sox's default stereo depth of 100 gives two filter arrays w = 0, 1.  r = rate / 44100,
+ *   scale = room_scale / 100 * 0.9 + 0.1; a sign s starts at +1 and flips after every filter, through the 8 combs and on
+ *   through the 4 all-passes; comb i has the delay int(scale r (comb[i] + 12 s w) + 0.5), all-pass j the delay
+ *   int(r (allpass[j] + 12 s w) + 0.5) (no scale).  a = -1 / ln(0.7), b = 100 / (ln(0.02) a + 1),
+ *   feedback = 1 - exp((reverberance - b) / (a b)), damp = damping / 100 * 0.3 + 0.2, wet_gain = 0.015 (0 dB, no pre-delay).
+ * and hands the kernel one row of W2V2_AUG_REVERB_PARAMS int32 per listed row, indexed by the position r: comb delays
+ * [w * 8 + i] at 0 .. 15, all-pass delays [w * 4 + j] at 16 .. 23, then the bits of the f32 feedback, damp, wet_gain and
+ * dry_gain.  In exact arithmetic, for n < len = clamp(lens[src_rows[r]], 0, N_in), x zero by index outside [0, len):
+ *   comb (a line of `delay` zeros, store = 0):  o = line[p];  store = o + (store - o) damp;  line[p] = x[n] + store feedback;
+ *                                               the output is o; p advances round the line
+ *   array w:  acc = 0, acc += comb_i(x[n]) for i = 7 down to 0;  then all-pass j = 3 down to 0, each
+ *             o = line[p], line[p] = in + 0.5 o, out = o - in;   wet_w[n] = out wet_gain
+ *   y[n] = 0.5 ((dry_gain x[n] + wet_0[n]) + (dry_gain x[n] + wet_1[n]))
+ * dry_gain = 1 is the reference, dry_gain = 0 the wet signal alone.  The length is unchanged (no drain); columns
+ * [len, N_out) of the dst row are zeros, a row longer than N_out is cropped.  sox's conversion to 32-bit integer samples
+ * and its clipping at +-1 between effects are left out.
+ * In f32 the low-pass `store` is evaluated as a scan over blocks of up to 64 samples with the carried store folded in
+ * (reverb.hip states the order), so the result is defined to a tolerance against the sequential loop, not bit for bit;
+ * the order is a function of the row's own table and length alone: a row is bit-identical to the same call on the row
+ * alone, and a repeated launch is bit-identical.  Every delay must lie in [1, W2V2_AUG_REVERB_MAX_DELAY]: enough for every
+ * room scale up to a sample rate of 27,940 Hz (at 32 kHz up to room scale 85, at 44.1 kHz up to 59).  A row with a delay
+ * outside that range is not run: its dst row comes out NaN.  One workgroup walks one row in time chunks of
+ * w2v2_aug_reverb_chunk() samples with the 24 delay lines in LDS; no workgroup waits on another, no workspace. */
+#define W2V2_AUG_REVERB_MAX_DELAY 1024
+#define W2V2_AUG_REVERB_PARAMS 28
+int w2v2_aug_reverb_chunk(void);
+int w2v2_aug_reverb(const float* src, int64_t ld_src, int N_in, const int32_t* lens, const int32_t* src_rows, float* dst,
+                    int64_t ld_dst, int N_out, const int32_t* dst_rows, int R, const int32_t* params, void* stream);
 
 /* ---------------------------------------------------------------------------------------- skinny linear layers
  * Exact-f32 nn.Linear / Conv1d(k=1) over a handful of rows (one per utterance): the SE bottleneck and the embedding

@@ -171,7 +171,9 @@ _SIGS = {
     "w2v2_aug_resample_tile": (c_i32, []),
     "w2v2_aug_resample": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp,
                                   c_i32, c_vp]),
-    "w2v2_asp_context": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "w2v2_aug_reverb_chunk": (c_i32, []),
+    "w2v2_aug_reverb": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "w2v2_asp_context":(c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "w2v2_asp_context_len": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "w2v2_asp_context_bias": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "w2v2_asp_bn_workspace_floats": (c_i32, [c_i32, c_i32]),

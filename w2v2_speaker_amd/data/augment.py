@@ -4,9 +4,9 @@ config/data/pipeline/xvector_*augment*.yaml: selector -> augmenter -> filterbank
 The host draws every row's parameters with the reference's ``np.random`` calls in the reference's order -- sample by
 sample, augmenter by augmenter -- and designs the filters in numpy; each draw is a small record, no sample is touched on
 the host.  The records of a step go up as ONE table through two pinned staging buffers used in turn, and the kernels of
-csrc/augment.hip (include/w2v2_hip.h, "waveform augmentation": the definition of the five operations) do the work on the
-[B, N] waveforms where they lie.  The reference runs the effects through WavAugment / libsox; what is restated from
-memory of that library is marked "as recollected" here and listed in DESIGN.md 7.
+csrc/augment.hip and csrc/reverb.hip (include/w2v2_hip.h, "waveform augmentation": the definition of the six operations)
+do the work on the [B, N] waveforms where they lie.  The reference runs the effects through WavAugment / libsox; what is
+restated from memory of that library is marked "as recollected" here and listed in DESIGN.md 7.
 """
 from __future__ import annotations
 
@@ -23,6 +23,12 @@ AUG_MAX_TAPS = 2561                 # ops.AUG_MAX_TAPS: five composed 513-tap st
 SINC_ATTENUATION_DB = 120.0         # the reference's `sinc -a 120`
 RESAMPLE_ATTENUATION_DB = 80.0      # the resampling prototype's Kaiser window (this module's choice)
 RESAMPLE_ZEROS = 32                 # zero crossings of the prototype on either side: half = 32 max(U, D)
+REVERB_MAX_DELAY = 1024             # ops.AUG_REVERB_MAX_DELAY
+REVERB_PARAMS = 28                  # ops.AUG_REVERB_PARAMS
+REVERB_COMB_LENGTHS = (1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617)      # at 44.1 kHz (sox reverb.c, as recollected)
+REVERB_ALLPASS_LENGTHS = (225, 341, 441, 556)
+REVERB_STEREO_ADJUST = 12
+REVERB_WET_GAIN = 0.015             # 0 dB wet gain, no pre-delay
 
 
 # ------------------------------------------------------------------------------------------------ filter design (numpy, f64)
@@ -129,6 +135,48 @@ class NoiseDraw:
     snr: float
     coef: float
     bank_row: int = -1                          # ChoiceRirsNoiseAugment: which noise of the bank
+
+
+@dataclass
+class ReverbDraw:
+    """One row of w2v2_aug_reverb's table: delays [array][filter], coefficients already rounded to f32."""
+    comb_delays: np.ndarray                     # int32 [2, 8]
+    allpass_delays: np.ndarray                  # int32 [2, 4]
+    feedback: np.float32
+    damp: np.float32
+    wet_gain: np.float32
+    dry_gain: np.float32 = np.float32(1.0)
+
+    def row(self) -> np.ndarray:
+        """int32 [REVERB_PARAMS]: the delays, then the f32 coefficients by their bits."""
+        coef = np.asarray([self.feedback, self.damp, self.wet_gain, self.dry_gain], np.float32).view(np.int32)
+        return np.concatenate([self.comb_delays.reshape(-1), self.allpass_delays.reshape(-1), coef]).astype(np.int32)
+
+
+def reverb_parameters(sample_rate: float, reverberance: float, damping: float, room_scale: float) -> ReverbDraw:
+    """sox's `reverb <reverberance> <damping> <room_scale>` on a mono input (stereo depth 100: two filter arrays), as
+    recollected from reverb.c and stated in include/w2v2_hip.h; the arithmetic in float64.  ValueError when a delay leaves
+    [1, REVERB_MAX_DELAY]."""
+    r = float(sample_rate) / 44100.0
+    scale = float(room_scale) / 100.0 * 0.9 + 0.1
+    combs, allpasses = np.zeros((2, 8), np.int32), np.zeros((2, 4), np.int32)
+    for w in range(2):
+        sign = 1.0                                      # flips after every filter, through the combs and on through the all-passes
+        for i, length in enumerate(REVERB_COMB_LENGTHS):
+            combs[w, i] = int(scale * r * (length + REVERB_STEREO_ADJUST * sign * w) + 0.5)
+            sign = -sign
+        for j, length in enumerate(REVERB_ALLPASS_LENGTHS):
+            allpasses[w, j] = int(r * (length + REVERB_STEREO_ADJUST * sign * w) + 0.5)
+            sign = -sign
+    lo, hi = min(combs.min(), allpasses.min()), max(combs.max(), allpasses.max())
+    if lo < 1 or hi > REVERB_MAX_DELAY:
+        raise ValueError(f"reverb at {sample_rate} Hz, room scale {room_scale}: delays {lo} .. {hi} outside "
+                         f"[1, {REVERB_MAX_DELAY}]")
+    a = -1.0 / math.log(1.0 - 0.3)
+    b = 100.0 / (math.log(1.0 - 0.98) * a + 1.0)
+    feedback = 1.0 - math.exp((float(reverberance) - b) / (a * b))
+    damp = float(damping) / 100.0 * 0.3 + 0.2
+    return ReverbDraw(combs, allpasses, np.float32(feedback), np.float32(damp), np.float32(REVERB_WET_GAIN))
 
 
 # ------------------------------------------------------------------------------------------------ the reference's classes
@@ -329,13 +377,14 @@ class ChoiceRirsNoiseAugment(WaveAugment):
 
 
 class ReverbAugment(WaveAugment):
-    """ref: augment.py:418-458.  The constructor and its three draws (reverberance, damping, room scale, once, at
-    construction) are the reference's; the effect is not on the device: sox's reverb is a bank of recursive comb and
-    all-pass filters, every output a function of the output before it."""
+    """ref: augment.py:418-458: `reverb <reverberance> <damping> <room_scale>` then `channels`.  The constructor and its
+    three draws (reverberance, damping, room scale, once, at construction) are the reference's.  ``on_device=True`` asks
+    for the device form (w2v2_aug_reverb): ``draw`` then returns the one record the three values give and makes no
+    np.random call.  Without it ``draw`` raises as it did before the device had the effect."""
     kind = "reverb"
 
     def __init__(self, sample_rate: int, reverberance_min: int = 50, reverberance_max: int = 50, damping_min: int = 50,
-                 damping_max: int = 50, room_scale_min: int = 0, room_scale_max: int = 100):
+                 damping_max: int = 50, room_scale_min: int = 0, room_scale_max: int = 100, *, on_device: bool = False):
         super().__init__(sample_rate, "add_reverb")
         self.reverberance_min, self.reverberance_max = reverberance_min, reverberance_max
         self.damping_min, self.damping_max = damping_min, damping_max
@@ -343,10 +392,14 @@ class ReverbAugment(WaveAugment):
         self.reverberance = _count(reverberance_min, reverberance_max)
         self.damping = _count(damping_min, damping_max)
         self.room_scale = _count(room_scale_min, room_scale_max)
+        self.on_device = bool(on_device)
+        self.parameters = reverb_parameters(sample_rate, self.reverberance, self.damping, self.room_scale) if on_device else None
 
-    def draw(self, n: int):
-        raise NotImplementedError("ReverbAugment has no device form: sox's reverb is a recursive filter bank, sequential "
-                                  "in time; leave it out of the augmenter's list")
+    def draw(self, n: int) -> ReverbDraw:
+        if not self.on_device:
+            raise NotImplementedError("ReverbAugment has no device form: sox's reverb is a recursive filter bank, sequential "
+                                      "in time; leave it out of the augmenter's list")
+        return self.parameters
 
 
 # ------------------------------------------------------------------------------------------------ the augmenter
@@ -414,7 +467,7 @@ class Augmenter:
     def _check_device_forms(self) -> None:
         for a in self.augmenters:
             if a.kind == "reverb":
-                a.draw(0)                               # raises NotImplementedError
+                a.draw(0)                               # raises NotImplementedError unless it was built with on_device=True
 
     def max_samples(self, n: int) -> int:
         """The longest row an input of n samples can give: nothing is cropped at this width."""
@@ -552,6 +605,8 @@ class Augmenter:
                 st["coef"] = tb.add(np.asarray([d.coef for d in ds], np.float32))
                 if a.kind == "mix_bank":
                     st["bank_row"] = tb.add(np.asarray([d.bank_row for d in ds], np.int32))
+            elif a.kind == "reverb":
+                st["params"] = tb.add(np.stack([d.row() for d in ds]))
             else:
                 raise NotImplementedError(f"augmenter kind {a.kind!r}")
             stages.append(st)
@@ -585,6 +640,8 @@ class Augmenter:
                     g_dst = sec(s_rows) if stack else sec(st["group_out"][g])
                     ops.aug_resample(src, dst, sec(s_rows), g_dst, U, D, None if U == D else self._prototype(U, D, dev),
                                      lens=src_lens)
+            elif kind == "reverb":
+                ops.aug_reverb(src, dst, iota, dst_rows, sec(st["params"]).view(B, REVERB_PARAMS), lens=src_lens)
             else:
                 ops.aug_resample(src, dst, iota, dst_rows, 1, 1, lens=src_lens)
                 if kind == "dropout":

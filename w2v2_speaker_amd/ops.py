@@ -1694,6 +1694,9 @@ def trial_metrics(scores, labels, c_miss=1, c_fa=1, p_target=0.05, out=None, wor
 AUG_MAX_TAPS = 2561                     # W2V2_AUG_MAX_TAPS of include/w2v2_hip.h
 AUG_FIR_TILE = 2048                     # outputs per workgroup of w2v2_aug_fir (w2v2_aug_fir_tile())
 AUG_RESAMPLE_TILE = 256                 # outputs per workgroup of w2v2_aug_resample (w2v2_aug_resample_tile())
+AUG_REVERB_MAX_DELAY = 1024             # W2V2_AUG_REVERB_MAX_DELAY
+AUG_REVERB_PARAMS = 28                  # W2V2_AUG_REVERB_PARAMS: int32 per row of w2v2_aug_reverb's table
+AUG_REVERB_CHUNK = 512                  # samples per time chunk of w2v2_aug_reverb (w2v2_aug_reverb_chunk())
 
 
 def _aug_wave(x, what: str) -> Tuple[int, int, int]:
@@ -1819,3 +1822,17 @@ def aug_resample(src, dst, src_rows, dst_rows, U: int, D: int, h=None, lens=None
     _lib.check(lib().w2v2_aug_resample(src.data_ptr(), lds, N_in, _p(lens), src_rows.data_ptr(), dst.data_ptr(), ldd, N_out,
                                        dst_rows.data_ptr(), _p(out_lens), R, U, D, h.data_ptr() if U != D else None, half,
                                        stream()), "aug_resample")
+
+
+def aug_reverb(src, dst, src_rows, dst_rows, params, lens=None) -> None:
+    """dst[dst_rows[r]] = the freeverb bank of params[r] over src[src_rows[r]] (w2v2_aug_reverb): int32 params
+    [R, AUG_REVERB_PARAMS] on the device -- 16 comb delays, 8 all-pass delays, then the bits of the float32 feedback,
+    damp, wet gain and dry gain (data/augment.py reverb_parameters builds a row).  A row with a delay outside
+    [1, AUG_REVERB_MAX_DELAY] comes out NaN.  lens: int32 per src row."""
+    N_in, lds, N_out, ldd, R = _aug_src_dst(src, dst, src_rows, dst_rows, lens, "aug_reverb")
+    if not isinstance(params, torch.Tensor) or params.dtype != torch.int32 or params.dim() != 2 \
+            or tuple(params.shape) != (R, AUG_REVERB_PARAMS) or not params.is_contiguous():
+        raise ValueError(f"aug_reverb: params is a contiguous int32 [{R}, {AUG_REVERB_PARAMS}] tensor")
+    _dev(src, dst, src_rows, dst_rows, params, lens)
+    _lib.check(lib().w2v2_aug_reverb(src.data_ptr(), lds, N_in, _p(lens), src_rows.data_ptr(), dst.data_ptr(), ldd, N_out,
+                                     dst_rows.data_ptr(), R, params.data_ptr(), stream()), "aug_reverb")
