@@ -797,6 +797,32 @@ int w2v2_aam_softmax_fwd_bwd(const float* cos, const int64_t* label, float* soft
                              const float* inv_w, float* rowdot, float* colprod, int B, int C,
                              int64_t ldc, float margin, float scale, const float* loss_scale,
                              float* correct_rows, int easy_margin /* ref: aam_softmax.py:60-61 */, int dtype, void* stream);
+/* Margin heads: sub-centres, the additive cosine margin and the inter-top-k penalty in one row pass.  These semantics
+ * are DEFINED HERE (no reference file has such a head; the oracle of the tests is float64 torch).
+ * cos [B][ld] f32 holds the cosines of C classes x K sub-centres, sub-centre k of class c in column c*K + k
+ * (1 <= K <= 8, ld >= C*K; columns [C*K, ld) are never read).  One row b with label y:
+ *   m_c = max_k cos[c*K + k], k*_c the smallest k that attains it;
+ *   label logit: W2V2_MARGIN_ARC: phi(m_y) as w2v2_aam_softmax_fwd_bwd (hard threshold or easy_margin);
+ *                W2V2_MARGIN_COS: phi = m_y - margin, dphi = 1 (easy_margin ignored);
+ *   inter-top-k: the n_top classes c != y with the largest m_c (ties: the smaller class index; the label column is never
+ *     a candidate) get psi = m_c cos(inter_margin) + sqrt(clamp(1 - m_c^2, 0, 1)) sin(inter_margin),
+ *     dpsi = cos(inter_margin) - sin(inter_margin) m_c / max(sine, 1e-12);  0 <= n_top <= min(C - 1, 16);
+ *   every other class z_c = m_c; all logits times `scale`; loss row = lse(z) - z_y.
+ * softmax [B][ldp] f32 over the C CLASSES (ldp >= C); correct_rows[b] = 1 when the first arg-max class is the label.
+ * Gradient g_c = dLoss/dm_c * loss_scale / B (dphi / dpsi included) goes to column c*K + k*_c alone; the other K - 1
+ * columns of the class get exact zeros in dcos_w, dcos_x and colprod:  dcos_w = g * inv_w[column], dcos_x = g * inv_x[b],
+ * colprod = g * cos ([B][C*K] f32, row stride C*K), rowdot[b] = sum g * cos.  The pointers loss_scale, inv_x, inv_w,
+ * dcos_w, dcos_x, rowdot, colprod and correct_rows follow the null conventions of w2v2_aam_softmax_fwd_bwd; a label outside
+ * [0, C): NaN loss row, zero gradients, correct 0.  No atomics, one writer per element, fixed-order folds; with K = 1,
+ * n_top = 0 and W2V2_MARGIN_ARC every output has the bits of w2v2_aam_softmax_fwd_bwd. */
+#define W2V2_MARGIN_ARC 0
+#define W2V2_MARGIN_COS 1
+int w2v2_margin_softmax_fwd_bwd(const float* cos, const int64_t* label, float* softmax, float* loss_rows,
+                                void* dcos_w, void* dcos_x, const float* inv_x, const float* inv_w,
+                                float* rowdot, float* colprod, int B, int C, int K, int64_t ld, int64_t ldp,
+                                float margin, float scale, int easy_margin, int margin_type, int n_top,
+                                float inter_margin, const float* loss_scale, float* correct_rows, int dtype,
+                                void* stream);
 /* F.normalize backward: dx = inv[r] * (g[r] - x[r] * inv[r] * dot[r]);  g, dx f32 (dx written or
  * added), x f32 or act dtype. */
 int w2v2_normalize_bwd(const float* g, const void* x, int64_t ldx, const float* inv,

@@ -209,12 +209,15 @@ class BnArena(FlatArena):
 class EcapaStore(BnArena):
     """Parameter arena of the ECAPA model + AAM head."""
 
-    def __init__(self, cfg: EcapaConfig, device, act_dtype: torch.dtype = torch.bfloat16, num_speakers: int = 5994):
+    def __init__(self, cfg: EcapaConfig, device, act_dtype: torch.dtype = torch.bfloat16, num_speakers: int = 5994,
+                 sub_centers: int = 1):
         assert act_dtype in (torch.bfloat16, torch.float32), "ECAPA: bf16 or f32 (the reference runs it in fp32; no loss scaler here)"
-        self.cfg, self.num_speakers = cfg, num_speakers
+        self.cfg, self.num_speakers, self.sub_centers = cfg, num_speakers, int(sub_centers)
+        if not 1 <= self.sub_centers <= 8:
+            raise ValueError(f"sub_centers {sub_centers}: 1 .. 8 sub-centres per speaker")
         self.embed_dim = cfg.lin_neurons
         shapes: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
-        shapes["loss_fn.fc_weights"] = (num_speakers, cfg.lin_neurons)
+        shapes["loss_fn.fc_weights"] = (num_speakers * self.sub_centers, cfg.lin_neurons)       # row c * K + k
         shapes.update(ecapa_param_shapes(cfg))
         super().__init__(shapes, device, act_dtype)
         self.asp_running = self.bn_running[FE + "asp.tdnn.norm.norm.weight"]
@@ -652,7 +655,10 @@ class EcapaPlan(TdnnPlan):
     """Static plan of one ECAPA-TDNN forward (+ backward) for a fixed [B, T, n_mels] input."""
 
     def __init__(self, store: EcapaStore, batch: int, frames: int, *, train: bool, aam_margin: float = 0.2,
-                 aam_scale: float = 30.0):
+                 aam_scale: float = 30.0, sub_centers: Optional[int] = None, margin_type: str = "arc",
+                 inter_topk: int = 0, inter_margin: float = 0.06):
+        if sub_centers is not None and int(sub_centers) != store.sub_centers:
+            raise ValueError(f"plan: sub_centers {sub_centers}, but the parameter store was built with {store.sub_centers}")
         super().__init__(store, batch, frames, train)
         cfg = store.cfg
         B, T, M, dev, adt, f32 = batch, frames, batch * frames, self.dev, self.adt, torch.float32
@@ -688,7 +694,8 @@ class EcapaPlan(TdnnPlan):
         self.head = ClassifierHead("aam", B, L, store.num_speakers, w_master=p("loss_fn.fc_weights"),
                                    w_operand=store.w("loss_fn.fc_weights"),
                                    w_grad=g("loss_fn.fc_weights") if train else None, emb=self.emb, act_dtype=adt,
-                                   train=train, margin=aam_margin, scale=aam_scale)
+                                   train=train, margin=aam_margin, scale=aam_scale, sub_centers=store.sub_centers,
+                                   margin_type=margin_type, inter_topk=int(inter_topk), inter_margin=float(inter_margin))
         if train:
             self.de2 = torch.empty(B, E2, dtype=f32, device=dev)
             self.dpooled = torch.empty(B, E2, dtype=f32, device=dev)
@@ -762,9 +769,9 @@ class EcapaTrainer(fused.WindowedTrainer):
 
     def __init__(self, store: EcapaStore, plan: EcapaPlan, schedule, process_group=None,
                  optimizer: Optional[OptimConfig] = None, gradient_clip_val: float = 0.0,
-                 accumulate_grad_batches: int = 1):
-        """optimizer (None = Adam, beta2 0.999, eps 1e-8, no weight decay) / gradient_clip_val / accumulate_grad_batches:
-        see SpeakerTrainer."""
+                 accumulate_grad_batches: int = 1, margin_schedule=None):
+        """optimizer (None = Adam, beta2 0.999, eps 1e-8, no weight decay) / gradient_clip_val / accumulate_grad_batches /
+        margin_schedule: see SpeakerTrainer."""
         self.pg = process_group                      # data parallel: ONE all-reduce of the flat gradient arena (25 MB)
         world = 1
         if process_group is not None:
@@ -772,6 +779,7 @@ class EcapaTrainer(fused.WindowedTrainer):
             world = dist.get_world_size(process_group)
         super().__init__(store, schedule, optimizer, gradient_clip_val, accumulate_grad_batches, world)
         self.plan = plan
+        self.margin_schedule = margin_schedule
 
     def _embed(self, x: torch.Tensor) -> None:
         """[B, T, n_mels] filterbank features, or [B, N] waveforms through the device front-end."""
@@ -786,6 +794,7 @@ class EcapaTrainer(fused.WindowedTrainer):
             dist.all_reduce(arena, group=self.pg)
 
     def train_step(self, feat: torch.Tensor, label: torch.Tensor):
+        self._apply_margin(self.plan)
         if self.accumulate_grad_batches > 1:
             return self._micro_batch(feat, label)
         self.store.zero_grad()

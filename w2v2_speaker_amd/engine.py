@@ -179,8 +179,15 @@ class Plan:
                  seed: int = 7, keep_hidden_states: bool = False, paired: bool = False,
                  sep_token_constant: float = -1.0, encoder_frames: Optional[int] = None,
                  triplet_margin: float = 1.0, triplet_coef: float = 1.0, final_dropout: float = 0.0,
-                 max_target: int = ops.CTC_LONG_MAX_TARGET):
+                 max_target: int = ops.CTC_LONG_MAX_TARGET, sub_centers: Optional[int] = None,
+                 margin_type: str = "arc", inter_topk: int = 0, inter_margin: float = 0.06):
         cfg = store.cfg
+        # the margin heads (heads.ClassifierHead): the sub-centre count is the store's (it shapes loss_fn.fc_weights)
+        K = getattr(store, "sub_centers", 1)
+        if sub_centers is not None and int(sub_centers) != K:
+            raise ValueError(f"plan: sub_centers {sub_centers}, but the parameter store was built with {K}")
+        self.margin_kw = dict(sub_centers=K, margin_type=margin_type, inter_topk=int(inter_topk),
+                              inter_margin=float(inter_margin))
         # the letter head (store.head "letter"): dropout in front of its Linear, the longest transcript it holds
         self.final_dropout, self.max_target = float(final_dropout), int(max_target)
         self.triplet_margin, self.triplet_coef = float(triplet_margin), float(triplet_coef)
@@ -444,7 +451,7 @@ class Plan:
                                        bias=None if aam else st.p(bname),
                                        bias_grad=None if (aam or not self.train) else st.g(bname),
                                        emb=head_in, act_dtype=self.adt, train=self.train, margin=self.margin,
-                                       scale=self.scale, loss_scale=st.scaler)
+                                       scale=self.scale, loss_scale=st.scaler, **(self.margin_kw if aam else {}))
         if self.train:
             self.demb = (self.head.demb if (self.head is not None and self.fc is None)
                          else self._e(self.head_rows, E, dtype=f32))

@@ -19,18 +19,30 @@ class ClassifierHead:
                  w_operand: torch.Tensor, w_grad: Optional[torch.Tensor], bias: Optional[torch.Tensor] = None,
                  bias_grad: Optional[torch.Tensor] = None, emb: torch.Tensor, act_dtype: torch.dtype,
                  train: bool, margin: float = 0.2, scale: float = 30.0, loss_scale: Optional[torch.Tensor] = None,
-                 easy_margin: bool = False):
+                 easy_margin: bool = False, sub_centers: int = 1, margin_type: str = "arc", inter_topk: int = 0,
+                 inter_margin: float = 0.06):
         assert kind in ("aam", "ce", "ctc")      # "ctc" (CtcHead): the Linear of "ce" under another row kernel
+        # the margin heads (include/w2v2_hip.h "margin heads"): K sub-centres per class, "arc" / "cos" margin, inter-top-k.
+        # With all four at their defaults the head is the single-centre AAM head, launch for launch; anything else goes
+        # through w2v2_margin_softmax_fwd_bwd, and every product below runs over classes * K rows or columns.
+        self.K, self.margin_type = int(sub_centers), margin_type
+        self.inter_topk, self.inter_margin = int(inter_topk), float(inter_margin)
+        ops.check_margin_head(classes, self.K, self.inter_topk, self.inter_margin, margin_type)
+        self.margin_head = (self.K, margin_type, self.inter_topk) != (1, "arc", 0)
+        if self.margin_head and kind != "aam":
+            raise ValueError(f"sub-centres, the cosine margin and inter-top-k belong to the 'aam' head, not to {kind!r}")
         self.loss_scale = loss_scale          # device record of the dynamic loss scale (fp16 activations) or None
         self.kind, self.B, self.E, self.C, self.train = kind, batch, embed_dim, classes, train
         self.margin, self.scale, self.easy_margin = margin, scale, bool(easy_margin)
         self.w_master, self.w_grad, self.bias, self.bias_grad, self.emb = w_master, w_grad, bias, bias_grad, emb
         dev, f32 = emb.device, torch.float32
-        B, E, Cn = batch, embed_dim, classes
+        B, E, Cn = batch, embed_dim, classes * self.K
+        self.Cn = Cn                          # weight rows = logit columns; self.C stays the number of classes
         self.ldc = (Cn + 7) // 8 * 8
+        self.ldp = (classes + 7) // 8 * 8     # row stride of the softmax over the classes (= ldc without sub-centres)
         self.emb_lp = torch.empty(B, E, dtype=act_dtype, device=dev) if act_dtype != f32 else emb
         self.logits = torch.zeros(B, self.ldc, dtype=f32, device=dev)
-        self.softmax = torch.zeros(B, self.ldc, dtype=f32, device=dev) if kind != "ctc" else None
+        self.softmax = torch.zeros(B, self.ldp, dtype=f32, device=dev) if kind != "ctc" else None
         self.loss_rows = torch.empty(B, dtype=f32, device=dev)
         self.correct = torch.zeros(B, dtype=f32, device=dev)      # 1 where argmax(prediction) == label (train_acc)
         aam = kind == "aam"
@@ -85,12 +97,20 @@ class ClassifierHead:
         assert label.dtype == torch.int64 and label.is_cuda and label.shape == (B,)
         aam, tr = self.kind == "aam", self.train
         self._forward_logits()
-        ops.aam_softmax_fwd_bwd(self.logits, label, self.softmax, self.loss_rows,
-                                self.dcos_w if tr else None, (self.dcos_x if aam else None) if tr else None,
-                                self.inv_x if aam else None, self.inv_w if aam else None,
-                                self.rowdot if (tr and aam) else None, self.colprod if (tr and aam) else None,
-                                B, Cn, self.ldc, self.margin if aam else -1.0, self.scale, self.loss_scale if tr else None,
-                                self.correct, easy_margin=self.easy_margin)
+        if self.margin_head:
+            ops.margin_softmax_fwd_bwd(self.logits, label, self.softmax, self.loss_rows, self.dcos_w if tr else None,
+                                       self.dcos_x if tr else None, self.inv_x, self.inv_w, self.rowdot if tr else None,
+                                       self.colprod if tr else None, B, Cn, self.K, self.ldc, self.ldp, self.margin,
+                                       self.scale, self.loss_scale if tr else None, self.correct,
+                                       easy_margin=self.easy_margin, margin_type=self.margin_type, n_top=self.inter_topk,
+                                       inter_margin=self.inter_margin)
+        else:
+            ops.aam_softmax_fwd_bwd(self.logits, label, self.softmax, self.loss_rows,
+                                    self.dcos_w if tr else None, (self.dcos_x if aam else None) if tr else None,
+                                    self.inv_x if aam else None, self.inv_w if aam else None,
+                                    self.rowdot if (tr and aam) else None, self.colprod if (tr and aam) else None,
+                                    B, Cn, self.ldc, self.margin if aam else -1.0, self.scale,
+                                    self.loss_scale if tr else None, self.correct, easy_margin=self.easy_margin)
         loss = torch.empty((), dtype=torch.float32, device=self.loss_rows.device)     # (allocator only: no kernel)
         ops.mean(self.loss_rows, loss)
         if tr:
@@ -99,7 +119,7 @@ class ClassifierHead:
 
     def _forward_logits(self) -> None:
         """The launches in front of the row kernel: operand cast, (AAM) row norms, the logit GEMM, the accumulators' zeroing."""
-        B, E, Cn = self.B, self.E, self.C
+        B, E, Cn = self.B, self.E, self.Cn
         aam, tr = self.kind == "aam", self.train
         if self.emb_lp is not self.emb:
             ops.cast(self.emb, self.emb_lp)
@@ -112,7 +132,7 @@ class ClassifierHead:
 
     def _backward_from_dlogits(self) -> None:
         """The launches behind the row kernel: d(emb) and the head's parameter gradients from dcos_w / dcos_x."""
-        B, E, Cn = self.B, self.E, self.C
+        B, E, Cn = self.B, self.E, self.Cn
         aam = self.kind == "aam"
         for g in self.g_dx:
             g()

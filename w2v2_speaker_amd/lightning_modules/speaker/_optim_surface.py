@@ -35,6 +35,7 @@ class OptimizerSurface:
     _window_trainer = None                           # the trainer whose calls opened the accumulation window
     _torch_optimizer = None
     _torch_schedule = None
+    margin_schedule = None                           # optim.schedule.MarginSchedule of the AAM head's margin, or None
 
     def set_optimizer(self, optimizer: torch.optim.Optimizer) -> None:
         """A ``torch.optim.Adam`` or ``torch.optim.SGD`` over ``self.parameters()``.  Anything the fused step does not
@@ -51,6 +52,12 @@ class OptimizerSurface:
             raise NotImplementedError(f"interval: {schedule['interval']!r}; the schedule advances once per optimiser step")
         self.schedule = from_torch_scheduler(sched)
         self._torch_schedule = schedule
+        self._trainers.clear()
+
+    def set_margin_schedule(self, schedule) -> None:
+        """An ``optim.schedule.MarginSchedule`` (any callable optimiser step -> margin), or None: the trainers write its
+        value to the AAM head before each micro-batch.  Derived from the step count: a checkpoint needs nothing new."""
+        self.margin_schedule = schedule
         self._trainers.clear()
 
     def configure_optimizers(self):

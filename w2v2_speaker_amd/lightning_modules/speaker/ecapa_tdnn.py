@@ -199,6 +199,11 @@ class EcapaTdnnModule(FilterbankSpeakerModule):
             raise NotImplementedError(f"loss {type(loss_fn).__name__}: the ECAPA path runs under "
                                       "AngularAdditiveMarginSoftMaxLoss (speechbrain's Classifier + CE is outside it)")
         aam_margin, aam_scale = float(loss_fn.margin), float(loss_fn.scale)
+        # the margin heads (optim.loss.SubCenterMarginSoftMaxLoss); a plain AAM loss has none of the attributes
+        sub_centers = int(getattr(loss_fn, "sub_centers", 1))
+        self.margin_kw = dict(margin_type=getattr(loss_fn, "margin_type", "arc"),
+                              inter_topk=int(getattr(loss_fn, "inter_topk", 0)),
+                              inter_margin=float(getattr(loss_fn, "inter_margin", 0.06)))
         del loss_fn
         self.hyperparameters_to_save = hyperparameters_to_save
         if not cfg.global_context:
@@ -209,7 +214,8 @@ class EcapaTdnnModule(FilterbankSpeakerModule):
         self.model_cfg = EcapaConfig(cfg.input_mel_coefficients, cfg.lin_neurons, tuple(cfg.channels),
                                      tuple(cfg.kernel_sizes), tuple(cfg.dilations), cfg.attention_channels,
                                      cfg.res2net_scale, cfg.se_channels)
-        self.store = EcapaStore(self.model_cfg, device, act_dtype, num_speakers=self.num_speakers)
+        self.store = EcapaStore(self.model_cfg, device, act_dtype, num_speakers=self.num_speakers,
+                                sub_centers=sub_centers)
         self.store.init_weights(init_seed)
         if cfg.pretrained_weights_path is not None:       # ref :88-91: a bare ECAPA_TDNN state dict
             sd = torch.load(cfg.pretrained_weights_path, map_location="cpu", weights_only=True)
@@ -221,20 +227,30 @@ class EcapaTdnnModule(FilterbankSpeakerModule):
 
     @classmethod
     def from_config(cls, cfg: EcapaTDNNModuleConfig, num_speakers: int, aam_margin: float = 0.2,
-                    aam_scale: float = 30.0, **kw) -> "EcapaTdnnModule":
-        """Short form for scripts and tests: the AAM loss by its two hyper-parameters instead of a constructor."""
-        from ...optim.loss import AngularAdditiveMarginSoftMaxLoss
+                    aam_scale: float = 30.0, sub_centers: int = 1, margin_type: str = "arc", inter_topk: int = 0,
+                    inter_margin: float = 0.06, **kw) -> "EcapaTdnnModule":
+        """Short form for scripts and tests: the AAM loss by its hyper-parameters instead of a constructor (the last
+        four: the margin heads of optim.loss.SubCenterMarginSoftMaxLoss)."""
+        from ...optim.loss import AngularAdditiveMarginSoftMaxLoss, SubCenterMarginSoftMaxLoss
         dev = kw.get("device", "cuda")
-        ctor = lambda: AngularAdditiveMarginSoftMaxLoss(2, 2, margin=aam_margin, scale=aam_scale, device=dev,
-                                                        act_dtype=torch.float32)
+        if (sub_centers, margin_type, inter_topk) == (1, "arc", 0):
+            ctor = lambda: AngularAdditiveMarginSoftMaxLoss(2, 2, margin=aam_margin, scale=aam_scale, device=dev,
+                                                            act_dtype=torch.float32)
+        else:      # placeholder sizes, large enough for the loss's own argument check
+            ctor = lambda: SubCenterMarginSoftMaxLoss(2, inter_topk + 2, margin=aam_margin, scale=aam_scale,
+                                                      sub_centers=sub_centers, margin_type=margin_type,
+                                                      inter_topk=inter_topk, inter_margin=inter_margin, device=dev,
+                                                      act_dtype=torch.float32)
         return cls(None, cfg, num_speakers, ctor, kw.pop("validation_pairs", None), kw.pop("test_pairs", None),
                    kw.pop("evaluator", None), **kw)
 
     def _new_plan(self, batch: int, frames: int, train: bool) -> EcapaPlan:
-        return EcapaPlan(self.store, batch, frames, train=train, aam_margin=self.margin, aam_scale=self.scale)
+        return EcapaPlan(self.store, batch, frames, train=train, aam_margin=self.margin, aam_scale=self.scale,
+                         **self.margin_kw)
 
     def _new_trainer(self, plan: EcapaPlan) -> EcapaTrainer:
-        return EcapaTrainer(self.store, plan, self.schedule, **self._trainer_options())
+        return EcapaTrainer(self.store, plan, self.schedule, margin_schedule=self.margin_schedule,
+                            **self._trainer_options())
 
     def compute_speaker_prediction(self, embedding_tensor: torch.Tensor) -> torch.Tensor:
         return embedding_tensor.squeeze()                  # ref :120-122 under AAM

@@ -215,6 +215,11 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
         # ref: src/layers/embedding_masking.py:79, wav2vec2_fc.py:162-169)
         loss_fn = loss_fn_constructor()
         self.triplet_margin, self.c_triplet = 1.0, 1.0
+        # the margin heads (optim.loss.SubCenterMarginSoftMaxLoss); the other losses have none of the attributes
+        sub_centers = int(getattr(loss_fn, "sub_centers", 1))
+        self.margin_kw = dict(margin_type=getattr(loss_fn, "margin_type", "arc"),
+                              inter_topk=int(getattr(loss_fn, "inter_topk", 0)),
+                              inter_margin=float(getattr(loss_fn, "inter_margin", 0.06)))
         if isinstance(loss_fn, AngularAdditiveMarginSoftMaxLoss):
             loss, margin, scale = "aam", float(loss_fn.margin), float(loss_fn.scale)
         elif isinstance(loss_fn, TripletCrossEntropyLoss):        # (before CrossEntropyLoss, which it derives from)
@@ -290,7 +295,7 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
             raise ValueError("could not determine size of speaker embeddings")
         self.store = ParamStore(self.model_cfg, device, act_dtype, head=loss,
                                 num_speakers=n_out - 1 if loss == "ctc" else n_out,      # (the store adds the blank)
-                                embed_dim=self.stat_pool_dimension, hidden_fc=hidden,
+                                embed_dim=self.stat_pool_dimension, hidden_fc=hidden, sub_centers=sub_centers,
                                 freeze_cnn=cfg.completely_freeze_feature_extractor,
                                 attentive_pool="attentive" in (cfg.stat_pooling_type, cfg.test_stat_pooling_type))
         self.store.init_weights(init_seed)
@@ -321,13 +326,24 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
 
     @classmethod
     def from_config(cls, cfg: Wav2vec2FCModuleConfig, num_speakers: int, loss: str = "aam", aam_margin: float = 0.2,
-                    aam_scale: float = 30.0, triplet_margin: float = 1.0, c_triplet: float = 1.0,
+                    aam_scale: float = 30.0, triplet_margin: float = 1.0, c_triplet: float = 1.0, sub_centers: int = 1,
+                    margin_type: str = "arc", inter_topk: int = 0, inter_margin: float = 0.06,
                     **kw) -> "Wav2vec2FCModule":
-        """Short form for scripts and tests: the loss by name instead of a constructor."""
+        """Short form for scripts and tests: the loss by name instead of a constructor.  ``sub_centers`` / ``margin_type`` /
+        ``inter_topk`` / ``inter_margin``: the margin heads of optim.loss.SubCenterMarginSoftMaxLoss ("aam" only)."""
+        plain = (sub_centers, margin_type, inter_topk) == (1, "arc", 0)
+        if not plain and loss != "aam":
+            raise ValueError(f"sub_centers / margin_type / inter_topk belong to loss='aam', not to {loss!r}")
         assert loss in ("aam", "ce", "triplet", "triplet_ce", "ctc")
         dev = kw.get("device", "cuda")
 
         def ctor():
+            if loss == "aam" and not plain:      # placeholder sizes, large enough for the loss's own argument check
+                from ...optim.loss import SubCenterMarginSoftMaxLoss
+                return SubCenterMarginSoftMaxLoss(2, inter_topk + 2, margin=aam_margin, scale=aam_scale,
+                                                  sub_centers=sub_centers, margin_type=margin_type,
+                                                  inter_topk=inter_topk, inter_margin=inter_margin, device=dev,
+                                                  act_dtype=torch.float32)
             if loss == "aam":      # placeholder sizes, like config/optim/loss/aam_softmax.yaml
                 return AngularAdditiveMarginSoftMaxLoss(2, 2, margin=aam_margin, scale=aam_scale, device=dev,
                                                         act_dtype=torch.float32)
@@ -382,7 +398,8 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
             insert_cls_token=(pooling == "first+cls"), aam_margin=self.margin, aam_scale=self.scale, **self._triplet_kw()))
 
     def _triplet_kw(self) -> dict:
-        return {"triplet_margin": self.triplet_margin, "triplet_coef": self.c_triplet}
+        """The loss-specific keywords of every Plan this module builds: the triplet losses' and the margin heads'."""
+        return {"triplet_margin": self.triplet_margin, "triplet_coef": self.c_triplet, **self.margin_kw}
 
     # ------------------------------------------------------------------ reference surface
     def compute_speaker_embedding(self, input_tensor: torch.Tensor) -> torch.Tensor:
@@ -490,7 +507,7 @@ class Wav2vec2FCModule(OptimizerSurface, EmbeddingEvaluation, torch.nn.Module):
         plan = self._plan(x.shape[0], x.shape[1], True)
         loss, pred = self._trainer_step(
             pkey, lambda: SpeakerTrainer(self.store, plan, self.schedule, process_group=self.process_group,
-                                         **self._trainer_options()),
+                                         margin_schedule=self.margin_schedule, **self._trainer_options()),
             lambda tr: self._run_step(tr, plan, x, label, triplets))
         self.on_after_backward()
         return {"loss": loss, "prediction": pred, "train_acc": self.train_acc}

@@ -713,6 +713,48 @@ def aam_softmax_fwd_bwd(cos, label, softmax, loss_rows, dcos_w, dcos_x, inv_x, i
                "aam_softmax")
 
 
+MARGIN_ARC, MARGIN_COS = 0, 1                 # W2V2_MARGIN_* of include/w2v2_hip.h
+MARGIN_TYPES = {"arc": MARGIN_ARC, "cos": MARGIN_COS}
+MARGIN_MAX_SUB_CENTERS, MARGIN_MAX_TOPK = 8, 16
+
+
+def check_margin_head(C: int, K: int, n_top: int, inter_margin: float, margin_type) -> int:
+    """The argument rules of w2v2_margin_softmax_fwd_bwd, on the host -> the margin type's code.  ValueError."""
+    if not 1 <= int(K) <= MARGIN_MAX_SUB_CENTERS:
+        raise ValueError(f"margin head: {K} sub-centres outside [1, {MARGIN_MAX_SUB_CENTERS}]")
+    if not 0 <= int(n_top) <= min(C - 1, MARGIN_MAX_TOPK):
+        raise ValueError(f"margin head: inter-top-k {n_top} outside [0, min({C} - 1, {MARGIN_MAX_TOPK})]")
+    if not inter_margin >= 0:
+        raise ValueError(f"margin head: negative inter-class margin {inter_margin}")
+    mt = MARGIN_TYPES.get(margin_type, margin_type)
+    if mt not in (MARGIN_ARC, MARGIN_COS):
+        raise ValueError(f"margin head: margin type {margin_type!r} is neither 'arc' nor 'cos'")
+    return mt
+
+
+def margin_softmax_fwd_bwd(cos, label, softmax, loss_rows, dcos_w, dcos_x, inv_x, inv_w, rowdot, colprod, B: int,
+                           C: int, K: int, ld: int, ldp: int, margin: float, scale: float, loss_scale=None,
+                           correct_rows=None, easy_margin: bool = False, margin_type=MARGIN_ARC, n_top: int = 0,
+                           inter_margin: float = 0.0) -> None:
+    """The margin row pass over C classes x K adjacent sub-centre columns of cos [B, ld] (include/w2v2_hip.h "margin
+    heads"): softmax [B, ldp] over the classes; the gradient of a class goes to its winning sub-centre's column of
+    dcos_w / dcos_x [B, ld] and colprod [B, C * K], the other columns get zeros.  The optional tensors are those of
+    aam_softmax_fwd_bwd.  margin_type: MARGIN_ARC / MARGIN_COS or "arc" / "cos".  Bad arguments: ValueError, no launch."""
+    mt = check_margin_head(C, K, n_top, inter_margin, margin_type)
+    if ld < C * K or ldp < C:
+        raise ValueError(f"margin head: row strides {ld} / {ldp} under {C} x {K} columns / {C} classes")
+    if mt == MARGIN_ARC and margin < 0:
+        raise ValueError("margin head: a negative angular margin (the plain head is aam_softmax_fwd_bwd's)")
+    _dev(cos, label, softmax, loss_rows, dcos_w, dcos_x, inv_x, inv_w, rowdot, colprod, loss_scale, correct_rows)
+    dty = dt(dcos_w) if dcos_w is not None else F32
+    _lib.check(lib().w2v2_margin_softmax_fwd_bwd(cos.data_ptr(), label.data_ptr(), softmax.data_ptr(),
+                                                 loss_rows.data_ptr(), _p(dcos_w), _p(dcos_x), _p(inv_x), _p(inv_w),
+                                                 _p(rowdot), _p(colprod), B, C, K, ld, ldp, margin, scale,
+                                                 int(easy_margin), mt, int(n_top), inter_margin, _p(loss_scale),
+                                                 _p(correct_rows), dty, stream()),
+               "margin_softmax")
+
+
 def normalize_bwd(g, x, inv, dot, dx, rows: int, cols: int, ldx: Optional[int] = None, add_to: bool = False) -> None:
     _dev(g, x, inv, dot, dx)
     _lib.check(lib().w2v2_normalize_bwd(g.data_ptr(), x.data_ptr(), ldx if ldx is not None else cols, inv.data_ptr(),

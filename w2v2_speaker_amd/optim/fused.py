@@ -80,6 +80,14 @@ class WindowedTrainer:
         self.stepped = False               # whether the last train_step / flush call ran the optimiser
         self.store, self.schedule, self.step, self.world = store, schedule, 0, world
         self.optimizer, self.gradient_clip_val = optimizer, float(gradient_clip_val)
+        self.margin_schedule = None        # optim.schedule.MarginSchedule (the trainers' ``margin_schedule`` keyword)
+
+    def _apply_margin(self, plan) -> None:
+        """``margin_schedule``: write the margin of optimiser step ``self.step`` to the plan's head before a micro-batch.
+        The step index moves with the optimiser, so the margin is constant within an accumulation window, and a
+        checkpoint that restores the step restores the margin."""
+        if self.margin_schedule is not None:
+            plan.head.margin = float(self.margin_schedule(self.step))
 
     def _optimizer_step(self, grad: Optional[torch.Tensor] = None, n_micro: int = 1, head_only: bool = False) -> None:
         """Step on the mean of ``grad`` (None = store.grad), the rank-summed gradient of ``n_micro`` micro-batches per rank,

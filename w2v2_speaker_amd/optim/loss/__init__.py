@@ -4,3 +4,4 @@ from .cross_entropy import CrossEntropyLoss  # noqa: F401
 from .ctc_loss import CtcLoss  # noqa: F401
 from .triplet_loss import TripletLoss  # noqa: F401
 from .triplet_ce_loss import TripletCrossEntropyLoss  # noqa: F401
+from .margin_softmax import SubCenterMarginSoftMaxLoss  # noqa: F401

@@ -51,16 +51,22 @@ class AngularAdditiveMarginSoftMaxLoss(torch.nn.Module):
             wlp = (torch.empty(C, E, dtype=self.act_dtype, device=device)
                    if self.act_dtype != torch.float32 else self.fc_weights.data)
             emb = torch.empty(batch, E, dtype=torch.float32, device=device)
-            head = ClassifierHead("aam", batch, E, C, w_master=self.fc_weights.data, w_operand=wlp,
+            head = ClassifierHead("aam", batch, E, C // self._margin_kw().get("sub_centers", 1),
+                                  w_master=self.fc_weights.data, w_operand=wlp,
                                   w_grad=torch.zeros_like(self.fc_weights.data), emb=emb,
                                   act_dtype=self.act_dtype, train=train, margin=self.margin, scale=self.scale,
-                                  easy_margin=self.easy_margin)
+                                  easy_margin=self.easy_margin, **self._margin_kw())
             self._heads[key] = (head, wlp)
         head, wlp = self._heads[key]
+        head.margin = self.margin                        # a plain attribute: a margin schedule may have moved it
         if wlp is not self.fc_weights.data:
             from ... import ops
             ops.cast(self.fc_weights.data, wlp)          # the parameter may have been stepped by any optimiser
         return head
+
+    def _margin_kw(self) -> dict:
+        """Keywords of the margin heads for ClassifierHead (SubCenterMarginSoftMaxLoss); none: the single-centre AAM head."""
+        return {}
 
     def forward(self, x, label=None):
         assert x.size()[0] == label.size()[0]

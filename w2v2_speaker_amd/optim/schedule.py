@@ -124,6 +124,33 @@ class MultiStep:
         return lr, self.momentum
 
 
+@dataclass
+class MarginSchedule:
+    """The margin of the classification head as a function of the OPTIMISER step (this project's own definition; the
+    trainers write it to ``plan.head.margin`` before each micro-batch):  r = clamp((step - start_step) / (end_step -
+    start_step), 0, 1);  "linear": initial + (final - initial) r;  "exp": initial + (final - initial) (1 - 1000^-r) /
+    (1 - 1/1000), which has covered half the way at r = 0.1.  ``end_step == start_step`` is a step function at that step.
+    Large-margin fine-tuning is the constant schedule ``MarginSchedule(m, initial=m)``."""
+    final: float
+    initial: float = 0.0
+    start_step: int = 0
+    end_step: int = 0
+    mode: str = "linear"
+
+    def __post_init__(self):
+        if self.mode not in ("linear", "exp"):
+            raise ValueError(f"margin schedule: mode {self.mode!r} is neither 'linear' nor 'exp'")
+        if self.end_step < self.start_step:
+            raise ValueError(f"margin schedule: end_step {self.end_step} before start_step {self.start_step}")
+
+    def __call__(self, step: int) -> float:
+        span = self.end_step - self.start_step
+        r = min(max((step - self.start_step) / span, 0.0), 1.0) if span > 0 else float(step >= self.start_step)
+        if self.mode == "exp":
+            r = (1.0 - 1000.0 ** -r) / (1.0 - 1.0 / 1000.0)
+        return self.initial + (self.final - self.initial) * r
+
+
 def from_torch_scheduler(sched):
     """A ``torch.optim.lr_scheduler.OneCycleLR`` -> ``OneCycle``, a ``LambdaLR`` -> ``LambdaSchedule``, a ``MultiStepLR`` ->
     ``MultiStep`` (what the reference's config/optim/schedule/{one_cycle,tri_stage,schedule_wav2spk}.yaml instantiate).  ``.at(step)`` of the result is the lr

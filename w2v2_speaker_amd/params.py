@@ -206,8 +206,10 @@ class ParamStore(FlatArena):
                  head: Optional[str] = "aam", num_speakers: int = 5994, embed_dim: Optional[int] = None,
                  freeze_cnn: bool = True, attentive_pool: bool = False, attention_channels: int = 128,
                  init_loss_scale: float = 16384.0, two_term_weights: bool = True, hidden_fc: Tuple[int, ...] = (),
-                 vocab_size: Optional[int] = None):
-        """embed_dim: size of the pooled embedding (statistics-pooling output).  hidden_fc: output sizes of the hidden
+                 vocab_size: Optional[int] = None, sub_centers: int = 1):
+        """embed_dim: size of the pooled embedding (statistics-pooling output).  sub_centers: K weight rows per speaker
+        of the AAM head (heads.ClassifierHead ``sub_centers``): ``loss_fn.fc_weights`` is [num_speakers * K, embed_dim],
+        sub-centre k of speaker c in row c * K + k.  hidden_fc: output sizes of the hidden
         Linear+ReLU layers between pooling and the loss head (ref: wav2vec2_fc.py:185-228 ``hidden_fc_layers_out``);
         the CE head's Linear is fc_list.{len(hidden_fc)}.0, the AAM weight keeps input size embed_dim like the
         reference (wav2vec2_fc.py:212-224)."""
@@ -218,6 +220,9 @@ class ParamStore(FlatArena):
         self.vocab_size = None if vocab_size is None else int(vocab_size)
         self.cfg, self.act_dtype = cfg, act_dtype
         self.head, self.num_speakers, self.freeze_cnn = head, num_speakers, freeze_cnn
+        self.sub_centers = int(sub_centers)
+        if not 1 <= self.sub_centers <= 8 or (self.sub_centers != 1 and head != "aam"):
+            raise ValueError(f"sub_centers {sub_centers}: 1 .. 8 sub-centres, and more than one for the \"aam\" head only")
         self.embed_dim = embed_dim if embed_dim is not None else 2 * cfg.hidden_size
         shapes: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
         self.hidden_fc = tuple(int(h) for h in hidden_fc)
@@ -227,7 +232,7 @@ class ParamStore(FlatArena):
             if self.hidden_fc and dims[-1] != self.embed_dim:
                 raise ValueError("AAM head: the reference builds the AAM weight with input_features = the pooled "
                                  f"embedding size ({self.embed_dim}); the last hidden layer must have that size")
-            shapes["loss_fn.fc_weights"] = (num_speakers, self.embed_dim)
+            shapes["loss_fn.fc_weights"] = (num_speakers * self.sub_centers, self.embed_dim)
         elif head in ("ce", "triplet_ce", "ctc"):     # triplet + CE owns exactly what CE owns
             # "ctc" too, with one more output: class 0 is the blank (ref: speaker_recognition_module.py:104-107
             # ``num_speakers += 1``), speaker i is class i + 1

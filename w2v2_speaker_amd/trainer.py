@@ -129,8 +129,9 @@ class SpeakerTrainer(fused.WindowedTrainer):
     def __init__(self, store: ParamStore, plan: Plan, schedule, process_group=None, beta2: float = 0.999,
                  eps: float = 1e-8, layerdrop_seed: int = 1234, mask_seed: int = 7, reducer=None,
                  optimizer: Optional[OptimConfig] = None, gradient_clip_val: float = 0.0,
-                 accumulate_grad_batches: int = 1):
-        """reducer: an object with bucket_ready(name) / wait() / world (default: BucketAllReducer over
+                 accumulate_grad_batches: int = 1, margin_schedule=None):
+        """margin_schedule: an ``optim.schedule.MarginSchedule`` (any callable step -> margin) for the AAM head's margin,
+        see optim.fused.WindowedTrainer._apply_margin.  reducer: an object with bucket_ready(name) / wait() / world (default: BucketAllReducer over
         torch.distributed; comm.CAbiBucketAllReducer runs the collective through the C ABI alone).
         optimizer: the optimiser description (ref: config/optim/algo/*.yaml); None = Adam with this constructor's
         ``beta2`` / ``eps`` and no weight decay.  The schedule's second value is beta1 under Adam and the momentum under
@@ -143,6 +144,7 @@ class SpeakerTrainer(fused.WindowedTrainer):
         super().__init__(store, schedule, optimizer if optimizer is not None else OptimConfig(beta2=beta2, eps=eps),
                          gradient_clip_val, accumulate_grad_batches, self.reducer.world)
         self.plan, self.beta2, self.eps = plan, beta2, eps
+        self.margin_schedule = margin_schedule
         if self.accumulate_grad_batches > 1 and self.world > 1:
             if not hasattr(self.reducer, "buffer"):
                 raise TypeError("accumulate_grad_batches > 1 on several ranks needs a reducer with a `buffer` attribute "
@@ -194,6 +196,7 @@ class SpeakerTrainer(fused.WindowedTrainer):
         """``triplets``: see train_step.  Step while the whole wav2vec2 network is frozen (ref: wav2vec2_fc.py:339-347 + PL ``freeze()`` =
         requires_grad False AND eval mode): eval-mode forward, head forward/backward, Adam on the head only."""
         store = self.store
+        self._apply_margin(frozen_plan)
         if self.accumulate_grad_batches > 1:
             return self._micro_batch_frozen_encoder(frozen_plan, wav, label, triplets=triplets, transcript=transcript)
         store.zero_grad()
@@ -218,6 +221,7 @@ class SpeakerTrainer(fused.WindowedTrainer):
         on the host avoids by passing them.  "triplet"
         returns (loss, None)."""
         plan, store = self.plan, self.store
+        self._apply_margin(plan)
         if skip_layers is None:
             skip_layers = self.sample_layerdrop()
         if mask is None:
