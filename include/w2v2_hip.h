@@ -919,6 +919,65 @@ int w2v2_score_pairs_norm(const float* cos, const int32_t* pairs, int P, const f
 int w2v2_segment_mean(const float* bank, int64_t ld, int N, int D, const int32_t* order, const int32_t* offsets, int S,
                       float* out, int64_t ld_out, void* stream);
 
+/* ---------------------------------------------------------------------------------- scoring back-ends (backend.hip)
+ * LDA and PLDA trial scoring beside the cosine back-end (ref: config/evaluator/{lda,plda}.yaml, src/evaluation/speaker/
+ * lda.py and plda.py).  The reference's two classes cannot run as shipped (a constructor keyword its base class lacks, a
+ * PCA hard-coded to 200 components, a PLDA library that is not installable, `10 ** llr` pushed through (s + 1) / 2), so
+ * THIS COMMENT IS THE DEFINITION and its oracle is float64 numpy.  Kept from the reference: the constructor keywords and
+ * the chain projection -> centring -> length norm -> score.  Inputs: a training bank X [N][D] f32 on the device, one
+ * speaker label per row (host; mapped to 0 .. C-1 in sorted order, as the cohort builder does), an evaluation bank and
+ * an int32 trial table as for w2v2_score_pairs.
+ *   1. class statistics.  Counts n_c; class means m_c (w2v2_segment_mean); global mean mu0 (w2v2_embed_stats);
+ *        S_w = sum_r (x_r - m_c(r)) (x_r - m_c(r))^T,   S_b = sum_c n_c (m_c - mu0) (m_c - mu0)^T,   S_t = S_w + S_b.
+ *      A scatter matrix is formed block by block over at most rows_per_block rows: w2v2_rows_center writes the f32 block
+ *      a_r = w_r (x_r - mean row), w2v2_gemm on f32 operands forms A^T A [D][D] in f32, w2v2_scatter_fold adds it into a
+ *      [D][D] float64 accumulator (one writer per element, blocks in ascending order); the host symmetrises
+ *      (S + S^T) / 2 in float64.  S_b runs over the C class-mean rows with w_c = sqrt(n_c) and mu0 subtracted.
+ *   2. projection to R dimensions, y = P (x - mu0), P [R][D] solved on the host in float64 (symmetric eigen-solves).
+ *      "pca": the top-R eigenpairs (lambda, v) of S_t / (N - 1), rows of P = v / sqrt(lambda) (whitening PCA: the
+ *      projected training covariance is the identity); R <= min(D, N - 1).  "lda": whiten S_w / (N - C), then the top-R
+ *      eigenvectors of the whitened S_b / (C - 1); R <= min(D, C - 1); the projected S_w / (N - C) is the identity.  A
+ *      kept eigenvalue <= 1e-10 lambda_max is an error (a singular covariance).  The bank is projected by w2v2_gemm
+ *      (f32) with a bias epilogue, b = -P mu0, into an [N][R4] bank, R4 = R rounded up to 4, pad columns zero.
+ *      Eigenvector signs are left as the solver gives them: every score below is invariant to them.
+ *   3. latent normalisation.  mean / std over the projected TRAINING rows (w2v2_embed_stats), then
+ *      (y - mean) / (std + 1e-12) and F.normalize: the transform of w2v2_score_pairs / w2v2_rows_transform.  The LDA
+ *      back-end stops here and scores with the cosine (w2v2_score_pairs on the projected bank, (s + 1) / 2 clipped).
+ *   4. PLDA, the two-covariance model z = mu + y_c + e in the normalised latent space, y_c ~ N(0, B), e ~ N(0, W), mu
+ *      fixed at the mean of the normalised training rows.  Statistics of step 1 over the normalised training rows
+ *      Z [N][R]: n_c, m_c, S_w.  W_0 = S_w / N, B_0 = (1 / C) sum_c (m_c - mu)(m_c - mu)^T; max_iterations EM steps on
+ *      the host in float64:
+ *        E   Phi_c = (B^-1 + n_c W^-1)^-1,   yhat_c = Phi_c n_c W^-1 (m_c - mu)
+ *        M   B = (1 / C) sum_c (Phi_c + yhat_c yhat_c^T)
+ *            W = (1 / N) [ S_w + sum_c n_c ((m_c - mu - yhat_c)(m_c - mu - yhat_c)^T + Phi_c) ].
+ *      Then A with A W A^T = I and A B A^T = diag(psi), psi descending; the first Q rows are kept and
+ *      u = A (z - mu) is one more f32 GEMM with bias into an [N][Q4] bank.  The score of a trial (e, t):
+ *        llr = k + sum_d p_d u_e,d u_t,d - sum_d q_d (u_e,d^2 + u_t,d^2)
+ *        p_d = psi_d / (2 psi_d + 1),  q_d = psi_d^2 / (2 (psi_d + 1)(2 psi_d + 1)),
+ *        k = sum_d [ log(psi_d + 1) - log(2 psi_d + 1) / 2 ],
+ *      the exact log-ratio of the same-speaker joint Gaussian to the product of the marginals.  It is unbounded and
+ *      goes to the metrics as it is: NOT through (s + 1) / 2 and not clipped.
+ * Conventions of the trial scoring above: f32 banks, D % 4 == 0, ld % 4 == 0, 16-byte vectors, 64-bit row offsets, no
+ * atomics on global memory, no workgroup waits on another, fixed-order folds (equal inputs give equal bits), nothing
+ * allocated, all work on `stream`.
+ *
+ * out[r][:] = w_r * (x[r][:] - means[seg_id[r]][:]) for `rows` rows: one f32 subtraction and one f32 multiplication per
+ * element, never contracted.  seg_id int32 [rows] or NULL (every row takes means[0]); means [S][ld_means]; row_weight f32
+ * [rows] or NULL (w = 1).  A seg_id outside [0, S) is not dereferenced: that row of out is NaN.  out != x. */
+int w2v2_rows_center(const float* x, int64_t ld, int rows, int D, const int32_t* seg_id /*int32 [rows] or NULL*/,
+                     const float* means, int64_t ld_means, int S, const float* row_weight /*f32 [rows] or NULL*/, float* out,
+                     int64_t ld_out, void* stream);
+/* acc [D][D] f64 (row stride D, 16-byte aligned) = (first ? 0 : acc) + block [D][ldb] f32.  With first != 0 acc is not
+ * read.  One writer per element; the sum over blocks takes the order of the calls. */
+int w2v2_scatter_fold(const float* block /*f32 [D][ldb]*/, int64_t ldb, double* acc /*f64 [D][D]*/, int D, int first,
+                      void* stream);
+/* The llr of step 4 for P trials over the diagonalised bank u [N][ld] with Q columns (Q % 4 == 0: pad columns carry
+ * p = q = 0); p, q f64 [Q] on the device, 16-byte aligned; k by value.  One trial per wavefront, one pass over the two
+ * rows; every product is formed and summed in double, the lanes fold in a fixed order, one rounding to f32.  An index
+ * outside [0, N) is not dereferenced: that trial is NaN. */
+int w2v2_plda_score_pairs(const float* u, int64_t ld, int N, int Q, const int32_t* pairs /*int32 [P][2]*/, int P,
+                          const double* p, const double* q, double k, float* llr_out /*[P]*/, void* stream);
+
 /* ---------------------------------------------------------------------------------- trial metrics (metrics.hip)
  * What follows the scores: ROC / EER / minDCF of a trial list without the P scores leaving the device.  No kernel waits
  * on another workgroup (no look-back, no flag, no cooperative launch): every order between workgroups is a launch

@@ -200,6 +200,9 @@ _SIGS = {
     "w2v2_topk_stats": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "w2v2_score_pairs_norm": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "w2v2_segment_mean": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
+    "w2v2_rows_center": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "w2v2_scatter_fold": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp]),
+    "w2v2_plda_score_pairs": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_f64, c_vp, c_vp]),
     "w2v2_sort_tile": (c_i32, []),
     "w2v2_sort_f32_index_workspace_bytes": (c_i64, [c_i64]),
     "w2v2_sort_f32_index": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),

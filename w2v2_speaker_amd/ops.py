@@ -1647,8 +1647,137 @@ def cohort_stats(bank, cohort, K: int, mean=None, std=None, length_norm: bool = 
     return mu, sd
 
 
+# ---------------------------------------------------------------------------------------------- scoring back-ends (backend.hip)
+SCATTER_ROWS_PER_BLOCK = 4096           # rows of one f32 block product of class_scatter by default
+SCATTER_BLOCKS_PER_LAUNCH = 4           # block products of one batched GEMM launch: a [D, D] product alone is 144 tiles at D = 1,536
+
+
+def _row_vector(t, rows: int, dtype, what: str, name: str) -> None:
+    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.shape != (rows,) or not t.is_contiguous()):
+        raise ValueError(f"{what}: {name} is a contiguous {str(dtype).replace('torch.', '')} [{rows}] tensor")
+
+
+def _ld(t) -> int:
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def rows_center(x, means, seg_id=None, row_weight=None, out=None) -> torch.Tensor:
+    """out[r] = w_r * (x[r] - means[seg_id[r]]) (w2v2_rows_center): x [rows, D] f32, means [S, D] f32, seg_id device int32
+    [rows] or None (every row takes means[0]), row_weight f32 [rows] or None (w = 1) -> out [rows, D].  One subtraction
+    and one multiplication in f32 per element.  seg_id is NOT checked here (it is on the device: a row whose id lies
+    outside [0, S) comes back NaN)."""
+    rows, D, ld = _bank(x, "rows_center")
+    S, Dm, ldm = _bank(means, "rows_center (means)")
+    if Dm != D:
+        raise ValueError(f"rows_center: means has D = {Dm}, the rows D = {D}")
+    _row_vector(seg_id, rows, torch.int32, "rows_center", "seg_id")
+    _row_vector(row_weight, rows, torch.float32, "rows_center", "row_weight")
+    if out is not None:
+        orows, oD, _ = _bank(out, "rows_center (out)")
+        if oD != D or orows < rows or out.data_ptr() == x.data_ptr():
+            raise ValueError(f"rows_center: out is float32 [{rows}, {D}], not the input")
+    _dev(x, means, seg_id, row_weight, out)
+    if out is None:
+        out = torch.empty(rows, D, dtype=torch.float32, device=x.device)
+    _lib.check(lib().w2v2_rows_center(x.data_ptr(), ld, rows, D, _p(seg_id), means.data_ptr(), ldm, S, _p(row_weight),
+                                      out.data_ptr(), _ld(out), stream()), "rows_center")
+    return out[:rows]
+
+
+def scatter_fold(block, acc, first: bool) -> torch.Tensor:
+    """acc = (0 if first else acc) + block (w2v2_scatter_fold): block [D, D] f32 (row stride a multiple of 4), acc a
+    contiguous float64 [D, D] on the device.  With ``first`` acc is not read."""
+    D, D2, ldb = _bank(block, "scatter_fold")
+    if D2 != D:
+        raise ValueError(f"scatter_fold: block is square (got [{D}, {D2}])")
+    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.float64 or acc.shape != (D, D) or not acc.is_contiguous() \
+            or acc.data_ptr() % 16 != 0:
+        raise ValueError(f"scatter_fold: acc is a contiguous float64 [{D}, {D}] tensor, 16-byte aligned")
+    _dev(block, acc)
+    _lib.check(lib().w2v2_scatter_fold(block.data_ptr(), ldb, acc.data_ptr(), D, int(bool(first)), stream()), "scatter_fold")
+    return acc
+
+
+def plda_score_pairs(u, pairs, p, q, k: float, llr_out=None) -> torch.Tensor:
+    """The PLDA log-likelihood ratio of the trials pairs [P, 2] (device int32 rows of the diagonalised bank u [N, Q] f32)
+    -> llr [P] f32: k + sum_d p_d u_e,d u_t,d - sum_d q_d (u_e,d^2 + u_t,d^2), every product and sum in double
+    (w2v2_plda_score_pairs).  p, q: contiguous float64 [Q] on the device; k a host float.  Unbounded.  The indices are NOT
+    checked here: a trial with an index outside [0, N) comes back NaN."""
+    N, Q, ld = _bank(u, "plda_score_pairs")
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 \
+            or pairs.shape[0] < 1 or not pairs.is_contiguous():
+        raise ValueError("plda_score_pairs: pairs is a contiguous int32 [P, 2] tensor, P >= 1")
+    for v in (p, q):
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float64 or v.shape != (Q,) or not v.is_contiguous() \
+                or v.data_ptr() % 16 != 0:
+            raise ValueError(f"plda_score_pairs: p / q are contiguous float64 [{Q}] tensors, 16-byte aligned")
+    _dev(u, pairs, p, q, llr_out)
+    P = pairs.shape[0]
+    llr_out = _score_out(llr_out, P, u.device, "plda_score_pairs")
+    _lib.check(lib().w2v2_plda_score_pairs(u.data_ptr(), ld, N, Q, pairs.data_ptr(), P, p.data_ptr(), q.data_ptr(), float(k),
+                                           llr_out.data_ptr(), stream()), "plda_score_pairs")
+    return llr_out
+
+
+def class_scatter_workspace(N: int, D: int, rows_per_block: int = SCATTER_ROWS_PER_BLOCK) -> int:
+    """float32 elements of the workspace of class_scatter: the centred blocks of one launch and their products."""
+    rpb = min(int(rows_per_block), int(N))
+    g = max(1, min(SCATTER_BLOCKS_PER_LAUNCH, int(N) // rpb))
+    return g * (rpb * int(D) + int(D) * int(D))
+
+
+def class_scatter(bank, seg_id, means, row_weight=None, rows_per_block: int = SCATTER_ROWS_PER_BLOCK,
+                  workspace=None) -> torch.Tensor:
+    """sum_r a_r a_r^T with a_r = w_r (bank[r] - means[seg_id[r]]) -> float64 [D, D] on the device (step 1 of
+    include/w2v2_hip.h, "scoring back-ends"): the bank goes in blocks of at most ``rows_per_block`` rows through
+    rows_center, the exact-f32 MFMA GEMM (A^T A in f32, one product per block, up to SCATTER_BLOCKS_PER_LAUNCH of them in
+    one batched launch) and scatter_fold (the f64 accumulator), blocks in ascending order.
+    seg_id device int32 [N] or None (one mean row), row_weight f32 [N] or None.  The result is not symmetrised (the two
+    triangles may differ in the last f32 bits of a block product); ``workspace``: class_scatter_workspace float32."""
+    N, D, _ = _bank(bank, "class_scatter")
+    S, Dm, _ = _bank(means, "class_scatter (means)")
+    if Dm != D:
+        raise ValueError(f"class_scatter: means has D = {Dm}, the bank D = {D}")
+    _row_vector(seg_id, N, torch.int32, "class_scatter", "seg_id")
+    _row_vector(row_weight, N, torch.float32, "class_scatter", "row_weight")
+    if isinstance(rows_per_block, bool) or not isinstance(rows_per_block, int) or rows_per_block < 1:
+        raise ValueError(f"class_scatter: rows_per_block = {rows_per_block!r} must be a positive integer")
+    rpb = min(rows_per_block, N)
+    need = class_scatter_workspace(N, D, rpb)
+    if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32
+                                  or not workspace.is_contiguous() or workspace.numel() < need
+                                  or workspace.data_ptr() % 16 != 0):
+        raise ValueError(f"class_scatter: workspace holds {need} float32 (class_scatter_workspace), contiguous, 16-byte aligned")
+    _dev(bank, seg_id, means, row_weight, workspace)
+    dev = bank.device
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=dev)
+    full = N // rpb                                     # whole blocks; the rows behind them are one more, shorter block
+    G = max(1, min(SCATTER_BLOCKS_PER_LAUNCH, full))
+    a_buf = workspace.view(-1)[:G * rpb * D].view(G * rpb, D)
+    prod = workspace.view(-1)[G * rpb * D:G * (rpb * D + D * D)].view(G, D, D)
+    acc = torch.empty(D, D, dtype=torch.float64, device=dev)
+    products = {}
+    r0 = 0
+    while r0 < N:
+        g = min(G, (N - r0) // rpb)                     # blocks of this launch: up to G whole ones, or the last short one
+        k = rpb if g else N - r0
+        g = max(g, 1)
+        rows = g * k
+        rows_center(bank[r0:r0 + rows], means, None if seg_id is None else seg_id[r0:r0 + rows],
+                    None if row_weight is None else row_weight[r0:r0 + rows], out=a_buf)
+        if (g, k) not in products:                      # (at most three shapes: G blocks, fewer blocks, the short block)
+            products[g, k] = Gemm(D, D, k, a_buf, a_buf, prod, lda=D, ldb=D, ldc=D, transA=True, transB=True, batch=g,
+                                  a_strides=(k * D, 0), b_strides=(k * D, 0), c_strides=(D * D, 0))
+        products[g, k]()
+        for z in range(g):                              # the fold keeps the blocks in ascending order
+            scatter_fold(prod[z], acc, first=r0 == 0 and z == 0)
+        r0 += rows
+    return acc
+
+
 # ---------------------------------------------------------------------------------------------- trial metrics (metrics.hip)
-SORT_TILE = 2048            # keys per workgroup per pass of w2v2_sort_f32_index (csrc/metrics.hip SORT_TILE)
+SORT_TILE = 2048           # keys per workgroup per pass of w2v2_sort_f32_index (csrc/metrics.hip SORT_TILE)
 TRIAL_METRICS_FIELDS = ("eer", "eer_threshold", "mdc", "mdc_threshold", "n_pos", "n_neg", "n_nan", "n_thresholds")
 
 
