@@ -1014,6 +1014,66 @@ int64_t w2v2_trial_metrics_workspace_bytes(int64_t P);
 int w2v2_trial_metrics(const float* scores, const uint8_t* labels, int64_t P, double c_miss, double c_fa, double p_target,
                        double* out, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------- score calibration (calibration.hip)
+ * What turns trial scores into log-likelihood ratios, and what says how good they are as such: a prior-weighted logistic
+ * regression of K systems' scores (K = 1: calibration; K > 1: linear fusion), its affine map applied on the device, and
+ * Cllr / actDCF of the result.  The reference project has no calibration: THIS BLOCK IS THE DEFINITION.  Conventions of
+ * the trial metrics above: no kernel waits on another workgroup, no atomics on global memory, per-workgroup partials in a
+ * caller-owned 16-byte aligned workspace folded in ascending order by one workgroup, nothing allocated, all work on
+ * `stream`.  Every sum and every transcendental is f64, no product is contracted into an fma, every fold has a fixed
+ * order: equal inputs give equal bits.
+ *
+ * Inputs: scores S [K][P] f32 with row stride ld >= P (the pad behind a row is never read), 1 <= K <=
+ * W2V2_CALIB_MAX_SYSTEMS, 1 <= P < 2^31; labels [P] uint8 (0 / 1); c_miss >= 1, c_fa >= 1, 0 < p_target < 1; ridge >= 0.
+ *   pi = p_target c_miss / (p_target c_miss + (1 - p_target) c_fa), tau = log(pi / (1 - pi)), theta = -tau.
+ * 1. Moments, two passes: m_k = sum_i s_ki / P; sd_k = sqrt(sum_i (s_ki - m_k)^2 / (P - 1)); r_k = 1 / sd_k;
+ *    x_i = (1, (s_1i - m_1) r_1, ...); N_tar, N_non, n_nan (trials with a NaN in any system).
+ * 2. At w in R^(K+1): l_i = w_0 + sum_k w_k x_ik (k ascending), z_i = l_i + tau, c_i = pi / N_tar (target) or
+ *    (1 - pi) / N_non;  e = exp(-|z|), sigma(|z|) = 1 / (1 + e), sigma(-|z|) = e / (1 + e), softplus(a) = max(a, 0) +
+ *    log1p(e);  J = sum c_i softplus(-z_i | target, z_i | non-target) + ridge / 2 sum_{k>=1} w_k^2;
+ *    g = sum c_i (sigma(z_i) - y_i) x_i (a target's sigma - 1 is -sigma(-z), never a difference) + ridge w_k;
+ *    H = sum c_i sigma(z_i) sigma(-z_i) x_i x_i^T + ridge on the diagonal behind element 0.
+ * 3. Newton with step halving from w = 0 (or w_start): a trial point whose J exceeds the accepted J is rejected and the
+ *    step along the kept direction halved; an accepted point gives d = H^-1 g by Cholesky and the decrement g.d / 2; the
+ *    fit has converged when that is < 1e-12 -- unless ridge = 0 and J < min(pi / N_tar, (1 - pi) / N_non) ln 2 there: a
+ *    trial on the wrong side of its threshold costs at least c_i ln 2, so such a J proves the set separable, J has no
+ *    minimum (it only falls towards 0, by about e per round) and the fit keeps running -- else the next trial point is
+ *    w - d.  status: 0 running (also: not converged
+ *    after max_iter rounds), 1 converged, 2 H not positive definite / a non-finite sum / n_nan > 0 / sd_k = 0 or not
+ *    finite / a class absent, 3 step below 2^-20.  The whole fit is enqueued by one call: two moment passes, then
+ *    max_iter rounds of one tiled statistics launch and one single-workgroup fold + solve launch.  Once the status is
+ *    non-zero the statistics launches return at once and the solve launches change nothing: the host never waits.
+ * 4. a_k = w_k r_k, a_0 = w_0 - sum_k a_k m_k (k ascending): llr_i = a_0 + sum_k a_k s_ki.
+ * The record, f64 [w2v2_calib_record_doubles()] on the device, written whole by every fit (N = K + 1, M =
+ * W2V2_CALIB_MAX_SYSTEMS): [0] status, [1] rounds used, [2] K, [3] accepted J, [4] step, [5] last decrement, [6] N_tar,
+ * [7] N_non, [8] n_nan, [9] J of the last trial point, [16 ..] accepted w [M + 1], then direction d [M + 1], trial w
+ * [M + 1], m [M], sd [M], r [M], a [M + 1], g [M + 1] and H [M + 1][M + 1] of the accepted point.
+ * w_start: HOST pointer to K + 1 doubles or NULL (w = 0); with max_iter = 1 the record then holds J, g and H at w_start.
+ * workspace: at least w2v2_calib_workspace_bytes(P) bytes (-1: P out of range), one row per tile of w2v2_calib_tile()
+ * trials; it serves w2v2_llr_metrics as well. */
+#define W2V2_CALIB_MAX_SYSTEMS 8
+int w2v2_calib_tile(void);
+int w2v2_calib_record_doubles(void);
+int64_t w2v2_calib_workspace_bytes(int64_t P);
+int w2v2_calib_fit(const float* scores, int64_t ld, int K, const uint8_t* labels, int64_t P, double c_miss, double c_fa,
+                   double p_target, double ridge, int max_iter, const double* w_start, double* record, void* workspace,
+                   void* stream);
+/* 5. llr_out[i] = f32(a[0] + sum_k a[k + 1] (double)s_ki), k ascending, every product and sum in double, one rounding.
+ * a: K + 1 doubles ON THE DEVICE (a fit's record + 16 + 3 (M + 1) + 3 M doubles: fit -> apply needs no host round trip).
+ * A NaN score gives a NaN llr.  llr_out may not overlap scores. */
+int w2v2_calib_apply(const float* scores, int64_t ld, int K, int64_t P, const double* a, float* llr_out, void* stream);
+/* 6. llr [P] f32 and labels [P] uint8 on the device -> out [8] f64 on the device: cllr, cllr_tar, cllr_non, act_dcf,
+ * act_p_miss, act_p_fa, n_pos, n_nan.  cllr_tar = mean over targets of log2(1 + e^-llr), cllr_non = mean over non-targets
+ * of log2(1 + e^llr) (softplus in nats as in step 2, the mean divided by ln 2), cllr their mean.  act_p_miss = #(target,
+ * llr < theta) / N_tar, act_p_fa = #(non-target, llr >= theta) / N_non: integer-exact counts, the comparison in double
+ * against theta = -log(pi / (1 - pi)) as the host computes it; act_dcf = (c_miss p_miss p_target + c_fa p_fa
+ * (1 - p_target)) / min(c_miss p_target, c_fa (1 - p_target)), calculate_mdc's expression, order and normaliser (ref:
+ * src/eval_metrics.py:90-206).  0 <= p_target <= 1 here.  NaN llrs are counted in n_nan and make the cllr of their class
+ * (and cllr) NaN: with both classes present, cllr is NaN exactly when n_nan > 0.  With a class absent the outputs that
+ * divide by its count are NaN or inf (never a fault). */
+int w2v2_llr_metrics(const float* llr, const uint8_t* labels, int64_t P, double c_miss, double c_fa, double p_target,
+                     double* out, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------ optimiser
  * torch.optim.Adam (ref: config/optim/algo/adam.yaml, src/main.py:323-335) over one flat f32
  * parameter arena; also refreshes the 16-bit copy (pb_dtype = W2V2_BF16 / W2V2_F16) the GEMMs read

@@ -208,6 +208,12 @@ _SIGS = {
     "w2v2_sort_f32_index": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "w2v2_trial_metrics_workspace_bytes": (c_i64, [c_i64]),
     "w2v2_trial_metrics": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_f64, c_f64, c_vp, c_vp, c_vp]),
+    "w2v2_calib_tile": (c_i32, []),
+    "w2v2_calib_record_doubles": (c_i32, []),
+    "w2v2_calib_workspace_bytes": (c_i64, [c_i64]),
+    "w2v2_calib_fit": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_f64, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "w2v2_calib_apply": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp]),
+    "w2v2_llr_metrics": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_f64, c_f64, c_vp, c_vp, c_vp]),
     "w2v2_adam_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32,
                                c_f32, c_f32, c_vp, c_i32, c_i32, c_vp]),
     "w2v2_optim_step": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32,

@@ -198,10 +198,24 @@ class CosineDistanceEvaluator:
         cos = torch.nn.functional.cosine_similarity(bank[e], bank[t], dim=1, eps=1e-8)
         return normalise_scores(cos, mu[e], sd[e], mu[t], sd[t], score_norm.mode).detach().cpu().numpy().tolist()
 
-    def evaluate(self, pairs: List[EvaluationPair], samples: List[EmbeddingSample], score_norm=None):
+    def _host_member_rows(self, pp, n: int) -> np.ndarray:
+        """The metric scores of every member of an ensemble on the host, float64 [n, P]: what a fusion takes."""
+        first = pp[0][0].embedding
+        if not isinstance(first, list) or len(first) != n:
+            raise ValueError(f"calibration: fitted on {n} systems: every sample carries a list of {n} embeddings")
+        rows = [self._compute_prediction_scores(
+            [(EmbeddingSample(sample_id=a.sample_id, embedding=a.embedding[i]),
+              EmbeddingSample(sample_id=b.sample_id, embedding=b.embedding[i])) for a, b in pp]) for i in range(n)]
+        return np.clip((np.array(rows, dtype=np.float64) + 1) / 2, 0, 1)
+
+    def evaluate(self, pairs: List[EvaluationPair], samples: List[EmbeddingSample], score_norm=None, calibration=None,
+                 llr_metrics: bool = False):
         """``score_norm`` (device_scoring.ScoreNorm, default None: the reference's evaluation, unchanged): the trial scores
         are normalised with its cohort first; they are then unbounded and go to the metrics as they are, NOT through
-        ``(s+1)/2`` and the clip."""
+        ``(s+1)/2`` and the clip.  ``calibration`` (calibration.ScoreCalibration, fitted; default None): the scores that go
+        to the metrics are the calibrated llrs of those scores (float64 numpy here), unbounded, and the dict gains cllr,
+        act_dcf, act_p_miss and act_p_fa; a K-system calibration fuses the K members of an ensemble.
+        ``llr_metrics=True`` without a calibration adds the same four keys for the scores as they are."""
         sample_map = {}
         for sample in samples:
             if sample.sample_id in sample_map:
@@ -214,10 +228,17 @@ class CosineDistanceEvaluator:
                 return {"eer": -1, "eer_threshold": -1, "mdc": -1, "mdc_threshold": -1}
             gt.append(1 if pair.same_speaker else 0)
             pp.append((sample_map[pair.sample1_id], sample_map[pair.sample2_id]))
-        if score_norm is not None:
+        if calibration is not None and calibration.num_systems != 1:
+            scores = calibration.apply(self._host_member_rows(pp, calibration.num_systems)).tolist()
+        elif score_norm is not None:
             scores = self._compute_normalised_scores(pp, score_norm)
         else:
             scores = np.clip((np.array(self._compute_prediction_scores(pp)) + 1) / 2, 0, 1).tolist()
+        if calibration is not None or llr_metrics:
+            from .device_scoring import host_llr_metrics
+            if calibration is not None and calibration.num_systems == 1:
+                scores = calibration.apply(np.asarray(scores, dtype=np.float64)).tolist()
+            return host_llr_metrics(gt, scores, calibration)
         try:
             eer, eer_threshold = calculate_eer(gt, scores, pos_label=1)
         except (ValueError, ZeroDivisionError) as e:       # reference falls back to a very bad score
@@ -250,8 +271,19 @@ class CosineDistanceEvaluator:
         leave the metrics on the device as well, and that takes ``score_norm``: ``evaluate_bank_metrics``.)"""
         return self.evaluate_bank_metrics(pairs, keys, bank, frame_offsets, metrics="host")
 
+    def _metric_scores_device(self, bank: torch.Tensor, index, score_norm=None) -> torch.Tensor:
+        """The scores the metrics would see for one pooled bank, float32 [P] on the device (ScoreCalibration.fit_bank)."""
+        from .device_scoring import score_trials_device
+        if self.center_before_scoring and (self.mean is None or self.std is None):
+            raise TypeError("center_before_scoring=True but fit_parameters() has not been called "
+                            "(mean / std are None)")
+        centre = self.center_before_scoring
+        return score_trials_device(bank, index, mean=self.mean if centre else None, std=self.std if centre else None,
+                                   length_norm=self.length_norm_before_scoring, keep_on_device=True,
+                                   **({} if score_norm is None else {"score_norm": score_norm})).device_scores
+
     def evaluate_bank_metrics(self, pairs: List[EvaluationPair], keys: List[str], bank, frame_offsets=None,
-                              metrics: str = "host", score_norm=None):
+                              metrics: str = "host", score_norm=None, calibration=None, llr_metrics: bool = False):
         """``evaluate_bank`` with the choice of where ROC / EER / minDCF are computed.  ``metrics="host"``: exactly
         ``evaluate_bank``.  ``metrics="device"`` (one bank or a frame bank): the scores stay on the device too, the metrics
         are computed there (csrc/metrics.hip, device_scoring.metrics_device) and eight doubles cross;
@@ -260,11 +292,16 @@ class CosineDistanceEvaluator:
         NotImplementedError for one; any other value of ``metrics`` raises ValueError.  ``score_norm``
         (device_scoring.ScoreNorm; one pooled bank only, anything else raises NotImplementedError): the scores are
         normalised on the device with its cohort (csrc/score_norm.hip) before they cross or reach the metrics; they are
-        unbounded, not mapped to [0, 1]."""
-        from .device_scoring import TrialIndex, host_metrics, metrics_device, score_trials_device
+        unbounded, not mapped to [0, 1].  ``calibration`` (calibration.ScoreCalibration, fitted; default None: all of the
+        above, unchanged): the scores become calibrated llrs on the device (csrc/calibration.hip) before they cross or reach
+        the metrics, and the dict gains cllr, act_dcf, act_p_miss and act_p_fa (ops.llr_metrics with ``metrics="device"``,
+        still eight doubles in one copy).  A list of n banks with an n-system calibration is fused on the device:
+        ``metrics="device"`` works for it, and P floats cross with ``metrics="host"``, not n * P.  ``llr_metrics=True``
+        without a calibration adds the four keys for the scores as they are."""
+        from .device_scoring import TrialIndex, finish_bank_metrics, score_trials_device
         if metrics not in ("host", "device"):
             raise ValueError(f"metrics={metrics!r}: 'host' or 'device'")
-        if metrics == "device" and isinstance(bank, (list, tuple)):
+        if metrics == "device" and isinstance(bank, (list, tuple)) and calibration is None:
             raise NotImplementedError("metrics='device' takes one bank: the members of an ensemble are combined on the host "
                                       "in the reference's Python-float order")
         index = TrialIndex(pairs, keys)
@@ -278,11 +315,6 @@ class CosineDistanceEvaluator:
         self.last_bank_scoring = score_trials_device(
             bank, index, mean=self.mean if centre else None, std=self.std if centre else None,
             length_norm=self.length_norm_before_scoring and frame_offsets is None, frame_offsets=frame_offsets,
-            keep_on_device=metrics == "device", **({} if score_norm is None else {"score_norm": score_norm}))
-        if metrics == "device":
-            record = []
-            res = metrics_device(self.last_bank_scoring.device_scores, index, record=record)
-            self.last_bank_metrics = record[0]
-            self.last_bank_scoring.host_copy_floats = record[0].host_copy_floats      # (the host path copied them after all)
-            return res
-        return host_metrics(index.ground_truth, self.last_bank_scoring.scores.tolist())
+            keep_on_device=metrics == "device", **({} if score_norm is None else {"score_norm": score_norm}),
+            **({} if calibration is None else {"calibration": calibration}))
+        return finish_bank_metrics(self, index, metrics, calibration, calibration is not None or llr_metrics)

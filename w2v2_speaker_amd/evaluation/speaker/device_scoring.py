@@ -180,7 +180,8 @@ class DeviceScores:
 
 def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial_index: TrialIndex, *, mean=None, std=None,
                         length_norm: bool = False, frame_offsets=None, cap: int = FRAME_CAP,
-                        keep_on_device: bool = False, score_norm: Optional[ScoreNorm] = None) -> DeviceScores:
+                        keep_on_device: bool = False, score_norm: Optional[ScoreNorm] = None,
+                        calibration=None) -> DeviceScores:
     """Score ``trial_index`` over ``bank`` on the device.  bank: an ``[N, D]`` device tensor; a list of those (an
     ensemble: every member scored into one ``[n, P]`` buffer, combined on the host in the reference's order
     ``score += s_i * (1 / n)`` as Python floats, ref: cosine_distance.py:172-181); or, with ``frame_offsets`` ([N + 1],
@@ -188,7 +189,11 @@ def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial
     non-pooled form (frames drawn by draw_frame_sets from the global ``random``; no centring, no length norm, as in the
     reference).  One device -> host copy; none with ``keep_on_device`` (one bank or a frame bank: the scores stay
     where ``metrics_device`` reads them; an ensemble is combined on the host and cannot stay).  ``score_norm`` (one pooled
-    bank only): the scores are the normalised ones (ops.cohort_stats + ops.score_pairs_norm), computed where the bank is."""
+    bank only): the scores are the normalised ones (ops.cohort_stats + ops.score_pairs_norm), computed where the bank is.
+    ``calibration`` (calibration.ScoreCalibration, fitted; default None: everything above, unchanged): the scores are the
+    calibrated llrs ``a_0 + sum_k a_k s_k`` of the members' metric scores, computed on the device (ops.calib_apply), unbounded
+    and not mapped again.  A list of n banks with an n-system calibration is FUSED there: ``keep_on_device`` works and P
+    floats cross otherwise, not n * P."""
     members = list(bank) if isinstance(bank, (list, tuple)) else [bank]
     if not members or not all(isinstance(b, torch.Tensor) for b in members):
         raise ValueError("bank is a device tensor or a non-empty list of them")
@@ -200,7 +205,7 @@ def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial
                                   "utterance")
     dev = members[0].device
     P = len(trial_index)
-    if keep_on_device and len(members) != 1:
+    if keep_on_device and len(members) != 1 and calibration is None:
         raise NotImplementedError("keep_on_device: the members of an ensemble are combined on the host in the reference's "
                                   "Python-float order")
     if frame_offsets is not None:
@@ -212,6 +217,8 @@ def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial
             raise ValueError(f"frame_offsets is [N + 1] = [{trial_index.num_rows + 1}], from 0 to the rows of the frame bank")
         sel, counts = draw_frame_sets(np.diff(off), trial_index, cap)
         _, score = ops.score_frame_sets(members[0], _upload(sel, dev), _upload(counts, dev))
+        if calibration is not None:
+            return calibrated_scores(score.unsqueeze(0), calibration, keep_on_device, members[0].numel())
         if keep_on_device:
             return DeviceScores(None, 0, members[0].numel(), score)
         host = score.cpu().numpy()
@@ -232,10 +239,14 @@ def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial
         cohort = score_norm.cohort.to(dev, torch.float32).contiguous()
         mu, sd = ops.cohort_stats(members[0], cohort, score_norm.top_k, mean, std, length_norm)
         normed = ops.score_pairs_norm(cos[0], table, mu, sd, score_norm.mode)
+        if calibration is not None:
+            return calibrated_scores(normed.unsqueeze(0), calibration, keep_on_device, bank_floats)
         if keep_on_device:
             return DeviceScores(None, 0, bank_floats, normed)
         host = normed.cpu().numpy()
         return DeviceScores(host.astype(np.float64), host.size, bank_floats)
+    if calibration is not None:
+        return calibrated_scores(score, calibration, keep_on_device, bank_floats)
     if n == 1 and keep_on_device:
         return DeviceScores(None, 0, bank_floats, score[0])
     if n == 1:
@@ -250,6 +261,34 @@ def score_trials_device(bank: Union[torch.Tensor, Sequence[torch.Tensor]], trial
             s += member_scores[i][idx] * (1 / n)
         combined.append(s)
     return DeviceScores(np.clip((np.array(combined) + 1) / 2, 0, 1), host.size, bank_floats)
+
+
+def calibrated_scores(rows: torch.Tensor, calibration, keep_on_device: bool, bank_floats: int) -> DeviceScores:
+    """The members' metric scores ``rows`` (float32 [K, P] on the device) through a fitted calibration -> the llrs as a
+    DeviceScores: on the device with ``keep_on_device``, else one copy of P floats."""
+    llr = calibration.apply(rows)
+    if keep_on_device:
+        return DeviceScores(None, 0, bank_floats, llr)
+    host = llr.cpu().numpy()
+    return DeviceScores(host.astype(np.float64), host.size, bank_floats)
+
+
+LLR_KEYS = ("cllr", "act_dcf", "act_p_miss", "act_p_fa")
+DEFAULT_POINT = (1, 1, 0.05)        # c_miss, c_fa, p_target of calculate_mdc's defaults: llr_metrics=True without a calibration
+
+
+def operating_point(calibration) -> Tuple[float, float, float]:
+    return DEFAULT_POINT if calibration is None else (calibration.c_miss, calibration.c_fa, calibration.p_target)
+
+
+def host_llr_metrics(ground_truth: Sequence[int], llr: Sequence[float], calibration=None) -> dict:
+    """``host_metrics`` of llrs plus cllr / act_dcf / act_p_miss / act_p_fa at the calibration's operating point (float64
+    numpy, calibration.llr_metrics_numpy)."""
+    from .calibration import llr_metrics_numpy
+    res = host_metrics(ground_truth, llr)
+    m = llr_metrics_numpy(llr, ground_truth, *operating_point(calibration))
+    res.update({k: m[k] for k in LLR_KEYS})
+    return res
 
 
 def host_metrics(ground_truth: Sequence[int], scores: Sequence[float]) -> dict:
@@ -306,3 +345,49 @@ def metrics_device(score: torch.Tensor, trial_index: TrialIndex, *, workspace=No
     if record is not None:
         record.append(DeviceMetrics("device", 0, 8, fields))
     return {k: fields[k] for k in ("eer", "eer_threshold", "mdc", "mdc_threshold")}
+
+
+def metrics_device_llr(score: torch.Tensor, trial_index: TrialIndex, calibration=None, *, record: Optional[list] = None) -> dict:
+    """``metrics_device`` for llrs (calibrated scores, or raw ones under ``llr_metrics=True``): EER / minDCF by
+    ops.trial_metrics and Cllr / actDCF at the calibration's operating point by ops.llr_metrics, both where the llrs are ->
+    the dict of ``evaluate`` with cllr, act_dcf, act_p_miss and act_p_fa added.  ONE device -> host copy of eight doubles:
+    the eight values of the dict.  The two cases of metrics_device take the host path here as well: a list of one class
+    (nothing is launched) and NaN among the llrs (then, and only then, cllr is NaN: the llrs are copied and the host
+    answers).  ``record`` receives one DeviceMetrics whose ``fields`` are the eight values by name."""
+    gt = trial_index.ground_truth
+    if not isinstance(score, torch.Tensor) or score.dim() != 1 or score.numel() != len(trial_index):
+        raise ValueError(f"metrics_device_llr: one llr per trial ({len(trial_index)})")
+    n_pos = sum(gt)
+    if n_pos == 0 or n_pos == len(gt):
+        if record is not None:
+            record.append(DeviceMetrics("host", score.numel(), 0))
+        return host_llr_metrics(gt, _host_scores(score), calibration)
+    labels = trial_index.device_labels(score.device)
+    both = torch.empty(16, dtype=torch.float64, device=score.device)
+    ops.trial_metrics(score, labels, out=both[:8])
+    ops.llr_metrics(score, labels, *operating_point(calibration), out=both[8:])
+    names = ("eer", "eer_threshold", "mdc", "mdc_threshold") + LLR_KEYS
+    fields = dict(zip(names, torch.cat([both[0:4], both[8:9], both[11:14]]).cpu().tolist()))
+    if fields["cllr"] != fields["cllr"]:
+        if record is not None:
+            record.append(DeviceMetrics("host", score.numel(), 8, fields))
+        return host_llr_metrics(gt, _host_scores(score), calibration)
+    if record is not None:
+        record.append(DeviceMetrics("device", 0, 8, fields))
+    return dict(fields)
+
+
+def finish_bank_metrics(evaluator, index: TrialIndex, metrics: str, calibration, llrs: bool) -> dict:
+    """What every evaluator's evaluate_bank_metrics does behind ``evaluator.last_bank_scoring``: the host or the device
+    metrics, with the four llr keys when the scores are llrs (``llrs``: a calibration, or llr_metrics=True)."""
+    rec = evaluator.last_bank_scoring
+    if metrics == "device":
+        record = []
+        res = metrics_device_llr(rec.device_scores, index, calibration, record=record) if llrs \
+            else metrics_device(rec.device_scores, index, record=record)
+        evaluator.last_bank_metrics = record[0]
+        rec.host_copy_floats = record[0].host_copy_floats          # (the host path copied them after all)
+        return res
+    if llrs:
+        return host_llr_metrics(index.ground_truth, rec.scores.tolist(), calibration)
+    return host_metrics(index.ground_truth, rec.scores.tolist())

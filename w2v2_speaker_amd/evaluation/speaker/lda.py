@@ -201,10 +201,12 @@ class LatentBackendEvaluator:
     def _device_scores(self, bank: torch.Tensor, index, keep_on_device: bool, score_norm):
         raise NotImplementedError
 
-    def evaluate(self, pairs: List[EvaluationPair], samples: List[EmbeddingSample], score_norm=None):
-        """ref: speaker_recognition_evaluator.py:45-101 with the fitted model in plain torch f32 on the CPU."""
+    def evaluate(self, pairs: List[EvaluationPair], samples: List[EmbeddingSample], score_norm=None, calibration=None,
+                 llr_metrics: bool = False):
+        """ref: speaker_recognition_evaluator.py:45-101 with the fitted model in plain torch f32 on the CPU.
+        ``calibration`` / ``llr_metrics``: as on CosineDistanceEvaluator.evaluate (one system)."""
         self._require_fit()
-        from .device_scoring import host_metrics
+        from .device_scoring import host_llr_metrics, host_metrics
         row_of, rows = {}, []
         for sample in samples:
             if sample.sample_id in row_of:
@@ -229,18 +231,28 @@ class LatentBackendEvaluator:
         scores = scores.numpy().astype(np.float64)
         if self.clip_scores and score_norm is None:
             scores = np.clip((scores + 1) / 2, 0, 1)
+        if calibration is not None:
+            scores = calibration.apply(scores)
+        if calibration is not None or llr_metrics:
+            return host_llr_metrics(gt, scores.tolist(), calibration)
         return host_metrics(gt, scores.tolist())
 
     def evaluate_bank(self, pairs: List[EvaluationPair], keys: List[str], bank, frame_offsets=None):
         return self.evaluate_bank_metrics(pairs, keys, bank, frame_offsets, metrics="host")
 
+    def _metric_scores_device(self, bank: torch.Tensor, index, score_norm=None) -> torch.Tensor:
+        """The scores the metrics would see for one bank, float32 [P] on the device (ScoreCalibration.fit_bank)."""
+        self._require_fit()
+        return self._device_scores(bank, index, True, score_norm).device_scores
+
     def evaluate_bank_metrics(self, pairs: List[EvaluationPair], keys: List[str], bank, frame_offsets=None,
-                              metrics: str = "host", score_norm=None):
+                              metrics: str = "host", score_norm=None, calibration=None, llr_metrics: bool = False):
         """``evaluate`` without the embeddings leaving the device, as CosineDistanceEvaluator.evaluate_bank_metrics:
         ``bank`` is an ``[N, D]`` f32 device tensor whose row r is the embedding of ``keys[r]``.  ``metrics="device"``
         leaves the scores on the device and computes EER / minDCF there.  ``last_bank_scoring`` / ``last_bank_metrics``
-        as on the cosine evaluator."""
-        from .device_scoring import TrialIndex, host_metrics, metrics_device
+        as on the cosine evaluator.  ``calibration`` (one system) / ``llr_metrics``: as there -- the scores become
+        calibrated llrs on the device and the dict gains cllr, act_dcf, act_p_miss and act_p_fa."""
+        from .device_scoring import TrialIndex, calibrated_scores, finish_bank_metrics
         if metrics not in ("host", "device"):
             raise ValueError(f"metrics={metrics!r}: 'host' or 'device'")
         if isinstance(bank, (list, tuple)):
@@ -254,14 +266,13 @@ class LatentBackendEvaluator:
             return {"eer": -1, "eer_threshold": -1, "mdc": -1, "mdc_threshold": -1}
         if not isinstance(bank, torch.Tensor) or bank.dim() != 2 or bank.shape[0] != index.num_rows:
             raise ValueError(f"bank of shape {tuple(getattr(bank, 'shape', ()))}: expected [{index.num_rows}, D]")
-        self.last_bank_scoring = self._device_scores(bank, index, metrics == "device", score_norm)
-        if metrics == "device":
-            record = []
-            res = metrics_device(self.last_bank_scoring.device_scores, index, record=record)
-            self.last_bank_metrics = record[0]
-            self.last_bank_scoring.host_copy_floats = record[0].host_copy_floats
-            return res
-        return host_metrics(index.ground_truth, self.last_bank_scoring.scores.tolist())
+        if calibration is None:
+            self.last_bank_scoring = self._device_scores(bank, index, metrics == "device", score_norm)
+        else:
+            raw = self._device_scores(bank, index, True, score_norm)
+            self.last_bank_scoring = calibrated_scores(raw.device_scores.unsqueeze(0), calibration, metrics == "device",
+                                                       raw.bank_floats)
+        return finish_bank_metrics(self, index, metrics, calibration, calibration is not None or llr_metrics)
 
 
 class LDAEvaluator(LatentBackendEvaluator):

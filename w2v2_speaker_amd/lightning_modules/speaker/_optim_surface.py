@@ -139,12 +139,13 @@ class EmbeddingEvaluation:
             raise ValueError("expecting a batch size of 1 for evaluating speaker embeddings")   # ref: :468-469
         return self.validation_step(batch, batch_idx)
 
-    def _evaluate_embeddings(self, outputs: List[dict], pairs, score_norm=None):
+    def _evaluate_embeddings(self, outputs: List[dict], pairs, score_norm=None, calibration=None, llr_metrics=False):
         samples = [EmbeddingSample(sample_id=k, embedding=o["embedding"][i]) for o in outputs
                    for i, k in enumerate(o["sample_id"])]
-        if score_norm is not None:
-            return self.evaluator.evaluate(pairs, samples, score_norm=score_norm)
-        return self.evaluator.evaluate(pairs, samples)
+        extra = {} if score_norm is None else {"score_norm": score_norm}
+        if calibration is not None or llr_metrics:
+            extra.update(calibration=calibration, llr_metrics=llr_metrics)
+        return self.evaluator.evaluate(pairs, samples, **extra)
 
     def validation_epoch_end(self, outputs: List[dict]):
         return self._evaluate_embeddings(outputs, self.validation_pairs)
@@ -153,7 +154,7 @@ class EmbeddingEvaluation:
         return self._evaluate_embeddings(outputs, self.test_pairs)
 
     def evaluate_trials(self, pairs, input_by_key, *, scoring: str = "host", metrics: str = "host", score_norm=None,
-                        **batching) -> dict:
+                        calibration=None, llr_metrics: bool = False, **batching) -> dict:
         """Score a trial list: every utterance the pairs name (key -> one input of compute_speaker_embeddings in
         ``input_by_key``) is embedded once with compute_speaker_embeddings (``batching``: its keyword arguments) and the
         module's evaluator scores the pairs -- the same dict as test_epoch_end over the batch-size-1 test loop.
@@ -161,7 +162,10 @@ class EmbeddingEvaluation:
         it there (pooled embeddings only).  ``metrics="device"`` (with ``scoring="device"`` only): EER / minDCF are
         computed on the device as well (``evaluate_bank_metrics(metrics="device")``) and eight doubles come back.
         ``score_norm`` (evaluation.speaker.device_scoring.ScoreNorm): the scores are normalised with its cohort, on the
-        device with ``scoring="device"`` and in plain torch on the CPU otherwise."""
+        device with ``scoring="device"`` and in plain torch on the CPU otherwise.  ``calibration``
+        (evaluation.speaker.calibration.ScoreCalibration, fitted) / ``llr_metrics``: the evaluator's keywords of the same
+        name -- calibrated llrs go to the metrics and the dict gains cllr, act_dcf, act_p_miss and act_p_fa; on the device
+        with ``scoring="device"``, in float64 numpy otherwise."""
         if scoring not in ("host", "device"):
             raise ValueError(f"scoring={scoring!r}: 'host' or 'device'")
         if metrics not in ("host", "device"):
@@ -175,9 +179,11 @@ class EmbeddingEvaluation:
                 raise NotImplementedError("scoring='device' takes pooled embeddings; score a no-pooling head's frames with "
                                           "evaluator.evaluate_bank(frame_offsets=)")
             extra = {} if score_norm is None else {"score_norm": score_norm}
+            if calibration is not None or llr_metrics:
+                extra.update(calibration=calibration, llr_metrics=llr_metrics)
             return self.evaluator.evaluate_bank_metrics(pairs, keys, torch.cat(embs).detach().float(), metrics=metrics, **extra)
         return self._evaluate_embeddings([{"embedding": torch.cat(embs).detach().to("cpu"), "sample_id": keys}], pairs,
-                                         score_norm)
+                                         score_norm, calibration, llr_metrics)
 
     @property
     def bucket_plans_built(self) -> int:

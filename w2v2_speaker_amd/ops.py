@@ -1858,6 +1858,150 @@ def trial_metrics(scores, labels, c_miss=1, c_fa=1, p_target=0.05, out=None, wor
     return out
 
 
+# ------------------------------------------------------------------------------------------ score calibration (calibration.hip)
+# include/w2v2_hip.h "score calibration" is the definition; evaluation/speaker/calibration.py is the user's side.
+CALIB_TILE = 2048          # trials per workgroup of w2v2_calib_fit / w2v2_llr_metrics (csrc/calibration.hip CAL_TILE)
+CALIB_MAX_SYSTEMS = 8      # W2V2_CALIB_MAX_SYSTEMS
+CALIB_RECORD_DOUBLES = 168  # w2v2_calib_record_doubles()
+CALIB_STATUS = {0: "running", 1: "converged", 2: "failed", 3: "small step"}
+LLR_METRICS_FIELDS = ("cllr", "cllr_tar", "cllr_non", "act_dcf", "act_p_miss", "act_p_fa", "n_pos", "n_nan")
+_CALIB_N = CALIB_MAX_SYSTEMS + 1
+# name -> (first double, count) of the record
+CALIB_RECORD = {"status": (0, 1), "rounds": (1, 1), "K": (2, 1), "J": (3, 1), "step": (4, 1), "decrement": (5, 1),
+                "n_tar": (6, 1), "n_non": (7, 1), "n_nan": (8, 1), "J_trial": (9, 1),
+                "w": (16, _CALIB_N), "d": (16 + _CALIB_N, _CALIB_N), "w_trial": (16 + 2 * _CALIB_N, _CALIB_N),
+                "mean": (16 + 3 * _CALIB_N, CALIB_MAX_SYSTEMS), "sd": (16 + 3 * _CALIB_N + CALIB_MAX_SYSTEMS, CALIB_MAX_SYSTEMS),
+                "r": (16 + 3 * _CALIB_N + 2 * CALIB_MAX_SYSTEMS, CALIB_MAX_SYSTEMS),
+                "a": (16 + 3 * _CALIB_N + 3 * CALIB_MAX_SYSTEMS, _CALIB_N),
+                "g": (16 + 4 * _CALIB_N + 3 * CALIB_MAX_SYSTEMS, _CALIB_N),
+                "H": (16 + 5 * _CALIB_N + 3 * CALIB_MAX_SYSTEMS, _CALIB_N * _CALIB_N)}
+
+
+def calib_record_fields(record) -> dict:
+    """One host copy of a fit's record (any sequence of CALIB_RECORD_DOUBLES numbers) -> its fields by name: scalars as
+    floats (status, rounds and K as ints), vectors cut to K (+ 1) elements, H as a [K + 1][K + 1] list."""
+    rec = [float(v) for v in (record.cpu().tolist() if isinstance(record, torch.Tensor) else record)]
+    if len(rec) < CALIB_RECORD_DOUBLES:
+        raise ValueError(f"calib_record_fields: a record has {CALIB_RECORD_DOUBLES} doubles")
+    K = int(rec[2])
+    out = {}
+    for name, (at, n) in CALIB_RECORD.items():
+        if n == 1:
+            out[name] = int(rec[at]) if name in ("status", "rounds", "K") else rec[at]
+        elif name == "H":
+            out[name] = [rec[at + i * _CALIB_N: at + i * _CALIB_N + K + 1] for i in range(K + 1)]
+        else:
+            out[name] = rec[at: at + (K if n == CALIB_MAX_SYSTEMS else K + 1)]
+    return out
+
+
+def _cost_checks(c_miss, c_fa, p_target, open_prior: bool = False) -> None:
+    if c_miss < 1:                                      # calculate_mdc's own errors
+        raise ValueError(f"c_miss={c_miss} should be >= 1")
+    if c_fa < 1:
+        raise ValueError(f"c_fa={c_fa} should be >= 1")
+    if p_target < 0 or p_target > 1:
+        raise ValueError(f"p_target={p_target} should be between 0 and 1")
+    if open_prior and (p_target == 0 or p_target == 1):
+        raise ValueError(f"p_target={p_target} should be strictly between 0 and 1: the prior log-odds must be finite")
+
+
+def _system_scores(scores, what: str) -> Tuple[int, int, int]:
+    """(K, P, ld) of scores [K, P] f32 (a 1-D [P] tensor is one system) whose trials are contiguous."""
+    if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.dim() not in (1, 2):
+        raise ValueError(f"{what}: scores is a float32 [K, P] tensor (or [P] for one system)")
+    if scores.dim() == 1:
+        scores = scores.unsqueeze(0)
+    K, P = scores.shape
+    if not 1 <= K <= CALIB_MAX_SYSTEMS:
+        raise ValueError(f"{what}: K = {K} systems outside [1, {CALIB_MAX_SYSTEMS}]")
+    if not 1 <= P < 2 ** 31:
+        raise ValueError(f"{what}: P = {P} outside [1, 2^31)")
+    ld = scores.stride(0) if K > 1 else max(scores.stride(0), P)
+    if scores.stride(1) != 1 or ld < P:
+        raise ValueError(f"{what}: the trials of a system are contiguous and the row stride ld = {ld} >= P = {P}")
+    return K, P, ld
+
+
+def calib_workspace(P: int, device) -> torch.Tensor:
+    """The workspace of calib_fit and llr_metrics for P trials."""
+    return torch.empty(_workspace_bytes("w2v2_calib_workspace_bytes", P), dtype=torch.uint8, device=device)
+
+
+llr_metrics_workspace = calib_workspace
+
+
+def calib_fit(scores, labels, c_miss=1, c_fa=1, p_target=0.05, ridge=0.0, max_iter=32, w_start=None, record=None,
+              workspace=None) -> torch.Tensor:
+    """Prior-weighted logistic-regression calibration (K = 1) or fusion (K > 1) of scores [K, P] f32 (row stride >= P)
+    with labels [P] uint8, both on the device (w2v2_calib_fit) -> the f64 record [CALIB_RECORD_DOUBLES] on the device
+    (calib_record_fields names its cells).  The whole fit is enqueued; nothing is copied or waited for.  ``w_start``: K + 1
+    host numbers, the first trial point (with ``max_iter=1`` the record then holds J, g and H there)."""
+    _cost_checks(c_miss, c_fa, p_target, open_prior=True)
+    K, P, ld = _system_scores(scores, "calib_fit")
+    if _trial_count(labels, torch.uint8, "calib_fit", "labels") != P:
+        raise ValueError(f"calib_fit: one label per trial (P = {P})")
+    if not (isinstance(ridge, (int, float)) and 0 <= ridge < float("inf")):
+        raise ValueError(f"calib_fit: ridge = {ridge!r} must be a finite number >= 0")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or not 1 <= max_iter <= 4096:
+        raise ValueError(f"calib_fit: max_iter = {max_iter!r} outside [1, 4096]")
+    start = None
+    if w_start is not None:
+        w = [float(v) for v in w_start]
+        if len(w) != K + 1 or not all(abs(v) < float("inf") for v in w):
+            raise ValueError(f"calib_fit: w_start holds K + 1 = {K + 1} finite numbers")
+        start = (C.c_double * (K + 1))(*w)
+    if record is not None and (not isinstance(record, torch.Tensor) or record.dtype != torch.float64
+                               or not record.is_contiguous() or record.numel() < CALIB_RECORD_DOUBLES):
+        raise ValueError(f"calib_fit: record is a contiguous float64 tensor of at least {CALIB_RECORD_DOUBLES} elements")
+    _dev(scores, labels, record, workspace)
+    if record is None:
+        record = torch.empty(CALIB_RECORD_DOUBLES, dtype=torch.float64, device=scores.device)
+    workspace = _byte_workspace(workspace, _workspace_bytes("w2v2_calib_workspace_bytes", P), scores.device, "calib_fit",
+                                "calib_workspace")
+    _lib.check(lib().w2v2_calib_fit(scores.data_ptr(), ld, K, labels.data_ptr(), P, float(c_miss), float(c_fa), float(p_target),
+                                    float(ridge), max_iter, None if start is None else C.addressof(start), record.data_ptr(),
+                                    workspace.data_ptr(), stream()), "calib_fit")
+    return record
+
+
+def calib_apply(scores, record, out=None) -> torch.Tensor:
+    """llr [P] f32 = a_0 + sum_k a_k s_k of scores [K, P] (or [P]) with the affine map of a fit's ``record`` -- read on the
+    device, no host round trip (w2v2_calib_apply).  ``record``: what calib_fit returned, or a float64 device tensor of
+    K + 1 coefficients."""
+    K, P, ld = _system_scores(scores, "calib_apply")
+    if not isinstance(record, torch.Tensor) or record.dtype != torch.float64 or not record.is_contiguous() \
+            or record.numel() not in (K + 1, CALIB_RECORD_DOUBLES):
+        raise ValueError(f"calib_apply: record is a fit's float64 record or K + 1 = {K + 1} float64 coefficients")
+    if out is not None and (out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < P):
+        raise ValueError(f"calib_apply: out is a contiguous float32 tensor of at least P = {P} elements")
+    _dev(scores, record, out)
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=scores.device)
+    a = record if record.numel() == K + 1 else record[CALIB_RECORD["a"][0]:]
+    _lib.check(lib().w2v2_calib_apply(scores.data_ptr(), ld, K, P, a.data_ptr(), out.data_ptr(), stream()), "calib_apply")
+    return out
+
+
+def llr_metrics(llr, labels, c_miss=1, c_fa=1, p_target=0.05, out=None, workspace=None) -> torch.Tensor:
+    """Cllr and actDCF at the Bayes threshold of llr [P] f32 and labels [P] uint8, both on the device (w2v2_llr_metrics)
+    -> out [8] float64 on the device, in the order of LLR_METRICS_FIELDS."""
+    _cost_checks(c_miss, c_fa, p_target)
+    P = _trial_count(llr, torch.float32, "llr_metrics", "llr")
+    if _trial_count(labels, torch.uint8, "llr_metrics", "labels") != P:
+        raise ValueError(f"llr_metrics: one label per llr (P = {P})")
+    if out is not None and (out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < 8):
+        raise ValueError("llr_metrics: out is a contiguous float64 tensor of at least 8 elements")
+    _dev(llr, labels, out, workspace)
+    if out is None:
+        out = torch.empty(8, dtype=torch.float64, device=llr.device)
+    workspace = _byte_workspace(workspace, _workspace_bytes("w2v2_calib_workspace_bytes", P), llr.device, "llr_metrics",
+                                "llr_metrics_workspace")
+    _lib.check(lib().w2v2_llr_metrics(llr.data_ptr(), labels.data_ptr(), P, float(c_miss), float(c_fa), float(p_target),
+                                      out.data_ptr(), workspace.data_ptr(), stream()), "llr_metrics")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ waveform augmentation
 # (csrc/augment.hip; include/w2v2_hip.h "waveform augmentation" defines every operation.)  Row lists and parameter tables
 # are DEVICE tensors the caller built on the host (data/augment.py uploads them in one copy per step): the wrappers check
