@@ -1,7 +1,7 @@
 #!/bin/bash
-# Device code of one .hip file in two source trees, kernel by kernel: compiles both to gfx950 assembly with the flags of
-# _build.FLAGS, drops comments / directives / metadata, renumbers the local labels and says per kernel whether the
-# instruction streams are identical.  What a host-side refactor has to show (the kernels did not move) --
+# Device code of one .hip file in two source trees, kernel by kernel: compiles both to gfx950 assembly with the flags
+# _build.py gives that file (FLAGS and its EXTRA_FLAGS entry, read from each tree's own _build.py: the code that ships),
+# drops comments / directives / metadata, renumbers the local labels and says per kernel whether the instruction streams are identical.  What a host-side refactor has to show (the kernels did not move) --
 # a differing kernel is listed with the index of its first differing instruction and of its last v_mfma: a difference
 # behind the last v_mfma left the K loop alone.  The offset of an LDS read is compared as a number: an explicit `offset:0`
 # counts as none and `offset:0x800` as `offset:2048` (inline assembly prints what its author or the compiler spelled).
@@ -15,7 +15,10 @@ for a in "$@"; do [ "$a" = "-v" ] && verbose=1; done
 tmp=$(mktemp -d); trap 'rm -rf "$tmp"' EXIT
 for side in old new; do
   root=${!side}
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result --cuda-device-only -S \
+  # the flags each tree builds the file with: its own _build.FLAGS + _build.EXTRA_FLAGS[file] (the one list there is)
+  flags=$(python3 -c 'import sys; sys.path.insert(0, sys.argv[1]); import _build; print(" ".join(_build.FLAGS + _build.EXTRA_FLAGS.get(sys.argv[2], [])))' \
+    "$root/w2v2_speaker_amd" "$f") || exit 1
+  /opt/rocm/bin/hipcc $flags --cuda-device-only -S \
     "$root/w2v2_speaker_amd/csrc/$f" -o "$tmp/$side.s" 2>"$tmp/$side.err" || { cat "$tmp/$side.err"; exit 1; }
 done
 python3 - "$tmp/old.s" "$tmp/new.s" "$verbose" "$f" <<'P'

@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libw2v2hip.so")
 SOURCES = ["api.hip", "gemm.hip", "gemm_ring.hip", "gemm_phased.hip", "gemm_f32.hip", "gemm_f32_dma.hip", "wgrad.hip", "wgrad_phased.hip", "norm.hip", "elementwise.hip", "conv0.hip", "posconv.hip", "posconv_direct.hip", "posconv_wgrad.hip",
            "softmax.hip", "attention.hip", "pool.hip", "asp.hip", "tdnn.hip", "wav2spk.hip", "fbank.hip", "augment.hip", "reverb.hip", "skinny.hip", "heads.hip", "margin_head.hip", "score.hip", "score_norm.hip", "backend.hip", "metrics.hip", "calibration.hip", "ctc.hip", "ctc_long.hip", "optim.hip", "comm.hip"]
-HEADERS = ["common.h", "gemm_common.h", "wgrad_common.h", "ctc_common.h", "strip_common.h", "tap_gather.h"]
+HEADERS = ["common.h", "gemm_common.h", "wgrad_common.h", "ctc_common.h", "strip_common.h", "tap_gather.h", "trial_common.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # per-file additions.  augment.hip: the FIR's 8 outputs x 4 taps are plain v_fmac_f32 at the full f32 vector rate; packed
 # into v_pk_fma_f32 pairs (no faster on gfx950) the odd taps need sample pairs at odd offsets, which the compiler
@@ -80,7 +80,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
             hdrs.append(os.path.join(CSRC, "wgrad_common.h"))
         if src.startswith("ctc"):
             hdrs.append(os.path.join(CSRC, "ctc_common.h"))
-        if src in ("tdnn.hip", "wav2spk.hip", "score.hip", "score_norm.hip", "backend.hip", "skinny.hip", "conv0.hip"):
+        if src in ("score.hip", "score_norm.hip", "backend.hip", "metrics.hip"):
+            hdrs.append(os.path.join(CSRC, "trial_common.h"))           # (which includes strip_common.h)
+        if src in ("tdnn.hip", "wav2spk.hip", "score.hip", "score_norm.hip", "backend.hip", "metrics.hip", "skinny.hip", "conv0.hip"):
             hdrs.append(os.path.join(CSRC, "strip_common.h"))
         if src in ("tdnn.hip", "wav2spk.hip", "conv0.hip"):
             hdrs.append(os.path.join(CSRC, "tap_gather.h"))

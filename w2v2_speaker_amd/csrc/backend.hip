@@ -7,12 +7,10 @@
 // eigen-solves and the EM run on the host in float64.
 // Conventions of the f32 strip kernels: 16-byte vectors, every guard per vector (D % 4 == 0, ld % 4 == 0), every row * ld
 // in 64 bits, no atomics on global memory, no workgroup waits on another, fixed-order folds (bitwise reproducible),
-// nothing allocated here, everything on the caller's stream.
-#include "strip_common.h"
+// nothing allocated here, everything on the caller's stream.  The NaN and the host's row-buffer check: trial_common.h.
+#include "trial_common.h"
 
 namespace {
-
-__device__ __forceinline__ float qnan() { return __uint_as_float(0x7fc00000u); }
 
 // ------------------------------------------------------------------------------------------ rows_center
 // One row per wavefront, four per workgroup, one pass.  Per element one subtraction and one multiplication, each rounded
@@ -80,7 +78,7 @@ __global__ __launch_bounds__(PL_WAVES * 64) void plda_score_pairs_kernel(const f
   const int64_t t = (int64_t)blockIdx.x * PL_WAVES + wave;
   if (t >= P) return;                                       // (a whole wave; the kernel has no barrier)
   const int i = pairs[2 * t], j = pairs[2 * t + 1];
-  if (i < 0 || i >= N || j < 0 || j >= N) {                 // not dereferenced
+  if (i < 0 || i >= N || j < 0 || j >= N) {                 // not dereferenced (kept local: trial_common.h says why)
     if (lane == 0) llr_out[t] = qnan();
     return;
   }
@@ -102,10 +100,6 @@ __global__ __launch_bounds__(PL_WAVES * 64) void plda_score_pairs_kernel(const f
   }
   s = wave_sum_d(s);
   if (lane == 0) llr_out[t] = (float)(k + s);
-}
-
-bool rows_ok(const void* p, int64_t ld, int64_t rows, int D) {
-  return p && rows > 0 && D > 0 && D % 4 == 0 && ld >= D && ld % 4 == 0 && ((uintptr_t)p & 15) == 0;
 }
 
 }  // namespace

@@ -8,8 +8,9 @@
 // atomics on global memory; the LDS counters are integers (any order of integer adds gives the same bits).  The output of
 // the sort is unique, every step behind it is exact integer work, and the real arithmetic is f64 on those integers and on
 // the f32 keys, evaluated WITHOUT contraction so that it rounds as numpy's separate operations do: equal inputs give equal
-// bits.  Nothing is allocated here, everything goes on the caller's stream.
-#include "common.h"
+// bits.  Nothing is allocated here, everything goes on the caller's stream.  The f32 -> u32 order key of the sort is
+// trial_common.h's (integer work only: it means the same above the pragma below as it would under it).
+#include "trial_common.h"
 
 #pragma clang fp contract(off)
 
@@ -103,20 +104,12 @@ int scan_u32(uint32_t* data, int64_t n, bool inclusive, uint32_t* scratch, hipSt
 }
 
 // ------------------------------------------------------------------------------------------ radix sort
-// f32 bits -> u32 whose unsigned order is numpy's: -0.0 becomes +0.0 and every NaN the one largest key first, then the
-// usual map (negative: all bits flipped; otherwise the sign bit set).  +inf maps to 0xff800000, the NaN key to 0xffffffff.
-__device__ __forceinline__ uint32_t sort_key_of(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) u = 0x7fffffffu;
-  else if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
+// The keys are order_key_of (trial_common.h) of the scores: their unsigned order is numpy's order of the values.
 __global__ __launch_bounds__(256) void sort_prepare_kernel(const float* __restrict__ keys, int64_t P, uint32_t* __restrict__ ukey,
                                                            int32_t* __restrict__ idx) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < P) {
-    ukey[i] = sort_key_of(keys[i]);
+    ukey[i] = order_key_of(keys[i]);
     idx[i] = (int32_t)i;
   }
 }

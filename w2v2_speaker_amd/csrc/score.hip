@@ -4,12 +4,12 @@
 //   w2v2_score_frame_sets  the non-pooled score: mean of all pairwise frame cosines of two frame sets
 // Conventions of the f32 strip kernels: a thread reads one 16-byte vector of 4 features per step, every guard is per
 // vector (D % 4 == 0, ld % 4 == 0), every row * ld is formed in 64 bits, no atomics and fixed-order folds (bitwise
-// reproducible), nothing allocated here, everything on the caller's stream.
-#include "strip_common.h"
+// reproducible), nothing allocated here, everything on the caller's stream.  The NaN of a bad trial, the centring of one
+// vector and the host's row-buffer check are those of every evaluation stage: trial_common.h.
+#include "trial_common.h"
 
 namespace {
 
-__device__ __forceinline__ float qnan() { return __uint_as_float(0x7fc00000u); }
 // (cos + 1) / 2 clipped to [0, 1] (ref: speaker_recognition_evaluator.py:81); NaN stays NaN
 __device__ __forceinline__ float score_of(double c) {
   const double s = (c + 1.0) * 0.5;
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(SP_WAVES * 64) void score_pairs_kernel(const float*
   const int64_t p = (int64_t)blockIdx.x * SP_WAVES + wave;
   if (p >= P) return;                                       // (a whole wave; the kernel has no barrier)
   const int i = pairs[2 * p], j = pairs[2 * p + 1];
-  if (i < 0 || i >= N || j < 0 || j >= N) {                 // not dereferenced
+  if (i < 0 || i >= N || j < 0 || j >= N) {                 // not dereferenced (kept local: trial_common.h says why)
     if (lane == 0) { cos_out[p] = qnan(); score_out[p] = qnan(); }
     return;
   }
@@ -106,11 +106,10 @@ __global__ __launch_bounds__(SP_WAVES * 64) void score_pairs_kernel(const float*
 #pragma unroll 2
   for (int d = lane * 4; d < D; d += 256) {
     float4 a = ld4(ra + d), b = ld4(rb + d);
-    if constexpr (CENTER) {                                 // center_batch: (x - mean) / (std + 1e-12), in f32
+    if constexpr (CENTER) {
       const float4 m = ld4(mean + d), s = ld4(sd + d);
-      const float s0 = s.x + 1e-12f, s1 = s.y + 1e-12f, s2 = s.z + 1e-12f, s3 = s.w + 1e-12f;
-      a.x = (a.x - m.x) / s0; a.y = (a.y - m.y) / s1; a.z = (a.z - m.z) / s2; a.w = (a.w - m.w) / s3;
-      b.x = (b.x - m.x) / s0; b.y = (b.y - m.y) / s1; b.z = (b.z - m.z) / s2; b.w = (b.w - m.w) / s3;
+      a = centre4(a, m, s);
+      b = centre4(b, m, s);
     }
     ab = fmaf(a.x, b.x, ab); ab = fmaf(a.y, b.y, ab); ab = fmaf(a.z, b.z, ab); ab = fmaf(a.w, b.w, ab);
     aa = fmaf(a.x, a.x, aa); aa = fmaf(a.y, a.y, aa); aa = fmaf(a.z, a.z, aa); aa = fmaf(a.w, a.w, aa);
@@ -218,15 +217,11 @@ __global__ __launch_bounds__(FS_WAVES * 64) void score_frame_sets_kernel(const f
   }
 }
 
-bool bank_ok(const void* bank, int64_t ld, int64_t rows, int D) {
-  return bank && rows > 0 && D > 0 && D % 4 == 0 && ld >= D && ld % 4 == 0 && ((uintptr_t)bank & 15) == 0;
-}
-
 }  // namespace
 
 extern "C" int w2v2_embed_stats(const float* bank, int64_t ld, int N, int D, float* mean_out, float* std_out,
                                 void* workspace, void* stream) {
-  W2V2_REQUIRE(bank_ok(bank, ld, N, D) && mean_out && std_out && workspace && ((uintptr_t)workspace & 7) == 0,
+  W2V2_REQUIRE(rows_ok(bank, ld, N, D) && mean_out && std_out && workspace && ((uintptr_t)workspace & 7) == 0,
                "embed_stats: bad arguments (D %% 4 == 0, ld >= D, ld %% 4 == 0, 16-byte aligned bank, 8-byte aligned workspace)");
   W2V2_REQUIRE(N >= 2, "embed_stats: the unbiased std needs N >= 2 rows (got %d)", N);
   const int nchunk = (int)cdiv(N, ST_ROWS);
@@ -242,7 +237,7 @@ extern "C" int w2v2_embed_stats(const float* bank, int64_t ld, int N, int D, flo
 
 extern "C" int w2v2_score_pairs(const float* bank, int64_t ld, int N, int D, const int32_t* pairs, int P, const float* mean,
                                 const float* std_, int length_norm, float* cos_out, float* score_out, void* stream) {
-  W2V2_REQUIRE(bank_ok(bank, ld, N, D) && pairs && P > 0 && cos_out && score_out,
+  W2V2_REQUIRE(rows_ok(bank, ld, N, D) && pairs && P > 0 && cos_out && score_out,
                "score_pairs: bad arguments (D %% 4 == 0, ld >= D, ld %% 4 == 0, 16-byte aligned bank)");
   W2V2_REQUIRE((mean == nullptr) == (std_ == nullptr), "score_pairs: mean and std are both null or both set");
   W2V2_REQUIRE(!mean || ((((uintptr_t)mean) | ((uintptr_t)std_)) & 15) == 0, "score_pairs: mean / std must be 16-byte aligned");
@@ -259,7 +254,7 @@ extern "C" int w2v2_score_pairs(const float* bank, int64_t ld, int N, int D, con
 
 extern "C" int w2v2_score_frame_sets(const float* frames, int64_t ld, int64_t rows, int D, const int32_t* sel,
                                      const int32_t* counts, int W, int P, float* cos_out, float* score_out, void* stream) {
-  W2V2_REQUIRE(bank_ok(frames, ld, rows, D) && sel && counts && P > 0 && cos_out && score_out,
+  W2V2_REQUIRE(rows_ok(frames, ld, rows, D) && sel && counts && P > 0 && cos_out && score_out,
                "score_frame_sets: bad arguments (D %% 4 == 0, ld >= D, ld %% 4 == 0, 16-byte aligned frames)");
   W2V2_REQUIRE(W >= 1 && W <= FS_MAX_W, "score_frame_sets: W = %d outside [1, %d]", W, FS_MAX_W);
   hipLaunchKernelGGL(score_frame_sets_kernel, dim3((unsigned)P), dim3(FS_WAVES * 64), 0, as_stream(stream), frames, ld, rows, D,

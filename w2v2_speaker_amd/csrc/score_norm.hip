@@ -15,12 +15,11 @@
 //                  Not mapped through (x + 1) / 2 and not clipped.  An index outside [0, N) gives NaN for that trial.
 // Conventions of the f32 strip kernels: 16-byte vectors, every guard per vector (D % 4 == 0, ld % 4 == 0), every row * ld
 // in 64 bits, no atomics on global memory (integer counters in LDS only), no workgroup waits on another, fixed-order
-// folds (bitwise reproducible), nothing allocated here, everything on the caller's stream.
-#include "strip_common.h"
+// folds (bitwise reproducible), nothing allocated here, everything on the caller's stream.  The centring of step 1, the
+// order keys of step 3, the NaN and the host's row-buffer check are defined once for all stages: trial_common.h.
+#include "trial_common.h"
 
 namespace {
-
-__device__ __forceinline__ float qnan() { return __uint_as_float(0x7fc00000u); }
 
 // the four waves of a 256-thread workgroup, folded in wave order -> every thread holds the sum; sh: 4 doubles of LDS
 __device__ __forceinline__ double block_sum_d(double v, double* sh) {
@@ -33,7 +32,7 @@ __device__ __forceinline__ double block_sum_d(double v, double* sh) {
 }
 
 // ------------------------------------------------------------------------------------------ rows_transform
-// One row per wavefront, four per workgroup.  A lane transforms its vectors in f32 exactly as score_pairs_kernel does and
+// One row per wavefront, four per workgroup.  A lane transforms its vectors in f32 with the centre4 of score_pairs_kernel and
 // sums their squares in double; the 64 lane sums fold through the xor butterfly.  Without length norm the transformed
 // vector is stored in the same loop; with it the row is read a second time (out of the cache) once its norm is known.
 constexpr int RT_WAVES = 4;
@@ -41,12 +40,8 @@ constexpr int RT_WAVES = 4;
 template <bool CENTER>
 __device__ __forceinline__ float4 rt_load(const float* __restrict__ row, const float* __restrict__ mean,
                                           const float* __restrict__ sd, int d) {
-  float4 a = ld4(row + d);
-  if constexpr (CENTER) {                                   // center_batch: (x - mean) / (std + 1e-12), in f32
-    const float4 m = ld4(mean + d), s = ld4(sd + d);
-    a.x = (a.x - m.x) / (s.x + 1e-12f); a.y = (a.y - m.y) / (s.y + 1e-12f);
-    a.z = (a.z - m.z) / (s.z + 1e-12f); a.w = (a.w - m.w) / (s.w + 1e-12f);
-  }
+  const float4 a = ld4(row + d);
+  if constexpr (CENTER) return centre4(a, ld4(mean + d), ld4(sd + d));
   return a;
 }
 
@@ -84,19 +79,8 @@ __global__ __launch_bounds__(RT_WAVES * 64) void rows_transform_kernel(const flo
 }
 
 // ------------------------------------------------------------------------------------------ topk_stats
-// f32 bits -> u32 whose unsigned order is the order of the values (the map of metrics.hip's sort, restated: that file is
-// compiled without contraction and keeps its instructions): -0.0 becomes +0.0, every NaN the one largest key 0xffffffff.
-__device__ __forceinline__ uint32_t tk_key_of(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) u = 0x7fffffffu;
-  else if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float tk_value_of(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
-// One workgroup per row.  The K-th largest key by a radix select, most significant byte first: per pass a 256-bin
+// One workgroup per row.  A value is its order key (order_key_of, trial_common.h: the key of metrics.hip's sort, so the two
+// tie the same values).  The K-th largest key by a radix select, most significant byte first: per pass a 256-bin
 // histogram in LDS of the keys that match the prefix found so far, a suffix sum over the bins (one bin per thread) and the
 // one bin that holds the K-th largest.  After four passes the prefix IS the key t of the K-th largest value and the
 // remaining rank is K - g, the copies of t inside the top K.  Then two folds in double: sum_{v > t} v (+ (K - g) t) and
@@ -116,13 +100,13 @@ __device__ __forceinline__ void tk_for_each(const float* __restrict__ row, const
       k = *reinterpret_cast<const uint4*>(keys_s + 4 * v);
     } else {
       const float4 a = ld4(row + 4 * v);
-      k = make_uint4(tk_key_of(a.x), tk_key_of(a.y), tk_key_of(a.z), tk_key_of(a.w));
+      k = make_uint4(order_key_of(a.x), order_key_of(a.y), order_key_of(a.z), order_key_of(a.w));
     }
     f(k, std::integral_constant<int, 4>{});
   }
   if ((int)threadIdx.x < (M & 3)) {                         // the tail: fewer than four values behind the last vector
     const int i = (nv << 2) + threadIdx.x;
-    f(make_uint4(STAGED ? keys_s[i] : tk_key_of(row[i]), 0u, 0u, 0u), std::integral_constant<int, 1>{});
+    f(make_uint4(STAGED ? keys_s[i] : order_key_of(row[i]), 0u, 0u, 0u), std::integral_constant<int, 1>{});
   }
 }
 
@@ -141,9 +125,9 @@ __global__ __launch_bounds__(TK_THREADS) void topk_stats_kernel(const float* __r
     const int nv = M >> 2;
     for (int v = tid; v < nv; v += TK_THREADS) {
       const float4 a = ld4(row + 4 * v);
-      *reinterpret_cast<uint4*>(keys_s + 4 * v) = make_uint4(tk_key_of(a.x), tk_key_of(a.y), tk_key_of(a.z), tk_key_of(a.w));
+      *reinterpret_cast<uint4*>(keys_s + 4 * v) = make_uint4(order_key_of(a.x), order_key_of(a.y), order_key_of(a.z), order_key_of(a.w));
     }
-    if (tid < (M & 3)) keys_s[(nv << 2) + tid] = tk_key_of(row[(nv << 2) + tid]);
+    if (tid < (M & 3)) keys_s[(nv << 2) + tid] = order_key_of(row[(nv << 2) + tid]);
   }
   uint32_t prefix = 0, mask = 0, k = (uint32_t)K;           // k: the rank still looked for among the keys under the prefix
   for (int shift = 24; shift >= 0; shift -= 8) {
@@ -198,13 +182,13 @@ __global__ __launch_bounds__(TK_THREADS) void topk_stats_kernel(const float* __r
     __syncthreads();                                        // (hist and chosen are rewritten by the next pass)
   }
   const uint32_t tkey = prefix;                             // the K-th largest; k = K - g of its copies are in the top K
-  const double t = (double)tk_value_of(tkey), copies = (double)k, Kd = (double)K;
+  const double t = (double)order_value_of(tkey), copies = (double)k, Kd = (double)K;
   double s = 0.0;
   tk_for_each<STAGED>(row, keys_s, M, [&](uint4 kv, auto n) {
     const uint32_t key[4] = {kv.x, kv.y, kv.z, kv.w};
 #pragma unroll
     for (int a = 0; a < n.value; ++a)
-      if (key[a] > tkey) s += (double)tk_value_of(key[a]);
+      if (key[a] > tkey) s += (double)order_value_of(key[a]);
   });
   s = block_sum_d(s, fold_s);
   const double mean = (s + copies * t) / Kd;
@@ -214,7 +198,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_stats_kernel(const float* __r
 #pragma unroll
     for (int a = 0; a < n.value; ++a)
       if (key[a] > tkey) {
-        const double d = (double)tk_value_of(key[a]) - mean;
+        const double d = (double)order_value_of(key[a]) - mean;
         q = fma(d, d, q);
       }
   });
@@ -235,7 +219,7 @@ __global__ __launch_bounds__(256) void score_pairs_norm_kernel(const float* __re
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= P) return;
   const int i = pairs[2 * p], j = pairs[2 * p + 1];
-  if (i < 0 || i >= N || j < 0 || j >= N) {                 // not dereferenced
+  if (i < 0 || i >= N || j < 0 || j >= N) {                 // not dereferenced (kept local: trial_common.h says why)
     score_out[p] = qnan();
     return;
   }
@@ -275,10 +259,6 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(const float* __restri
   const int cc = blockIdx.y * STRIP_CW + tid;
   if (tid < STRIP_CW && cc < D)
     out[(int64_t)spk * ld_out + cc] = (float)(strip_lane_sum<SmGeom::RL>(red, tid) / (double)(end - begin));
-}
-
-bool rows_ok(const void* p, int64_t ld, int64_t rows, int D) {
-  return p && rows > 0 && D > 0 && D % 4 == 0 && ld >= D && ld % 4 == 0 && ((uintptr_t)p & 15) == 0;
 }
 
 }  // namespace

@@ -14,6 +14,8 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
+from ...ops import cost_checks as check_costs       # one statement of calculate_mdc's conditions, the wrappers' own
+
 MAX_SYSTEMS = 8
 DEC_STOP = 1e-12
 STEP_MIN = 2.0 ** -20
@@ -32,17 +34,6 @@ class CalibrationError(ValueError):
     def __init__(self, message: str, status: int, fields: Optional[dict] = None):
         super().__init__(message)
         self.status, self.fields = status, fields
-
-
-def check_costs(c_miss, c_fa, p_target, open_prior: bool = False) -> None:
-    if c_miss < 1:
-        raise ValueError(f"c_miss={c_miss} should be >= 1")
-    if c_fa < 1:
-        raise ValueError(f"c_fa={c_fa} should be >= 1")
-    if p_target < 0 or p_target > 1:
-        raise ValueError(f"p_target={p_target} should be between 0 and 1")
-    if open_prior and (p_target == 0 or p_target == 1):
-        raise ValueError(f"p_target={p_target} should be strictly between 0 and 1: the prior log-odds must be finite")
 
 
 def effective_prior(c_miss, c_fa, p_target) -> float:

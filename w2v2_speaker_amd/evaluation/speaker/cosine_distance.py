@@ -10,8 +10,6 @@ from warnings import warn
 import numpy as np
 import torch
 
-from ...eval_metrics import calculate_eer, calculate_mdc
-
 
 @dataclass
 class EvaluationPair:
@@ -86,6 +84,31 @@ def normalise_scores(cos: torch.Tensor, mu_e, sd_e, mu_t, sd_t, mode: str) -> to
         raise ValueError(f"score_norm: mode={mode!r}: 'z', 't' or 's'")
     ze, zt = (cos - mu_e) / (sd_e + 1e-12), (cos - mu_t) / (sd_t + 1e-12)
     return ze if mode == "z" else (zt if mode == "t" else (ze + zt) / 2)
+
+
+def resolve_trials(pairs: List[EvaluationPair], keys):
+    """The trial list against the sample ids (``keys[r]`` names row r; ref: speaker_recognition_evaluator.py:45-72) ->
+    (ground_truth, rows, missing): the 0 / 1 list and the (row of sample1, row of sample2) list of the trials, and None -- or,
+    from the first trial that names an id the keys do not hold, that trial's two ids.  Duplicate keys raise.  Every
+    evaluator's ``evaluate`` and device_scoring.TrialIndex resolve with this."""
+    row_of = {}
+    for r, k in enumerate(keys):
+        if k in row_of:
+            raise ValueError(f"duplicate key {k}")
+        row_of[k] = r
+    gt, rows = [], []
+    for pair in pairs:
+        if pair.sample1_id not in row_of or pair.sample2_id not in row_of:
+            return gt, rows, (pair.sample1_id, pair.sample2_id)
+        gt.append(1 if pair.same_speaker else 0)
+        rows.append((row_of[pair.sample1_id], row_of[pair.sample2_id]))
+    return gt, rows, None
+
+
+def missing_pair_answer(missing: Tuple[str, str]) -> dict:
+    """What the reference answers to a trial whose sample is missing: a warning (in the caller's name) and -1 throughout."""
+    warn(f"{missing[0]} or {missing[1]} not in sample_map", stacklevel=2)
+    return {"eer": -1, "eer_threshold": -1, "mdc": -1, "mdc_threshold": -1}
 
 
 class CosineDistanceEvaluator:
@@ -216,18 +239,12 @@ class CosineDistanceEvaluator:
         to the metrics are the calibrated llrs of those scores (float64 numpy here), unbounded, and the dict gains cllr,
         act_dcf, act_p_miss and act_p_fa; a K-system calibration fuses the K members of an ensemble.
         ``llr_metrics=True`` without a calibration adds the same four keys for the scores as they are."""
-        sample_map = {}
-        for sample in samples:
-            if sample.sample_id in sample_map:
-                raise ValueError(f"duplicate key {sample.sample_id}")
-            sample_map[sample.sample_id] = sample
-        gt, pp = [], []
-        for pair in pairs:
-            if pair.sample1_id not in sample_map or pair.sample2_id not in sample_map:
-                warn(f"{pair.sample1_id} or {pair.sample2_id} not in sample_map")
-                return {"eer": -1, "eer_threshold": -1, "mdc": -1, "mdc_threshold": -1}
-            gt.append(1 if pair.same_speaker else 0)
-            pp.append((sample_map[pair.sample1_id], sample_map[pair.sample2_id]))
+        from .device_scoring import host_llr_metrics, host_metrics
+        samples = list(samples)
+        gt, rows, missing = resolve_trials(pairs, [s.sample_id for s in samples])
+        if missing is not None:
+            return missing_pair_answer(missing)
+        pp = [(samples[a], samples[b]) for a, b in rows]
         if calibration is not None and calibration.num_systems != 1:
             scores = calibration.apply(self._host_member_rows(pp, calibration.num_systems)).tolist()
         elif score_norm is not None:
@@ -235,21 +252,10 @@ class CosineDistanceEvaluator:
         else:
             scores = np.clip((np.array(self._compute_prediction_scores(pp)) + 1) / 2, 0, 1).tolist()
         if calibration is not None or llr_metrics:
-            from .device_scoring import host_llr_metrics
             if calibration is not None and calibration.num_systems == 1:
                 scores = calibration.apply(np.asarray(scores, dtype=np.float64)).tolist()
             return host_llr_metrics(gt, scores, calibration)
-        try:
-            eer, eer_threshold = calculate_eer(gt, scores, pos_label=1)
-        except (ValueError, ZeroDivisionError) as e:       # reference falls back to a very bad score
-            print(f"EER calculation had {e}")
-            eer, eer_threshold = 1, 1337
-        try:
-            mdc, mdc_threshold = calculate_mdc(gt, scores)
-        except (ValueError, ZeroDivisionError) as e:
-            print(f"mdc calculation had {e}")
-            mdc, mdc_threshold = 1, 1337
-        return {"eer": eer, "eer_threshold": eer_threshold, "mdc": mdc, "mdc_threshold": mdc_threshold}
+        return host_metrics(gt, scores)
 
     # ------------------------------------------------------------------ the same evaluation over a bank on the device
     def fit_parameters_bank(self, bank: torch.Tensor):
@@ -298,16 +304,14 @@ class CosineDistanceEvaluator:
         still eight doubles in one copy).  A list of n banks with an n-system calibration is fused on the device:
         ``metrics="device"`` works for it, and P floats cross with ``metrics="host"``, not n * P.  ``llr_metrics=True``
         without a calibration adds the four keys for the scores as they are."""
-        from .device_scoring import TrialIndex, finish_bank_metrics, score_trials_device
-        if metrics not in ("host", "device"):
-            raise ValueError(f"metrics={metrics!r}: 'host' or 'device'")
+        from .device_scoring import TrialIndex, check_metrics_choice, finish_bank_metrics, score_trials_device
+        check_metrics_choice(metrics)
         if metrics == "device" and isinstance(bank, (list, tuple)) and calibration is None:
             raise NotImplementedError("metrics='device' takes one bank: the members of an ensemble are combined on the host "
                                       "in the reference's Python-float order")
         index = TrialIndex(pairs, keys)
         if index.missing is not None:
-            warn(f"{index.missing[0]} or {index.missing[1]} not in sample_map")
-            return {"eer": -1, "eer_threshold": -1, "mdc": -1, "mdc_threshold": -1}
+            return missing_pair_answer(index.missing)
         centre = self.center_before_scoring and frame_offsets is None
         if centre and (self.mean is None or self.std is None):
             raise TypeError("center_before_scoring=True but fit_parameters() has not been called "

@@ -16,6 +16,7 @@ import torch
 
 from ... import ops
 from ...eval_metrics import calculate_eer, calculate_mdc
+from .cosine_distance import resolve_trials
 
 FRAME_CAP = 50      # frames per side of a non-pooled trial (ref: cosine_distance.py:203-232)
 
@@ -35,21 +36,9 @@ class TrialIndex:
     the two ids (``evaluate`` answers that with a warning and a dict of -1).  Duplicate keys raise, as in ``evaluate``."""
 
     def __init__(self, pairs, keys: Sequence[str]):
-        self.row_of = {}
-        for r, k in enumerate(keys):
-            if k in self.row_of:
-                raise ValueError(f"duplicate key {k}")
-            self.row_of[k] = r
-        self.num_rows = len(self.row_of)
-        self.missing: Optional[Tuple[str, str]] = None
-        self.ground_truth: List[int] = []
-        rows = []
-        for pair in pairs:
-            if pair.sample1_id not in self.row_of or pair.sample2_id not in self.row_of:
-                self.missing = (pair.sample1_id, pair.sample2_id)
-                break
-            self.ground_truth.append(1 if pair.same_speaker else 0)
-            rows.append((self.row_of[pair.sample1_id], self.row_of[pair.sample2_id]))
+        keys = list(keys)
+        self.num_rows = len(keys)
+        self.ground_truth, rows, self.missing = resolve_trials(pairs, keys)
         self.table = None if self.missing else self._checked(rows, self.num_rows)
         self._device_table = None
         self._device_labels = None
@@ -58,7 +47,7 @@ class TrialIndex:
     def from_rows(cls, rows, ground_truth: Sequence[int], num_rows: int) -> "TrialIndex":
         """From row numbers directly (a caller that has no string keys); an index outside [0, num_rows) raises."""
         self = cls.__new__(cls)
-        self.row_of, self.num_rows, self.missing = {}, int(num_rows), None
+        self.num_rows, self.missing = int(num_rows), None
         self.ground_truth = [int(g) for g in ground_truth]
         self.table = cls._checked(rows, self.num_rows)
         if len(self.ground_truth) != len(self.table):
@@ -375,6 +364,11 @@ def metrics_device_llr(score: torch.Tensor, trial_index: TrialIndex, calibration
     if record is not None:
         record.append(DeviceMetrics("device", 0, 8, fields))
     return dict(fields)
+
+
+def check_metrics_choice(metrics) -> None:              # the first check of every evaluate_bank_metrics
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics={metrics!r}: 'host' or 'device'")
 
 
 def finish_bank_metrics(evaluator, index: TrialIndex, metrics: str, calibration, llrs: bool) -> dict:

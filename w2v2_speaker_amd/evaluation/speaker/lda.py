@@ -13,14 +13,13 @@ plain torch f32 on the CPU, ``evaluate_bank`` / ``evaluate_bank_metrics`` on the
 from __future__ import annotations
 
 from typing import List, Optional, Sequence
-from warnings import warn
 
 import numpy as np
 import torch
 
 from . import backend
 from .cosine_distance import (EmbeddingSample, EvaluationPair, center_batch, cohort_stats_host, length_norm_batch,
-                              normalise_scores)
+                              missing_pair_answer, normalise_scores, resolve_trials)
 
 
 class LatentBackendEvaluator:
@@ -207,20 +206,11 @@ class LatentBackendEvaluator:
         ``calibration`` / ``llr_metrics``: as on CosineDistanceEvaluator.evaluate (one system)."""
         self._require_fit()
         from .device_scoring import host_llr_metrics, host_metrics
-        row_of, rows = {}, []
-        for sample in samples:
-            if sample.sample_id in row_of:
-                raise ValueError(f"duplicate key {sample.sample_id}")
-            row_of[sample.sample_id] = len(rows)
-            rows.append(sample.embedding)
-        gt, e, t = [], [], []
-        for pair in pairs:
-            if pair.sample1_id not in row_of or pair.sample2_id not in row_of:
-                warn(f"{pair.sample1_id} or {pair.sample2_id} not in sample_map")
-                return {"eer": -1, "eer_threshold": -1, "mdc": -1, "mdc_threshold": -1}
-            gt.append(1 if pair.same_speaker else 0)
-            e.append(row_of[pair.sample1_id])
-            t.append(row_of[pair.sample2_id])
+        samples = list(samples)
+        gt, trials, missing = resolve_trials(pairs, [s.sample_id for s in samples])
+        if missing is not None:
+            return missing_pair_answer(missing)
+        rows, e, t = [s.embedding for s in samples], [a for a, _ in trials], [b for _, b in trials]
         if any(isinstance(r, (list, tuple)) for r in rows):
             raise NotImplementedError(f"{self.name}: one embedding per sample: an ensemble has no fitted back-end")
         if any(torch.as_tensor(r).dim() != 1 for r in rows):
@@ -252,9 +242,8 @@ class LatentBackendEvaluator:
         leaves the scores on the device and computes EER / minDCF there.  ``last_bank_scoring`` / ``last_bank_metrics``
         as on the cosine evaluator.  ``calibration`` (one system) / ``llr_metrics``: as there -- the scores become
         calibrated llrs on the device and the dict gains cllr, act_dcf, act_p_miss and act_p_fa."""
-        from .device_scoring import TrialIndex, calibrated_scores, finish_bank_metrics
-        if metrics not in ("host", "device"):
-            raise ValueError(f"metrics={metrics!r}: 'host' or 'device'")
+        from .device_scoring import TrialIndex, calibrated_scores, check_metrics_choice, finish_bank_metrics
+        check_metrics_choice(metrics)
         if isinstance(bank, (list, tuple)):
             raise NotImplementedError(f"{self.name}: one bank: an ensemble has no fitted back-end")
         if frame_offsets is not None:
@@ -262,8 +251,7 @@ class LatentBackendEvaluator:
         self._require_fit()
         index = TrialIndex(pairs, keys)
         if index.missing is not None:
-            warn(f"{index.missing[0]} or {index.missing[1]} not in sample_map")
-            return {"eer": -1, "eer_threshold": -1, "mdc": -1, "mdc_threshold": -1}
+            return missing_pair_answer(index.missing)
         if not isinstance(bank, torch.Tensor) or bank.dim() != 2 or bank.shape[0] != index.num_rows:
             raise ValueError(f"bank of shape {tuple(getattr(bank, 'shape', ()))}: expected [{index.num_rows}, D]")
         if calibration is None:

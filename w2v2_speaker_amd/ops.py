@@ -1389,13 +1389,18 @@ STATS_CHUNK_ROWS = 128      # rows per partial of w2v2_embed_stats (csrc/score.h
 FRAME_SET_MAX_W = 256       # slots per side of w2v2_score_frame_sets (csrc/score.hip FS_MAX_W)
 
 
+def _ld(t) -> int:
+    """The row stride of a 2-D tensor; a one-row tensor's stride(0) is arbitrary, so at least its width."""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
 def _bank(bank, what: str) -> Tuple[int, int, int]:
     """(rows, D, ld) of an f32 bank [rows, D] whose rows are ``ld`` elements apart; shape errors first (they need no
     device), then the device check every op makes."""
     if not isinstance(bank, torch.Tensor) or bank.dim() != 2 or bank.dtype != torch.float32:
         raise ValueError(f"{what}: the bank is a 2-D float32 tensor")
     rows, D = bank.shape
-    ld = bank.stride(0) if rows > 1 else max(bank.stride(0), D)
+    ld = _ld(bank)
     if rows < 1 or D < 4 or D % 4 != 0:
         raise ValueError(f"{what}: D = {D} must be a positive multiple of 4 (and the bank non-empty)")
     if bank.stride(1) != 1 or ld < D or ld % 4 != 0 or bank.data_ptr() % 16 != 0:
@@ -1404,12 +1409,30 @@ def _bank(bank, what: str) -> Tuple[int, int, int]:
     return rows, D, ld
 
 
-def _score_out(t, P: int, device, what: str) -> torch.Tensor:
+def _out(t, n: int, device, what: str, name: str, dtype=torch.float32) -> torch.Tensor:
+    """An optional output of n elements: checked when given, allocated on ``device`` otherwise."""
     if t is None:
-        return torch.empty(P, dtype=torch.float32, device=device)
-    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < P:
-        raise ValueError(f"{what}: outputs are contiguous float32 tensors of at least P = {P} elements")
+        return torch.empty(n, dtype=dtype, device=device)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.numel() < n:
+        raise ValueError(f"{what}: {name} is a contiguous {str(dtype).replace('torch.', '')} tensor of at least {n} elements")
     return t
+
+
+def _pairs(pairs, what: str) -> int:
+    """P of a trial table: device int32 [P, 2].  The row numbers are not read here (the kernels answer a bad one with NaN)."""
+    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 \
+            or pairs.shape[0] < 1 or not pairs.is_contiguous():
+        raise ValueError(f"{what}: pairs is a contiguous int32 [P, 2] tensor, P >= 1")
+    return pairs.shape[0]
+
+
+def _centring(mean, std, D: int, what: str) -> None:
+    if (mean is None) != (std is None):
+        raise ValueError(f"{what}: mean and std are given together or not at all")
+    for v in (mean, std):
+        if v is not None and (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.shape != (D,)
+                              or not v.is_contiguous()):
+            raise ValueError(f"{what}: mean / std are contiguous float32 [{D}]")
 
 
 def embed_stats_workspace(N: int, D: int, device) -> torch.Tensor:
@@ -1423,8 +1446,8 @@ def embed_stats(bank, mean_out=None, std_out=None, workspace=None) -> Tuple[torc
     if N < 2:
         raise ValueError(f"embed_stats: the unbiased std needs N >= 2 rows (got {N})")
     _dev(bank, mean_out, std_out, workspace)
-    mean_out = _score_out(mean_out, D, bank.device, "embed_stats")
-    std_out = _score_out(std_out, D, bank.device, "embed_stats")
+    mean_out = _out(mean_out, D, bank.device, "embed_stats", "mean_out")
+    std_out = _out(std_out, D, bank.device, "embed_stats", "std_out")
     if workspace is None:
         workspace = embed_stats_workspace(N, D, bank.device)
     need = embed_stats_workspace(N, D, "meta").numel()
@@ -1442,18 +1465,11 @@ def score_pairs(bank, pairs, mean=None, std=None, length_norm: bool = False, cos
     (w2v2_score_pairs).  The indices are NOT checked here (they are on the device: a trial with an index outside [0, N)
     comes back NaN); TrialIndex checks a list before it is uploaded."""
     N, D, ld = _bank(bank, "score_pairs")
-    if (mean is None) != (std is None):
-        raise ValueError("score_pairs: mean and std are given together or not at all")
-    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 \
-            or pairs.shape[0] < 1 or not pairs.is_contiguous():
-        raise ValueError("score_pairs: pairs is a contiguous int32 [P, 2] tensor, P >= 1")
-    for v in (mean, std):
-        if v is not None and (v.dtype != torch.float32 or v.shape != (D,) or not v.is_contiguous()):
-            raise ValueError(f"score_pairs: mean / std are contiguous float32 [{D}]")
+    _centring(mean, std, D, "score_pairs")
+    P = _pairs(pairs, "score_pairs")
     _dev(bank, pairs, mean, std, cos_out, score_out)
-    P = pairs.shape[0]
-    cos_out = _score_out(cos_out, P, bank.device, "score_pairs")
-    score_out = _score_out(score_out, P, bank.device, "score_pairs")
+    cos_out = _out(cos_out, P, bank.device, "score_pairs", "cos_out")
+    score_out = _out(score_out, P, bank.device, "score_pairs", "score_out")
     _lib.check(lib().w2v2_score_pairs(bank.data_ptr(), ld, N, D, pairs.data_ptr(), P, _p(mean), _p(std),
                                       int(bool(length_norm)), cos_out.data_ptr(), score_out.data_ptr(), stream()),
                "score_pairs")
@@ -1473,8 +1489,8 @@ def score_frame_sets(frames, sel, counts, cos_out=None, score_out=None) -> Tuple
             or not counts.is_contiguous():
         raise ValueError(f"score_frame_sets: counts is a contiguous int32 [{P}, 2] tensor")
     _dev(frames, sel, counts, cos_out, score_out)
-    cos_out = _score_out(cos_out, P, frames.device, "score_frame_sets")
-    score_out = _score_out(score_out, P, frames.device, "score_frame_sets")
+    cos_out = _out(cos_out, P, frames.device, "score_frame_sets", "cos_out")
+    score_out = _out(score_out, P, frames.device, "score_frame_sets", "score_out")
     _lib.check(lib().w2v2_score_frame_sets(frames.data_ptr(), ld, rows, D, sel.data_ptr(), counts.data_ptr(), W, P,
                                            cos_out.data_ptr(), score_out.data_ptr(), stream()), "score_frame_sets")
     return cos_out, score_out
@@ -1485,15 +1501,6 @@ TOPK_LDS_KEYS = 8192                    # longest row w2v2_topk_stats stages in 
 TOPK_MAX_M = 2 ** 24                    # M of w2v2_topk_stats stays below this
 SCORE_NORM_MODES = {"z": 0, "t": 1, "s": 2}
 COHORT_WORKSPACE_BYTES = 256 << 20      # the default block of cohort_stats keeps its [rows_per_block, ldS] buffer at or below this
-
-
-def _centring(mean, std, D: int, what: str) -> None:
-    if (mean is None) != (std is None):
-        raise ValueError(f"{what}: mean and std are given together or not at all")
-    for v in (mean, std):
-        if v is not None and (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.shape != (D,)
-                              or not v.is_contiguous()):
-            raise ValueError(f"{what}: mean / std are contiguous float32 [{D}]")
 
 
 def _top_k(K, M: int, what: str) -> int:
@@ -1518,10 +1525,9 @@ def rows_transform(x, mean=None, std=None, length_norm: bool = False, out=None,
     _dev(x, mean, std, out, inv_norm)
     if out is None and not plain:
         out = torch.empty(rows, D, dtype=torch.float32, device=x.device)
-    inv_norm = _score_out(inv_norm, rows, x.device, "rows_transform")
+    inv_norm = _out(inv_norm, rows, x.device, "rows_transform", "inv_norm")
     _lib.check(lib().w2v2_rows_transform(x.data_ptr(), ld, rows, D, _p(mean), _p(std), int(bool(length_norm)), _p(out),
-                                         0 if out is None else (out.stride(0) if out.shape[0] > 1 else max(out.stride(0), D)),
-                                         inv_norm.data_ptr(), stream()), "rows_transform")
+                                         0 if out is None else _ld(out), inv_norm.data_ptr(), stream()), "rows_transform")
     return (None if out is None else out[:rows]), inv_norm
 
 
@@ -1533,15 +1539,15 @@ def topk_stats(S, K: int, M: Optional[int] = None, mu_out=None, sd_out=None) -> 
         raise ValueError("topk_stats: S is a 2-D float32 tensor")
     R = S.shape[0]
     M = S.shape[1] if M is None else int(M)
-    ldS = S.stride(0) if R > 1 else max(S.stride(0), S.shape[1])
+    ldS = _ld(S)
     if not 2 <= M <= S.shape[1] or M >= TOPK_MAX_M:
         raise ValueError(f"topk_stats: M = {M} outside [2, min({S.shape[1]} columns, 2^24 - 1)]")
     if S.stride(1) != 1 or ldS % 4 != 0 or S.data_ptr() % 16 != 0:
         raise ValueError(f"topk_stats: row stride ldS = {ldS} must be a multiple of 4, values contiguous, base 16-byte aligned")
     K = _top_k(K, M, "topk_stats")
     _dev(S, mu_out, sd_out)
-    mu_out = _score_out(mu_out, R, S.device, "topk_stats")
-    sd_out = _score_out(sd_out, R, S.device, "topk_stats")
+    mu_out = _out(mu_out, R, S.device, "topk_stats", "mu_out")
+    sd_out = _out(sd_out, R, S.device, "topk_stats", "sd_out")
     _lib.check(lib().w2v2_topk_stats(S.data_ptr(), ldS, R, M, K, mu_out.data_ptr(), sd_out.data_ptr(), stream()), "topk_stats")
     return mu_out, sd_out
 
@@ -1552,10 +1558,7 @@ def score_pairs_norm(cos, pairs, mu, sd, mode: str = "s", score_out=None) -> tor
     "s" -> their mean.  Unbounded: not mapped to [0, 1].  An index outside [0, N) gives NaN for that trial."""
     if mode not in SCORE_NORM_MODES:
         raise ValueError(f"score_pairs_norm: mode={mode!r}: 'z', 't' or 's'")
-    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 \
-            or pairs.shape[0] < 1 or not pairs.is_contiguous():
-        raise ValueError("score_pairs_norm: pairs is a contiguous int32 [P, 2] tensor, P >= 1")
-    P = pairs.shape[0]
+    P = _pairs(pairs, "score_pairs_norm")
     if not isinstance(cos, torch.Tensor) or cos.dtype != torch.float32 or cos.dim() != 1 or cos.numel() != P \
             or not cos.is_contiguous():
         raise ValueError(f"score_pairs_norm: cos is a contiguous float32 [{P}] tensor")
@@ -1564,7 +1567,7 @@ def score_pairs_norm(cos, pairs, mu, sd, mode: str = "s", score_out=None) -> tor
                 or not v.is_contiguous() or v.shape != mu.shape:
             raise ValueError("score_pairs_norm: mu / sd are contiguous float32 [N] tensors")
     _dev(cos, pairs, mu, sd, score_out)
-    score_out = _score_out(score_out, P, cos.device, "score_pairs_norm")
+    score_out = _out(score_out, P, cos.device, "score_pairs_norm", "score_out")
     _lib.check(lib().w2v2_score_pairs_norm(cos.data_ptr(), pairs.data_ptr(), P, mu.data_ptr(), sd.data_ptr(), mu.numel(),
                                            SCORE_NORM_MODES[mode], score_out.data_ptr(), stream()), "score_pairs_norm")
     return score_out
@@ -1640,9 +1643,7 @@ def cohort_stats(bank, cohort, K: int, mean=None, std=None, length_norm: bool = 
         blk = bank[r0:r0 + rows]
         u, inv = rows_transform(blk, mean, std, length_norm, out=u_buf, inv_norm=inv_buf)
         u = blk if u is None else u
-        Gemm(rows, M, D, u, c_u, S, lda=u.stride(0) if rows > 1 else max(u.stride(0), D),
-             ldb=c_u.stride(0) if M > 1 else max(c_u.stride(0), D), ldc=ldS, epilogue=EPI_SCALE_RC, row_scale=inv,
-             col_scale=c_inv)()
+        Gemm(rows, M, D, u, c_u, S, lda=_ld(u), ldb=_ld(c_u), ldc=ldS, epilogue=EPI_SCALE_RC, row_scale=inv, col_scale=c_inv)()
         topk_stats(S[:rows], K, M, mu[r0:r0 + rows], sd[r0:r0 + rows])
     return mu, sd
 
@@ -1655,10 +1656,6 @@ SCATTER_BLOCKS_PER_LAUNCH = 4           # block products of one batched GEMM lau
 def _row_vector(t, rows: int, dtype, what: str, name: str) -> None:
     if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.shape != (rows,) or not t.is_contiguous()):
         raise ValueError(f"{what}: {name} is a contiguous {str(dtype).replace('torch.', '')} [{rows}] tensor")
-
-
-def _ld(t) -> int:
-    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
 def rows_center(x, means, seg_id=None, row_weight=None, out=None) -> torch.Tensor:
@@ -1704,16 +1701,13 @@ def plda_score_pairs(u, pairs, p, q, k: float, llr_out=None) -> torch.Tensor:
     (w2v2_plda_score_pairs).  p, q: contiguous float64 [Q] on the device; k a host float.  Unbounded.  The indices are NOT
     checked here: a trial with an index outside [0, N) comes back NaN."""
     N, Q, ld = _bank(u, "plda_score_pairs")
-    if not isinstance(pairs, torch.Tensor) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 \
-            or pairs.shape[0] < 1 or not pairs.is_contiguous():
-        raise ValueError("plda_score_pairs: pairs is a contiguous int32 [P, 2] tensor, P >= 1")
+    P = _pairs(pairs, "plda_score_pairs")
     for v in (p, q):
         if not isinstance(v, torch.Tensor) or v.dtype != torch.float64 or v.shape != (Q,) or not v.is_contiguous() \
                 or v.data_ptr() % 16 != 0:
             raise ValueError(f"plda_score_pairs: p / q are contiguous float64 [{Q}] tensors, 16-byte aligned")
     _dev(u, pairs, p, q, llr_out)
-    P = pairs.shape[0]
-    llr_out = _score_out(llr_out, P, u.device, "plda_score_pairs")
+    llr_out = _out(llr_out, P, u.device, "plda_score_pairs", "llr_out")
     _lib.check(lib().w2v2_plda_score_pairs(u.data_ptr(), ld, N, Q, pairs.data_ptr(), P, p.data_ptr(), q.data_ptr(), float(k),
                                            llr_out.data_ptr(), stream()), "plda_score_pairs")
     return llr_out
@@ -1789,6 +1783,24 @@ def _trial_count(t, dtype, what: str, name: str) -> int:
     return t.numel()
 
 
+def _labels(labels, P: int, what: str, unit: str) -> None:
+    if _trial_count(labels, torch.uint8, what, "labels") != P:
+        raise ValueError(f"{what}: one label per {unit} (P = {P})")
+
+
+def cost_checks(c_miss, c_fa, p_target, open_prior: bool = False) -> None:
+    """The operating point of a detection cost, with calculate_mdc's own errors (ref: src/eval_metrics.py:90-206);
+    ``open_prior``: a fit also needs finite prior log-odds.  evaluation.speaker.calibration checks with this as well."""
+    if c_miss < 1:
+        raise ValueError(f"c_miss={c_miss} should be >= 1")
+    if c_fa < 1:
+        raise ValueError(f"c_fa={c_fa} should be >= 1")
+    if p_target < 0 or p_target > 1:
+        raise ValueError(f"p_target={p_target} should be between 0 and 1")
+    if open_prior and (p_target == 0 or p_target == 1):
+        raise ValueError(f"p_target={p_target} should be strictly between 0 and 1: the prior log-odds must be finite")
+
+
 def _byte_workspace(workspace, need: int, device, what: str, sizer: str) -> torch.Tensor:
     if workspace is None:
         return torch.empty(need, dtype=torch.uint8, device=device)
@@ -1814,13 +1826,10 @@ def sort_f32_index(keys, order_out=None, keys_out=None, workspace=None) -> Tuple
     given) receives keys[order].  The order the host metrics take with two argsorts (ref: src/eval_metrics.py:54-79 through
     roc_curve, :90-206)."""
     P = _trial_count(keys, torch.float32, "sort_f32_index", "keys")
-    if order_out is not None and (order_out.dtype != torch.int32 or not order_out.is_contiguous() or order_out.numel() < P):
-        raise ValueError(f"sort_f32_index: order_out is a contiguous int32 tensor of at least P = {P} elements")
-    if keys_out is not None and (keys_out.dtype != torch.float32 or not keys_out.is_contiguous() or keys_out.numel() < P):
-        raise ValueError(f"sort_f32_index: keys_out is a contiguous float32 tensor of at least P = {P} elements")
+    order_out = _out(order_out, P, keys.device, "sort_f32_index", "order_out", torch.int32)
+    if keys_out is not None:                            # (not allocated: without it the sorted keys are not written)
+        _out(keys_out, P, keys.device, "sort_f32_index", "keys_out")
     _dev(keys, order_out, keys_out, workspace)
-    if order_out is None:
-        order_out = torch.empty(P, dtype=torch.int32, device=keys.device)
     workspace = _byte_workspace(workspace, _workspace_bytes("w2v2_sort_f32_index_workspace_bytes", P), keys.device,
                                 "sort_f32_index", "sort_f32_index_workspace")
     _lib.check(lib().w2v2_sort_f32_index(keys.data_ptr(), P, order_out.data_ptr(), _p(keys_out), workspace.data_ptr(),
@@ -1837,20 +1846,11 @@ def trial_metrics(scores, labels, c_miss=1, c_fa=1, p_target=0.05, out=None, wor
     src/eval_metrics.py:54-79 calculate_eer, :90-206 calculate_mdc) -> out [8] float64 on the device, in the order of
     TRIAL_METRICS_FIELDS.  With NaN scores (n_nan > 0) or one class absent the
     other fields are unspecified: evaluation.speaker.device_scoring.metrics_device answers those on the host."""
-    if c_miss < 1:                                      # calculate_mdc's own errors
-        raise ValueError(f"c_miss={c_miss} should be >= 1")
-    if c_fa < 1:
-        raise ValueError(f"c_fa={c_fa} should be >= 1")
-    if p_target < 0 or p_target > 1:
-        raise ValueError(f"p_target={p_target} should be between 0 and 1")
+    cost_checks(c_miss, c_fa, p_target)
     P = _trial_count(scores, torch.float32, "trial_metrics", "scores")
-    if _trial_count(labels, torch.uint8, "trial_metrics", "labels") != P:
-        raise ValueError(f"trial_metrics: one label per score (P = {P})")
-    if out is not None and (out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < 8):
-        raise ValueError("trial_metrics: out is a contiguous float64 tensor of at least 8 elements")
+    _labels(labels, P, "trial_metrics", "score")
+    out = _out(out, 8, scores.device, "trial_metrics", "out", torch.float64)
     _dev(scores, labels, out, workspace)
-    if out is None:
-        out = torch.empty(8, dtype=torch.float64, device=scores.device)
     workspace = _byte_workspace(workspace, _workspace_bytes("w2v2_trial_metrics_workspace_bytes", P), scores.device,
                                 "trial_metrics", "trial_metrics_workspace")
     _lib.check(lib().w2v2_trial_metrics(scores.data_ptr(), labels.data_ptr(), P, float(c_miss), float(c_fa), float(p_target),
@@ -1895,17 +1895,6 @@ def calib_record_fields(record) -> dict:
     return out
 
 
-def _cost_checks(c_miss, c_fa, p_target, open_prior: bool = False) -> None:
-    if c_miss < 1:                                      # calculate_mdc's own errors
-        raise ValueError(f"c_miss={c_miss} should be >= 1")
-    if c_fa < 1:
-        raise ValueError(f"c_fa={c_fa} should be >= 1")
-    if p_target < 0 or p_target > 1:
-        raise ValueError(f"p_target={p_target} should be between 0 and 1")
-    if open_prior and (p_target == 0 or p_target == 1):
-        raise ValueError(f"p_target={p_target} should be strictly between 0 and 1: the prior log-odds must be finite")
-
-
 def _system_scores(scores, what: str) -> Tuple[int, int, int]:
     """(K, P, ld) of scores [K, P] f32 (a 1-D [P] tensor is one system) whose trials are contiguous."""
     if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.dim() not in (1, 2):
@@ -1917,7 +1906,7 @@ def _system_scores(scores, what: str) -> Tuple[int, int, int]:
         raise ValueError(f"{what}: K = {K} systems outside [1, {CALIB_MAX_SYSTEMS}]")
     if not 1 <= P < 2 ** 31:
         raise ValueError(f"{what}: P = {P} outside [1, 2^31)")
-    ld = scores.stride(0) if K > 1 else max(scores.stride(0), P)
+    ld = _ld(scores)
     if scores.stride(1) != 1 or ld < P:
         raise ValueError(f"{what}: the trials of a system are contiguous and the row stride ld = {ld} >= P = {P}")
     return K, P, ld
@@ -1937,10 +1926,9 @@ def calib_fit(scores, labels, c_miss=1, c_fa=1, p_target=0.05, ridge=0.0, max_it
     with labels [P] uint8, both on the device (w2v2_calib_fit) -> the f64 record [CALIB_RECORD_DOUBLES] on the device
     (calib_record_fields names its cells).  The whole fit is enqueued; nothing is copied or waited for.  ``w_start``: K + 1
     host numbers, the first trial point (with ``max_iter=1`` the record then holds J, g and H there)."""
-    _cost_checks(c_miss, c_fa, p_target, open_prior=True)
+    cost_checks(c_miss, c_fa, p_target, open_prior=True)
     K, P, ld = _system_scores(scores, "calib_fit")
-    if _trial_count(labels, torch.uint8, "calib_fit", "labels") != P:
-        raise ValueError(f"calib_fit: one label per trial (P = {P})")
+    _labels(labels, P, "calib_fit", "trial")
     if not (isinstance(ridge, (int, float)) and 0 <= ridge < float("inf")):
         raise ValueError(f"calib_fit: ridge = {ridge!r} must be a finite number >= 0")
     if isinstance(max_iter, bool) or not isinstance(max_iter, int) or not 1 <= max_iter <= 4096:
@@ -1951,12 +1939,8 @@ def calib_fit(scores, labels, c_miss=1, c_fa=1, p_target=0.05, ridge=0.0, max_it
         if len(w) != K + 1 or not all(abs(v) < float("inf") for v in w):
             raise ValueError(f"calib_fit: w_start holds K + 1 = {K + 1} finite numbers")
         start = (C.c_double * (K + 1))(*w)
-    if record is not None and (not isinstance(record, torch.Tensor) or record.dtype != torch.float64
-                               or not record.is_contiguous() or record.numel() < CALIB_RECORD_DOUBLES):
-        raise ValueError(f"calib_fit: record is a contiguous float64 tensor of at least {CALIB_RECORD_DOUBLES} elements")
+    record = _out(record, CALIB_RECORD_DOUBLES, scores.device, "calib_fit", "record", torch.float64)
     _dev(scores, labels, record, workspace)
-    if record is None:
-        record = torch.empty(CALIB_RECORD_DOUBLES, dtype=torch.float64, device=scores.device)
     workspace = _byte_workspace(workspace, _workspace_bytes("w2v2_calib_workspace_bytes", P), scores.device, "calib_fit",
                                 "calib_workspace")
     _lib.check(lib().w2v2_calib_fit(scores.data_ptr(), ld, K, labels.data_ptr(), P, float(c_miss), float(c_fa), float(p_target),
@@ -1973,11 +1957,8 @@ def calib_apply(scores, record, out=None) -> torch.Tensor:
     if not isinstance(record, torch.Tensor) or record.dtype != torch.float64 or not record.is_contiguous() \
             or record.numel() not in (K + 1, CALIB_RECORD_DOUBLES):
         raise ValueError(f"calib_apply: record is a fit's float64 record or K + 1 = {K + 1} float64 coefficients")
-    if out is not None and (out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < P):
-        raise ValueError(f"calib_apply: out is a contiguous float32 tensor of at least P = {P} elements")
+    out = _out(out, P, scores.device, "calib_apply", "out")
     _dev(scores, record, out)
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=scores.device)
     a = record if record.numel() == K + 1 else record[CALIB_RECORD["a"][0]:]
     _lib.check(lib().w2v2_calib_apply(scores.data_ptr(), ld, K, P, a.data_ptr(), out.data_ptr(), stream()), "calib_apply")
     return out
@@ -1986,15 +1967,11 @@ def calib_apply(scores, record, out=None) -> torch.Tensor:
 def llr_metrics(llr, labels, c_miss=1, c_fa=1, p_target=0.05, out=None, workspace=None) -> torch.Tensor:
     """Cllr and actDCF at the Bayes threshold of llr [P] f32 and labels [P] uint8, both on the device (w2v2_llr_metrics)
     -> out [8] float64 on the device, in the order of LLR_METRICS_FIELDS."""
-    _cost_checks(c_miss, c_fa, p_target)
+    cost_checks(c_miss, c_fa, p_target)
     P = _trial_count(llr, torch.float32, "llr_metrics", "llr")
-    if _trial_count(labels, torch.uint8, "llr_metrics", "labels") != P:
-        raise ValueError(f"llr_metrics: one label per llr (P = {P})")
-    if out is not None and (out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < 8):
-        raise ValueError("llr_metrics: out is a contiguous float64 tensor of at least 8 elements")
+    _labels(labels, P, "llr_metrics", "llr")
+    out = _out(out, 8, llr.device, "llr_metrics", "out", torch.float64)
     _dev(llr, labels, out, workspace)
-    if out is None:
-        out = torch.empty(8, dtype=torch.float64, device=llr.device)
     workspace = _byte_workspace(workspace, _workspace_bytes("w2v2_calib_workspace_bytes", P), llr.device, "llr_metrics",
                                 "llr_metrics_workspace")
     _lib.check(lib().w2v2_llr_metrics(llr.data_ptr(), labels.data_ptr(), P, float(c_miss), float(c_fa), float(p_target),
@@ -2020,7 +1997,7 @@ def _aug_wave(x, what: str) -> Tuple[int, int, int]:
             or x.stride(1) != 1:
         raise ValueError(f"{what}: a 2-D float32 [rows, N] tensor with contiguous samples")
     B, N = x.shape
-    ld = x.stride(0) if B > 1 else max(x.stride(0), N)
+    ld = _ld(x)
     if ld < N:
         raise ValueError(f"{what}: row stride {ld} below N = {N}")
     return B, N, ld
@@ -2113,9 +2090,8 @@ def aug_fir(src, dst, src_rows, dst_rows, taps, ntaps, lens=None) -> None:
         raise ValueError(f"aug_fir: taps is a float32 [{R}, ldt] tensor")
     _aug_i32(ntaps, R, "aug_fir: ntaps")
     _dev(src, dst, src_rows, dst_rows, taps, ntaps, lens)
-    ldt = taps.stride(0) if R > 1 else max(taps.stride(0), taps.shape[1])
     _lib.check(lib().w2v2_aug_fir(src.data_ptr(), lds, N_in, _p(lens), src_rows.data_ptr(), dst.data_ptr(), ldd, N_out,
-                                  dst_rows.data_ptr(), R, taps.data_ptr(), ldt, ntaps.data_ptr(), stream()), "aug_fir")
+                                  dst_rows.data_ptr(), R, taps.data_ptr(), _ld(taps), ntaps.data_ptr(), stream()), "aug_fir")
 
 
 def aug_resample(src, dst, src_rows, dst_rows, U: int, D: int, h=None, lens=None, out_lens=None) -> None:
