@@ -1074,6 +1074,51 @@ int w2v2_calib_apply(const float* scores, int64_t ld, int K, int64_t P, const do
 int w2v2_llr_metrics(const float* llr, const uint8_t* labels, int64_t P, double c_miss, double c_fa, double p_target,
                      double* out, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------ layer mix (layer_mix.hip)
+ * What connects the wav2vec2 encoder to the ECAPA-TDNN back-end: a learned softmax-weighted sum of ALL J = L + 1 hidden
+ * states (prologue output, then layer 1 .. L), instance-normalised over time, written into the back-end's feature buffer.
+ * The reference project has no such model (its wav2vec_xvector.py points the same way: a pre-trained front-end into a
+ * TDNN back-end, frozen for the first steps); the recipe is the one published with UniSpeech's speaker-verification
+ * downstream, restated from memory: THIS BLOCK IS THE DEFINITION.  No atomics, fixed summation orders: equal inputs
+ * give equal bits.
+ *
+ * Inputs: xs = DEVICE table of J base pointers (1 <= J <= W2V2_LAYER_MIX_MAX_STATES) to hidden states x_j [B * T][H]
+ * (contiguous rows, dtype_x f32 / bf16 / f16, 16-byte aligned); logits a [J] f32; lens = int32 [B] frame counts n_b on the
+ * device (clamped to 0 .. T) or NULL (n_b = T).  H must be a multiple of 8 (16-byte vector accesses of 8 channels).
+ * Forward:
+ *   1. w = softmax(a) in f32, max-subtracted (written to w_out [J] when that is not NULL).
+ *   2. m = sum_j w_j x_j: f32, ascending j, one fused multiply-add per term.
+ *   3. mu[b,c] = (1 / n_b) sum_{t < n_b} m.
+ *   4. var[b,c] = (1 / n_b) sum_{t < n_b} (m - mu)^2 -- biased, centred, never E[m^2] - mu^2.
+ *   5. r = 1 / sqrt(var + 1e-5), saved as f32 rstd [B][H].
+ *   6. y[b,t,c] = (m - mu) r for t < n_b and 0 for t >= n_b; y is f32 or bf16 (one rounding) with row stride ldy >= H
+ *      (a multiple of 8); columns >= H of a row are not touched.
+ *   instance_norm = 0: y = m (0 past n_b), no statistics, rstd untouched.
+ * The sums over t depend on (n_b, c) only: a row with a length equals, bit for bit, the utterance alone in a (1, n_b)
+ * launch.  m is staged in LDS up to W2V2_LAYER_MIX_LDS_FRAMES frames; longer inputs need `stage`, f32 [B * T][H] (NULL
+ * otherwise).  Every hidden state is read once either way.
+ * Backward (training, no lengths form): g = dL/dy and the stored y (dtype_g f32 / bf16, row strides ldg / ldy), rstd.
+ *   s1[b,c] = mean_t g;  s2[b,c] = mean_t (g y);  dm = r ((g - s1) - y s2), f32 [B * T][H]  (instance_norm = 0: dm = g);
+ *   the two means, dm and the products dm x_j are carried in f64 (rstd reaches 316 where a channel hardly moves, and a mean
+ *   rounded to f32 then leaves 316 ulp per frame in every d_j); only the stored dm is rounded, once, to f32;
+ *   d_j = sum_{b,t,c} dm x_j: per thread, per workgroup (one f64 each in the 16-byte aligned workspace of
+ *   w2v2_layer_mix_workspace_floats floats, -1 for bad arguments), then folded in a fixed order by a second launch;
+ *   grad_logits[j] += w_j (d_j - sum_k w_k d_k)  (ADDED: the arena's zero_grad clears it).
+ * w2v2_scale_add: G = (overwrite ? 0 : G) + (sum_{j = lo .. hi} w_j) dm over n elements (a multiple of 8): the weights
+ * summed in f32 in ascending j, one fused multiply-add, one rounding to G's dtype (f32 / bf16 / f16); dm is f32 or bf16;
+ * w stays on the device.  It injects the mix's gradient into the encoder's running activation gradient. */
+#define W2V2_LAYER_MIX_MAX_STATES 32
+#define W2V2_LAYER_MIX_LDS_FRAMES 512
+int w2v2_layer_mix_fwd(const void* const* xs, const float* logits, int J, const int* lens, void* y, int64_t ldy, float* rstd,
+                       float* w_out, float* stage, int B, int T, int H, int instance_norm, int dtype_x, int dtype_y,
+                       void* stream);
+int64_t w2v2_layer_mix_workspace_floats(int B, int T, int H, int J);
+int w2v2_layer_mix_bwd(const void* const* xs, const float* logits, int J, const void* g, int64_t ldg, const void* y,
+                       int64_t ldy, const float* rstd, float* dm, float* grad_logits, float* workspace, int B, int T, int H,
+                       int instance_norm, int dtype_x, int dtype_g, void* stream);
+int w2v2_scale_add(void* G, const void* dm, const float* w, int lo, int hi, int overwrite, int64_t n, int dtype_g,
+                   int dtype_dm, void* stream);
+
 /* ------------------------------------------------------------------------------------ optimiser
  * torch.optim.Adam (ref: config/optim/algo/adam.yaml, src/main.py:323-335) over one flat f32
  * parameter arena; also refreshes the 16-bit copy (pb_dtype = W2V2_BF16 / W2V2_F16) the GEMMs read

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libw2v2hip.so")
 SOURCES = ["api.hip", "gemm.hip", "gemm_ring.hip", "gemm_phased.hip", "gemm_f32.hip", "gemm_f32_dma.hip", "wgrad.hip", "wgrad_phased.hip", "norm.hip", "elementwise.hip", "conv0.hip", "posconv.hip", "posconv_direct.hip", "posconv_wgrad.hip",
-           "softmax.hip", "attention.hip", "pool.hip", "asp.hip", "tdnn.hip", "wav2spk.hip", "fbank.hip", "augment.hip", "reverb.hip", "skinny.hip", "heads.hip", "margin_head.hip", "score.hip", "score_norm.hip", "backend.hip", "metrics.hip", "calibration.hip", "ctc.hip", "ctc_long.hip", "optim.hip", "comm.hip"]
+           "softmax.hip", "attention.hip", "pool.hip", "asp.hip", "tdnn.hip", "wav2spk.hip", "fbank.hip", "augment.hip", "reverb.hip", "skinny.hip", "heads.hip", "margin_head.hip", "score.hip", "score_norm.hip", "backend.hip", "metrics.hip", "calibration.hip", "layer_mix.hip", "ctc.hip", "ctc_long.hip", "optim.hip", "comm.hip"]
 HEADERS = ["common.h", "gemm_common.h", "wgrad_common.h", "ctc_common.h", "strip_common.h", "tap_gather.h", "trial_common.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # per-file additions.  augment.hip: the FIR's 8 outputs x 4 taps are plain v_fmac_f32 at the full f32 vector rate; packed

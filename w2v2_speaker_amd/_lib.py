@@ -214,6 +214,12 @@ _SIGS = {
     "w2v2_calib_fit": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_f64, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "w2v2_calib_apply": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp]),
     "w2v2_llr_metrics": (c_i32, [c_vp, c_vp, c_i64, c_f64, c_f64, c_f64, c_vp, c_vp, c_vp]),
+    "w2v2_layer_mix_fwd": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                   c_i32, c_vp]),
+    "w2v2_layer_mix_workspace_floats": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    "w2v2_layer_mix_bwd": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32,
+                                   c_i32, c_i32, c_i32, c_vp]),
+    "w2v2_scale_add": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_i32, c_i32, c_vp]),
     "w2v2_adam_step": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32,
                                c_f32, c_f32, c_vp, c_i32, c_i32, c_vp]),
     "w2v2_optim_step": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32,

@@ -210,7 +210,9 @@ class EcapaStore(BnArena):
     """Parameter arena of the ECAPA model + AAM head."""
 
     def __init__(self, cfg: EcapaConfig, device, act_dtype: torch.dtype = torch.bfloat16, num_speakers: int = 5994,
-                 sub_centers: int = 1):
+                 sub_centers: int = 1, feature_weight: int = 0):
+        """feature_weight: J > 0 adds the parameter ``feature_weight`` [J] (f32, zeros: the logits of the learned layer mix
+        of ssl_ecapa.SslEcapaPlan) behind everything else in the arena; 0 (default): the arena is what it always was."""
         assert act_dtype in (torch.bfloat16, torch.float32), "ECAPA: bf16 or f32 (the reference runs it in fp32; no loss scaler here)"
         self.cfg, self.num_speakers, self.sub_centers = cfg, num_speakers, int(sub_centers)
         if not 1 <= self.sub_centers <= 8:
@@ -219,6 +221,11 @@ class EcapaStore(BnArena):
         shapes: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
         shapes["loss_fn.fc_weights"] = (num_speakers * self.sub_centers, cfg.lin_neurons)       # row c * K + k
         shapes.update(ecapa_param_shapes(cfg))
+        self.feature_weight = int(feature_weight)
+        if self.feature_weight:
+            if not 1 <= self.feature_weight <= ops.LAYER_MIX_MAX_STATES:
+                raise ValueError(f"feature_weight {feature_weight}: 1 .. {ops.LAYER_MIX_MAX_STATES} hidden states")
+            shapes["feature_weight"] = (self.feature_weight,)
         super().__init__(shapes, device, act_dtype)
         self.asp_running = self.bn_running[FE + "asp.tdnn.norm.norm.weight"]
 
@@ -228,6 +235,8 @@ class EcapaStore(BnArena):
             if n.endswith("norm.weight"):
                 t = torch.ones(s)
             elif n.endswith("bias"):
+                t = torch.zeros(s)
+            elif n == "feature_weight":
                 t = torch.zeros(s)
             elif n == "loss_fn.fc_weights":
                 t = torch.randn(s, generator=g) * math.sqrt(2.0 / (s[0] + s[1]))
@@ -656,9 +665,13 @@ class EcapaPlan(TdnnPlan):
 
     def __init__(self, store: EcapaStore, batch: int, frames: int, *, train: bool, aam_margin: float = 0.2,
                  aam_scale: float = 30.0, sub_centers: Optional[int] = None, margin_type: str = "arc",
-                 inter_topk: int = 0, inter_margin: float = 0.06):
+                 inter_topk: int = 0, inter_margin: float = 0.06, input_grad: bool = False):
+        """input_grad (training plans; off by default): allocate ``d_feat`` [B * T, n_mels] and have the backward write
+        d(loss)/d(feat) into it -- for a front-end that trains through this plan (ssl_ecapa.SslEcapaPlan)."""
         if sub_centers is not None and int(sub_centers) != store.sub_centers:
             raise ValueError(f"plan: sub_centers {sub_centers}, but the parameter store was built with {store.sub_centers}")
+        if input_grad and not train:
+            raise ValueError("plan: input_grad needs a training plan")
         super().__init__(store, batch, frames, train)
         cfg = store.cfg
         B, T, M, dev, adt, f32 = batch, frames, batch * frames, self.dev, self.adt, torch.float32
@@ -701,6 +714,7 @@ class EcapaPlan(TdnnPlan):
             self.dpooled = torch.empty(B, E2, dtype=f32, device=dev)
             self.d_cat = torch.empty(M, C[-1], dtype=adt, device=dev)
             self.d_x0 = torch.empty(M, C[0], dtype=adt, device=dev)
+        self.d_feat = torch.empty(M, F_, dtype=adt, device=dev) if input_grad else None
         self._wgs = None
 
     def _tdnns(self) -> List[_Tdnn]:
@@ -708,6 +722,15 @@ class EcapaPlan(TdnnPlan):
         for b in self.blocks:
             out += b.blocks()
         return out + [self.mfa]
+
+    def embed_features(self, lengths=None) -> torch.Tensor:
+        """The forward from an already written ``self.feat`` (a front-end on the device wrote it, in its dtype and row
+        stride): what embed() does behind its input copy.  lengths: see embed()."""
+        self._len, self.frame_lengths = None, None
+        if lengths is not None:
+            self._set_lengths(lengths)
+        self._refresh()
+        return self._embed_features()
 
     def _embed_features(self) -> torch.Tensor:
         """The forward from the plan's feature buffer on (shared by embed and embed_waveform)."""
@@ -747,7 +770,7 @@ class EcapaPlan(TdnnPlan):
                 blk.backward(dout, C[-1], self.d_x0, C[0], False)
             else:
                 blk.backward(dout, C[-1], self.d_cat[:, (i - 2) * C[1]:], C[-1], True)
-        self.block0.backward(self.d_x0, C[0], None, 0, False, defer_dw=True)
+        self.block0.backward(self.d_x0, C[0], self.d_feat, self.cfg.input_mel_coefficients, False, defer_dw=True)
         # every da / conv input is final (each TDNN owns its buffers): the weight + bias gradients of ALL grouped TDNN
         # blocks in one launch (29 problems, ~550 tiles of equal length: three full rounds of the chip instead of one
         # third-filled round per SE-Res2Net block), then the tap-major -> torch layout unpack of the k > 1 kernels

@@ -135,6 +135,50 @@ def encoder_backward_schedule(num_layers: int, skip: Sequence[int], pair_uppers:
     return ev
 
 
+def mix_injection_points(events, num_layers: int):
+    """Where Plan.backward(dmix=, mix_weights=) adds w_j * dm into the running activation gradient G, derived from the event
+    list of encoder_backward_schedule (plain data, no device work): a list of (index, lo, hi, overwrite) -- before event
+    `index` (len(events): behind the last one, in front of the prologue backward) G = (0 if overwrite else G) +
+    (w_lo + ... + w_hi) dm.  G must hold the full gradient of X[l + 1] when the data-gradient chain ("body") of layer l
+    starts, and it passes through a LayerDrop-skipped layer unchanged: the states above a body that have not been added
+    yet go in as ONE add in front of it, the first add (which holds j = L) overwrites instead of the pool backward, and
+    what is left (j = 0 at least) goes in behind the last event."""
+    points, hi = [], num_layers
+    for i, ev in enumerate(events):
+        if ev[0] == "body":
+            l = ev[1]
+            points.append((i, l + 1, hi, hi == num_layers))
+            hi = l
+    points.append((len(events), 0, hi, hi == num_layers))
+    return points
+
+
+def mix_backward_check(*, train: bool, stable: bool, scaler, B: int, T: int, H: int, L: int, dmix, mix_weights,
+                       demb=None, dhidden=None) -> None:
+    """The argument rules of Plan.backward(dmix=, mix_weights=), checked before any device work."""
+    if (dmix is None) != (mix_weights is None):
+        raise ValueError("backward: dmix and mix_weights come together (the gradient of the layer mix and its J = L + 1 "
+                         "softmax weights)")
+    if dmix is None:
+        return
+    if demb is not None or dhidden is not None:
+        raise ValueError("backward: dmix replaces demb / dhidden (the mix's gradient arrives at every layer output)")
+    if not train:
+        raise ValueError("backward: dmix needs a training plan")
+    if stable:
+        raise NotImplementedError("do_stable_layer_norm: the layer-mix backward (dmix) is built for the post-LN encoder only")
+    if scaler is not None:
+        raise NotImplementedError("backward(dmix=): f16 encoder training is not supported here -- the store has a loss "
+                                  "scaler and the ECAPA side that produces dmix has none")
+    if not isinstance(dmix, torch.Tensor) or dmix.numel() != B * T * H or dmix.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"backward: dmix is [B, T, H] = [{B}, {T}, {H}] in float32 or bfloat16")
+    if not dmix.is_contiguous():
+        raise ValueError("backward: dmix must be contiguous")
+    if (not isinstance(mix_weights, torch.Tensor) or mix_weights.dtype != torch.float32 or mix_weights.dim() != 1
+            or mix_weights.numel() != L + 1):
+        raise ValueError(f"backward: mix_weights is a float32 vector of J = L + 1 = {L + 1} softmax weights on the device")
+
+
 def valid_lengths(cfg: W2V2Config, lengths, batch: int, n_samples: int) -> List[int]:
     """Per-utterance valid sample counts of a variable-length forward as Python ints, checked against the plan: one per
     row, at most the plan's N, and long enough for one encoder frame (400 samples for the standard conv stack)."""
@@ -1122,17 +1166,33 @@ class Plan:
     # ------------------------------------------------------------------------------------------ backward
     def backward(self, demb: Optional[torch.Tensor] = None,
                  on_bucket_ready: Optional[Callable[[str], None]] = None,
-                 dhidden: Optional[torch.Tensor] = None) -> None:
+                 dhidden: Optional[torch.Tensor] = None, dmix: Optional[torch.Tensor] = None,
+                 mix_weights: Optional[torch.Tensor] = None) -> None:
         """Backward of embed(): demb [B,E] f32 (default self.demb from the head) -> parameter gradients
         accumulated into store.grad.  on_bucket_ready(name) fires as soon as a gradient bucket
-        ('head', 'layer11', ..., 'layer0', 'prologue', 'projection') is final, for the overlapped all-reduce."""
-        assert self.train, "backward needs a training plan"
+        ('head', 'layer11', ..., 'layer0', 'prologue', 'projection') is final, for the overlapped all-reduce.
+        dmix [B,T,H] (f32 or bf16) with mix_weights [L + 1] f32 on the device: the gradient of a softmax-weighted sum of
+        ALL hidden states (include/w2v2_hip.h, "layer mix") -- d loss / d X[j] receives w_j * dmix in addition to what
+        flows down from above, at the points mix_injection_points derives from the event list; the host never reads the
+        weights.  Post-LN encoder, no loss scaler; a store with head=None has no head bucket to notify."""
         cfg, st, reg = self.cfg, self.store, self.reg
         B, T, M, H = self.B, self.T, self.M, cfg.hidden_size
+        mix_backward_check(train=self.train, stable=self.stable, scaler=st.scaler, B=B, T=T, H=H, L=cfg.num_hidden_layers,
+                           dmix=dmix, mix_weights=mix_weights, demb=demb, dhidden=dhidden)
+        assert self.train, "backward needs a training plan"
         mp, mg = st.mp, st.mg
         step = self._step
         notify = on_bucket_ready or (lambda name: None)
-        if dhidden is not None:           # gradient wrt last_hidden_state given directly (module surface)
+        events = () if self.stable else encoder_backward_schedule(cfg.num_hidden_layers, self._skip, self.g_wgrad_pair,
+                                                                  self.grouped,
+                                                                  1 if self.sw.no_wgrad_pairs else self.wg_group)
+        inject = {}
+        if dmix is not None:
+            inject = {i: (lo, hi, ow) for i, lo, hi, ow in mix_injection_points(events, cfg.num_hidden_layers)}
+            dmix = dmix.view(-1)
+        if dmix is not None:
+            pass                          # G starts as w_L * dmix: the first injection overwrites it
+        elif dhidden is not None:         # gradient wrt last_hidden_state given directly (module surface)
             self.G.view(B, T, H).copy_(dhidden)
         else:
             if demb is None:
@@ -1145,13 +1205,14 @@ class Plan:
                 ops.pool_bwd(self.out, self.emb, demb, self.G.view(B, T, H), ops.POOL_INDEX_BASE + self._rand_idx)
             else:
                 ops.pool_bwd(self.out, self.emb, demb, self.G.view(B, T, H), self.pool_mode)
-        notify("head")
+        if not (dmix is not None and st.head is None and not st.attentive_pool):
+            notify("head")
         lnfold = None if self.sw.no_ln_fold else self._lnfold
         if self.stable:
             self._backward_encoder_stable(notify)               # leaves d(loss)/d(hx + pos) in self.G
-        for ev in (() if self.stable else
-                   encoder_backward_schedule(cfg.num_hidden_layers, self._skip, self.g_wgrad_pair, self.grouped,
-                                             1 if self.sw.no_wgrad_pairs else self.wg_group)):
+        for i, ev in enumerate(events):
+            if i in inject:                                     # G holds the full gradient of X[l + 1] before body l
+                ops.scale_add(self.G, dmix, mix_weights, *inject[i])
             kind = ev[0]
             if kind == "body":
                 self._layer_backward_body(ev[1], lnfold)
@@ -1165,6 +1226,8 @@ class Plan:
                     lnfold.fold()                               # gamma / beta of the bucket's LayerNorms: one launch
             else:
                 notify(f"layer{ev[1]}")
+        if len(events) in inject:                               # X[0] (and the states of skipped layers right above it)
+            ops.scale_add(self.G, dmix, mix_weights, *inject[len(events)])
         # encoder prologue: x0 = drop(LN(hx + pos)), pos = GELU(posconv(hx) + b)
         ph = reg.hidden_dropout
         if not self.stable:

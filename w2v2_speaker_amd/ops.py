@@ -691,6 +691,128 @@ def pool_bwd(x, out, dout, dx, mode: int) -> None:
                                    dt(x), stream()), "pool_bwd")
 
 
+# ------------------------------------------------------------------------------------------------ layer mix
+LAYER_MIX_MAX_STATES = 32      # W2V2_LAYER_MIX_MAX_STATES
+LAYER_MIX_LDS_FRAMES = 512     # W2V2_LAYER_MIX_LDS_FRAMES: longer inputs stage m in a caller-owned f32 buffer
+_MIX_X = (torch.float32, torch.bfloat16, torch.float16)
+_MIX_Y = (torch.float32, torch.bfloat16)
+
+
+def _is_f32_vec(t, n: int) -> bool:
+    return isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 1 and t.numel() == n and t.is_contiguous()
+
+
+class LayerMixTable:
+    """The device table of J base pointers the layer-mix kernels read their hidden states through (include/w2v2_hip.h,
+    "layer mix"): J tensors of one shape [..., H] and dtype, each contiguous -- built once per plan."""
+
+    def __init__(self, states):
+        states = list(states)
+        if not 1 <= len(states) <= LAYER_MIX_MAX_STATES:
+            raise ValueError(f"layer_mix_table: 1 .. {LAYER_MIX_MAX_STATES} hidden states, got {len(states)}")
+        x0 = states[0]
+        for x in states:
+            if not isinstance(x, torch.Tensor) or x.dtype not in _MIX_X or x.dim() < 2:
+                raise ValueError("layer_mix_table: hidden states are f32, bf16 or f16 tensors [..., H]")
+            if x.shape != x0.shape or x.dtype != x0.dtype or not x.is_contiguous():
+                raise ValueError("layer_mix_table: hidden states must share one shape and dtype and be contiguous")
+        self.H, self.rows, self.J, self.dtype = int(x0.shape[-1]), x0.numel() // int(x0.shape[-1]), len(states), x0.dtype
+        if self.H % 8 or self.H < 8:
+            raise ValueError(f"layer_mix_table: H must be a multiple of 8 (16-byte vector accesses), got {self.H}")
+        if any(x.data_ptr() % 16 for x in states):
+            raise ValueError("layer_mix_table: hidden states need 16-byte aligned bases")
+        _dev(*states)
+        self.ptrs = torch.tensor([x.data_ptr() for x in states], dtype=torch.int64).to(x0.device)
+        self._keep = states
+
+
+def _mix_check(name: str, table, logits, B: int, T: int, y, ldy: int, rstd, instance_norm: bool) -> None:
+    if not isinstance(table, LayerMixTable):
+        raise ValueError(f"{name}: table is a LayerMixTable")
+    if B < 1 or T < 1 or B * T != table.rows:
+        raise ValueError(f"{name}: B x T = {B} x {T} does not match the table's {table.rows} rows")
+    if not _is_f32_vec(logits, table.J):
+        raise ValueError(f"{name}: logits is a contiguous float32 vector of {table.J} values")
+    if not isinstance(y, torch.Tensor) or y.dtype not in _MIX_Y:
+        raise ValueError(f"{name}: y is a float32 or bfloat16 tensor")
+    if ldy < table.H or ldy % 8 or y.numel() < (B * T - 1) * ldy + table.H or y.data_ptr() % 16:
+        raise ValueError(f"{name}: y needs a 16-byte aligned base, a row stride >= H = {table.H} that is a multiple of 8 "
+                         f"and B * T rows (stride {ldy}, {y.numel()} elements)")
+    if instance_norm and not _is_f32_vec(rstd.reshape(-1) if isinstance(rstd, torch.Tensor) else rstd, B * table.H):
+        raise ValueError(f"{name}: instance_norm needs rstd, contiguous float32 [B, H]")
+
+
+def layer_mix_workspace(B: int, T: int, H: int, J: int, device) -> torch.Tensor:
+    """The f32 workspace of layer_mix_bwd: one row of per-workgroup partials of the J logit gradients per workgroup."""
+    n = lib().w2v2_layer_mix_workspace_floats(B, T, H, J)
+    if n < 0:
+        raise ValueError(f"layer_mix_workspace: bad shape B {B}, T {T}, H {H} (a multiple of 8), J {J} (1 .. {LAYER_MIX_MAX_STATES})")
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def layer_mix_fwd(table: LayerMixTable, logits, y, ldy: int, B: int, T: int, rstd=None, lens=None, w_out=None, stage=None,
+                  instance_norm: bool = True) -> None:
+    """y[b,t,:H] = instance norm over time of sum_j softmax(logits)_j x_j (include/w2v2_hip.h, "layer mix"); y is the
+    ECAPA plan's feature buffer (f32 / bf16, row stride ldy).  lens: device int32 [B] frame counts or None.  w_out: f32
+    [J] receives the softmax weights.  stage: f32 [B * T, H], needed beyond LAYER_MIX_LDS_FRAMES frames."""
+    name = "layer_mix_fwd"
+    _mix_check(name, table, logits, B, T, y, ldy, rstd, instance_norm)
+    if lens is not None and not (isinstance(lens, torch.Tensor) and lens.dtype == torch.int32 and lens.numel() == B
+                                 and lens.is_contiguous()):
+        raise ValueError(f"{name}: lens is a contiguous int32 tensor of B = {B} frame counts")
+    if w_out is not None and not _is_f32_vec(w_out, table.J):
+        raise ValueError(f"{name}: w_out is a contiguous float32 vector of {table.J} values")
+    if instance_norm and T > LAYER_MIX_LDS_FRAMES and not (isinstance(stage, torch.Tensor) and stage.dtype == torch.float32
+                                                            and stage.numel() >= B * T * table.H and stage.is_contiguous()):
+        raise ValueError(f"{name}: more than {LAYER_MIX_LDS_FRAMES} frames need stage, contiguous float32 [B * T, H]")
+    _dev(table.ptrs, logits, y, rstd, lens, w_out, stage)
+    _lib.check(lib().w2v2_layer_mix_fwd(table.ptrs.data_ptr(), logits.data_ptr(), table.J, _p(lens), y.data_ptr(), ldy,
+                                        _p(rstd), _p(w_out), _p(stage), B, T, table.H, int(instance_norm), dt(table._keep[0]),
+                                        dt(y), stream()), name)
+
+
+def layer_mix_bwd(table: LayerMixTable, logits, g, ldg: int, y, ldy: int, rstd, dm, grad_logits, workspace, B: int, T: int,
+                  instance_norm: bool = True) -> None:
+    """Backward of layer_mix_fwd from g = dL/dy and the stored y / rstd: dm f32 [B * T, H] (written), grad_logits f32 [J]
+    (ADDED to).  Two launches, no atomics: equal inputs give equal bits."""
+    name = "layer_mix_bwd"
+    _mix_check(name, table, logits, B, T, g, ldg, rstd, instance_norm)
+    if instance_norm:
+        _mix_check(name, table, logits, B, T, y, ldy, rstd, True)
+        if y.dtype != g.dtype:
+            raise ValueError(f"{name}: g and y share a dtype")
+    if not (isinstance(dm, torch.Tensor) and dm.dtype == torch.float32 and dm.numel() == B * T * table.H and dm.is_contiguous()):
+        raise ValueError(f"{name}: dm is contiguous float32 [B * T, H]")
+    if not _is_f32_vec(grad_logits, table.J):
+        raise ValueError(f"{name}: grad_logits is a contiguous float32 vector of {table.J} values")
+    need = 2 * B * -(-table.H // 64) * LAYER_MIX_MAX_STATES        # one f64 per workgroup and logit
+    if not (isinstance(workspace, torch.Tensor) and workspace.dtype == torch.float32 and workspace.numel() >= need):
+        raise ValueError(f"{name}: workspace is float32 with at least {need} values (layer_mix_workspace)")
+    _dev(table.ptrs, logits, g, y, rstd, dm, grad_logits, workspace)
+    _lib.check(lib().w2v2_layer_mix_bwd(table.ptrs.data_ptr(), logits.data_ptr(), table.J, g.data_ptr(), ldg, _p(y), ldy,
+                                        _p(rstd), dm.data_ptr(), grad_logits.data_ptr(), workspace.data_ptr(), B, T, table.H,
+                                        int(instance_norm), dt(table._keep[0]), dt(g), stream()), name)
+
+
+def scale_add(G, dm, w, lo: int, hi: int, overwrite: bool) -> None:
+    """G = (0 if overwrite else G) + (w[lo] + ... + w[hi]) * dm, rounded once to G's dtype; w f32 on the device (the host
+    never reads it).  G f32 / bf16 / f16 and dm f32 / bf16, both contiguous with the same number of elements."""
+    name = "scale_add"
+    if not (isinstance(G, torch.Tensor) and isinstance(dm, torch.Tensor) and G.dtype in _MIX_X and dm.dtype in _MIX_Y):
+        raise ValueError(f"{name}: G is f32 / bf16 / f16 and dm f32 / bf16")
+    if G.numel() != dm.numel() or G.numel() % 8 or G.numel() == 0 or not (G.is_contiguous() and dm.is_contiguous()):
+        raise ValueError(f"{name}: G and dm are contiguous with the same number of elements, a multiple of 8")
+    if not (isinstance(w, torch.Tensor) and w.dtype == torch.float32 and w.dim() == 1 and w.is_contiguous()):
+        raise ValueError(f"{name}: w is a contiguous float32 vector")
+    if not 0 <= lo <= hi < min(w.numel(), LAYER_MIX_MAX_STATES):
+        raise ValueError(f"{name}: 0 <= lo <= hi < {min(w.numel(), LAYER_MIX_MAX_STATES)}, got {lo} .. {hi}")
+    if G.data_ptr() % 16 or dm.data_ptr() % 16:
+        raise ValueError(f"{name}: G and dm need 16-byte aligned bases")
+    _dev(G, dm, w)
+    _lib.check(lib().w2v2_scale_add(G.data_ptr(), dm.data_ptr(), w.data_ptr(), lo, hi, int(bool(overwrite)), G.numel(),
+                                    dt(G), dt(dm), stream()), name)
+
+
 # ------------------------------------------------------------------------------------------------ heads
 def row_invnorm(x, inv, rows: int, cols: int, ld: Optional[int] = None) -> None:
     _dev(x, inv)
