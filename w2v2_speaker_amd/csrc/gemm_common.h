@@ -506,6 +506,52 @@ __device__ __forceinline__ void tile_ptrs(const OpDev& o, const bf16_t* base, in
   }
 }
 
+// ------------------------------------------------------------------------------ persistent tile walk (256x128 ring)
+// A persistent workgroup takes one tile per round of G = gridDim.x tiles.  The ring kernel asks for the NEXT round's
+// tile and its source addresses while the current tile is still in its K loop (that tile's first operand stages are
+// requested from there and land under the epilogue), so the decode and the address code stand here once and are called
+// from both places: ahead of the first tile and inside the stream.
+// Tile of the round that starts at t0 for this workgroup; -1: it has none (a short last round, or no round left).
+__device__ __forceinline__ int persistent_tile(int t0, int ntile, int G) {
+  if (t0 >= ntile) return -1;
+  const int nchunk = min(G, ntile - t0);
+  if ((int)blockIdx.x >= nchunk) return -1;
+  return t0 + xcd_remap(blockIdx.x, nchunk);
+}
+
+// 256x128 ring: tile index -> (tm, tn).  Longest tiles first: with two-term weight columns (n >= n_ext_from) a tile of
+// those columns runs twice the K steps.  In plain row-major order a workgroup of the fused QKV product (702 tiles, 3
+// rounds) can draw two double tiles and a single one (60 K steps against a mean of 44); enumerating all double tiles
+// before the single ones bounds it at 48.  Tiles of one row panel stay adjacent inside each class (L2 reuse of the A rows).
+__device__ __forceinline__ void ring_tile_coords(const GemmArgs& g, int tile, int& tm, int& tn) {
+  constexpr int BN = 128;
+  const int tl = (g.k_ext > 0 && g.n_ext_from > 0) ? min(g.tiles_n, g.n_ext_from / BN) : 0;   // single-K columns
+  const int th = g.tiles_n - tl;
+  if (tl == 0 || th == 0) {
+    tm = tile / g.tiles_n;
+    tn = tile - tm * g.tiles_n;
+  } else if (tile < g.tiles_m * th) {
+    tm = tile / th;
+    tn = tl + (tile - tm * th);
+  } else {
+    const int t2 = tile - g.tiles_m * th;
+    tm = t2 / tl;
+    tn = t2 - tm * tl;
+  }
+}
+// 256x128 ring: per-lane sources of this wave's six DMA pieces of one stage (A0..A3, B0, B1) for the tile at (m0, n0)
+__device__ __forceinline__ void ring_tile_srcs(const GemmArgs& g, const bf16_t* Ab, const bf16_t* Bb, int m0, int n0,
+                                               int wave, int lane, const bf16_t** ap, const bf16_t** bp) {
+  const int c8 = lane & 7, r8 = lane >> 3;
+  int ca[4], cb[2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) ca[j] = (c8 ^ swz((wave * 4 + j) * 8 + r8)) << 3;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) cb[j] = (c8 ^ swz_b((wave * 2 + j) * 8 + r8)) << 3;
+  tile_ptrs<4>(g.A, Ab, m0, 256, g.M, wave * 32 + r8, 8, ca, ap);
+  tile_ptrs<2>(g.B, Bb, n0, 128, g.N, wave * 16 + r8, 8, cb, bp);
+}
+
 // CUs the persistent grids may fill: w2v2_device_cus() (common.h) minus W2V2_RESERVE_CUS, which keeps some out for RCCL's
 // channels -- data-parallel runs: the persistent ring kernels fill every CU's registers, so RCCL's all-reduce workgroups
 // (side stream) only run between them

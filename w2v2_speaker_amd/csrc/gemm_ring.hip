@@ -42,65 +42,30 @@ __global__ __launch_bounds__(512) void gemm16_ring_256x128_kernel(const GemmArgs
     }
   };
   // Persistent over tiles: gridDim.x = min(tiles, CUs) workgroups, each takes tiles t, t + G, ...  (one 144 KiB
-  // workgroup per CU anyway).  The next tile's first two DMA stages are issued right behind the epilogue's stores,
-  // so their latency -- and a workgroup launch -- hides under the store drain instead of following it.
+  // workgroup per CU anyway).  The tiles of a workgroup are ONE K stream through the ring: K tile kt of a tile lives in
+  // stage (phase + kt) % 3 where `phase` runs on from the previous tile, the last two ring steps of a tile (which have
+  // nothing of their own left to request) request K tiles 0 and 1 of the NEXT tile, and that tile enters its loop on
+  // the counted wait -- no barrier and no prologue between tiles: the operands land under the epilogue.  (Measured in
+  // the step, A B A B A B on one box: 10.15 -> 9.99 ms, profiles/stream_tiles_ab.txt.)
   const int ntile = g.tiles_m * g.tiles_n;
   const int G = gridDim.x;
   const int z = blockIdx.z;
-#pragma unroll 1
-  for (int t0 = 0; t0 < ntile; t0 += G) {
-  const int nchunk = min(G, ntile - t0);
-  if ((int)blockIdx.x >= nchunk) break;
-  const int tile = t0 + xcd_remap(blockIdx.x, nchunk);
-  int tm, tn;
-  {
-    // Longest tiles first: with two-term weight columns (n >= n_ext_from) a tile of those columns runs twice the K
-    // steps.  In plain row-major order a workgroup of the fused QKV product (702 tiles, 3 rounds) can draw two double
-    // tiles and a single one (60 K steps against a mean of 44); enumerating all double tiles before the single ones
-    // bounds it at 48.  Tiles of one row panel stay adjacent inside each class (L2 reuse of the A rows).
-    const int tl = (g.k_ext > 0 && g.n_ext_from > 0) ? min(g.tiles_n, g.n_ext_from / BN) : 0;   // single-K columns
-    const int th = g.tiles_n - tl;
-    if (tl == 0 || th == 0) {
-      tm = tile / g.tiles_n;
-      tn = tile - tm * g.tiles_n;
-    } else if (tile < g.tiles_m * th) {
-      tm = tile / th;
-      tn = tl + (tile - tm * th);
-    } else {
-      const int t2 = tile - g.tiles_m * th;
-      tm = t2 / tl;
-      tn = t2 - tm * tl;
-    }
-  }
-  const int m0 = tm * BM, n0 = tn * BN;
   const int z0 = z / g.batch_inner, z1 = z - z0 * g.batch_inner;
-  // K steps of this tile: nk1 over (A, B) + for the tiles of the two-term weight columns nk - nk1 more over (A, B_lo)
+  // K steps of a tile: nk1 over (A, B) + for the tiles of the two-term weight columns nk - nk1 more over (A, B_lo)
   const int nk1 = g.K >> 6;
-  const int nk = nk1 + ((g.k_ext > 0 && n0 >= g.n_ext_from) ? (g.k_ext >> 6) : 0);
+  auto tile_nk = [&](int n0) -> int { return nk1 + ((g.k_ext > 0 && n0 >= g.n_ext_from) ? (g.k_ext >> 6) : 0); };
   auto koff_a = [&](int kt) -> int { return (kt < nk1 ? kt : kt - nk1) * 64; };
   auto koff_b = [&](int kt) -> int64_t { return kt < nk1 ? (int64_t)kt * 64 : (int64_t)(kt - nk1) * 64 + g.b_lo_off; };
 
   const bf16_t* Ab = reinterpret_cast<const bf16_t*>(g.A.ptr) + z0 * g.a_s0 + z1 * g.a_s1;
   const bf16_t* Bb = reinterpret_cast<const bf16_t*>(g.B.ptr) + z0 * g.b_s0 + z1 * g.b_s1;
 
-  const int c8 = lane & 7, r8 = lane >> 3;
+  // per-lane sources of this wave's DMA pieces (gemm_common.h: ring_tile_srcs).  They belong to the tile whose operands
+  // are being requested: the current one until its last K tile has been requested, then the NEXT one
   const bf16_t* ap[4];
   const bf16_t* bp[2];
-  {
-    int ca[4], cb[2];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ca[j] = (c8 ^ swz((wave * 4 + j) * 8 + r8)) << 3;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) cb[j] = (c8 ^ swz_b((wave * 2 + j) * 8 + r8)) << 3;
-    tile_ptrs<4>(g.A, Ab, m0, BM, g.M, wave * 32 + r8, 8, ca, ap);
-    tile_ptrs<2>(g.B, Bb, n0, BN, g.N, wave * 16 + r8, 8, cb, bp);
-  }
 
   f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   auto stage = [&](bf16_t* base, int kt) {
     bf16_t* ad = base + wave * 4 * 8 * 64;
@@ -173,79 +138,126 @@ __global__ __launch_bounds__(512) void gemm16_ring_256x128_kernel(const GemmArgs
       }
     }
   };
-  bf16_t* s0 = smem;
-  bf16_t* s1 = smem + STAGE;
-  bf16_t* s2 = smem + 2 * STAGE;
+  // ---- the stream.  phase = ring stage of the K tile the next step multiplies; inflight = K tiles requested and not
+  // yet waited for (1 or 2 at a step's wait: the one it multiplies and, mostly, the one behind it)
+  int phase = 0, inflight = 0, kt = 0, nk = 0;
+  // one ring step: K tile kt of the current tile is in stage `phase`; when kload >= 0, K tile kload of the tile ap / bp
+  // point into goes to the stage two further on, which held the step before this one's and is free behind the barrier.
+  // The counted wait holds whatever else the wave has in flight: vmcnt retires in order and every other operation
+  // (deferred stores, an epilogue's loads) is OLDER than the newest K tile's six pieces or is drained explicitly.
+  // Deferred stores of the previous tile ride on the first three steps, AHEAD of the step's DMA pieces: behind them
+  // they would make the next step's vmcnt(6) wait for part of the K tile after next.
+  auto step = [&](int kload) {
+    if (!(dbg & 4)) { if (inflight > 1) wait_vmcnt<6>(); else wait_vmcnt<0>(); }
+    --inflight;
+    if (!(dbg & 2)) __builtin_amdgcn_s_barrier();
+    if (pending) {                                         // (only where nk >= 3: shorter tiles flush in one piece)
+      if (kt == 0) flush(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
+      else if (kt == 1) flush(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{});
+      else { flush(std::integral_constant<int, 6>{}, std::integral_constant<int, 2>{}); pending = false; }
+    }
+    compute(smem + phase * STAGE, smem + (phase == 0 ? 2 : phase - 1) * STAGE, kload);
+    if (kload >= 0) ++inflight;
+    phase = phase == 2 ? 0 : phase + 1;
+    ++kt;
+  };
 
-  // one ring step: tile kt is in `cur`; tile kt+2 goes to `nxt` (which held tile kt-1)
-#define W2V2_RING_STEP(cur, nxt)                                   \
-  {                                                                \
-    if (!(dbg & 4)) { if (kt + 1 < nk) wait_vmcnt<6>(); else wait_vmcnt<0>(); }   \
-    if (!(dbg & 2)) __builtin_amdgcn_s_barrier();                  \
-    compute(cur, nxt, kt + 2 < nk ? kt + 2 : -1);                  \
-    ++kt;                                                          \
+  int t0 = 0;
+  int tile = persistent_tile(t0, ntile, G);
+  if (tile < 0) return;
+  int m0, n0;
+  {
+    int tm, tn;
+    ring_tile_coords(g, tile, tm, tn);
+    m0 = tm * BM;
+    n0 = tn * BN;
   }
-  w2v2_vmcnt0_visible();                 // (common.h: keeps the compiler's own vmcnt(0) out of the loop; nothing of this wave's is in flight here but the previous tile's epilogue loads / non-deferred stores)
-  __builtin_amdgcn_s_barrier();          // every wave has finished reading the previous tile's stages
-  if (nk > 0) stage(s0, 0);
-  if (nk > 1) stage(s1, 1);
-  int kt = 0;
-  if (pending) {
-    if (nk >= 3) {                                         // one peeled rotation of the ring carries the stores
-      wait_vmcnt<6>();
-      __builtin_amdgcn_s_barrier();
-      flush(std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
-      compute(s0, s2, nk > 2 ? 2 : -1);
-      kt = 1;
-      wait_vmcnt<6>();
-      __builtin_amdgcn_s_barrier();
-      flush(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{});
-      compute(s1, s0, nk > 3 ? 3 : -1);
-      kt = 2;
-      if (nk > 3) wait_vmcnt<6>(); else wait_vmcnt<0>();
-      __builtin_amdgcn_s_barrier();
-      flush(std::integral_constant<int, 6>{}, std::integral_constant<int, 2>{});
-      compute(s2, s1, nk > 4 ? 4 : -1);
-      kt = 3;
-    } else {
+  nk = tile_nk(n0);
+  ring_tile_srcs(g, Ab, Bb, m0, n0, wave, lane, ap, bp);
+  int pre = 0;                           // K tiles of the current tile that the previous tile's last steps requested
+  w2v2_vmcnt0_visible();                 // (common.h: keeps the compiler's own vmcnt(0) out of the loop)
+#pragma unroll 1
+  for (;;) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // K tiles 0 and 1 where no step has requested them (the first tile; the tile behind a one-step tile).  Their stages
+    // held the K tiles three and two steps back: every wave has left those (this wave passed the last step's barrier).
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      if (j >= pre && j < nk) {
+        const int sj = phase + j;
+        stage(smem + (sj >= 3 ? sj - 3 : sj) * STAGE, j);
+        ++inflight;
+      }
+    kt = 0;
+    if (pending && nk < 3) {
       flush(std::integral_constant<int, 0>{}, std::integral_constant<int, 8>{});
+      pending = false;
     }
-    pending = false;
-  }
-  while (kt < nk) {
-    W2V2_RING_STEP(s0, s2)
-    if (kt >= nk) break;
-    W2V2_RING_STEP(s1, s0)
-    if (kt >= nk) break;
-    W2V2_RING_STEP(s2, s1)
-  }
-#undef W2V2_RING_STEP
+    // steps that still have a K tile of their own tile to request
+#pragma unroll 1
+    while (kt + 2 < nk) step(kt + 2);
+    // ---- the last two steps: the sources of this tile are dead, they become the next tile's (decode and addresses
+    // cost ~600 dependent instructions: here they run while K tiles nk - 2 and nk - 1 are landing)
+    t0 += G;
+    tile = persistent_tile(t0, ntile, G);
+    int m0n = 0, n0n = 0, nkn = 0;
+    if (tile >= 0) {
+      int tm, tn;
+      ring_tile_coords(g, tile, tm, tn);
+      m0n = tm * BM;
+      n0n = tn * BN;
+      nkn = tile_nk(n0n);
+      ring_tile_srcs(g, Ab, Bb, m0n, n0n, wave, lane, ap, bp);
+    }
+    // (a one-step tile has no second step to request K tile 0 of the next tile from: that tile requests its own)
+    const bool stream = tile >= 0 && nk >= 2;
+#pragma unroll 1
+    while (kt < nk) {
+      const int j = kt + 2 - nk;
+      step(stream && j < nkn ? j : -1);
+    }
+    pre = stream ? min(nkn, 2) : 0;
 
-  // Register epilogue: thanks to the permuted B rows a lane holds, for each of its four rows, 16 consecutive
-  // output columns (32 B of bf16): bias / GELU / residual are applied in registers and stored as 2 x 16 B per lane,
-  // four lanes covering 128 contiguous bytes of a row -- no LDS round trip and no barrier after the main loop.
-  if (DBG && (dbg & 32)) { if (g.M > 0) { asm volatile("" :: "v"(acc[0][0]), "v"(acc[3][3])); continue; } }   // (tools: no epilogue)
-  TC* Cz = reinterpret_cast<TC*>(g.C) + z0 * g.c_s0 + z1 * g.c_s1;
-  TC* auxz = g.aux ? reinterpret_cast<TC*>(g.aux) + z0 * g.aux_s0 + z1 * g.aux_s1 : nullptr;
-  const float* bias = g.bias ? g.bias + z1 * g.bias_s1 : nullptr;
-  const int nc = n0 + wn * 64 + fk * 16;
-  float cv0[8], cv1[8];
-  load_col8(g, bias, nc, cv0);
-  load_col8(g, bias, nc + 8, cv1);
-  if constexpr (sizeof(TC) == 2) {
-    if (g.defer_ok) {            // (the host grants defer_ok only where lines_ok holds)
-      W2V2_EPI_DISPATCH((epilogue_lines<TC, EPI, 4, true>(g, Cz, auxz, acc, m0 + wm * 64, nc, lane, cv0, cv1, pend)));
-      pending = true;
-      pend_m = m0 + wm * 64 + (frow & 7);
-      pend_n = nc + (frow < 8 ? 0 : 8);
-    } else if (lines_ok(g)) {
-      W2V2_EPI_DISPATCH((epilogue_lines<TC, EPI, 4>(g, Cz, auxz, acc, m0 + wm * 64, nc, lane, cv0, cv1, pend)));
+    // Register epilogue: thanks to the permuted B rows a lane holds, for each of its four rows, 16 consecutive
+    // output columns (32 B of bf16): bias / GELU / residual are applied in registers and stored as 2 x 16 B per lane,
+    // four lanes covering 128 contiguous bytes of a row -- no LDS round trip and no barrier after the main loop.
+    if (DBG && (dbg & 32) && g.M > 0) {                  // (tools: no epilogue)
+      asm volatile("" :: "v"(acc[0][0]), "v"(acc[3][3]));
     } else {
-      W2V2_EPI_DISPATCH((epilogue_direct<TC, EPI, 4>(g, Cz, auxz, acc, m0 + wm * 64 + frow, nc, cv0, cv1)));
+      TC* Cz = reinterpret_cast<TC*>(g.C) + z0 * g.c_s0 + z1 * g.c_s1;
+      TC* auxz = g.aux ? reinterpret_cast<TC*>(g.aux) + z0 * g.aux_s0 + z1 * g.aux_s1 : nullptr;
+      const float* bias = g.bias ? g.bias + z1 * g.bias_s1 : nullptr;
+      const int nc = n0 + wn * 64 + fk * 16;
+      float cv0[8], cv1[8];
+      load_col8(g, bias, nc, cv0);
+      load_col8(g, bias, nc + 8, cv1);
+      if constexpr (sizeof(TC) == 2) {
+        if (g.defer_ok) {            // (the host grants defer_ok only where lines_ok holds)
+          W2V2_EPI_DISPATCH((epilogue_lines<TC, EPI, 4, true>(g, Cz, auxz, acc, m0 + wm * 64, nc, lane, cv0, cv1, pend)));
+          pending = true;
+          pend_m = m0 + wm * 64 + (frow & 7);
+          pend_n = nc + (frow < 8 ? 0 : 8);
+        } else if (lines_ok(g)) {
+          W2V2_EPI_DISPATCH((epilogue_lines<TC, EPI, 4>(g, Cz, auxz, acc, m0 + wm * 64, nc, lane, cv0, cv1, pend)));
+        } else {
+          W2V2_EPI_DISPATCH((epilogue_direct<TC, EPI, 4>(g, Cz, auxz, acc, m0 + wm * 64 + frow, nc, cv0, cv1)));
+        }
+      } else {
+        W2V2_EPI_DISPATCH((epilogue_direct<TC, EPI, 4>(g, Cz, auxz, acc, m0 + wm * 64 + frow, nc, cv0, cv1)));
+      }
     }
-  } else {
-    W2V2_EPI_DISPATCH((epilogue_direct<TC, EPI, 4>(g, Cz, auxz, acc, m0 + wm * 64 + frow, nc, cv0, cv1)));
-  }
+    if (tile < 0) break;
+    m0 = m0n;
+    n0 = n0n;
+    nk = nkn;
+    // stores that were not deferred are drained here, as before; with deferred stores the stream runs on the counted
+    // waits.  (The compiler still guards the registers of column operands an epilogue kind loaded without using them
+    // with one vmcnt(0) of its own at the tile entry -- tools/loop_waits.sh shows it OUTSIDE both K loops: by then the
+    // two requested stages have had the epilogue to land.)
+    if (!pending) w2v2_vmcnt0_visible();
   }   // tile loop
   if (pending) flush(std::integral_constant<int, 0>{}, std::integral_constant<int, 8>{});
 }
